@@ -35,6 +35,13 @@ One JSON line on rank 0 with metric/value plus
                 call stream on one host core, plus an N-process run (one
                 process per core, frames replayed independently) with the core
                 count stated
+
+--dump-outputs DIR  after the timed regions, the window the last timed frame
+                left (what a caller reads back) as DIR/*.npy: per-row channel
+                sums of the whole window (float64) and a seeded sample of 2^20
+                pixels (float32) with their indices.  The workloads are seeded,
+                so two builds run with the same arguments can be compared file
+                for file.
 """
 import argparse
 import json
@@ -63,6 +70,22 @@ def measured_ceiling():
             "store_only_1GiB_GBps": pick("store_wg_1GiB"), "copy_1GiB_GBps": pick("copy_1GiB"), "empty_launch_us": r.get("empty_launch", {}).get("median_us"),
             "source": "profiles/" + os.path.basename(files[-1])}
 REPEATS = 7            # timed regions per run; the median is reported
+DUMP_PIXELS = 1 << 20  # window pixels --dump-outputs samples (16 MB as float32 RGBA): the whole window of a 1024x1024 target
+
+
+def dump_outputs(out_dir, window):
+    """--dump-outputs: the window the last timed frame left (uint8 [H, W, 4] in framebuffer row order, what the caller reads back) as
+    float arrays another build's dump can be compared with: every row's channel sums over the whole window, and a fixed, seeded sample
+    of whole pixels with their indices into the H * W pixels.  Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    h, w, c = window.shape
+    idx = np.sort(np.random.default_rng(0).choice(h * w, size=min(h * w, DUMP_PIXELS), replace=False))
+    arrays = {"window_row_sums": window.sum(axis=1, dtype=np.float64),
+              "window_sample": window.reshape(h * w, c)[idx].astype(np.float32),
+              "window_sample_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 def pin_to_gpu_numa_node(local_rank):
@@ -298,7 +321,13 @@ def main():
     ap.add_argument("--emulate-world", type=int, default=0, metavar="W",
                     help="on ONE GPU: every rank's share of a W-rank run (its strip's rows, its frame's uploads) timed back to back, "
                          "and a PROJECTED W-GPU rate under a stated xGMI gather model (no collective runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the window the last one computed as DIR/*.npy (float32 / float64, seeded sample)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.emulate_world:
+        ap.error("--dump-outputs needs a timed path: not with --emulate-world")
     if args.emulate_world:
         return emulate_world(args)
 
@@ -400,6 +429,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)        # every region: the slowest rank
         regions = [float(v) for v in t.tolist()]
     elapsed = float(np.median(regions))
+    dumped = None
+    if args.dump_outputs and rank == 0:      # (read before any other pass renders the frame again)
+        dumped = dump_outputs(args.dump_outputs, player.assembled() if sharded else player.read_pixels())
     # per-frame latency with a Finish after every frame (what `wrench perf` samples)
     lat = player.frames(0, min(args.steps, 50))
 
@@ -550,6 +582,8 @@ def main():
             out["vs_baseline"] = out["speedup_vs_single_gpu"]
             out["vs_baseline_note"] = "value / single_gpu_same_workload.value (same workload, unsharded, rank 0's GPU, this run); BASELINE.md has no published number"
         out["host_affinity"] = affinity
+        if dumped:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "shapes": dumped}
         if host:
             out["host"] = host
             if roof:

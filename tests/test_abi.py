@@ -1,9 +1,11 @@
 """The C-ABI boundary: include/wrhip.h declares exactly the reference's 99
 `extern "C"` functions (swgl/src/swgl_fns.rs:23-322) and libwrhip.so exports
 every one of them (no compute calls here: loading the library needs no GPU)."""
+import json
 import os
 import re
 import subprocess
+import sys
 from conftest import ROOT, wrhip_lib
 from webrender_amd.glapi import SIGNATURES, EXTRA_SIGNATURES
 
@@ -26,18 +28,19 @@ def test_header_declares_reference_abi():
 
 
 def test_signature_table_matches_reference_extern_block():
-    if not os.path.exists(REFERENCE_FNS):
-        import pytest
-        pytest.skip("reference tree not present")
-    src = open(REFERENCE_FNS).read()
-    block = src[src.index('extern "C" {'):src.index("#[derive(Clone, Copy)]")]
-    ref = re.findall(r"fn (\w+)\(", block)
+    """against the extern block as tests/golden/make_abi_fns.py extracted it (tests/golden/swgl_fns.json), re-derived where the
+    reference tree is present"""
+    with open(os.path.join(ROOT, "tests", "golden", "swgl_fns.json")) as f:
+        fns = json.load(f)["functions"]
+    if os.path.exists(REFERENCE_FNS):
+        sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+        from make_abi_fns import extern_block_functions
+        assert extern_block_functions(open(REFERENCE_FNS).read()) == fns, "tests/golden/swgl_fns.json is stale"
+    ref = [name for name, _ in fns]
     assert len(ref) == 99
     assert ref == list(SIGNATURES), "same functions, same order as swgl_fns.rs:23-322"
     # argument counts agree too
-    for m in re.finditer(r"fn (\w+)\((.*?)\)(?: -> [^;]+)?;", block, flags=re.S):
-        name, args = m.group(1), m.group(2).strip()
-        n = 0 if not args else len([a for a in args.split(",") if a.strip()])
+    for name, n in fns:
         assert n == len(SIGNATURES[name][1]), name
 
 
