@@ -3175,7 +3175,8 @@ void DrawElementsInstanced(GLenum mode, GLsizei count, GLenum type, GLintptr off
                      info->kind == WR_SH_BRUSH_IMAGE_REPEAT || info->kind == WR_SH_BRUSH_IMAGE_REPEAT_ALPHA || info->kind == WR_SH_BRUSH_IMAGE_REPEAT_DUAL ||
                      info->kind == WR_SH_BRUSH_LINEAR_GRADIENT || info->kind == WR_SH_BRUSH_LINEAR_GRADIENT_ALPHA ||
                      info->kind == WR_SH_BRUSH_BLEND || info->kind == WR_SH_BRUSH_BLEND_ALPHA ||
-                     info->kind == WR_SH_BRUSH_MIX_BLEND || info->kind == WR_SH_BRUSH_MIX_BLEND_ALPHA;
+                     info->kind == WR_SH_BRUSH_MIX_BLEND || info->kind == WR_SH_BRUSH_MIX_BLEND_ALPHA ||
+                     info->kind == WR_SH_BRUSH_YUV || info->kind == WR_SH_BRUSH_YUV_ALPHA;
     // (glyph quads under a rotation -- local raster space -- ride on the same path; the program never asks for swgl_antiAlias,
     // and a glyph instance's third word is not a brush's flags: the transform ids alone decide)
     const bool text = info->kind == WR_SH_PS_TEXT_RUN || info->kind == WR_SH_PS_TEXT_RUN_DUAL || info->kind == WR_SH_PS_TEXT_RUN_GT || info->kind == WR_SH_PS_TEXT_RUN_DUAL_GT;

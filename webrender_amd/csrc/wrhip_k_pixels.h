@@ -183,7 +183,7 @@ WR_DEVICE void wr_quad_row_edges(const WrQuadRec& Q, int si, int y, WrQuadRowCac
     for (int i = 0; i < dy; i++) {
       L.xl = L.xl + S.ls; L.xr = L.xr + S.rs;
       L.lu = L.lu + S.luvs[0]; L.lv = L.lv + S.luvs[1]; L.ru = L.ru + S.ruvs[0]; L.rv = L.rv + S.ruvs[1];
-      if (Q.pad || Q.base_kind == WR_PK_MIX_BLEND) {
+      if (Q.pad || Q.base_kind == WR_PK_MIX_BLEND || Q.base_kind == WR_PK_YUV) {
         L.wl = L.wl + Q.persp.lws[si]; L.wr = L.wr + Q.persp.rws[si];
         L.zl = L.zl + Q.persp.lzs[si]; L.zr = L.zr + Q.persp.rzs[si];
       }
@@ -193,7 +193,7 @@ WR_DEVICE void wr_quad_row_edges(const WrQuadRec& Q, int si, int y, WrQuadRowCac
     L.lu = wr_accum(S.luv[0], S.luvs[0], y - S.lrow); L.lv = wr_accum(S.luv[1], S.luvs[1], y - S.lrow);
     L.ru = wr_accum(S.ruv[0], S.ruvs[0], y - S.rrow); L.rv = wr_accum(S.ruv[1], S.ruvs[1], y - S.rrow);
     L.wl = L.wr = L.zl = L.zr = 0.0f;
-    if (Q.pad || Q.base_kind == WR_PK_MIX_BLEND) {
+    if (Q.pad || Q.base_kind == WR_PK_MIX_BLEND || Q.base_kind == WR_PK_YUV) {
       L.wl = wr_accum(Q.persp.lw[si], Q.persp.lws[si], y - S.lrow); L.wr = wr_accum(Q.persp.rw[si], Q.persp.rws[si], y - S.rrow);
       L.zl = wr_accum(Q.persp.lz[si], Q.persp.lzs[si], y - S.lrow); L.zr = wr_accum(Q.persp.rz[si], Q.persp.rzs[si], y - S.rrow);
     }
@@ -325,7 +325,9 @@ __device__ __noinline__ WrWide wr_filter_pixel(const WrPrim* Pp, const WrFilterR
 __device__ __noinline__ WrWide wr_filter_eval(const WrPrim* Pp, const WrFilterRec* Fp, const WrDrawDesc* D, float cu, float cv);
 __device__ __noinline__ WrWide wr_gradient_main(const WrGradRec* Gp, const WrDrawDesc* D, float lu, float lv);
 __device__ __noinline__ WrWide wr_quad_mask_pixel(const WrPrim* Pp, const WrClipRec* Cp, const WrDrawDesc* D, int x, int y, const WrRuns* runs);
-__device__ __noinline__ WrWide wr_yuv_pixel(const WrPrim* Pp, const WrYuvRec* Yp, const WrDrawDesc* D, int x, int y, const WrRuns* runs);
+__device__ __noinline__ WrWide wr_yuv_pixel(const WrPrim* Pp, const WrYuvRec* Yp, const WrDrawDesc* D, int x, int y, const WrRuns* runs, const float* row);
+WR_DEVICE void wr_yuv_main_sample(const WrTexDesc& t, int pl, float cu, float cv, float (&fs)[3]);
+WR_DEVICE WrWide wr_yuv_main_rgb(const WrYuvRec& Y, const float (&fs)[3], bool clamp01);
 __device__ __noinline__ WrWide wr_mix_blend_pixel(const WrPrim* Pp, const WrMixRec* Mp, const WrDrawDesc* D, int x, int y, const WrRuns* runs);
 __device__ __noinline__ WrWide wr_mix_blend_main(const WrMixRec* Mp, const WrDrawDesc* D, float bu, float bv, float su, float sv);
 __device__ __noinline__ WrWide wr_svg_filter_pixel(const WrPrim* Pp, const WrSvgRec* Sp, const WrDrawDesc* D, int x, int y, const WrRuns* runs);
@@ -458,6 +460,26 @@ __device__ __noinline__ unsigned long long wr_quad_tex_pixel_rgba8(const WrPrim*
       bu = wr_clamp(bu, Pl.uv_bounds[0], Pl.uv_bounds[2]); bv = wr_clamp(bv, Pl.uv_bounds[1], Pl.uv_bounds[3]);
       su_ = wr_clamp(su_, Q.mix.s_bounds[0], Q.mix.s_bounds[2]); sv_ = wr_clamp(sv_, Q.mix.s_bounds[1], Q.mix.s_bounds[3]);
       src = wr_mix_blend_main(&Q.mix, D, bu, bv, su_, sv_);
+    } else if (Q.base_kind == WR_PK_YUV) {
+      // brush_yuv_image: main() on every pixel (sample_yuv in float), vUv_Y and vUv_U each interpolated / w along the span and times
+      // 1 / gl_FragCoord.w, each clamped to its own bounds; vUv_V is vUv_U (wr_yuv_persp_ok), sampled from its own plane
+      float pu, pv, fw;
+      lane_at(k, pu, pv, fw);
+      const float wq = 1.0f / fw;
+      const float* e = Q.rowtab_stride >= 14 ? wr_quad_rowtab_entry(Q, y) : nullptr;
+      const float L2u = e ? e[10] : wr_accum(Q.persp.l2u[si], Q.persp.l2us[si], y - S.lrow), L2v = e ? e[11] : wr_accum(Q.persp.l2v[si], Q.persp.l2vs[si], y - S.lrow);
+      const float R2u = e ? e[12] : wr_accum(Q.persp.r2u[si], Q.persp.r2us[si], y - S.rrow), R2v = e ? e[13] : wr_accum(Q.persp.r2v[si], Q.persp.r2vs[si], y - S.rrow);
+      const float su2 = (R2u - L2u) * stepScale, sv2 = (R2v - L2v) * stepScale;
+      float qu = L2u + su2 * start, qv = L2v + sv2 * start;
+      for (int i = 0; i < (k & 3); i++) { qu = qu + su2; qv = qv + sv2; }
+      qu = wr_accum(qu, (su2 * 4.0f) * 1.0f, k >> 2); qv = wr_accum(qv, (sv2 * 4.0f) * 1.0f, k >> 2);
+      const WrYuvRec& Y = Q.yuv;
+      const float cu = qu * wq, cv = qv * wq;
+      float fs[3] = {0.f, 0.f, 0.f};
+      wr_yuv_main_sample(t, 0, wr_clamp(pu * wq, Pl.uv_bounds[0], Pl.uv_bounds[2]), wr_clamp(pv * wq, Pl.uv_bounds[1], Pl.uv_bounds[3]), fs);
+      wr_yuv_main_sample(D->tex[WR_S_COLOR1], 1, wr_clamp(cu, Y.u_bounds[0], Y.u_bounds[2]), wr_clamp(cv, Y.u_bounds[1], Y.u_bounds[3]), fs);
+      if (Y.format == 3) wr_yuv_main_sample(D->tex[WR_S_COLOR2], 2, wr_clamp(cu, Y.v_bounds[0], Y.v_bounds[2]), wr_clamp(cv, Y.v_bounds[1], Y.v_bounds[3]), fs);
+      src = wr_yuv_main_rgb(Y, fs, (Pl.flags & WR_PF_TAIL_MODULATE) != 0);
     } else {
     float pu, pv, fw;
     lane_at(k, pu, pv, fw);
@@ -499,13 +521,22 @@ __device__ __noinline__ unsigned long long wr_quad_tex_pixel_rgba8(const WrPrim*
     M2.sL0[0] = E.zl; M2.sL0[1] = E.wl; M2.sR0[0] = E.zr; M2.sR0[1] = E.wr;
     M2.sLs[0] = M2.sLs[1] = M2.sRs[0] = M2.sRs[1] = 0.0f;
     src = wr_mix_blend_pixel(&Pl, &M2, D, x, y, runs);
-  } else if (Q.base_kind == WR_PK_GRADIENT || Q.base_kind == WR_PK_FILTER || Q.base_kind == WR_PK_QUAD_MASK) {
+  } else if (Q.base_kind == WR_PK_GRADIENT || Q.base_kind == WR_PK_FILTER || Q.base_kind == WR_PK_QUAD_MASK || Q.base_kind == WR_PK_YUV) {
     // shader replays that take their interpolants from the prim: hand them this row as a one-row axis-aligned prim (the span
     // [s0, s1), the edges' x and interpolants on this row, no row stepping left to do)
     Pl.uvL0[0] = Lu; Pl.uvL0[1] = Lv; Pl.uvR0[0] = Ru; Pl.uvR0[1] = Rv;
     Pl.uvLs[0] = Pl.uvLs[1] = Pl.uvRs[0] = Pl.uvRs[1] = 0.0f;
     Pl.xl = xl; Pl.xr = xr; Pl.x0 = s0; Pl.x1 = s1; Pl.y0 = y; Pl.y1 = y + 1; Pl.rows_linear = 1;
-    if (Q.base_kind == WR_PK_GRADIENT) src = wr_gradient_row4(&Pl, &Q.grad, D, x, y, runs).v[0];
+    if (Q.base_kind == WR_PK_YUV) {
+      // brush_yuv_image: the chroma varyings' edge values on this row too -- vUv_U from the walk's second-varying slots, vUv_V from its z / w
+      float ch[8];
+      const float* e = Q.rowtab_stride >= 14 ? wr_quad_rowtab_entry(Q, y) : nullptr;
+      ch[0] = e ? e[10] : wr_accum(Q.persp.l2u[si], Q.persp.l2us[si], y - S.lrow); ch[1] = e ? e[11] : wr_accum(Q.persp.l2v[si], Q.persp.l2vs[si], y - S.lrow);
+      ch[2] = e ? e[12] : wr_accum(Q.persp.r2u[si], Q.persp.r2us[si], y - S.rrow); ch[3] = e ? e[13] : wr_accum(Q.persp.r2v[si], Q.persp.r2vs[si], y - S.rrow);
+      ch[4] = E.zl; ch[5] = E.wl; ch[6] = E.zr; ch[7] = E.wr;
+      src = wr_yuv_pixel(&Pl, &Q.yuv, D, x, y, runs, ch);
+    }
+    else if (Q.base_kind == WR_PK_GRADIENT) src = wr_gradient_row4(&Pl, &Q.grad, D, x, y, runs).v[0];
     else if (Q.base_kind == WR_PK_FILTER) src = wr_filter_pixel(&Pl, &Q.filt, D, x, y, runs);
     else src = wr_quad_mask_pixel(&Pl, &Q.clip, D, x, y, runs);
   } else if (Q.base_kind == WR_PK_TEX_REPEAT && Pl.dual && Pl.blend == WR_BLEND_DUAL_SRC) {
@@ -1461,13 +1492,32 @@ WR_DEVICE void wr_yuv_row_setup(WrYuvRowArgs& R, const WrTexDesc& Ty, const WrTe
   }
 }
 
+// The prim as chroma plane `pl` (1: vUv_U, 2: vUv_V) sees it: that plane's edge interpolants and bounds.  `row`: the prim is one row of a
+// general quad (wr_quad_tex_pixel_rgba8), and these are the planes' edge values on it -- vUv_U left (u, v), right (u, v), then vUv_V
+WR_DEVICE void wr_yuv_chroma_prim(WrPrim& P2, const WrYuvRec& Y, int pl, const float* row) {
+  const float* Bd = pl == 1 ? Y.u_bounds : Y.v_bounds;
+  if (row) {
+    const float* e = row + 4 * (pl - 1);
+    P2.uvL0[0] = e[0]; P2.uvL0[1] = e[1]; P2.uvR0[0] = e[2]; P2.uvR0[1] = e[3];
+    P2.uvLs[0] = P2.uvLs[1] = P2.uvRs[0] = P2.uvRs[1] = 0.0f;
+  } else {
+    const float* L0 = pl == 1 ? Y.uL0 : Y.vL0; const float* Ls = pl == 1 ? Y.uLs : Y.vLs;
+    const float* R0 = pl == 1 ? Y.uR0 : Y.vR0; const float* Rs = pl == 1 ? Y.uRs : Y.vRs;
+    P2.uvL0[0] = L0[0]; P2.uvL0[1] = L0[1]; P2.uvLs[0] = Ls[0]; P2.uvLs[1] = Ls[1];
+    P2.uvR0[0] = R0[0]; P2.uvR0[1] = R0[1]; P2.uvRs[0] = Rs[0]; P2.uvRs[1] = Rs[1];
+  }
+  P2.uv_bounds[0] = Bd[0]; P2.uv_bounds[1] = Bd[1]; P2.uv_bounds[2] = Bd[2]; P2.uv_bounds[3] = Bd[3];
+  P2.rows_linear = 0;
+}
+
 // The span pixels of a PLANAR frame under a TEXTURE_RECT key: three linear sampler2DRect planes select blendYUV's second overload
 // (swgl_ext.h:1195-1283).  When the planes agree (one format, chroma planes of one size sampled at the same coordinates, no change of
 // row along the span, x increasing) the span is cut in three: chunks before both clamp rects are entered take the quantised float
 // stepping (blendYUVFallback), the chunks inside them CompositeYUV's inner loop (linear_row_yuv from the coordinates reached by
 // ONE multiply-add), the rest the float stepping again from where that run ended.  Returns false where the shared routine's value is
 // the reference's (conditions not met, or the pixel lies in the first part).
-WR_DEVICE bool wr_yuv_rect_span_pixel(const WrPrim* Pp, const WrYuvRec& Y, const WrDrawDesc* D, int x, int y, const WrRuns* runs, WrWide& out) {
+WR_DEVICE bool wr_yuv_rect_span_pixel(const WrPrim* Pp, const WrYuvRec& Y, const WrDrawDesc* D, int x, int y, const WrRuns* runs, WrWide& out,
+                                      const float* row) {
   const WrTexDesc& T0 = D->tex[WR_S_COLOR0]; const WrTexDesc& T1 = D->tex[WR_S_COLOR1]; const WrTexDesc& T2 = D->tex[WR_S_COLOR2];
   if (!(T0.format == T1.format && T1.format == T2.format && T1.width == T2.width && T1.height == T2.height)) return false;
   float q[3][4], qy[3][4], stepx[3], stepy[3], minx[3], maxx[3], miny[3], maxy[3];
@@ -1475,14 +1525,7 @@ WR_DEVICE bool wr_yuv_rect_span_pixel(const WrPrim* Pp, const WrYuvRec& Y, const
   for (int pl = 0; pl < 3; pl++) {
     WrPrim P2 = *Pp;
     P2.kind = WR_PK_TEX_R8;
-    if (pl > 0) {
-      const float* L0 = pl == 1 ? Y.uL0 : Y.vL0; const float* Ls = pl == 1 ? Y.uLs : Y.vLs;
-      const float* R0 = pl == 1 ? Y.uR0 : Y.vR0; const float* Rs = pl == 1 ? Y.uRs : Y.vRs; const float* Bd = pl == 1 ? Y.u_bounds : Y.v_bounds;
-      P2.uvL0[0] = L0[0]; P2.uvL0[1] = L0[1]; P2.uvLs[0] = Ls[0]; P2.uvLs[1] = Ls[1];
-      P2.uvR0[0] = R0[0]; P2.uvR0[1] = R0[1]; P2.uvRs[0] = Rs[0]; P2.uvRs[1] = Rs[1];
-      P2.uv_bounds[0] = Bd[0]; P2.uv_bounds[1] = Bd[1]; P2.uv_bounds[2] = Bd[2]; P2.uv_bounds[3] = Bd[3];
-      P2.rows_linear = 0;
-    }
+    if (pl > 0) wr_yuv_chroma_prim(P2, Y, pl, row);
     const WrTexDesc& t = D->tex[WR_S_COLOR0 + pl];
     const WrTexRow r = wr_tex_row(P2, t, y, runs, x, false);
     if (pl == 0) { n = x - r.x0; span = r.span; if (n >= span) return false; }
@@ -1529,14 +1572,45 @@ WR_DEVICE bool wr_yuv_rect_span_pixel(const WrPrim* Pp, const WrYuvRec& Y, const
   return true;
 }
 
-__device__ __noinline__ WrWide wr_yuv_pixel(const WrPrim* Pp, const WrYuvRec* Yp, const WrDrawDesc* D, int x, int y, const WrRuns* runs = nullptr) {
+// main()'s sample of one plane (sample_yuv: TEX_SAMPLE of the clamped uv) as floats in fs[pl] (RG planes: fs[1], fs[2])
+WR_DEVICE void wr_yuv_main_sample(const WrTexDesc& t, int pl, float cu, float cv, float (&fs)[3]) {
+  const float W = t.sw, H = t.sh;
+  if (t.format == WR_FMT_R16 || t.format == WR_FMT_RG16) {      // textureLinearR16 / RG16: sample * (1 / 32767)
+    int v4[4] = {0, 0, 0, 0};
+    const int iqx = int(cu * W * 128.0f + (0.5f - 64.0f)), iqy = int(cv * H * 128.0f + (0.5f - 64.0f));
+    if (t.format == WR_FMT_RG16) { wr_bilinear16<2>(t, iqx, iqy, v4); fs[1] = float(v4[0]) * (1.0f / 32767.0f); fs[2] = float(v4[1]) * (1.0f / 32767.0f); }
+    else { wr_bilinear16<1>(t, iqx, iqy, v4); fs[pl] = float(v4[0]) * (1.0f / 32767.0f); }
+  } else if (t.format == WR_FMT_RG8) {
+    int v4[4] = {0, 0, 0, 0};
+    if (t.linear) wr_bilinear<2>(t, int(cu * W * 128.0f + (0.5f - 64.0f)), int(cv * H * 128.0f + (0.5f - 64.0f)), v4);
+    else wr_fetch_texel<2>(t, (size_t)wr_clamp_coord(int(cu * W), t.width) + (size_t)wr_clamp_coord(int(cv * H), t.height) * t.stride, v4);
+    fs[1] = float(v4[0]) * (1.0f / 255.0f); fs[2] = float(v4[1]) * (1.0f / 255.0f);
+  } else {
+    fs[pl] = wr_r8_texture(t, cu, cv);
+  }
+}
+// ... and the rest of main(): rgb = vRgbFromDebiasedYcbcr * (ycbcr_sample - vYcbcrBias); ALPHA_PASS: clamp to [0, 1]; alpha 1
+WR_DEVICE WrWide wr_yuv_main_rgb(const WrYuvRec& Y, const float (&fs)[3], bool clamp01) {
+  const float d0 = fs[0] - Y.bias[0], d1 = fs[1] - Y.bias[1], d2 = fs[2] - Y.bias[2];
+  float rgb[3];
+  for (int i = 0; i < 3; i++) rgb[i] = Y.mat[i] * d0 + Y.mat[3 + i] * d1 + Y.mat[6 + i] * d2;
+  if (clamp01) for (int i = 0; i < 3; i++) rgb[i] = wr_clamp(rgb[i], 0.0f, 1.0f);
+  uint32_t pc[2];
+  wr_pack_color(wf4{rgb[0], rgb[1], rgb[2], 1.0f}, pc);
+  WrWide s; s.bg = pc[0]; s.ra = pc[1];
+  return s;
+}
+
+// `row`: see wr_yuv_chroma_prim (nullptr: the chroma planes' edges of the record)
+__device__ __noinline__ WrWide wr_yuv_pixel(const WrPrim* Pp, const WrYuvRec* Yp, const WrDrawDesc* D, int x, int y, const WrRuns* runs = nullptr,
+                                            const float* row = nullptr) {
   const WrYuvRec& Y = *Yp;
   const int planes = Y.format == 3 ? 3 : 2;
   bool all_linear = true;
   for (int pl = 0; pl < planes; pl++) all_linear = all_linear && D->tex[WR_S_COLOR0 + pl].linear != 0;
   if ((D->flags & WR_DF_TEX_RECT) && planes == 3 && all_linear) {
     WrWide w;
-    if (wr_yuv_rect_span_pixel(Pp, Y, D, x, y, runs, w)) return w;
+    if (wr_yuv_rect_span_pixel(Pp, Y, D, x, y, runs, w, row)) return w;
   }
   int sample[3] = {0, 0, 0};          // y, u, v as the span shader's u16 lanes
   float fs[3] = {0.f, 0.f, 0.f};      // ... and as main()'s floats
@@ -1544,14 +1618,7 @@ __device__ __noinline__ WrWide wr_yuv_pixel(const WrPrim* Pp, const WrYuvRec* Yp
   for (int pl = 0; pl < planes; pl++) {
     WrPrim P2 = *Pp;                  // the same walk on this plane's varying (wr_mix_blend_pixel)
     P2.kind = WR_PK_TEX_R8;           // (the quantised fallback stepping of an R8 / RG8 plane: filter 1)
-    if (pl > 0) {
-      const float* L0 = pl == 1 ? Y.uL0 : Y.vL0; const float* Ls = pl == 1 ? Y.uLs : Y.vLs;
-      const float* R0 = pl == 1 ? Y.uR0 : Y.vR0; const float* Rs = pl == 1 ? Y.uRs : Y.vRs; const float* Bd = pl == 1 ? Y.u_bounds : Y.v_bounds;
-      P2.uvL0[0] = L0[0]; P2.uvL0[1] = L0[1]; P2.uvLs[0] = Ls[0]; P2.uvLs[1] = Ls[1];
-      P2.uvR0[0] = R0[0]; P2.uvR0[1] = R0[1]; P2.uvRs[0] = Rs[0]; P2.uvRs[1] = Rs[1];
-      P2.uv_bounds[0] = Bd[0]; P2.uv_bounds[1] = Bd[1]; P2.uv_bounds[2] = Bd[2]; P2.uv_bounds[3] = Bd[3];
-      P2.rows_linear = 0;
-    }
+    if (pl > 0) wr_yuv_chroma_prim(P2, Y, pl, row);
     const WrTexDesc& t = D->tex[WR_S_COLOR0 + pl];
     const WrTexRow r = wr_tex_row(P2, t, y, runs, x, !all_linear);
     const int n = x - r.x0;
@@ -1582,31 +1649,11 @@ __device__ __noinline__ WrWide wr_yuv_pixel(const WrPrim* Pp, const WrYuvRec* Yp
       tail = true;
       float cu, cv;
       wr_tex_tail_uv(P2, r, n, cu, cv);
-      if (t.format == WR_FMT_R16 || t.format == WR_FMT_RG16) {      // textureLinearR16 / RG16: sample * (1 / 32767)
-        int v4[4] = {0, 0, 0, 0};
-        const int iqx = int(cu * W * 128.0f + (0.5f - 64.0f)), iqy = int(cv * H * 128.0f + (0.5f - 64.0f));
-        if (t.format == WR_FMT_RG16) { wr_bilinear16<2>(t, iqx, iqy, v4); fs[1] = float(v4[0]) * (1.0f / 32767.0f); fs[2] = float(v4[1]) * (1.0f / 32767.0f); }
-        else { wr_bilinear16<1>(t, iqx, iqy, v4); fs[pl] = float(v4[0]) * (1.0f / 32767.0f); }
-      } else if (t.format == WR_FMT_RG8) {
-        int v4[4] = {0, 0, 0, 0};
-        if (t.linear) wr_bilinear<2>(t, int(cu * W * 128.0f + (0.5f - 64.0f)), int(cv * H * 128.0f + (0.5f - 64.0f)), v4);
-        else wr_fetch_texel<2>(t, (size_t)wr_clamp_coord(int(cu * W), t.width) + (size_t)wr_clamp_coord(int(cv * H), t.height) * t.stride, v4);
-        fs[1] = float(v4[0]) * (1.0f / 255.0f); fs[2] = float(v4[1]) * (1.0f / 255.0f);
-      } else {
-        fs[pl] = wr_r8_texture(t, cu, cv);
-      }
+      wr_yuv_main_sample(t, pl, cu, cv, fs);
     }
   }
   if (!tail) return wr_yuv_convert(Y, sample[0], sample[1], sample[2]);
-  // rgb = vRgbFromDebiasedYcbcr * (ycbcr_sample - vYcbcrBias); ALPHA_PASS: clamp to [0, 1]; alpha 1
-  const float d0 = fs[0] - Y.bias[0], d1 = fs[1] - Y.bias[1], d2 = fs[2] - Y.bias[2];
-  float rgb[3];
-  for (int i = 0; i < 3; i++) rgb[i] = Y.mat[i] * d0 + Y.mat[3 + i] * d1 + Y.mat[6 + i] * d2;
-  if (Pp->flags & WR_PF_TAIL_MODULATE) for (int i = 0; i < 3; i++) rgb[i] = wr_clamp(rgb[i], 0.0f, 1.0f);
-  uint32_t pc[2];
-  wr_pack_color(wf4{rgb[0], rgb[1], rgb[2], 1.0f}, pc);
-  WrWide s; s.bg = pc[0]; s.ra = pc[1];
-  return s;
+  return wr_yuv_main_rgb(Y, fs, (Pp->flags & WR_PF_TAIL_MODULATE) != 0);
 }
 
 // ---------------------------------------------------------------------------

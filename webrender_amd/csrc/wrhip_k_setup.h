@@ -1066,10 +1066,11 @@ WR_DEVICE void wr_vs_brush(const WrDrawDesc& d, const uint8_t* arena, int inst, 
     o.tail_clamp = 1;
     o.tail_modulate = d.shader == WR_SH_BRUSH_YUV_ALPHA ? 1 : 0;      // (here: main() clamps the rgb to [0, 1] -- the ALPHA_PASS key, yuv.glsl:231-235)
     o.has_color = 0; o.color = wf4{1.f, 1.f, 1.f, 1.f};
-    // (axis-aligned prims; the interleaved format and rotated video: reported)
+    // (the interleaved format: reported; rotations, skews, swgl_antiAlias and projective transforms: the general-quad path of
+    // wr_finish_prim, which reports what it cannot draw -- video cut by the near plane)
     bool fmt_ok = planes > 0 && wr_yuv_planes_ok(d, format, depth);
     if (wr_yuv_rect_fast_path(d, format)) fmt_ok = false;
-    o.kind = (fmt_ok && transform.axis_aligned && vww[0] == 1.0f && vww[1] == 1.0f && vww[2] == 1.0f && vww[3] == 1.0f) ? WR_PK_YUV : WR_PK_UNSUPPORTED;
+    o.kind = fmt_ok ? WR_PK_YUV : WR_PK_UNSUPPORTED;
     return;
   }
   if (image == 8) {
@@ -2679,8 +2680,9 @@ WR_DEVICE void wr_quad_build_rowtab(const WrTargetDesc* Tp, const WrPrim* Pp, Wr
   Q.rowtab = nullptr; Q.rowtab_rows = 0; Q.rowtab_stride = 0; Q.rowtab_y0 = 0; Q.rowtab_pad = 0;
   const int rows = P.y1 - P.y0;
   if (!T.qtab || !T.qtab_ctl || (T.qtab_pad & 1u) || rows < WR_QTAB_MIN_ROWS || Q.nseg <= 0) return;
-  const bool zw = Q.pad != 0 || (P.kind == WR_PK_TEX_QUAD && Q.base_kind == WR_PK_MIX_BLEND);
-  const int stride = zw ? 10 : (P.kind == WR_PK_TEX_QUAD ? 6 : 2);
+  const bool yuv = P.kind == WR_PK_TEX_QUAD && Q.base_kind == WR_PK_YUV;
+  const bool zw = Q.pad != 0 || (P.kind == WR_PK_TEX_QUAD && Q.base_kind == WR_PK_MIX_BLEND) || yuv;
+  const int stride = yuv ? 14 : (zw ? 10 : (P.kind == WR_PK_TEX_QUAD ? 6 : 2));
   float* tab = (float*)wr_pool_words(T, (unsigned long long)rows * (unsigned long long)stride);
   if (!tab) return;
   for (int i = 0; i < Q.nseg; i++) {          // (in order: where two runs hold a row, the later one is the one the raster stage picks)
@@ -2722,6 +2724,16 @@ WR_DEVICE void wr_quad_build_rowtab(const WrTargetDesc* Tp, const WrPrim* Pp, Wr
           wl = wl + lws; wr = wr + rws; zl = zl + lzs; zr = zr + rzs;
         }
       }
+      if (stride >= 14) {      // (a pass of its own: vUv_U's edges, summed the same way)
+        float l2u = wr_accum(Q.persp.l2u[i], Q.persp.l2us[i], ya - S.lrow), l2v = wr_accum(Q.persp.l2v[i], Q.persp.l2vs[i], ya - S.lrow);
+        float r2u = wr_accum(Q.persp.r2u[i], Q.persp.r2us[i], ya - S.rrow), r2v = wr_accum(Q.persp.r2v[i], Q.persp.r2vs[i], ya - S.rrow);
+        const float l2us = Q.persp.l2us[i], l2vs = Q.persp.l2vs[i], r2us = Q.persp.r2us[i], r2vs = Q.persp.r2vs[i];
+        float* __restrict__ e2 = tab + (size_t)(ya - P.y0) * (size_t)stride;
+        for (int y = ya; y < yb; y++, e2 += stride) {
+          e2[10] = l2u; e2[11] = l2v; e2[12] = r2u; e2[13] = r2v;
+          l2u = l2u + l2us; l2v = l2v + l2vs; r2u = r2u + r2us; r2v = r2v + r2vs;
+        }
+      }
     }
   }
   Q.rowtab_y0 = P.y0; Q.rowtab_rows = rows; Q.rowtab_stride = stride;
@@ -2745,6 +2757,25 @@ WR_DEVICE bool wr_quad_row_span(const WrQuadRec& Q, int y, int& s0, int& s1) {
     s1 = S.rmask ? int(ceilf(wr_clamp(xr + radr, S.b0, S.b1))) : int(floorf(wr_clamp(xr, S.b0, S.b1) + 0.5f));
   }
   return true;
+}
+
+// brush_yuv_image under a projective transform: the quad walk carries the luma varying, one chroma varying (l2u ..) and z / 1/w, so a
+// PLANAR prim is drawn only where vUv_V is vUv_U bit for bit (4:2:0 video whose chroma planes share one rect); NV12 / P010 have one
+static_assert(offsetof(WrQuadRec, yuv) >= sizeof(WrYuvRec), "the YUV record moves into the quad record's union: the two must not overlap");
+WR_DEVICE bool wr_yuv_persp_ok(const WrVsOut& o, const WrYuvRec& Y) {
+  if (Y.format != 3) return true;
+  bool same = true;
+  for (int n = 0; n < 4; n++) {
+    uint32_t a, b, c, e;
+    __builtin_memcpy(&a, &o.u2[n], 4); __builtin_memcpy(&b, &o.u3[n], 4); __builtin_memcpy(&c, &o.v2[n], 4); __builtin_memcpy(&e, &o.v3[n], 4);
+    same = same && a == b && c == e;
+  }
+  return same;
+}
+// `bytes` (a multiple of 4) from `src` to `dst`, word by word through a register: the regions must not overlap
+WR_DEVICE void wr_copy_words(void* dst, const void* src, int bytes) {
+  int32_t* d = (int32_t*)dst; const int32_t* s = (const int32_t*)src;
+  for (int i = 0; i < bytes / 4; i++) d[i] = s[i];
 }
 
 // draw_quad (rasterize.h:1549-1633) + the axis-aligned closed form of
@@ -2776,7 +2807,8 @@ WR_DEVICE void wr_finish_prim(const WrDrawDesc& d, int draw_index, const WrVsOut
     // (and brush_opacity, brush_blend, brush_linear_gradient: main() on the perspective-correct varying)
     const bool ptex = ((d.shader == WR_SH_PS_QUAD_TEXTURED || o.persp_div >= 0.0f) && (o.kind == WR_PK_TEX_RGBA8 || o.kind == WR_PK_TEX_FS)) ||
                       ((d.shader == WR_SH_PS_TEXT_RUN || d.shader == WR_SH_PS_TEXT_RUN_DUAL) && (o.kind == WR_PK_TEX_R8 || o.kind == WR_PK_TEX_RGBA8)) ||      /* (the GLYPH_TRANSFORM keys never reach here with a projective transform: their vertex stage reports it) */
-                      o.kind == WR_PK_FILTER || o.kind == WR_PK_MIX_BLEND || (o.kind == WR_PK_QUAD_MASK && auxp->clip.w == 1.0f) || (o.kind == WR_PK_TEX_REPEAT && o.persp_div >= 0.0f) || (o.kind == WR_PK_GRADIENT && (d.shader == WR_SH_BRUSH_LINEAR_GRADIENT || d.shader == WR_SH_BRUSH_LINEAR_GRADIENT_ALPHA ||
+                      o.kind == WR_PK_FILTER || o.kind == WR_PK_MIX_BLEND || (o.kind == WR_PK_QUAD_MASK && auxp->clip.w == 1.0f) ||
+                      (o.kind == WR_PK_YUV && inside && wr_yuv_persp_ok(o, auxp->yuv)) || (o.kind == WR_PK_TEX_REPEAT && o.persp_div >= 0.0f) || (o.kind == WR_PK_GRADIENT && (d.shader == WR_SH_BRUSH_LINEAR_GRADIENT || d.shader == WR_SH_BRUSH_LINEAR_GRADIENT_ALPHA ||
                                                                               d.shader == WR_SH_PS_QUAD_RADIAL_GRADIENT || d.shader == WR_SH_PS_QUAD_CONIC_GRADIENT));
     if (!(o.kind == WR_PK_SOLID || ptex)) { atomicAdd(&cnt->perspective_prims, 1u); return; }
     clipped = !inside;           // a vertex outside the near / far planes: clip_side first (wr_persp_clipped_walk)
@@ -2849,7 +2881,7 @@ WR_DEVICE void wr_finish_prim(const WrDrawDesc& d, int draw_index, const WrVsOut
   const bool texq = (d.flags & WR_DF_QUADS) &&
                     (o.kind == WR_PK_TEX_RGBA8 || o.kind == WR_PK_TEX_FS || o.kind == WR_PK_TEX_R8 || o.kind == WR_PK_TEX_REPEAT ||
                      o.kind == WR_PK_GRADIENT || o.kind == WR_PK_FILTER || o.kind == WR_PK_QUAD_MASK || (o.kind == WR_PK_SOLID && masked) ||
-                     o.kind == WR_PK_MIX_BLEND);
+                     o.kind == WR_PK_MIX_BLEND || o.kind == WR_PK_YUV);
   if (aa && (o.kind != WR_PK_SOLID || masked) && !texq) {      // AA on masked solids / other shader families: "next"
     P.kind = WR_PK_UNSUPPORTED; atomicAdd(&cnt->unsupported_prims, 1u); return;
   }
@@ -2859,7 +2891,7 @@ WR_DEVICE void wr_finish_prim(const WrDrawDesc& d, int draw_index, const WrVsOut
   if ((!typeA && !typeB) || (aa && texq) || persp) {
     // general convex quad (rotation / skew), or an anti-aliased textured one: the scanline walk is done here, per prim
     const bool solidq = o.kind == WR_PK_SOLID && !masked && !(d.flags & WR_DF_SIMPLE);
-    if (persp && !solidq && !(texq && (o.kind == WR_PK_TEX_RGBA8 || o.kind == WR_PK_TEX_FS || o.kind == WR_PK_TEX_R8 || o.kind == WR_PK_TEX_REPEAT || o.kind == WR_PK_FILTER || o.kind == WR_PK_GRADIENT || o.kind == WR_PK_QUAD_MASK || (o.kind == WR_PK_SOLID && masked) || o.kind == WR_PK_MIX_BLEND))) {
+    if (persp && !solidq && !(texq && (o.kind == WR_PK_TEX_RGBA8 || o.kind == WR_PK_TEX_FS || o.kind == WR_PK_TEX_R8 || o.kind == WR_PK_TEX_REPEAT || o.kind == WR_PK_FILTER || o.kind == WR_PK_GRADIENT || o.kind == WR_PK_QUAD_MASK || (o.kind == WR_PK_SOLID && masked) || o.kind == WR_PK_MIX_BLEND || o.kind == WR_PK_YUV))) {
       atomicAdd(&cnt->perspective_prims, 1u); return;
     }
     if (!solidq && !texq) {
@@ -2872,6 +2904,9 @@ WR_DEVICE void wr_finish_prim(const WrDrawDesc& d, int draw_index, const WrVsOut
     else if (o.kind == WR_PK_GRADIENT) base.grad = auxp->grad;
     else if (o.kind == WR_PK_FILTER) base.filt = auxp->filt;
     else if (o.kind == WR_PK_QUAD_MASK) base.clip = auxp->clip;
+    // (brush_yuv_image's record is moved word by word, memory to memory, into the quad record's union before the walk overwrites it: it
+    // is larger than every other base record, and held in `base` it would take the setup kernels' scratch past their budget)
+    if (o.kind == WR_PK_YUV && !clipped) wr_copy_words(&auxp->quad.yuv, &auxp->yuv, sizeof(WrYuvRec));
     int bx0, by0, bx1, by1;
     // (perspective: the edges also carry screen z and 1/w -- Point3D edges step exactly like interpolants, rasterize.h:1127-1152 --
     // the interpolants are pre-multiplied by the vertex's 1/w (:1138-1143), and draw_perspective_spans picks the same start
@@ -2886,11 +2921,15 @@ WR_DEVICE void wr_finish_prim(const WrDrawDesc& d, int draw_index, const WrVsOut
       auxp->quad.nseg = -1; auxp->quad.rowtab = nullptr; auxp->quad.rowtab_rows = 0;
       bx0 = int(cx0); by0 = int(cy0); bx1 = int(cx0) + 1; by1 = int(cy0) + 1;      // (a placeholder box: replaced by the walk's)
     }
-    else if (o.kind == WR_PK_MIX_BLEND && persp) {
+    else if ((o.kind == WR_PK_MIX_BLEND && persp) || o.kind == WR_PK_YUV) {
       // ... under a projective transform the z / w slots are taken: the second varying, divided by w like the first, on edges of its own
-      float qu2[4], qv2[4];
-      for (int n = 0; n < 4; n++) { qu2[n] = o.u2[n] * pw3[n]; qv2[n] = o.v2[n] * pw3[n]; }
-      if (!wr_quad_walk(sx, sy, qu, qv, cx0, cy0, cx1, cy1, aa, o.aa_edges, auxp->quad, bx0, by0, bx1, by1, pz3, pw3, true, qu2, qv2)) return;
+      // (brush_yuv_image: vUv_U there; vUv_V in the z / w slots of a rotated / skewed prim, the same as vUv_U under a projective one)
+      float qu2[4], qv2[4], z4[4], w4[4];
+      for (int n = 0; n < 4; n++) {
+        qu2[n] = persp ? o.u2[n] * pw3[n] : o.u2[n]; qv2[n] = persp ? o.v2[n] * pw3[n] : o.v2[n];
+        z4[n] = persp ? pz3[n] : o.u3[n]; w4[n] = persp ? pw3[n] : o.v3[n];
+      }
+      if (!wr_quad_walk(sx, sy, qu, qv, cx0, cy0, cx1, cy1, aa, o.aa_edges, auxp->quad, bx0, by0, bx1, by1, z4, w4, true, qu2, qv2)) return;
     }
     else if (o.kind == WR_PK_MIX_BLEND) {
       // brush_mix_blend's second varying (v_src_uv) rides in the walk's z / w slots

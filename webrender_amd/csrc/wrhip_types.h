@@ -589,7 +589,8 @@ struct WrQuadRec {
   // Row table (wr_quad_build_rowtab): the edge values of every target row y in [rowtab_y0, rowtab_y0 + rowtab_rows) of this prim, written
   // ONCE by the setup stage -- rowtab[(y - rowtab_y0) * rowtab_stride + ...] = x of the left and right edge (stride 2: WR_PK_SOLID_QUAD),
   // then the two interpolants of both edges (stride 6), then 1/w and z of both edges (stride 10: perspective, or brush_mix_blend's
-  // second varying) -- instead of one row-by-row sum (wr_accum) per value, lane, row and prim in the raster stage.  nullptr: no table.
+  // second varying), then brush_yuv_image's vUv_U of both edges (stride 14: WR_PK_YUV) -- instead of one row-by-row sum (wr_accum) per
+  // value, lane, row and prim in the raster stage.  nullptr: no table.
   const float* rowtab;
   int32_t rowtab_y0, rowtab_rows;
   int32_t rowtab_stride, rowtab_pad;
@@ -601,6 +602,9 @@ struct WrQuadRec {
     WrClipRec clip;                 // WR_PK_QUAD_MASK
     WrMixRec mix;                   // WR_PK_MIX_BLEND (rotations / skews only): op and the source's sample bounds; the second varying's edges
                                     // travel in `persp`'s z / w slots (z = u, w = v of v_src_uv: Point3D edges step exactly like interpolants)
+    WrYuvRec yuv;                   // WR_PK_YUV: the flat varyings and the matrix (its chroma edge fields are unused: vUv_U's edges travel in
+                                    // `persp`'s l2u .. slots, vUv_V's in its z / w slots -- rotations / skews; under a projective transform the
+                                    // z / w slots hold z and 1/w and a planar prim is drawn only where vUv_V == vUv_U)
   };
   WrPerspRec persp;                 // pad != 0: screen z and 1 / w of the runs' edges (beside the base kind's record: filters and gradients
                                     // under perspective need both)

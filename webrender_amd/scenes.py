@@ -2529,6 +2529,8 @@ def make_workload(workload, **kw):
         return cfg3_text(**kw)
     if workload == "transforms":          # wrench/benchmarks/transforms-simple.yaml (not a BASELINE config)
         return transforms_simple(**kw)
+    if workload == "video-transforms":    # rotated, skewed and perspective video (brush_yuv_image on general quads) at the 4K target
+        return video_transforms(**kw)
     if workload == "simple-batching":     # wrench/benchmarks/simple-batching.yaml at the 4K target
         return simple_batching(width=3840, height=2160, **kw)
     from . import wrench_scenes           # the rest of wrench/benchmarks/benchmarks.list
@@ -3035,9 +3037,15 @@ def quad_gradients(width=1024, height=1024, n=60, seed=181, tile_filter=None, on
 YUV_FORMAT_NV12, YUV_FORMAT_PLANAR = 0, 3
 
 
-def yuv_grid(width=1024, height=1024, n=60, seed=301, tile_filter=None, only=None, nearest=False, hdr=False, planar=True):
+def yuv_grid(width=1024, height=1024, n=60, seed=301, tile_filter=None, only=None, nearest=False, hdr=False, planar=True,
+             rotate=False, perspective=False, masked=False, force_aa=False, formats=None):
     """hdr: 10-bit video -- three R16 planes holding the low 10 bits (YUV_FORMAT_PLANAR, channel bit depth 10: the span shader
-    rescales by 6 bits) and R16 + RG16 planes with the sample in the high bits (YUV_FORMAT_P010)."""
+    rescales by 6 bits) and R16 + RG16 planes with the sample in the high bits (YUV_FORMAT_P010).
+    rotate: two alpha-pass videos in three (and every third opaque-pass one) sit under a rotation / skew about their centre (a
+    <video> under transform: rotate(..) / skew(..): the general-quad path with swgl_antiAlias on all four edges), every fourth of
+    those cut by a local clip rect; perspective: the alpha-pass ones with a projective row on top (a 3-D card; "mixed": every other one); masked: clip
+    masks on two alpha-pass videos in three; force_aa: BRUSH_FLAG_FORCE_AA on every other axis-aligned alpha-pass video;
+    formats: "planar" / "semi" draws only that layout."""
     rng = np.random.default_rng(seed)
     frame = Frame(width, height, (1.0, 1.0, 1.0, 1.0))
     A = 1024
@@ -3111,6 +3119,33 @@ def yuv_grid(width=1024, height=1024, n=60, seed=301, tile_filter=None, only=Non
         semi = (k // 2) % 2 == 1 or not planar
         spec = frame.gpu_cache.push([[depth, float((k * 3 + 1) % 7), fmt_semi if semi else float(YUV_FORMAT_PLANAR), 0.0]])
         prims.append(((px, py, px + w, py + h), spec, (ry, rc, rc, 0), False, semi))
+    if formats is not None:
+        prims = [p for p in prims if p[4] == (formats == "semi")]
+    # (rotate / perspective / masked / force_aa: per prim, a transform id, the box it can reach, a local clip rect, a clip task, brush
+    # flags; the default frame draws none of them and asks nothing more of the generator)
+    tids, bbs, lclips, clip_tasks = [0] * len(prims), [p[0] for p in prims], [(-BIG, -BIG, BIG, BIG)] * len(prims), [None] * len(prims)
+    if rotate or perspective:
+        for k, (rect, spec, ud, opaque, nv12) in enumerate(prims):
+            if (k % 3 == 1) if not opaque else (perspective or k % 3 != 0):
+                continue
+            cxx, cyy, rad = (rect[0] + rect[2]) / 2, (rect[1] + rect[3]) / 2, 0.5 * float(np.hypot(rect[2] - rect[0], rect[3] - rect[1]))
+            pk = bool(perspective) and (perspective != "mixed" or k % 2 == 0)      # "mixed": every other one projective
+            # (perspective == "clip": every other one reaches behind the camera plane -- cut by the near plane: reported, not drawn)
+            tids[k] = rotation_about(frame, rng, cxx, cyy, k, rad if pk else None,
+                                     strength=(1.1, 2.6) if (perspective == "clip" and k % 2 == 0) else (0.15, 0.6))
+            bbs[k] = rotated_bounds(rect)
+            if pk:
+                rr = rad * 2.8 + 4
+                bbs[k] = (cxx - rr, cyy - rr, cxx + rr, cyy + rr)
+            if k % 4 == 3:        # cut by the local clip rect: the cut edges are anti-aliased as well
+                lclips[k] = (rect[0] + 0.15 * (rect[2] - rect[0]), rect[1] + 0.1 * (rect[3] - rect[1]), rect[2] - 0.2 * (rect[2] - rect[0]), rect[3])
+    t_mask = None
+    if masked:
+        t_mask = TextureRef("clip_mask_atlas", 1024, 1024, G.GL_R8, G.GL_LINEAR, pixels=mask_atlas(1024), upload_format=G.GL_RED)
+        frame.static_textures.append(t_mask)
+        alpha = [k for k, p in enumerate(prims) if not p[3]]
+        for k, ct in zip(alpha, prim_clip_tasks(rng, [rotated_bounds(prims[k][0]) if tids[k] else prims[k][0] for k in alpha], 1024, True)):
+            clip_tasks[k] = ct
     targets = []
     for (tx, ty, ox, oy) in tile_grid(width, height):
         if tile_filter is not None and not tile_filter(tx, ty):
@@ -3124,17 +3159,24 @@ def yuv_grid(width=1024, height=1024, n=60, seed=301, tile_filter=None, only=Non
         for zi, (rect, spec, ud, opaque, nv12) in enumerate(prims):
             if only is not None and zi not in only:
                 continue
-            if not (rect[0] < x1 and rect[2] > x0 and rect[1] < y1 and rect[3] > y0):
+            bb = bbs[zi]
+            if not (bb[0] < x1 and bb[2] > x0 and bb[1] < y1 and bb[3] > y0):
                 continue
-            ph = frame.add_prim_header(rect, (-BIG, -BIG, BIG, BIG), zi + 1, spec, 0, task, ud)
-            inst = frame.brush_instance(ph, CLIP_TASK_EMPTY)
+            ph = frame.add_prim_header(rect, lclips[zi], zi + 1, spec, tids[zi], task, ud)
+            ct = clip_tasks[zi]
+            bf = 1024 if (force_aa and not opaque and zi % 2 == 0 and not tids[zi]) else 0      # BRUSH_FLAG_FORCE_AA
+            if tids[zi] or bf or ct is not None:
+                clip_addr = CLIP_TASK_EMPTY if ct is None else frame.add_render_task(ct[0], 1.0, ct[1])
+                inst = frame.brush_instance(ph, clip_addr, edge_flags=15, brush_flags=bf)
+            else:
+                inst = frame.brush_instance(ph, CLIP_TASK_EMPTY)
             if opaque:
                 batches.setdefault((True, nv12), []).append(inst)
             else:
                 if not order or order[-1][0] != nv12:
                     order.append((nv12, []))
                 order[-1][1].append(inst)
-        tex_of = lambda nv12: {0: t_y_msb, 1: t_uv} if nv12 else {0: t_y, 1: t_u, 2: t_v}
+        tex_of = lambda nv12, mask=False: {**({0: t_y_msb, 1: t_uv} if nv12 else {0: t_y, 1: t_u, 2: t_v}), **({9: t_mask} if mask else {})}
         for nv12 in (False, True):
             op = batches.get((True, nv12))
             if op:
@@ -3142,12 +3184,22 @@ def yuv_grid(width=1024, height=1024, n=60, seed=301, tile_filter=None, only=Non
                                           textures=tex_of(nv12)))
         for nv12, al in order:
             target.alpha.append(Step("brush_yuv_image ALPHA_PASS,TEXTURE_2D,YUV", "PRIM_INSTANCES", np.array(al, dtype=np.int32),
-                                     "PremultipliedAlpha", "alpha", textures=tex_of(nv12)))
+                                     "PremultipliedAlpha", "alpha", textures=tex_of(nv12, masked)))
         targets.append(target)
         rect = (float(x0), float(y0), float(x1), float(y1))
         clip = (float(x0), float(y0), float(min(x1, width)), float(min(y1, height)))
         frame.composite_tiles.append(CompositeTile(tex, rect, clip, opaque=True))
     frame.passes.append(targets)
+    return frame
+
+
+def video_transforms(width=3840, height=2160, n=160, seed=321, **kw):
+    """A 4K frame of video under transforms: yuv_grid's planar / NV12 frames, two alpha-pass videos in three rotated or skewed
+    (every other one of those with a projective row on top) -- the workload of `bench.py --workload video-transforms`."""
+    kw.pop("encoding", None)          # (bench.py's prim encoding: video has the brush one only)
+    kw.setdefault("rotate", True)
+    kw.setdefault("perspective", "mixed")
+    frame = yuv_grid(width=width, height=height, n=n, seed=seed, **kw)
     return frame
 
 
