@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- frames/s of the WebRender batched-primitive raster path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full]
   (N>1: launched by torch.distributed.run, one rank per GPU)
 
 A "step" is one frame: the complete C-ABI call stream WebRender's render thread
@@ -12,16 +12,22 @@ configs[1]: 1000 overlapping translucent rects at 3840x2160 ("cfg2").  At N>1
 it is configs[4] -- 100 k rects at 7680x4320 ("cfg5"), the configuration the
 tile sharding is for: one frame split N ways ("strong" scaling), the window
 reassembled on rank 0 -- the presenting GPU -- by an RCCL gather of the ranks'
-strips; the line also carries the same workload on one GPU measured in the same
-run (`single_gpu_same_workload`), the all-gather variant (every rank ends up
-with the window) and every rank's prims / upload bytes per frame.
+strips; with --full the line also carries the same workload on one GPU measured
+in the same run (`single_gpu_same_workload`), the all-gather variant (every rank
+ends up with the window) and every rank's prims / upload bytes per frame.
 
 The timed region (K frames issued back to back + one Finish, between barrier +
 synchronize) is repeated REPEATS times and the median region is reported, so a
 short driver run (--steps 20 = 2 ms of cfg2) is a steady-state number and not
 one pipeline fill.
 
-One JSON line on rank 0 with metric/value plus
+A plain run does only what the headline needs: it sets up, warms up, times the
+regions, writes --dump-outputs if asked, and prints one JSON line on rank 0
+(metric, value, ms_per_step, the regions, the configuration).  --full then runs
+the passes that each take time of their own and adds to the line
+  frame_latency_ms  mean frame time with a Finish after every frame (<= 50 frames)
+  host          the library's own phase timers over one more streamed region;
+                with the roofline pass, gpu_busy_frac and host_bound
   roofline      the DOMINANT kernel -- the raster-kernel variant with the largest
                 summed GPU time per frame: its own algorithmic bytes per launch /
                 its own average launch duration (hipEvents on the context's
@@ -34,7 +40,7 @@ One JSON line on rank 0 with metric/value plus
                 the shipping flags of swgl/build.rs) replaying the same
                 call stream on one host core, plus an N-process run (one
                 process per core, frames replayed independently) with the core
-                count stated
+                count stated; --no-cpu-baseline leaves it out
 
 --dump-outputs DIR  after the timed regions, the window the last timed frame
                 left (what a caller reads back) as DIR/*.npy: per-row channel
@@ -316,7 +322,11 @@ def main():
                     help="default: cfg2 (BASELINE configs[1], the headline) on one GPU, cfg5 (configs[4]: 100 k rects at 8K, "
                          "the configuration the tile sharding is for) on several")
     ap.add_argument("--encoding", default="quad", choices=["quad", "brush"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the passes the headline does not need: per-frame latency, the host's phase "
+                         "timers, per-kernel rooflines, the swgl CPU baseline; at N > 1 the same workload on one GPU, per-rank work and "
+                         "the all-gather variant")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the swgl CPU baseline")
     ap.add_argument("--sharded", action="store_true", help="take the N > 1 code path (sharded player, collectives) even with one rank: a self-test")
     ap.add_argument("--emulate-world", type=int, default=0, metavar="W",
                     help="on ONE GPU: every rank's share of a W-rank run (its strip's rows, its frame's uploads) timed back to back, "
@@ -365,10 +375,10 @@ def main():
     if not os.path.exists(lib):
         raise SystemExit("libwrhip.so missing; run __graft_entry__.build()")
 
-    single = None            # N > 1: the same workload unsharded on one GPU (rank 0), measured in this run: the 1-GPU point of the curve
+    single = None            # N > 1, --full: the same workload unsharded on one GPU (rank 0), measured in this run: the 1-GPU point of the curve
     if sharded:
         from webrender_amd.dist import ShardedFramePlayer
-        if rank == 0:
+        if rank == 0 and args.full:
             rec1, _ = record_scene(lib, make_frame(args.workload, encoding=args.encoding))
             p1 = ScenePlayer(lib, rec1)
             p1.frames(args.warmup, 0)
@@ -432,12 +442,13 @@ def main():
     dumped = None
     if args.dump_outputs and rank == 0:      # (read before any other pass renders the frame again)
         dumped = dump_outputs(args.dump_outputs, player.assembled() if sharded else player.read_pixels())
+    # ---- --full from here on: passes of their own after the timed regions ---------------------------------------------------
     # per-frame latency with a Finish after every frame (what `wrench perf` samples)
-    lat = player.frames(0, min(args.steps, 50))
+    lat = player.frames(0, min(args.steps, 50)) if args.full else None
 
     # ---- N > 1: per-rank work, and the same frames with the window gathered on rank 0 only ------------------------------------
     multi = None
-    if sharded:
+    if sharded and args.full:
         import ctypes as C
         import torch.distributed as dist
         st = glapi.WrhipStats()
@@ -469,7 +480,7 @@ def main():
     # ---- where the host side of a frame goes: the library's own phase timers over one more streamed region -------
     import ctypes as C
     host = None
-    if not sharded:
+    if not sharded and args.full:
         _get = C.CFUNCTYPE(None, C.c_void_p)(player.symbol("WrhipGetStats"))
         _reset = C.CFUNCTYPE(None)(player.symbol("WrhipResetStats"))
         barrier()
@@ -489,7 +500,7 @@ def main():
 
     # ---- per-kernel rooflines (separate, event-timed pass: one event pair + wait per launch) -------
     roof = None
-    if not sharded:
+    if not sharded and args.full:
         get_stats = C.CFUNCTYPE(None, C.c_void_p)(player.symbol("WrhipGetStats"))
         get_kstats = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int)(player.symbol("WrhipGetKernelStats"))
         reset = C.CFUNCTYPE(None)(player.symbol("WrhipResetStats"))
@@ -553,7 +564,6 @@ def main():
             "dtype": "u8",
             "data": "synthetic",
             "mpixels_per_s": round(fps * frame_w * frame_h / 1e6, 1),
-            "frame_latency_ms": round(float(np.mean(lat)), 4),
             "timed_regions_ms": [round(1e3 * r, 3) for r in regions],
             "config": {"workload": f"{args.workload}: " + wrench_desc.get(args.workload, "") + {
                 "cfg2": "1000 overlapping translucent rects (ps_quad_textured + premultiplied-alpha blend), "
@@ -571,14 +581,17 @@ def main():
                 "parallelism": "single GPU" if not sharded else
                 f"tile rows sharded over {world} GPUs + RCCL gather of framebuffer strips to rank 0"},
         }
+        if lat is not None:
+            out["frame_latency_ms"] = round(float(np.mean(lat)), 4)
         if multi:
             out["multi_gpu"] = multi
+        if sharded:
+            # N > 1 runs another workload than the N = 1 headline (configs[4], the one the sharding is for): the metric names it
+            out["metric"] += f" [N > 1: {args.workload}, one frame split over the ranks]"
         if single:
+            # the baseline of a strong-scaling point is the same frame on one GPU, measured in this very run
             out["single_gpu_same_workload"] = single
             out["speedup_vs_single_gpu"] = round(fps / single["value"], 3)
-            # N > 1 runs another workload than the N = 1 headline (configs[4], the one the sharding is for): the metric names it, and
-            # the baseline of a strong-scaling point is the same frame on one GPU, measured in this very run
-            out["metric"] += f" [N > 1: {args.workload}, one frame split over the ranks]"
             out["vs_baseline"] = out["speedup_vs_single_gpu"]
             out["vs_baseline_note"] = "value / single_gpu_same_workload.value (same workload, unsharded, rank 0's GPU, this run); BASELINE.md has no published number"
         out["host_affinity"] = affinity
@@ -594,7 +607,7 @@ def main():
                 out["host_work_us_per_frame"] = round(host_work, 2)
         if roof:
             out["roofline"] = roof
-        if not sharded and not args.no_cpu_baseline:
+        if not sharded and args.full and not args.no_cpu_baseline:
             cb = cpu_baseline(rec)
             if cb:
                 out["cpu_baseline"] = cb

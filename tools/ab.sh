@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT && export TMPDIR=/tmp
 w=$1; shift
 for round in 1 2 3; do
   for lib in "$@"; do
-    WRHIP_LIB_PATH=$PWD/$lib python bench.py --workload $w --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | grep metric | python3 -c "
+    WRHIP_LIB_PATH=$PWD/$lib python bench.py --full --workload $w --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | grep metric | python3 -c "
 import sys, json
 for l in sys.stdin:
     d = json.loads(l); r = d.get('roofline') or {}

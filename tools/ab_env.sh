@@ -7,7 +7,7 @@ for w in $wls; do
   for round in 1 2 3; do
     for variant in default off; do
       if [ $variant = off ]; then pre="env $envs"; else pre=""; fi
-      $pre python bench.py --workload $w --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '"metric"' | python3 -c "
+      $pre python bench.py --full --workload $w --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '"metric"' | python3 -c "
 import sys, json
 for l in sys.stdin:
     d = json.loads(l); r = d.get('roofline') or {}

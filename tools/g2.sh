@@ -4,7 +4,7 @@ WRHIP_LIB_PATH=$PWD/ab/libwrhip_timing.so WRHIP_DEBUG_COUNTERS=1 WRHIP_PRIM_TIME
 grep "dbg counters" gpurun_out/r06_i/timing_cfg2.err | tail -12
 for m in 1 2 3; do
 echo "setup mode $m"
-WRHIP_SETUP_MODE=$m WRHIP_LIB_PATH=$PWD/ab/libwrhip_timing.so python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '"metric"' | python3 -c "
+WRHIP_SETUP_MODE=$m WRHIP_LIB_PATH=$PWD/ab/libwrhip_timing.so python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '"metric"' | python3 -c "
 import sys, json
 for l in sys.stdin:
     d = json.loads(l); r = d.get('roofline') or {}

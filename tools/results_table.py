@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """usage: tools/results_table.py <tag> [dir]  -- the markdown table of a measurement pass (tools/round.sh <tag> cpu): one row per bench line
-found as <dir>/<tag>_bench_*.json (default dir: profiles/) or gpurun_out/<tag>/bench_*.json -- frames/s, the swgl CPU baseline beside it
+found as <dir>/<tag>_bench_*.json (default dir: profiles/) or $WRHIP_OUT/<tag>/bench_*.json (default out/) -- frames/s, the swgl CPU baseline beside it
 (one core / one process per core), the dominant kernel with its mean launch time and roofline fractions, host and GPU time per frame."""
 import glob, json, os, sys
 tag = sys.argv[1]
 d = sys.argv[2] if len(sys.argv) > 2 else "profiles"
-files = sorted(glob.glob(os.path.join(d, f"{tag}_bench_*.json"))) or sorted(glob.glob(os.path.join("gpurun_out", tag, "bench_*.json")))
+files = sorted(glob.glob(os.path.join(d, f"{tag}_bench_*.json"))) or sorted(glob.glob(os.path.join(os.environ.get("WRHIP_OUT", "out"), tag, "bench_*.json")))
 order = ["cfg1", "cfg2", "cfg3", "cfg4", "cfg5"]
 rows = []
 for f in files:
