@@ -232,6 +232,9 @@ typedef struct WrhipStats {
   uint64_t host_flush_ns;      /* flush: descriptor arena, staging copy, kernel launches (no waiting) */
   uint64_t host_wait_ns;       /* Finish / ReadPixels / queries: blocked on the stream               */
   uint64_t row_launches;       /* launches of the row kernels (wr_span_rows_kernel / wr_tile_rows_kernel); included in raster_launches */
+  uint64_t setup_carried;      /* flushes whose setup stage (and upload scatter) went out in a held-back raster launch of the flush before */
+  uint64_t carrier_lost;       /* flushes that planned such a carrier and found the held-back launches already gone (0 unless broken) */
+  uint64_t scratch_grown_held; /* scratch buffers of a flush replaced while the launches of the flush before were held back */
 } WrhipStats;
 void WrhipGetStats(WrhipStats* out);
 void WrhipResetStats(void);

@@ -1,13 +1,18 @@
 """Pipelined-sequence sweep (test infrastructure, not collected by pytest): random sequences of 6-15 frames from a menu of fifteen scenes
 streamed without a Finish in between (harness.render_pipelined), every frame against the oracle's render of that scene alone.
-python tests/sweep_pipelined.py <rng seed> <iterations>"""
+--streamed: harness.render_streamed instead -- no blit between the frames, so that every flush can hand its setup stage to the
+held-back launches of the one before (the blit drains them); only the last frame of a sequence is seen, every prefix is checked.
+python tests/sweep_pipelined.py [--streamed] <rng seed> <iterations>"""
 import os, sys, hashlib
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from conftest import hostsim_lib, oracle_ref
 from webrender_amd import scenes
-from webrender_amd.harness import render_direct, render_pipelined
+from webrender_amd.harness import render_direct, render_pipelined, render_streamed
+streamed = "--streamed" in sys.argv
+if streamed:
+    sys.argv.remove("--streamed")
 hs, orc = hostsim_lib(), oracle_ref("gcc")
 W = dict(width=512, height=512)
 MENU = [
@@ -47,6 +52,12 @@ rng = np.random.default_rng(int(sys.argv[1]))
 bad = 0
 for it in range(int(sys.argv[2])):
     seq = [int(rng.choice(ok)) for _ in range(int(rng.integers(6, 16)))]
+    if streamed:
+        for n in range(1, len(seq) + 1):
+            g, st = render_streamed(hs, [MENU[i]() for i in seq[:n]])
+            if not np.array_equal(g, want[seq[n - 1]]) or st["carrier_lost"]:
+                bad += 1; print("iter", it, "seq", seq[:n], "last frame differs" if st["carrier_lost"] == 0 else "carrier lost", flush=True)
+        continue
     got = render_pipelined(hs, [MENU[i]() for i in seq])
     for k, (g, i) in enumerate(zip(got, seq)):
         if not np.array_equal(g[..., [2, 1, 0, 3]], want[i]):

@@ -725,3 +725,58 @@ def test_hip_text_reftests_full_4k(name, _small, kw):
             assert np.array_equal(got[k], want[k]), k
     else:
         assert np.array_equal(got, want)
+
+
+# ---- frames streamed through the fused setup launch (tests/test_stream_parity.py on the device) ----
+# The host simulation runs launches one after the other; only the device shows whether a carrier's first workgroups (upload scatter,
+# setup stage) have finished before its raster body, and the launches after it, use what they wrote.
+from stream_cases import GROWTH as STREAM_GROWTH, UPLOAD_CARRY, NEW_STATIC, MENU as STREAM_MENU, DEVICE_INEXACT, random_sequences, carriers_expected, check_streamed  # noqa: E402
+
+_STREAM_FIXED = STREAM_GROWTH + [UPLOAD_CARRY, NEW_STATIC]
+
+
+def _stream_oracle():
+    ref = oracle_ref()
+    if not ref:
+        pytest.skip("oracle not built")
+    return ref
+
+
+@pytest.mark.parametrize("name,make", _STREAM_FIXED, ids=[c[0] for c in _STREAM_FIXED])
+def test_hip_streamed_sequences_match_oracle(name, make):
+    check_streamed(wrhip_lib(), _stream_oracle(), make())
+
+
+_STREAM_SWEEP = random_sequences(seed=2027, count=40)
+
+
+def test_hip_streamed_random_sequences_match_oracle():
+    """40 sequences of 4-10 menu frames, streamed; every sequence's last frame against the oracle -- or, for the frames the device
+    does not draw bit for bit like it (DEVICE_INEXACT), against the device's render of that frame alone (all sequences run, then
+    the differing ones are listed)."""
+    ref = _stream_oracle()
+    bad = []
+    for k, seq in enumerate(_STREAM_SWEEP):
+        try:
+            check_streamed(wrhip_lib(), wrhip_lib() if seq[-1] in DEVICE_INEXACT else ref, [STREAM_MENU[i]() for i in seq],
+                           carried=carriers_expected(seq))
+        except AssertionError as e:
+            bad.append((k, seq, str(e)[:300]))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("mode", ["readback", "wrap", "realloc", "pool"])
+def test_hip_staging_mirror_views_and_pool_word(mode):
+    """tests/test_stream_parity.py's early batch closes (draws recorded on mirror views, the ring then lapped or reallocated) and
+    stale pool word, on the device (1 MB ring, one subprocess each)."""
+    import subprocess
+    import sys
+    from stream_driver import frame_for
+    want, _ = render_direct(_stream_oracle(), frame_for(mode))
+    e = dict(os.environ, WRHIP_STAGING_BYTES=str(1 << 20))
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "stream_driver.py"), wrhip_lib(), mode], env=e, capture_output=True,
+                       text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    got = json.loads(p.stdout.strip().splitlines()[-1])
+    assert "pool ran out" not in p.stderr, p.stderr[-2000:]
+    assert got["gl_error"] == 0 and got["digest"] == digest(want), got

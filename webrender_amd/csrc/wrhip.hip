@@ -504,6 +504,11 @@ struct Context {
   uint64_t lap_ns[8] = {0, 0, 0, 0, 0, 0, 0, 0}; uint64_t lap_n = 0;      // WRHIP_DEBUG_LAPS=1: where flush_work's time goes (printed at context destruction)
   uint64_t upload_batch = 1;      // id of the open (or next) batch: Texture::up_batch / view_batch compare with it
   bool scatter_first = false;     // a recorded draw's setup stage reads a data texture the open batch writes PARTLY: the scatter has to precede it
+  // Data textures that recorded draws may read in the staging mirror (the open batch uploads them whole).  The draws keep the
+  // texture's own address; flush_work turns it into the mirror view only if that batch is still open when the draws are flushed --
+  // a batch closed earlier (a readback of another texture, a ring wrap or reallocation) has been scattered already, and its staging
+  // bytes are reused once the ring laps them, while the draws are still waiting for their flush.
+  std::vector<GLuint> view_texs;
   struct PendingScatter { size_t seg_off = 0; int nseg = 0, parts = 0; uint64_t bytes = 0; bool valid = false; } ps;   // a batch's scatter handed to the flush's setup-carrying launch
   bool fuse_scatter = true;       // WRHIP_NO_FUSE_SCATTER=1: the scatter keeps its own launch
   uint8_t* dupload = nullptr;     // HBM mirror of the staging ring
@@ -605,6 +610,7 @@ struct Context {
                                        // re-running a flush whose targets load their old content is not idempotent), up to 4 GB of the 288
   unsigned long long* last_qctl = nullptr;     // the most recent flush's pool word (in the staging mirror) and the capacity it was given
   size_t last_qtab_cap = 0;
+  uint64_t last_qctl_v = 0;            // ... its virtual ring address: once the ring may reuse it (ring_safe beyond it, a new ring) it is dropped unread
   bool cell_raster = true;             // WRHIP_NO_CELLS=1: rect-only bins always take the pixel walk
   bool thin_r8 = true;                 // WRHIP_NO_THIN=1: small R8 launches keep the 4-wave workgroup shape
   int thin_parts = 4;                  // workgroups per bin of a thin launch (WRHIP_THIN_PARTS = 1, 2, 4, 8, 16): 16 / parts waves each, so that a wave shares its SIMD with fewer others
@@ -757,6 +763,13 @@ const size_t STAGING_BYTES_DEFAULT = size_t(96) << 20;
 static size_t staging_bytes() { static const size_t v = getenv("WRHIP_STAGING_BYTES") ? std::max<size_t>(1 << 16, (size_t)atoll(getenv("WRHIP_STAGING_BYTES"))) : STAGING_BYTES_DEFAULT; return v; }
 bool ring_make_safe(uint64_t need_v, bool may_drain);
 
+// The ring may now overwrite what lies below ring_safe: a pool word there (Finish reads it, Context::last_qctl) would be read
+// as whatever lands on it next -- it is given up instead (the flush it belonged to is long done; its share stays as it was).
+void ring_retired() {
+  Context* c = ctx;
+  if (c->last_qctl && c->last_qctl_v < c->ring_safe) c->last_qctl = nullptr;
+}
+
 // Make the virtual addresses below `need_v` of the staging ring reusable.  `may_drain`: fall back to draining the stream when no
 // recorded fence frees them (false: report failure instead -- flush_uploads asks from inside a batch).
 bool ring_make_safe(uint64_t need_v, bool may_drain) {
@@ -770,12 +783,14 @@ bool ring_make_safe(uint64_t need_v, bool may_drain) {
     HostTimer ht(&c->stats.host_wait_ns);
     wrrt::event_sync(&c->ring_fence[k % Context::RING_FENCES].ev);
     c->ring_safe = prev.v;
+    ring_retired();
     return true;
   }
   if (!may_drain) return false;
   flush_uploads(771);                  // (what is staged goes out, then everything enqueued completes)
   sync_stream();
   c->ring_safe = c->ring_base + c->staging_pos;
+  ring_retired();
   return true;
 }
 // End of a flush: the fence that (once the NEXT one has completed) frees what was shipped up to here.
@@ -808,6 +823,7 @@ size_t staging_alloc(size_t n) {
     c->dupload = (uint8_t*)wrrt::dev_alloc(c->staging_size);
     c->staging_pos = 0;
     c->ring_base = c->ring_safe = 0; c->ring_fences = 0;      // (a new ring: nothing in flight refers to it)
+    c->last_qctl = nullptr;
   }
   if (c->staging_pos + n > c->staging_size) {
     flush_uploads(808);                // the pending batch must stay contiguous
@@ -1452,6 +1468,14 @@ void sync_stream() {
   HostTimer ht(&ctx->stats.host_wait_ns);
   wrrt::stream_sync(ctx->stream);
 }
+// Before flush_work replaces buffers of its scratch set (flush_seq & 1): their last readers, the launches of the flush two back, went out
+// with the flush before and have to complete.  The held-back launches of the flush before read the OTHER set: they stay held, and can
+// still carry this flush's setup stage.
+void sync_scratch() {
+  if (ctx->tail.pending) ctx->stats.scratch_grown_held++;
+  HostTimer ht(&ctx->stats.host_wait_ns);
+  wrrt::stream_sync(ctx->stream);
+}
 
 // Forwarded composites.  A target whose pending work is [full clear,] N draws of `composite FAST_PATH` that each copy a whole
 // RGBA8 target of the same flush, unblended, texel for pixel (integer placement, optional y flip through the projection),
@@ -1839,7 +1863,7 @@ void flush_work(const std::vector<int>& sel_in) {
     // the prim arrays of this flush's scratch set, sized here: the address of its glyph records goes into the target descriptors
     Context::Scratch& S = c->scratch[c->flush_seq & 1];
     if (S.prims_cap < (size_t)n_prims + 1) {
-      sync_stream();       // (drains the tail: nothing in flight references the buffers being replaced)
+      sync_scratch();
       wrrt::dev_free(S.prims); wrrt::dev_free(S.recs); wrrt::dev_free(S.aux);
       S.prims_cap = (size_t)(n_prims + 1) * 2;
       S.prims = (WrPrim*)wrrt::dev_alloc(S.prims_cap * sizeof(WrPrim));
@@ -1847,7 +1871,7 @@ void flush_work(const std::vector<int>& sel_in) {
       S.aux = (WrAux*)wrrt::dev_alloc(S.prims_cap * sizeof(WrAux));
     }
     if (S.bin_ctr_cap < (size_t)n_bins || !S.bin_ctr) {
-      sync_stream();
+      sync_scratch();
       wrrt::dev_free(S.bin_ctr);
       S.bin_ctr_cap = (size_t)std::max(n_bins, 64) * 2;
       S.bin_ctr = (unsigned*)wrrt::dev_alloc(S.bin_ctr_cap * sizeof(unsigned));
@@ -1857,10 +1881,26 @@ void flush_work(const std::vector<int>& sel_in) {
     // row tables (<= 64 MB), and the depth runs' share (WRHIP_RUNS_POOL_WORDS, 64 MB by default)
     const size_t qtab_want = gtab_words + std::min<size_t>(qtab_need, (size_t)16 << 20) + (runs_pool ? runs_pool_words : 0);
     if (S.qtab_cap < qtab_want) {
-      sync_stream();
+      sync_scratch();
       wrrt::dev_free(S.qtab);
       S.qtab_cap = qtab_want + qtab_want / 4;
       S.qtab = (float*)wrrt::dev_alloc(S.qtab_cap * sizeof(float));
+    }
+    // ... and the vertex tables and coverage masks: the set's buffers are all sized before the flush picks a held-back launch to
+    // carry its setup stage and defers its upload scatter to it (fuse_at, below)
+    if (S.vtab_cap < vtab_cursor + 1 || S.masks_cap < (size_t)n_words + 1) {
+      sync_scratch();
+      if (S.vtab_cap < vtab_cursor + 1) {
+        wrrt::dev_free(S.vtab);
+        S.vtab_cap = (vtab_cursor + 1) * 2;
+        S.vtab = (float*)wrrt::dev_alloc(S.vtab_cap * sizeof(float));
+      }
+      if (S.masks_cap < (size_t)n_words + 1) {
+        wrrt::dev_free(S.masks);
+        S.masks_cap = (size_t)(n_words + 1) * 2;
+        S.masks = (unsigned long long*)wrrt::dev_alloc(S.masks_cap * 8);
+        wrrt::memset8(S.masks, 0, S.masks_cap * 8, c->stream);   // raster workgroups re-zero what they consume
+      }
     }
     for (WrTargetDesc& T : targets) {
       T.grecs = (const WrGlyphRec*)(S.recs + S.prims_cap); T.bin_ctr = S.bin_ctr + T.first_bin;
@@ -1878,7 +1918,7 @@ void flush_work(const std::vector<int>& sel_in) {
     const size_t want_slots = (size_t)std::min<uint64_t>(mr_slots, WR_MR_MAX_SLOTS);
     const size_t want_bytes = (size_t)std::min<uint64_t>(mr_bytes, mr_safe ? kCap : ((uint64_t)256 << 20));
     if (S.mr_slots_cap < want_slots || S.mr_store_cap < want_bytes) {
-      sync_stream();
+      sync_scratch();
       if (S.mr_slots_cap < want_slots) {
         wrrt::dev_free(S.mr_slots);
         S.mr_slots_cap = std::min<size_t>(want_slots * 2, WR_MR_MAX_SLOTS);
@@ -1902,7 +1942,7 @@ void flush_work(const std::vector<int>& sel_in) {
   if (flat_words && any_work && !no_flat) {
     Context::Scratch& S = c->scratch[c->flush_seq & 1];
     if (S.flat_cap < flat_words) {
-      sync_stream();
+      sync_scratch();
       wrrt::dev_free(S.flat);
       S.flat_cap = flat_words * 2;
       S.flat = (uint32_t*)wrrt::dev_alloc(S.flat_cap * 4);
@@ -1927,6 +1967,15 @@ void flush_work(const std::vector<int>& sel_in) {
     size_t total = off_mrctl + 512 + 256;
     size_t aoff = staging_alloc(total);
     uint8_t* h = c->staging + aoff;
+    // (the last call that can close the open batch before this flush ships it: the mirror views are decided here)
+    for (GLuint id : c->view_texs) {
+      Texture* t = c->textures.find(id);
+      if (!t || !t->dptr || !c->upload_open || t->view_batch != c->upload_batch) continue;
+      const void* view = c->dupload + t->view_off;
+      for (WrDrawDesc& d : draws)
+        for (WrTexDesc& td : d.tex) if (td.ptr == t->dptr) td.ptr = view;
+    }
+    c->view_texs.clear();
     memset(h + off_qctl, 0, 64 + 512);
     if (mr_on) {
       Context::Scratch& Sm = c->scratch[c->flush_seq & 1];
@@ -1936,7 +1985,7 @@ void flush_work(const std::vector<int>& sel_in) {
     *(unsigned long long*)(h + off_qctl) = (unsigned long long)gtab_words;      // (WR_GTAB_WORDS is a multiple of 4: the pieces behind stay on 16 bytes)
     for (WrTargetDesc& T : targets) T.qtab_ctl = T.qtab ? (unsigned long long*)(c->dupload + aoff + off_qctl) : nullptr;
     c->last_qctl = nullptr;
-    for (const WrTargetDesc& T : targets) if (T.qtab) { c->last_qctl = T.qtab_ctl; c->last_qtab_cap = T.qtab_cap; break; }
+    for (const WrTargetDesc& T : targets) if (T.qtab) { c->last_qctl = T.qtab_ctl; c->last_qtab_cap = T.qtab_cap; c->last_qctl_v = c->ring_base + aoff + off_qctl; break; }
     if (nd) stage_copy(h + off_draws, draws.data(), sizeof(WrDrawDesc) * nd);
     stage_copy(h + off_targets, targets.data(), sizeof(WrTargetDesc) * n_targets);
     if (inst_bytes >= PARALLEL_COPY_MIN && inst_segs.size() > 1) {
@@ -1987,22 +2036,8 @@ void flush_work(const std::vector<int>& sel_in) {
     c->stats.h2d_bytes += total;
     algo_bytes += inst_bytes + sizeof(WrDrawDesc) * nd;
     lap(2);      // DMA + scatter queued
-    // ---- scratch (two sets: the deferred tail of the previous flush still reads the other one) ----
+    // ---- scratch (two sets: the deferred tail of the previous flush still reads the other one; vtab / masks: sized above) ----
     Context::Scratch& S = c->scratch[c->flush_seq & 1];
-    if (S.vtab_cap < vtab_cursor + 1 || S.masks_cap < (size_t)n_words + 1) {      // (prims / recs / aux: sized above)
-      sync_stream();       // (drains the tail: nothing in flight references the buffers being replaced)
-      if (S.vtab_cap < vtab_cursor + 1) {
-        wrrt::dev_free(S.vtab);
-        S.vtab_cap = (vtab_cursor + 1) * 2;
-        S.vtab = (float*)wrrt::dev_alloc(S.vtab_cap * sizeof(float));
-      }
-      if (S.masks_cap < (size_t)n_words + 1) {
-        wrrt::dev_free(S.masks);
-        S.masks_cap = (size_t)(n_words + 1) * 2;
-        S.masks = (unsigned long long*)wrrt::dev_alloc(S.masks_cap * 8);
-        wrrt::memset8(S.masks, 0, S.masks_cap * 8, c->stream);   // raster workgroups re-zero what they consume
-      }
-    }
 #ifdef WRHIP_HOSTSIM
     wrrt::memset8(S.masks, 0, (size_t)n_words * 8, c->stream);
 #endif
@@ -2031,6 +2066,12 @@ void flush_work(const std::vector<int>& sel_in) {
         drain_tail();                                            // the previous flush's raster launches, concurrently
         wrrt::stream_wait_event(c->stream, &c->ev_setup);
       } else {
+      if (fuse_at >= 0 && !(c->tail.pending && fuse_at < (int)c->tail.held.size())) {
+        // the carrier is gone (something drained the tail after fuse_at was chosen): the setup stage and the deferred scatter go
+        // out on their own, below -- a launch more, never a flush whose setup stage did not run
+        c->stats.carrier_lost++;
+        fuse_at = -1;
+      }
       if (fuse_at >= 0) {
         // the previous flush's held-back raster launches, in order; the first one the fused kernel has a
         // variant for (normally the tile pass, the longest) carries this flush's setup stage along
@@ -2042,9 +2083,11 @@ void flush_work(const std::vector<int>& sel_in) {
           carried += c->ps.bytes;
           c->ps.valid = false;
         }
+        c->stats.setup_carried++;
         launch_held(T.held, T.targets, T.n_targets, T.draws, c->scratch[T.set], fuse_at, &SA, n_setup_blocks, carried);
         tail_launched();
       } else {
+        launch_pending_scatter();      // (the setup stage reads the data textures it uploads)
         prof_begin();
         WR_LAUNCH(wr_setup_kernel, n_setup_blocks, 256, c->stream, ddraws, nd_arg, dinst, S.prims, S.recs, S.aux, n_prims,
                   dtargets, S.masks, S.vtab, c->dcounters, dblk);
@@ -2056,11 +2099,12 @@ void flush_work(const std::vector<int>& sel_in) {
     } else {
       drain_tail();
     }
-    launch_pending_scatter();      // (nothing is pending unless a carrier was planned and not used)
+    launch_pending_scatter();      // (nothing is pending here: a deferred scatter went out with its carrier or ahead of the setup stage)
     lap(3);      // setup + held launches queued
 #ifdef WRHIP_HOSTSIM
     if (getenv("WRHIP_DEBUG")) {
-      fprintf(stderr, "flush: targets %d draws %d prims %d bins %d words %d\n", n_targets, nd, n_prims, n_bins, n_words);
+      fprintf(stderr, "flush: targets %d draws %d prims %d bins %d words %d vtab %zu set %d carried %llu grown_held %llu\n", n_targets, nd, n_prims, n_bins,
+              n_words, vtab_cursor, (int)(c->flush_seq & 1), (unsigned long long)c->stats.setup_carried, (unsigned long long)c->stats.scratch_grown_held);
       for (int i = 0; i < n_targets; i++)
         fprintf(stderr, "  T%d %dx%d fmt %d load %d init %08x prims [%d,%d) wpb %d\n", i, targets[i].width, targets[i].height,
                 targets[i].format, targets[i].load_color, targets[i].init_color, targets[i].first_prim, targets[i].end_prim,
@@ -2192,6 +2236,7 @@ void flush_work(const std::vector<int>& sel_in) {
   for (GLuint id : c->referenced)
     if (Texture* t = c->textures.find(id)) { t->pending_read = t->pending_write = false; t->pending_target = -1; }
   c->referenced.clear();
+  c->view_texs.clear();
   for (size_t i = 0; i < c->work.size(); i++) {
     mark_ref(c->work[i].tex, c->textures[c->work[i].tex], true, (int)i);
     for (GLuint id : c->work[i].reads) if (Texture* t = c->textures.find(id)) mark_ref(id, *t, false);
@@ -3102,8 +3147,9 @@ void DrawElementsInstanced(GLenum mode, GLsizei count, GLenum type, GLintptr off
     // which runs beside it in the same launch.  A texture the open batch uploads whole is read in the staging mirror (same layout,
     // alive as long as the flush's arena); one it writes in part keeps the scatter in front of the setup stage.
     if (!((rmask >> s) & 1) && c->upload_open && t->up_batch == c->upload_batch) {
-      if (t->view_batch == c->upload_batch && c->fuse_scatter) td.ptr = c->dupload + t->view_off;
-      else {
+      if (t->view_batch == c->upload_batch && c->fuse_scatter) {
+        if (std::find(c->view_texs.begin(), c->view_texs.end(), tid) == c->view_texs.end()) c->view_texs.push_back(tid);
+      } else {
         static const bool dbg = getenv("WRHIP_DEBUG_SCATTER") != nullptr;
         if (dbg && !c->scatter_first) fprintf(stderr, "scatter first: slot %d texture %u %dx%d fmt %x (the open batch writes it in part)\n", s, tid, t->width, t->height, t->internal_format);
         c->scatter_first = true;
@@ -3246,7 +3292,8 @@ void Finish(void) {
       wrrt::d2h(&asked, ctx->last_qctl, sizeof(asked), ctx->stream);
       sync_stream();
       ctx->last_qctl = nullptr;
-      if (asked > (unsigned long long)ctx->last_qtab_cap) {
+      // (a count of more words than the device has memory is not one a flush asked for: it is ignored, not turned into growth)
+      if (asked > (unsigned long long)ctx->last_qtab_cap && asked <= (1ull << 36)) {
         const unsigned long long extra = asked - ctx->last_qtab_cap;
         const size_t want = std::min<size_t>(((size_t)1 << 30) - ((size_t)80 << 20), ctx->runs_pool_words + (size_t)(extra + extra / 4) + ((size_t)1 << 20));
         if (want > ctx->runs_pool_words) {

@@ -120,3 +120,25 @@ def render_pipelined(backend_path, frames):
     out = [d.read_texture(k) for k in keepers]
     r.destroy()
     return out
+
+
+def render_streamed(backend_path, frames):
+    """Render `frames` (same window size) back to back through one Renderer with nothing between them that drains the
+    backend's held-back raster launches -- no Finish, readback, blit or query -- then one Finish: the window (RGBA8, as
+    render_direct returns it), which shows the LAST frame, and the backend's statistics (libwrhip; None otherwise).
+    This is the path a frame loop takes: every flush's setup stage and upload scatter ride in the first workgroups of a
+    raster launch the flush before held back (WrhipStats::setup_carried)."""
+    gl = GL(backend_path)
+    w, h = frames[0].width, frames[0].height
+    r = Renderer(gl, w, h)
+    for f in frames:
+        assert (f.width, f.height) == (w, h), "render_streamed: one window size"
+        r.render(f)
+    r.finish()
+    err = gl.GetError()
+    px = r.read_pixels()
+    stats = gl.stats() if gl.is_wrhip else None
+    if stats is not None:
+        stats["gl_error"] = int(err)
+    r.destroy()
+    return px, stats
