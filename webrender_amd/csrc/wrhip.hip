@@ -722,6 +722,7 @@ int wr_format(GLenum f) {
     case GL_R16: return WR_FMT_R16;
     case GL_RG16: return WR_FMT_RG16;
     case GL_DEPTH_COMPONENT24: return WR_FMT_DEPTH24;
+    case GL_RGB_RAW_422_APPLE: return WR_FMT_YUY2;
     default: return WR_FMT_NONE;
   }
 }

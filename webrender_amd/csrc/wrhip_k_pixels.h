@@ -477,7 +477,7 @@ __device__ __noinline__ unsigned long long wr_quad_tex_pixel_rgba8(const WrPrim*
       const float cu = qu * wq, cv = qv * wq;
       float fs[3] = {0.f, 0.f, 0.f};
       wr_yuv_main_sample(t, 0, wr_clamp(pu * wq, Pl.uv_bounds[0], Pl.uv_bounds[2]), wr_clamp(pv * wq, Pl.uv_bounds[1], Pl.uv_bounds[3]), fs);
-      wr_yuv_main_sample(D->tex[WR_S_COLOR1], 1, wr_clamp(cu, Y.u_bounds[0], Y.u_bounds[2]), wr_clamp(cv, Y.u_bounds[1], Y.u_bounds[3]), fs);
+      if (Y.format != 4) wr_yuv_main_sample(D->tex[WR_S_COLOR1], 1, wr_clamp(cu, Y.u_bounds[0], Y.u_bounds[2]), wr_clamp(cv, Y.u_bounds[1], Y.u_bounds[3]), fs);      // (interleaved: sColor0 alone)
       if (Y.format == 3) wr_yuv_main_sample(D->tex[WR_S_COLOR2], 2, wr_clamp(cu, Y.v_bounds[0], Y.v_bounds[2]), wr_clamp(cv, Y.v_bounds[1], Y.v_bounds[3]), fs);
       src = wr_yuv_main_rgb(Y, fs, (Pl.flags & WR_PF_TAIL_MODULATE) != 0);
     } else {
@@ -1446,6 +1446,48 @@ __device__ __noinline__ WrWide wr_svg_filter_pixel(const WrPrim* Pp, const WrSvg
 // sample_yuv (yuv.glsl:187-237) in float.
 WR_DEVICE int wr_sat16(int v) { return v > 32767 ? 32767 : (v < -32768 ? -32768 : v); }
 WR_DEVICE int wr_wrap16(int v) { return (int)(int16_t)v; }
+// An interleaved 4:2:2 texture (YUY2, GL_RGB_RAW_422_APPLE): two-pixel chunks of four bytes, Y0 Cb Y1 Cr; offsets and the stride count
+// 16-bit units (one per pixel), a chunk starts on an even one.
+struct WrYuv3 { int y, u, v; };
+struct WrYuy2Pair { uint32_t c0, c1; };      // two adjacent chunks of one row: g0 b g1 r | G0 B G1 R (4-byte aligned, one 8-byte load)
+// textureLinearPlanarYUY2 (texture.h:877-949) for ONE pixel, (qx, qy) the quantised coordinate (x 128) after the LINEAR_QUANTIZE_UV
+// clamp: the row pair blended first, then the columns, a + (((b - a) * f) >> 7) in 16-bit lanes.  Luma goes g0 -> g1 or g1 -> G0 by
+// the pixel's place in its chunk (the selector), chroma (b, r) -> (B, R) of the next chunk with half the luma's fraction.
+// The reads stay inside the texture: computeRow's margin of 2 clamps the column to width - 3, the chunk it lies in starts at most at
+// column width - 4 (wr_yuv_planes_ok: the width is even and >= 4), so the 8 bytes end with the row; the stride is 2 * width bytes (even
+// in 16-bit units, the selector is the column's parity), the second row is row + 1 only while row < height - 1 -- on the last chunk
+// of the last row both loads end on the allocation's last byte, and nothing reads past them.
+__device__ __noinline__ WrYuv3 wr_yuy2_linear(const WrTexDesc* tp, int qx, int qy) {
+  const WrTexDesc& t = *tp;
+  const int ix = qx >> 7, iy = qy >> 7;
+  const size_t row = (size_t)wr_clamp_coord(ix, t.width - 2) + (size_t)wr_clamp_coord(iy, t.height) * t.stride;      // computeRow(sampler, i, 2)
+  const int sel = int(row & 1);
+  const size_t row0 = row & ~size_t(1), row1 = row0 + ((iy >= 0 && iy < t.height - 1) ? t.stride : 0);
+  const int fx = ix >= 0 ? qx : 0;                      // frac.x &= (i.x >= 0)
+  const int over = ix > t.width - 3 ? -1 : 0;           // both fractions saturate where the next chunk would lie outside
+  const int fracl = (fx | over) & 0x7F, fracc = ((fx >> 1) | over) & 0x7F, fracy = qy & 0x7F;
+  const uint16_t* buf = (const uint16_t*)t.ptr;
+  const WrYuy2Pair a = *(const WrYuy2Pair*)(buf + row0), b = *(const WrYuy2Pair*)(buf + row1);
+  auto rows = [&](uint32_t wa, uint32_t wb, int k) -> int {
+    const int p = int((wa >> (8 * k)) & 0xFF), q = int((wb >> (8 * k)) & 0xFF);
+    return wr_wrap16(p + wr_wrap16(wr_wrap16((q - p) * fracy) >> 7));
+  };
+  auto cols = [](int p, int q, int f) -> int { return wr_wrap16(p + wr_wrap16(wr_wrap16((q - p) * f) >> 7)); };
+  const int g1 = rows(a.c0, b.c0, 2);
+  WrYuv3 s;
+  s.y = sel ? cols(g1, rows(a.c1, b.c1, 0), fracl) : cols(rows(a.c0, b.c0, 0), g1, fracl);
+  s.u = cols(rows(a.c0, b.c0, 1), rows(a.c1, b.c1, 1), fracc);
+  s.v = cols(rows(a.c0, b.c0, 3), rows(a.c1, b.c1, 3), fracc);
+  return s;
+}
+// texelFetchYUY2 (texture.h:192-214): texel (x, y), clamped by the caller -- the chunk it lies in, luma by the selector
+WR_DEVICE WrYuv3 wr_yuy2_fetch(const WrTexDesc& t, int x, int y) {
+  const size_t off = (size_t)x + (size_t)y * t.stride;
+  const uint32_t c = *(const uint32_t*)((const uint16_t*)t.ptr + (off & ~size_t(1)));
+  WrYuv3 s;
+  s.y = int(((off & 1) ? c >> 16 : c) & 0xFF); s.u = int((c >> 8) & 0xFF); s.v = int(c >> 24);
+  return s;
+}
 WR_DEVICE WrWide wr_yuv_convert(const WrYuvRec& Y, int y, int u, int v) {
   // yy = (u16(y) * yCoeffs) >> 1 (16-bit wrap), - yBias; uv - uvBias; br = addsat(yy & mask, coeff * uv) >> 6;
   // gg = addsat(yy, addsat(gu * u, gv * v)) >> 6; pack with unsigned saturation, alpha 255
@@ -1572,10 +1614,15 @@ WR_DEVICE bool wr_yuv_rect_span_pixel(const WrPrim* Pp, const WrYuvRec& Y, const
   return true;
 }
 
-// main()'s sample of one plane (sample_yuv: TEX_SAMPLE of the clamped uv) as floats in fs[pl] (RG planes: fs[1], fs[2])
+// main()'s sample of one plane (sample_yuv: TEX_SAMPLE of the clamped uv) as floats in fs[pl] (RG planes: fs[1], fs[2]; the one
+// interleaved plane: all three)
 WR_DEVICE void wr_yuv_main_sample(const WrTexDesc& t, int pl, float cu, float cv, float (&fs)[3]) {
   const float W = t.sw, H = t.sh;
-  if (t.format == WR_FMT_R16 || t.format == WR_FMT_RG16) {      // textureLinearR16 / RG16: sample * (1 / 32767)
+  if (t.format == WR_FMT_YUY2) {      // texture(sColor0, uv).gbr: textureLinearYUY2 (texture.h:951-959) / texelFetchYUY2, (y, cb, cr) * (1 / 255)
+    const WrYuv3 s = t.linear ? wr_yuy2_linear(&t, int(cu * W * 128.0f + (0.5f - 64.0f)), int(cv * H * 128.0f + (0.5f - 64.0f)))
+                              : wr_yuy2_fetch(t, wr_clamp_coord(int(cu * W), t.width), wr_clamp_coord(int(cv * H), t.height));
+    fs[0] = float(s.y) * (1.0f / 255.0f); fs[1] = float(s.u) * (1.0f / 255.0f); fs[2] = float(s.v) * (1.0f / 255.0f);
+  } else if (t.format == WR_FMT_R16 || t.format == WR_FMT_RG16) {      // textureLinearR16 / RG16: sample * (1 / 32767)
     int v4[4] = {0, 0, 0, 0};
     const int iqx = int(cu * W * 128.0f + (0.5f - 64.0f)), iqy = int(cv * H * 128.0f + (0.5f - 64.0f));
     if (t.format == WR_FMT_RG16) { wr_bilinear16<2>(t, iqx, iqy, v4); fs[1] = float(v4[0]) * (1.0f / 32767.0f); fs[2] = float(v4[1]) * (1.0f / 32767.0f); }
@@ -1605,7 +1652,7 @@ WR_DEVICE WrWide wr_yuv_main_rgb(const WrYuvRec& Y, const float (&fs)[3], bool c
 __device__ __noinline__ WrWide wr_yuv_pixel(const WrPrim* Pp, const WrYuvRec* Yp, const WrDrawDesc* D, int x, int y, const WrRuns* runs = nullptr,
                                             const float* row = nullptr) {
   const WrYuvRec& Y = *Yp;
-  const int planes = Y.format == 3 ? 3 : 2;
+  const int planes = Y.format == 3 ? 3 : (Y.format == 4 ? 1 : 2);      // (YUV_FORMAT_INTERLEAVED: blendYUV's one-sampler overload, swgl_ext.h:1027-1047)
   bool all_linear = true;
   for (int pl = 0; pl < planes; pl++) all_linear = all_linear && D->tex[WR_S_COLOR0 + pl].linear != 0;
   if ((D->flags & WR_DF_TEX_RECT) && planes == 3 && all_linear) {
@@ -1631,7 +1678,12 @@ __device__ __noinline__ WrWide wr_yuv_pixel(const WrPrim* Pp, const WrYuvRec* Yp
       const float minx = wr_max(P2.uv_bounds[0] * W * qs + qo, 0.0f), miny = wr_max(P2.uv_bounds[1] * H * qs + qo, 0.0f);
       const float maxx = wr_max(P2.uv_bounds[2] * W * qs + qo, minx), maxy = wr_max(P2.uv_bounds[3] * H * qs + qo, miny);
       int v4[4];
-      if (t.format == WR_FMT_R16 || t.format == WR_FMT_RG16) {
+      if (t.format == WR_FMT_YUY2) {
+        // (the same stepping; sampleYUV's one-sampler overload hands textureLinearPlanarYUY2's lanes to the matrix as (y, u, v))
+        const int c = n >> 2, k = n & 3;
+        const WrYuv3 s = wr_yuy2_linear(&t, int(wr_clamp(wr_accum(q[k], stepx, c), minx, maxx)), int(wr_clamp(wr_accum(qy[k], stepy, c), miny, maxy)));
+        sample[0] = s.y; sample[1] = s.u; sample[2] = s.v;
+      } else if (t.format == WR_FMT_R16 || t.format == WR_FMT_RG16) {
         // (blendYUV's stepping, as wr_linear_span_pixel's fallback does it; the samples shifted down to the matrix's 8 + rescale bits)
         const int c = n >> 2, k = n & 3;
         const int iqx = int(wr_clamp(wr_accum(q[k], stepx, c), minx, maxx)), iqy = int(wr_clamp(wr_accum(qy[k], stepy, c), miny, maxy));

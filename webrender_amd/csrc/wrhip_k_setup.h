@@ -672,10 +672,12 @@ WR_DEVICE void wr_yuv_setup(WrYuvRec& Y, int depth, int color_space, int format)
 }
 
 // The plane layouts the YUV span shader has a sampler for (sampleYUV, swgl_ext.h:1050-1150): three R8 or three R16 planes
-// (YUV_FORMAT_PLANAR), R8 + RG8 (NV12) or R16 + RG16 (P010, 16-bit NV12); 16-bit planes linear-filtered.  The interleaved (YUY2)
-// format and anything else is reported.
+// (YUV_FORMAT_PLANAR), R8 + RG8 (NV12) or R16 + RG16 (P010, 16-bit NV12); 16-bit planes linear-filtered; one 8-bit YUY2 texture
+// (YUV_FORMAT_INTERLEAVED, sampleYUV's one-sampler overload :1007-1025) of an even width >= 4 -- what wr_yuy2_linear's chunk-pair
+// reads need to stay inside it.  NV16 (no branch in the reference's vertex stage or span shader) and anything else is reported.
 WR_DEVICE bool wr_yuv_planes_ok(const WrDrawDesc& d, int format, int depth) {
   const WrTexDesc& t0 = d.tex[WR_S_COLOR0]; const WrTexDesc& t1 = d.tex[WR_S_COLOR1]; const WrTexDesc& t2 = d.tex[WR_S_COLOR2];
+  if (format == 4) return t0.ptr && t0.format == WR_FMT_YUY2 && depth == 8 && (t0.width & 1) == 0 && t0.width >= 4;
   if (!t0.ptr || !t1.ptr) return false;
   if (depth != 8 && depth != 10 && depth != 12 && depth != 16) return false;
   const bool wide = t0.format == WR_FMT_R16;
@@ -1066,8 +1068,8 @@ WR_DEVICE void wr_vs_brush(const WrDrawDesc& d, const uint8_t* arena, int inst, 
     o.tail_clamp = 1;
     o.tail_modulate = d.shader == WR_SH_BRUSH_YUV_ALPHA ? 1 : 0;      // (here: main() clamps the rgb to [0, 1] -- the ALPHA_PASS key, yuv.glsl:231-235)
     o.has_color = 0; o.color = wf4{1.f, 1.f, 1.f, 1.f};
-    // (the interleaved format: reported; rotations, skews, swgl_antiAlias and projective transforms: the general-quad path of
-    // wr_finish_prim, which reports what it cannot draw -- video cut by the near plane)
+    // (rotations, skews, swgl_antiAlias and projective transforms: the general-quad path of wr_finish_prim, which reports what it
+    // cannot draw -- video cut by the near plane; a layout without a sampler -- NV16 -- is reported here)
     bool fmt_ok = planes > 0 && wr_yuv_planes_ok(d, format, depth);
     if (wr_yuv_rect_fast_path(d, format)) fmt_ok = false;
     o.kind = fmt_ok ? WR_PK_YUV : WR_PK_UNSUPPORTED;

@@ -28,7 +28,8 @@ enum WrSlot {
 
 enum WrTexFormat {  // texture.h TextureFormat
   WR_FMT_NONE = 0, WR_FMT_RGBA32F, WR_FMT_RGBA32I, WR_FMT_RGBA8, WR_FMT_R8,
-  WR_FMT_RG8, WR_FMT_R16, WR_FMT_RG16, WR_FMT_DEPTH24
+  WR_FMT_RG8, WR_FMT_R16, WR_FMT_RG16, WR_FMT_DEPTH24,
+  WR_FMT_YUY2       // GL_RGB_RAW_422_APPLE: two-pixel chunks Y0 Cb Y1 Cr, 2 bytes per pixel; WrTexDesc::stride in 16-bit units
 };
 
 // Shader programs known to the backend.  Keys are the "name FEATURES" strings

@@ -3033,8 +3033,27 @@ def quad_gradients(width=1024, height=1024, n=60, seed=181, tile_filter=None, on
 # brush_yuv_image: video frames as YUV planes (batch.rs:2301-2390 YuvImage prims; shade.rs brush_yuv_image).  One R8 texture per
 # plane for YUV_FORMAT_PLANAR (chroma at half resolution, 4:2:0), an R8 luma + an RG8 interleaved chroma texture for
 # YUV_FORMAT_NV12.  The brush's gpu-cache block is YuvImageData (prim_store/image.rs write_prim_gpu_blocks): [channel bit depth,
-# YuvRangedColorSpace, YuvFormat, 0]; prim_user_data = the planes' ImageSource addresses.
-YUV_FORMAT_NV12, YUV_FORMAT_PLANAR = 0, 3
+# YuvRangedColorSpace, YuvFormat, 0]; prim_user_data = the planes' ImageSource addresses.  YUV_FORMAT_INTERLEAVED: one packed 4:2:2
+# texture (YuvData::InterleavedYCbCr -- GL_RGB_RAW_422_APPLE, uploaded as GL_RGB_422_APPLE / GL_UNSIGNED_SHORT_8_8_REV_APPLE), one
+# image source.
+YUV_FORMAT_NV12, YUV_FORMAT_PLANAR, YUV_FORMAT_INTERLEAVED = 0, 3, 4
+
+
+def pack_yuy2(ypl, cb, cr):
+    """[h, w] luma and [h, w / 2] chroma (4:2:2: halved horizontally, full height) -> [h, w, 2] bytes, Y0 Cb Y1 Cr per pixel pair"""
+    h, w = ypl.shape
+    assert w % 2 == 0 and cb.shape == (h, w // 2) and cr.shape == (h, w // 2)
+    out = np.empty((h, w, 2), np.uint8)
+    out[..., 0] = ypl
+    out[:, 0::2, 1] = cb
+    out[:, 1::2, 1] = cr
+    return out
+
+
+def yuy2_texture(name, ypl, cb, cr, filt):
+    h, w = ypl.shape
+    return TextureRef(name, w, h, G.GL_RGB_RAW_422_APPLE, filt, pixels=pack_yuy2(ypl, cb, cr), upload_format=G.GL_RGB_422_APPLE,
+                      upload_type=G.GL_UNSIGNED_SHORT_8_8_REV_APPLE)
 
 
 def yuv_grid(width=1024, height=1024, n=60, seed=301, tile_filter=None, only=None, nearest=False, hdr=False, planar=True,
@@ -3045,7 +3064,11 @@ def yuv_grid(width=1024, height=1024, n=60, seed=301, tile_filter=None, only=Non
     <video> under transform: rotate(..) / skew(..): the general-quad path with swgl_antiAlias on all four edges), every fourth of
     those cut by a local clip rect; perspective: the alpha-pass ones with a projective row on top (a 3-D card; "mixed": every other one); masked: clip
     masks on two alpha-pass videos in three; force_aa: BRUSH_FLAG_FORCE_AA on every other axis-aligned alpha-pass video;
-    formats: "planar" / "semi" draws only that layout."""
+    formats: "planar" / "semi" draws only that layout; "interleaved": every video from one packed 4:2:2 (YUY2) atlas instead --
+    the same 8-bit pattern, the chroma at full height; every other video's uv rect starts one column in (an odd x origin: the
+    sampler's second-pixel-of-a-chunk branch), every third one's ends a column early, and one more video lies in the atlas's
+    last columns and rows."""
+    interleaved = formats == "interleaved"
     rng = np.random.default_rng(seed)
     frame = Frame(width, height, (1.0, 1.0, 1.0, 1.0))
     A = 1024
@@ -3066,6 +3089,32 @@ def yuv_grid(width=1024, height=1024, n=60, seed=301, tile_filter=None, only=Non
         x += w
         shelf = max(shelf, h)
     filt = G.GL_NEAREST if nearest else G.GL_LINEAR
+    t_yuy2 = None
+    if interleaved:
+        assert not hdr, "interleaved video is 8-bit"
+        # (a generator of its own, and image sources pushed only here: the frames of the other layouts keep every draw and address)
+        rng2 = np.random.default_rng([seed, 422])
+        cb, cr = np.repeat(upl, 2, axis=0), np.repeat(vpl, 2, axis=0)
+        cb[1::2] ^= rng2.integers(0, 64, size=cb[1::2].shape, dtype=np.uint8)
+        cr[1::2] ^= rng2.integers(0, 64, size=cr[1::2].shape, dtype=np.uint8)
+        y422 = ypl.copy()
+        cw, ch = 90, 62               # the corner video: its uv rect ends on the texture's last column and last row
+        assert y + shelf <= A - ch
+        y422[A - ch:, A - cw:] = rng2.integers(0, 256, size=(ch, cw), dtype=np.uint8)
+        cb[A - ch:, (A - cw) // 2:] = rng2.integers(0, 256, size=(ch, cw // 2), dtype=np.uint8)
+        cr[A - ch:, (A - cw) // 2:] = rng2.integers(0, 256, size=(ch, cw // 2), dtype=np.uint8)
+        t_yuy2 = yuy2_texture("yuv_interleaved", y422, cb, cr, filt)
+        rects = []
+        x = y = shelf = 0
+        for i, (w, h, _, _) in enumerate(videos):
+            if x + w > A:
+                x, y, shelf = 0, y + shelf, 0
+            rects.append((x + (i % 2), y, x + w - (1 if i % 3 == 2 else 0), y + h))
+            x += w
+            shelf = max(shelf, h)
+        rects[5] = (A - cw, A - ch, A, A)
+        rects[8] = (A - cw + 1, A - ch, A, A)
+        videos = [(r[2] - r[0], r[3] - r[1], frame.gpu_cache.push([list(r), [0.0, 0.0, 0.0, 0.0]]), 0) for r in rects]
     if hdr:
         # 10-bit samples: the 8-bit pattern extended by two random low bits
         ext = lambda p: (p.astype(np.uint16) << 2) | rng.integers(0, 4, size=p.shape).astype(np.uint16)
@@ -3078,6 +3127,8 @@ def yuv_grid(width=1024, height=1024, n=60, seed=301, tile_filter=None, only=Non
         t_uv = TextureRef("p010_plane_uv", A // 2, A // 2, G.GL_RG16, filt, pixels=np.ascontiguousarray(np.stack([u10 << 6, v10 << 6], axis=2).astype(np.uint16)),
                           upload_format=G.GL_RG, upload_type=US)
         frame.static_textures += [t_y, t_u, t_v, t_y_msb, t_uv]
+    elif interleaved:
+        frame.static_textures.append(t_yuy2)
     else:
         t_y = TextureRef("yuv_plane_y", A, A, G.GL_R8, filt, pixels=ypl, upload_format=G.GL_RED)
         t_u = TextureRef("yuv_plane_u", A // 2, A // 2, G.GL_R8, filt, pixels=upl, upload_format=G.GL_RED)
@@ -3086,6 +3137,7 @@ def yuv_grid(width=1024, height=1024, n=60, seed=301, tile_filter=None, only=Non
         t_uv = TextureRef("yuv_plane_uv", A // 2, A // 2, G.GL_RG8, filt, pixels=np.ascontiguousarray(np.stack([upl, vpl], axis=2)), upload_format=G.GL_RG)
         frame.static_textures += [t_y, t_u, t_v, t_uv]
     depth, fmt_semi = (10.0, 1.0) if hdr else (8.0, float(YUV_FORMAT_NV12))      # (YUV_FORMAT_P010 = 1)
+    fmt_of = (lambda semi: float(YUV_FORMAT_INTERLEAVED)) if interleaved else (lambda semi: fmt_semi if semi else float(YUV_FORMAT_PLANAR))
     prims = []         # (rect, brush data address, user data, opaque pass, nv12)
     band, gx, k = 200, 4.0, 0
     while True:        # opaque-pass videos on a disjoint grid in the top band (see image_grid)
@@ -3096,7 +3148,8 @@ def yuv_grid(width=1024, height=1024, n=60, seed=301, tile_filter=None, only=Non
             break
         off = 0.37 if k % 5 == 1 else 0.0
         semi = k % 2 == 1 or not planar          # (planar=False: two-plane frames only -- NV12 / P010)
-        spec = frame.gpu_cache.push([[depth, float(k % 7), fmt_semi if semi else float(YUV_FORMAT_PLANAR), 0.0]])
+        semi = semi and not interleaved
+        spec = frame.gpu_cache.push([[depth, float(k % 7), fmt_of(semi), 0.0]])
         prims.append(((gx + off, 4.0 + off, gx + off + w, 4.0 + off + h), spec, (ry, rc, rc, 0), True, semi))
         gx += float(np.ceil(w)) + 6.0
         k += 1
@@ -3117,9 +3170,10 @@ def yuv_grid(width=1024, height=1024, n=60, seed=301, tile_filter=None, only=Non
             w, h = vw * float(rng.uniform(0.3, 1.7)), vh * float(rng.uniform(0.3, 1.7))
             px, py = float(rng.uniform(0, width - w)), float(rng.uniform(band, height - h))
         semi = (k // 2) % 2 == 1 or not planar
-        spec = frame.gpu_cache.push([[depth, float((k * 3 + 1) % 7), fmt_semi if semi else float(YUV_FORMAT_PLANAR), 0.0]])
+        semi = semi and not interleaved
+        spec = frame.gpu_cache.push([[depth, float((k * 3 + 1) % 7), fmt_of(semi), 0.0]])
         prims.append(((px, py, px + w, py + h), spec, (ry, rc, rc, 0), False, semi))
-    if formats is not None:
+    if formats is not None and not interleaved:
         prims = [p for p in prims if p[4] == (formats == "semi")]
     # (rotate / perspective / masked / force_aa: per prim, a transform id, the box it can reach, a local clip rect, a clip task, brush
     # flags; the default frame draws none of them and asks nothing more of the generator)
@@ -3176,7 +3230,8 @@ def yuv_grid(width=1024, height=1024, n=60, seed=301, tile_filter=None, only=Non
                 if not order or order[-1][0] != nv12:
                     order.append((nv12, []))
                 order[-1][1].append(inst)
-        tex_of = lambda nv12, mask=False: {**({0: t_y_msb, 1: t_uv} if nv12 else {0: t_y, 1: t_u, 2: t_v}), **({9: t_mask} if mask else {})}
+        tex_of = lambda nv12, mask=False: {**({0: t_yuy2} if interleaved else {0: t_y_msb, 1: t_uv} if nv12 else {0: t_y, 1: t_u, 2: t_v}),
+                                           **({9: t_mask} if mask else {})}
         for nv12 in (False, True):
             op = batches.get((True, nv12))
             if op:
@@ -3203,10 +3258,12 @@ def video_transforms(width=3840, height=2160, n=160, seed=321, **kw):
     return frame
 
 
-def yuv_composites(width=1024, height=768, seed=311, nearest=False, planar=True):
+def yuv_composites(width=1024, height=768, seed=311, nearest=False, planar=True, formats=None):
     """Video surfaces composited straight into the window ("composite TEXTURE_2D,YUV": composite.rs ExternalSurfaceDependency::Yuv,
     renderer/mod.rs:3335-3420): planar and NV12 frames, every colour space, 1:1 / scaled / clipped / flipped, opaque and
-    (premultiplied-alpha blended) on top of a picture-cache tile."""
+    (premultiplied-alpha blended) on top of a picture-cache tile.  formats="interleaved": every surface one packed 4:2:2 (YUY2)
+    texture instead, the sub-rect case from an odd column to the texture's last column and row."""
+    interleaved = formats == "interleaved"
     rng = np.random.default_rng(seed)
     frame = Frame(width, height, (0.2, 0.3, 0.4, 1.0))
     filt = G.GL_NEAREST if nearest else G.GL_LINEAR
@@ -3217,7 +3274,14 @@ def yuv_composites(width=1024, height=768, seed=311, nearest=False, planar=True)
         ypl = ((xx * 255 // (w - 1)) ^ rng.integers(0, 64, size=(h, w))).astype(np.uint8)
         upl, vpl = rng.integers(0, 256, size=(h // 2, w // 2), dtype=np.uint8), rng.integers(0, 256, size=(h // 2, w // 2), dtype=np.uint8)
         t_y = TextureRef(f"video{i}_y", w, h, G.GL_R8, filt, pixels=ypl, upload_format=G.GL_RED)
-        if i % 2 == 0 and planar:
+        if interleaved:
+            rng2 = np.random.default_rng([seed, 422, i])
+            cb, cr = np.repeat(upl, 2, axis=0), np.repeat(vpl, 2, axis=0)
+            cb[1::2] ^= rng2.integers(0, 64, size=cb[1::2].shape, dtype=np.uint8)
+            cr[1::2] ^= rng2.integers(0, 64, size=cr[1::2].shape, dtype=np.uint8)
+            planes = [yuy2_texture(f"video{i}_yuy2", ypl, cb, cr, filt)]
+            fmt = YUV_FORMAT_INTERLEAVED
+        elif i % 2 == 0 and planar:
             planes = [t_y, TextureRef(f"video{i}_u", w // 2, h // 2, G.GL_R8, filt, pixels=upl, upload_format=G.GL_RED),
                       TextureRef(f"video{i}_v", w // 2, h // 2, G.GL_R8, filt, pixels=vpl, upload_format=G.GL_RED)]
             fmt = YUV_FORMAT_PLANAR
@@ -3234,6 +3298,8 @@ def yuv_composites(width=1024, height=768, seed=311, nearest=False, planar=True)
     ]
     for k, (vi, x, y, sx, sy, flip, sub) in enumerate(cases):
         w, h, planes, fmt = vids[vi]
+        if sub and interleaved:
+            sub = (float(w) - 81.0, float(h) - 64.0, float(w), float(h))
         sr = sub or (0.0, 0.0, float(w), float(h))
         dw, dh = (sr[2] - sr[0]) * sx, (sr[3] - sr[1]) * sy
         rect = (x, y, x + dw, y + dh)
