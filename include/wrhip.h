@@ -235,6 +235,9 @@ typedef struct WrhipStats {
   uint64_t setup_carried;      /* flushes whose setup stage (and upload scatter) went out in a held-back raster launch of the flush before */
   uint64_t carrier_lost;       /* flushes that planned such a carrier and found the held-back launches already gone (0 unless broken) */
   uint64_t scratch_grown_held; /* scratch buffers of a flush replaced while the launches of the flush before were held back */
+  uint64_t forwarded_targets;  /* targets whose finished pixels were also stored through to the target an opaque 1:1 composite copies them to */
+  uint64_t cell_bins;          /* bins launched on the rect-only RGBA8 raster variant with the cell raster on: each that starts from a clear
+                                  goes through wr_raster_cells (0 in the host simulation, which has no cell raster) */
 } WrhipStats;
 void WrhipGetStats(WrhipStats* out);
 void WrhipResetStats(void);

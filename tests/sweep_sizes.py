@@ -1,5 +1,6 @@
 """Target-size sweep (test infrastructure, not collected by pytest): twelve families at random odd target sizes (520..1500 x 520..1100) and
-random seeds, hostsim library against the oracle.  python tests/sweep_sizes.py <rng seed> <iterations>"""
+random seeds, drawn into picture-cache tiles of a random size (32..1100 x 32..600, scenes.tile_size), hostsim library against the oracle.
+python tests/sweep_sizes.py <rng seed> <iterations>"""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -26,12 +27,14 @@ rng = np.random.default_rng(int(sys.argv[1]))
 bad = 0
 for it in range(int(sys.argv[2])):
     w = int(rng.integers(520, 1500)); h = int(rng.integers(520, 1100)); s = int(rng.integers(1, 1 << 20))
+    tw = int(rng.integers(32, 1101)); th = int(rng.integers(32, 601))
     for name, mk in F.items():
         try:
-            want, _ = render_direct(orc, mk(s, w, h)); got, st = render_direct(hs, mk(s, w, h))
+            with scenes.tile_size(tw, th):
+                want, _ = render_direct(orc, mk(s, w, h)); got, st = render_direct(hs, mk(s, w, h))
         except Exception as e:
-            print(name, s, w, h, type(e).__name__, str(e)[:100], flush=True); continue
+            print(name, s, w, h, f"tiles {tw}x{th}", type(e).__name__, str(e)[:100], flush=True); continue
         d = int((got != want).sum())
         if d or st["gl_error"]:
-            bad += 1; print(f"{name} seed {s} {w}x{h}: {d} bytes differ, gl_error {st['gl_error']:#x}", flush=True)
+            bad += 1; print(f"{name} seed {s} {w}x{h} tiles {tw}x{th}: {d} bytes differ, gl_error {st['gl_error']:#x}", flush=True)
 print("bad", bad)

@@ -1442,6 +1442,9 @@ void launch_raster(const Context::Held& H, const WrTargetDesc* targets, int n_ta
   prof_end(thin_wgs ? (fused ? 13 : 12) : fused ? (H.dense ? 7 : 6) : (H.dense ? 5 : 2), H.fmt, H.depth, H.feat, H.algo_bytes + (fused ? setup_bytes : 0),
            thin_wgs ? thin_wgs : (uint64_t)H.nb + (fused ? n_setup_blocks : 0));
   c->stats.kernel_launches++; c->stats.raster_launches++;
+#ifndef WRHIP_HOSTSIM
+  if (H.fmt == WR_FMT_RGBA8 && H.feat == 0 && c->cell_raster) c->stats.cell_bins += (uint64_t)H.nb;      // (wr_raster_body's CELLS instantiations)
+#endif
 }
 // A flush's raster launches in order; runs of chainable() launches of one variant (only the first may have mask rows: its rows
 // launch goes ahead of the chain) leave as one launch.  `fuse_at`: the launch that carries the next flush's setup stage.
@@ -1708,6 +1711,7 @@ void flush_work(const std::vector<int>& sel_in) {
     T.fwd_color = nullptr;
     if (w.fwd_tex) {
       Texture& ft = c->textures[w.fwd_tex];
+      c->stats.forwarded_targets++;
       T.fwd_color = ft.dptr; T.fwd_stride = ft.stride; T.fwd_dx = w.fwd_dx; T.fwd_y0 = w.fwd_y0; T.fwd_ys = w.fwd_ys;
       for (int k = 0; k < 4; k++) T.fwd_clip[k] = w.fwd_clip[k];
     }

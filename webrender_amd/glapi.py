@@ -144,7 +144,7 @@ class WrhipStats(C.Structure):
         "flushes", "kernel_launches", "raster_launches", "raster_ns",
         "raster_algo_bytes", "raster_pixels", "prims", "h2d_bytes", "d2h_bytes",
         "host_record_ns", "host_upload_ns", "host_flush_ns", "host_wait_ns", "row_launches",
-        "setup_carried", "carrier_lost", "scratch_grown_held")]
+        "setup_carried", "carrier_lost", "scratch_grown_held", "forwarded_targets", "cell_bins")]
 
 
 class WrhipKernelStat(C.Structure):

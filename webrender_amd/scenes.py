@@ -13,6 +13,7 @@ render target with its own picture task (task_rect at the texture origin,
 content_origin = tile origin), and only primitives intersecting a tile are
 batched into it (command_buffer.rs / batch.rs:813-).
 """
+import contextlib
 import os
 import numpy as np
 from . import glconst as G
@@ -21,6 +22,20 @@ from .frame import (Frame, Target, Step, TextureRef, CompositeTile,
 
 TILE_W, TILE_H = 1024, 512
 BIG = 1.0e16  # "no clip" sentinel the batcher uses (LayoutRect::max_rect analog)
+
+
+@contextlib.contextmanager
+def tile_size(w, h):
+    """Builders called inside draw into picture-cache tiles of w x h instead of 1024x512 (scrollbar tiles are 1024x32 and
+    32x1024, picture.rs:273-284; the tests use it for targets that are no multiple of the raster's 64-px bin).  Every builder
+    reads TILE_W / TILE_H when it is called; the previous size is back on exit, also when the body raises."""
+    global TILE_W, TILE_H
+    saved = TILE_W, TILE_H
+    TILE_W, TILE_H = int(w), int(h)
+    try:
+        yield
+    finally:
+        TILE_W, TILE_H = saved
 
 
 def tile_grid(width, height):
@@ -866,11 +881,19 @@ def clip_rect_instance(task_rect, screen_origin, dps, local_pos, size, radii, mo
     return inst
 
 
-def clip_masks(n=24, atlas=1024, seed=31, dps=1.0, window=(256, 256)):
+def _pinned_to_corner(atlas, x, y, shelf, tw, th):
+    """origin of a tw x th task rect that ends at (atlas, atlas), behind a shelf packer's cursor (x, y) and open shelf"""
+    px, py = atlas - tw, atlas - th
+    assert px >= 0 and py >= 0 and (py >= y + shelf + 4 or (py >= y and px >= x)), "pin_corner: the atlas is full"
+    return px, py
+
+
+def clip_masks(n=24, atlas=1024, seed=31, dps=1.0, window=(256, 256), pin_corner=False):
     """`n` rounded-rect mask tasks in one R8 alpha target: even tasks have a
     uniform radius (FAST_PATH program), odd ones four different elliptical
     corners (general program); a third of them clip-out; some are followed by a
-    second clip multiplied on top (draw_clip_batch_list, renderer/mod.rs:3564-3640)."""
+    second clip multiplied on top (draw_clip_batch_list, renderer/mod.rs:3564-3640).
+    pin_corner: the last task sits against the atlas's right and bottom edges (its rect ends at (atlas, atlas))."""
     rng = np.random.default_rng(seed)
     frame = Frame(window[0], window[1], (1.0, 1.0, 1.0, 1.0))
     t_mask = TextureRef("clip_masks", atlas, atlas, G.GL_R8, G.GL_LINEAR, render_target=True)
@@ -887,6 +910,8 @@ def clip_masks(n=24, atlas=1024, seed=31, dps=1.0, window=(256, 256)):
         th = int(np.ceil(h * dps)) + int(rng.integers(-12, 13))
         if x + tw + 4 > atlas:
             x, y, shelf = 4, y + shelf + 4, 0
+        if pin_corner and k == n - 1:
+            x, y = _pinned_to_corner(atlas, x, y, shelf, tw, th)
         task = (float(x), float(y), float(x + tw), float(y + th))
         x += tw + 4
         shelf = max(shelf, th)
@@ -942,7 +967,8 @@ def blurred_shadow_tile(size, radius, sigma, rng):
     return np.clip(img * 255.0 + 0.5, 0, 255).astype(np.uint8)
 
 
-def box_shadow_masks(n=16, atlas=1024, seed=41, dps=1.0, window=(256, 256)):
+def box_shadow_masks(n=16, atlas=1024, seed=41, dps=1.0, window=(256, 256), pin_corner=False):
+    """pin_corner: the last task sits against the atlas's right and bottom edges (its rect ends at (atlas, atlas))."""
     rng = np.random.default_rng(seed)
     frame = Frame(window[0], window[1], (1.0, 1.0, 1.0, 1.0))
     cache = np.zeros((512, 512), np.uint8)
@@ -974,6 +1000,8 @@ def box_shadow_masks(n=16, atlas=1024, seed=41, dps=1.0, window=(256, 256)):
         th = int(np.ceil(h * dps)) + int(rng.integers(-10, 11))
         if x + tw + 4 > atlas:
             x, y, shelf = 4, y + shelf + 4, 0
+        if pin_corner and k == n - 1:
+            x, y = _pinned_to_corner(atlas, x, y, shelf, tw, th)
         task = (float(x), float(y), float(x + tw), float(y + th))
         x += tw + 4
         shelf = max(shelf, th)
@@ -1234,7 +1262,7 @@ def cfg4_box_shadow(width=3840, height=2160, dps=1.0, n_shadows=1, tile_filter=N
 COPY_DTYPE = np.dtype([("src", "<f4", (4,)), ("dst", "<f4", (4,)), ("size", "<f4", (2,))])
 
 
-def texture_cache_copies(n=60, seed=191, src_size=512, dst_size=768, chained=True):
+def texture_cache_copies(n=60, seed=191, src_size=512, dst_size=768, chained=True, pin_corner=False):
     """`n` copies out of an RGBA8 and an R8 source atlas into cache textures of another size (later copies overwrite earlier
     ones where they overlap); `chained`: a second pass copies out of the first pass' destination (a cache texture that is
     defragmented right after it was filled)."""
@@ -1255,6 +1283,8 @@ def texture_cache_copies(n=60, seed=191, src_size=512, dst_size=768, chained=Tru
                 w, h = int(r.integers(1, 4)), int(r.integers(1, 4))            # glyph-sized
             sx, sy = int(r.integers(0, src_w - w + 1)), int(r.integers(0, src_w - h + 1))
             dx, dy = int(r.integers(0, dst_w - w + 1)), int(r.integers(0, dst_w - h + 1))
+            if pin_corner and i == k - 1:      # the last copy: from the source's last columns and rows to the destination's
+                sx, sy, dx, dy = src_w - w, src_w - h, dst_w - w, dst_w - h
             inst["src"][i] = (sx, sy, sx + w, sy + h)
             inst["dst"][i] = (dx, dy, dx + w, dy + h)
             inst["size"][i] = (dst_w, dst_w)
@@ -2552,7 +2582,7 @@ SEG_TL, SEG_TR, SEG_BR, SEG_BL, SEG_LEFT, SEG_TOP, SEG_RIGHT, SEG_BOTTOM = range
 BORDER_STYLE_SOLID = 1
 
 
-def border_solid(n=40, seed=131, atlas=1024):
+def border_solid(n=40, seed=131, atlas=1024, pin_corner=False):
     rng = np.random.default_rng(seed)
     frame = Frame(atlas, atlas, (1.0, 1.0, 1.0, 1.0))
     t_cache = TextureRef("border_cache", atlas, atlas, G.GL_RGBA8, G.GL_LINEAR, render_target=True)
@@ -2560,12 +2590,20 @@ def border_solid(n=40, seed=131, atlas=1024):
     inst = []
     x = y = shelf = 2
 
+    pinned = None       # (pin_corner: the rect of the first task of a whole number of pixels, against the atlas's right and bottom edges)
+
     def place(w, h):
-        nonlocal x, y, shelf
+        nonlocal x, y, shelf, pinned
+        whole = w == np.ceil(w) and h == np.ceil(h)
         w, h = int(np.ceil(w)), int(np.ceil(h))
+        if pin_corner and pinned is None and whole:
+            pinned = (atlas - w, atlas - h)
+            return (float(pinned[0]), float(pinned[1]))
         if x + w + 2 > atlas:
             x, y, shelf = 2, y + shelf + 2, 0
         if y + h + 2 > atlas:
+            return None
+        if pinned and x + w + 2 > pinned[0] and y + h + 2 > pinned[1]:
             return None
         o = (float(x), float(y))
         x += w + 2
@@ -2668,7 +2706,7 @@ BS_NONE, BS_SOLID, BS_DOUBLE, BS_DOTTED, BS_DASHED, BS_HIDDEN, BS_GROOVE, BS_RID
 CLIP_NONE, CLIP_DASH_CORNER, CLIP_DASH_EDGE, CLIP_DOT = range(4)
 
 
-def border_segments(n=60, seed=141, atlas=1024):
+def border_segments(n=60, seed=141, atlas=1024, pin_corner=False):
     rng = np.random.default_rng(seed)
     frame = Frame(atlas, atlas, (1.0, 1.0, 1.0, 1.0))
     t_cache = TextureRef("border_cache", atlas, atlas, G.GL_RGBA8, G.GL_LINEAR, render_target=True)
@@ -2676,12 +2714,20 @@ def border_segments(n=60, seed=141, atlas=1024):
     inst = []
     x = y = shelf = 2
 
+    pinned = None       # (pin_corner: the rect of the first task of a whole number of pixels, against the atlas's right and bottom edges)
+
     def place(w, h):
-        nonlocal x, y, shelf
+        nonlocal x, y, shelf, pinned
+        whole = w == np.ceil(w) and h == np.ceil(h)
         w, h = int(np.ceil(w)), int(np.ceil(h))
+        if pin_corner and pinned is None and whole:
+            pinned = (atlas - w, atlas - h)
+            return (float(pinned[0]), float(pinned[1]))
         if x + w + 2 > atlas:
             x, y, shelf = 2, y + shelf + 2, 0
         if y + h + 2 > atlas:
+            return None
+        if pinned and x + w + 2 > pinned[0] and y + h + 2 > pinned[1]:
             return None
         o = (float(x), float(y))
         x += w + 2
@@ -2800,19 +2846,27 @@ RGRAD_DTYPE = np.dtype([("task", "<f4", (4,)), ("center", "<f4", (2,)), ("scale"
                         ("extend", "<i4"), ("addr", "<i4")])
 
 
-def cache_decorations(n_lines=60, n_grads=40, n_lgrads=30, n_rgrads=0, n_cgrads=0, seed=151, atlas=1024):
+def cache_decorations(n_lines=60, n_grads=40, n_lgrads=30, n_rgrads=0, n_cgrads=0, seed=151, atlas=1024, pin_corner=False):
     rng = np.random.default_rng(seed)
     frame = Frame(atlas, atlas, (1.0, 1.0, 1.0, 1.0))
     t_cache = TextureRef("decoration_cache", atlas, atlas, G.GL_RGBA8, G.GL_LINEAR, render_target=True)
     tgt = Target(t_cache, "texture_cache", clear_color=(0.0, 0.0, 0.0, 0.0))
     x = y = shelf = 2
 
+    pinned = None       # (pin_corner: the rect of the first task of a whole number of pixels, against the atlas's right and bottom edges)
+
     def place(w, h):
-        nonlocal x, y, shelf
+        nonlocal x, y, shelf, pinned
+        whole = w == np.ceil(w) and h == np.ceil(h)
         w, h = int(np.ceil(w)), int(np.ceil(h))
+        if pin_corner and pinned is None and whole:
+            pinned = (atlas - w, atlas - h)
+            return (float(pinned[0]), float(pinned[1]))
         if x + w + 2 > atlas:
             x, y, shelf = 2, y + shelf + 2, 0
         if y + h + 2 > atlas:
+            return None
+        if pinned and x + w + 2 > pinned[0] and y + h + 2 > pinned[1]:
             return None
         o = (float(x), float(y))
         x += w + 2

@@ -26,7 +26,7 @@ import numpy as np
 from . import glconst as G
 from .frame import Frame, Step, Target, TextureRef, CompositeTile, CLIP_TASK_EMPTY
 from . import scenes
-from .scenes import TILE_W, TILE_H, BIG, tile_grid, premultiply
+from .scenes import BIG, tile_grid, premultiply
 
 # wrench's named colours (yaml_helper.rs:55-66 string_to_color: "green" is (0, 1, 0), not the CSS keyword's (0, 0.5, 0))
 CSS = {"red": (255, 0, 0, 255), "green": (0, 255, 0, 255), "blue": (0, 0, 255, 255), "white": (255, 255, 255, 255), "black": (0, 0, 0, 255),
@@ -48,10 +48,10 @@ def _tiles(frame, width, height, tile_filter, dps=1.0):
     for (tx, ty, ox, oy) in tile_grid(width, height):
         if tile_filter is not None and not tile_filter(tx, ty):
             continue
-        x0, y0, x1, y1 = ox, oy, ox + TILE_W, oy + TILE_H
-        tex = TextureRef(f"tile_{tx}_{ty}", TILE_W, TILE_H, G.GL_RGBA8, G.GL_LINEAR, render_target=True, with_depth=True)
+        x0, y0, x1, y1 = ox, oy, ox + scenes.TILE_W, oy + scenes.TILE_H
+        tex = TextureRef(f"tile_{tx}_{ty}", scenes.TILE_W, scenes.TILE_H, G.GL_RGBA8, G.GL_LINEAR, render_target=True, with_depth=True)
         target = Target(tex, "picture_tile", clear_color=(1.0, 1.0, 1.0, 1.0), clear_depth=True)
-        task = frame.add_render_task((0.0, 0.0, float(TILE_W), float(TILE_H)), dps, (float(ox), float(oy)))
+        task = frame.add_render_task((0.0, 0.0, float(scenes.TILE_W), float(scenes.TILE_H)), dps, (float(ox), float(oy)))
         out.append((target, task, (x0, y0, x1, y1)))
         rect = (float(x0), float(y0), float(x1), float(y1))
         clip = (float(x0), float(y0), float(min(x1, width)), float(min(y1, height)))
