@@ -872,7 +872,10 @@ WR_DEVICE void wr_vs_ps_quad_textured(const WrDrawDesc& d, const uint8_t* arena,
         C->plane[k][0] = nx[k]; C->plane[k][1] = ny[k]; C->plane[k][2] = nx[k] * dx[k] + ny[k] * dy[k];
       }
     }
-    o.kind = (cw[1] != cw[0] || cw[2] != cw[0] || cw[3] != cw[0] || !(quad_flags & 16)) ? WR_PK_UNSUPPORTED : WR_PK_QUAD_MASK;   // affine clip transforms, QF_IS_MASK
+    // (QF_IS_MASK is not asked for: the batcher sets it on image masks only, render_target.rs:1272; a rounded-rect mask instance
+    // carries APPLY_RENDER_TASK_CLIP or nothing, :1391-1395, and the flag changes nothing here -- pattern_fragment returns
+    // vec4(alpha), of which ps_quad.glsl:411-413's .rrrr is the identity)
+    o.kind = (cw[1] != cw[0] || cw[2] != cw[0] || cw[3] != cw[0]) ? WR_PK_UNSUPPORTED : WR_PK_QUAD_MASK;   // affine clip transforms
     o.color = prim_color; o.has_color = 0;
     o.tex_slot = WR_S_GPU_BUFFER_F;
     return;

@@ -923,6 +923,284 @@ def text_reftest(name="text", width=3840, height=2160, tile_filter=None, **kw):
     return _finish(frame, tiles)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# The reftest manifest lines pinned to the reference's expected PNGs (tests/golden/reftest_png.json, tests/test_reftest_png.py): what
+# the frame builder hands the backend for a flat display list of rects under complex clips, linear gradients, an unblurred inset box
+# shadow and generated images.  `items` is the fixture's parsed display list (the test loads the JSON); `perturb` names a deliberate
+# misreading the tests use to show that the comparison bites: "radius+1", "swap-clip-mode", "swap-gradient".
+QF_PRIM_TASK = 1 | 2 | 8        # IS_OPAQUE | APPLY_RENDER_TASK_CLIP | USE_AA_SEGMENTS: an opaque axis-aligned prim > 4 px in its own task
+QF_COMPOSITE = 2 | 4            # APPLY_RENDER_TASK_CLIP | IGNORE_DEVICE_PIXEL_SCALE (quad.rs add_composite_prim / add_pattern_prim)
+MIN_BRUSH_SPLIT_AREA = 128.0 * 128.0      # prepare.rs:44
+MIN_QUAD_SPLIT_SIZE, MAX_TILES_PER_QUAD = 256.0, 4          # quad.rs:27-28
+
+
+def _color_of(c):
+    """a fixture colour (a wrench colour name, or [r, g, b (0..255), a (0..1)]) -> premultiplied floats"""
+    if isinstance(c, str):
+        c = [CSS[c][0], CSS[c][1], CSS[c][2], CSS[c][3] / 255.0]
+    a = float(c[3])
+    return (c[0] / 255.0 * a, c[1] / 255.0 * a, c[2] / 255.0 * a, a)
+
+
+def _abs_rect(b, origin):
+    return (b[0] + origin[0], b[1] + origin[1], b[0] + b[2] + origin[0], b[1] + b[3] + origin[1])
+
+
+def reftest_png_scene(items, width=1920, height=1080, tile_filter=None, perturb=None, **kw):
+    """One pinned reftest display list as a frame.
+      * `rect` under complex clips, and `box-shadow` with blur radius 0 -- which box_shadow.rs:343-401 turns into a Rectangle prim on the
+        box under two rounded-rect clips (inset: the shadow rect = box + offset, ClipOut; the box, Clip) --: the QUAD path.  A Rectangle
+        whose clip chain holds only (rounded) rectangles never takes the brush path (prepare.rs:109-135, 244-256).  prepare_quad
+        (quad.rs:62-720) picks by get_prim_render_strategy (:722-792): a prim below 256 px on both axes is drawn INDIRECTLY -- the whole
+        prim into a colour task of its own (cleared transparent, blend off: render_target.rs:374-406, renderer/mod.rs:2199-2238), every
+        clip of the chain multiplied over it by ps_quad_mask (FAST_PATH iff the radius is uniform AND circular, render_target.rs:1213-1245;
+        ClipSpace::Raster, the quad = the task's world rect, all four edge flags), and the task composited into the picture by
+        one ps_quad_textured segment in the prim's colour --; a larger prim under ONE rounded Clip whose radii fit half the rect is a
+        NINE-PATCH in device space: the four corners as indirect tasks, the other five segments direct and opaque; anything else larger
+        is tiled (not needed by the pinned lines).  Clip-out needs nothing special here: the mode rides in the mask's clip block.
+      * `gradient`: a LinearGradient prim on the gradient brush (not cached under swgl); below 256 px along its axis it is NOT decomposed
+        (prim_store/gradient/linear.rs:185-190), so all eight stops go into one LUT: linear_gradients' single-prim reading.
+      * `image`: the brush path (prepare.rs:1273-1285): above MIN_BRUSH_SPLIT_AREA the rounded clip's nine-patch segments it
+        (segment.rs:397-470); corners carry a cs_clip_rectangle mask and go to the alpha pass, the rest is opaque; an unclipped opaque
+        image is one opaque brush_image.  The image is generated as wrench does (yaml_frame_reader.rs:195-247 checkerboard)."""
+    frame = Frame(width, height, (1.0, 1.0, 1.0, 1.0))
+    tiles = _tiles(frame, width, height, tile_filter)
+    pot = lambda v: 1 << int(np.ceil(np.log2(max(v, 64))))
+    big = (-BIG, -BIG, BIG, BIG)
+    prim_tasks = []                 # (x, y, w, h, prim instance, [(mask instance, fast)]) of the indirect tasks, packed below
+    draws = []                      # per prim: dict(bb, opaque=[(key, inst builder)], alpha=[...])
+    z = [0]
+
+    def next_z():
+        z[0] += 1
+        return z[0]
+
+    def clip_block(c):
+        rect, rad = _abs_rect(c["rect"], c["origin"]), [list(r) for r in c["radii"]]
+        mode = 1.0 if c["mode"] == "clip-out" else 0.0
+        if perturb == "radius+1":
+            rad = [[r[0] + 1.0, r[1] + 1.0] for r in rad]
+        if perturb == "swap-clip-mode":
+            mode = 1.0 - mode
+        rad = [list(r) for r in ensure_no_corner_overlap(tuple(tuple(r) for r in rad), (rect[2] - rect[0], rect[3] - rect[1]))]
+        uniform = all(r == rad[0] for r in rad) and rad[0][0] == rad[0][1]              # BorderRadius::is_uniform
+        if uniform:
+            return frame.gpu_buffer_f.push([list(rect), [rad[0][0], 0.0, 0.0, 0.0], [mode, 0.0, 0.0, 0.0]]), True, rect, rad, mode
+        return frame.gpu_buffer_f.push([list(rect), rad[0] + rad[1], rad[2] + rad[3], [mode, 0.0, 0.0, 0.0]]), False, rect, rad, mode
+
+    def quad_rect(rect, color, clips):
+        blocks = [clip_block(c) for c in clips]
+        local_clip = big
+        for _, _, crect, _, mode in blocks:
+            if mode == 0.0:                                   # a Clip-mode item narrows the chain's local clip rect, a ClipOut one cannot
+                local_clip = _isect(local_clip, crect)
+        cov = _isect(rect, local_clip)                        # pic_coverage_rect (identity transforms, device pixel scale 1)
+        if cov[0] >= cov[2] or cov[1] >= cov[3]:
+            return
+        surf = (float(np.floor(cov[0])), float(np.floor(cov[1])), float(np.ceil(cov[2])), float(np.ceil(cov[3])))
+        surf = _isect(surf, (0.0, 0.0, float(width), float(height)))
+        tcount = lambda v: int(np.ceil(max(min(v / MIN_QUAD_SPLIT_SIZE, float(MAX_TILES_PER_QUAD)), 1.0)))
+        split = tcount(cov[2] - cov[0]) > 1 or tcount(cov[3] - cov[1]) > 1
+        direct, indirect = [], []
+        if not split:
+            indirect.append(surf)
+        else:
+            assert len(blocks) == 1 and blocks[0][4] == 0.0, "tiled quads are not restated"
+            crect, rad = blocks[0][2], blocks[0][3]
+            rw, rh = max(r[0] for r in rad), max(r[1] for r in rad)
+            assert rw <= 0.5 * (crect[2] - crect[0]) and rh <= 0.5 * (crect[3] - crect[1]), "tiled quads are not restated"
+            xs = sorted([np.floor(crect[0]), np.ceil(crect[0] + rw), np.floor(crect[2] - rw), np.ceil(crect[2])])
+            ys = sorted([np.floor(crect[1]), np.ceil(crect[1] + rh), np.floor(crect[3] - rh), np.ceil(crect[3])])
+            for j in range(3):
+                for i in range(3):
+                    r = _isect((float(xs[i]), float(ys[j]), float(xs[i + 1]), float(ys[j + 1])), surf)
+                    if r[0] < r[2] and r[1] < r[3]:
+                        (indirect if (i != 1 and j != 1) else direct).append(r)
+        d = dict(bb=cov, direct=None, composite=None)
+        if direct:          # add_pattern_prim: the prim in device space, one opaque instance per direct segment
+            segs = [(r, (0.0, 0.0, 0.0, 0.0)) for r in direct]
+            d["direct"] = (rect, cov, color, segs, [next_z() for _ in direct])
+        seg_tasks = []
+        for r in indirect:
+            tw, th = int(r[2] - r[0]), int(r[3] - r[1])
+            seg_tasks.append((r, len(prim_tasks)))
+            prim_tasks.append(dict(size=(tw, th), origin=(r[0], r[1]), rect=rect, clip=local_clip, color=color, masks=[(b[0], b[1]) for b in blocks]))
+        d["composite"] = (cov, color, seg_tasks, [next_z() for _ in indirect])
+        draws.append(d)
+
+    images = {}
+    for it in items:
+        t = it["type"]
+        rect = _abs_rect(it["bounds"], it["origin"])
+        if t == "rect":
+            assert it["clips"], "an unclipped rect is not among the pinned lines"
+            quad_rect(rect, _color_of(it["color"]), it["clips"])
+        elif t == "box-shadow":
+            assert it["blur-radius"] == 0.0 and it["clip-mode"] == "inset" and it["spread-radius"] == 0.0
+            o = it["offset"]
+            assert o[0] != 0.0 or o[1] != 0.0
+            b = it["bounds"]
+            clips = [dict(rect=[b[0] + o[0], b[1] + o[1], b[2], b[3]], radii=it["border-radius"], mode="clip-out", origin=it["origin"]),
+                     dict(rect=b, radii=it["border-radius"], mode="clip", origin=it["origin"])]
+            quad_rect(rect, _color_of(it["color"]), clips)
+        elif t == "gradient":
+            sp, ep = it["start"], it["end"]
+            if perturb == "swap-gradient":
+                sp, ep = ep, sp
+            stops = [(off, tuple(v / 255.0 for v in CSS[c])) for off, c in it["stops"]]
+            reverse = sp[0] > ep[0] or (sp[0] == ep[0] and sp[1] > ep[1])          # scene_building.rs:3369-3378
+            if reverse:
+                sp, ep = ep, sp
+            w, h = it["bounds"][2], it["bounds"][3]
+            horizontal, vertical = abs(sp[1] - ep[1]) < 1e-6, abs(sp[0] - ep[0]) < 1e-6
+            assert it["repeat"] or not ((horizontal and w >= 256.0) or (vertical and h >= 256.0)), "decomposed gradients are not restated"
+            lut = frame.gpu_buffer_f.push(scenes.build_gradient_lut(stops, reverse=reverse))
+            spec = frame.gpu_cache.push([[sp[0], sp[1], ep[0], ep[1]], [1.0 if it["repeat"] else 0.0, w, h, 0.0]])
+            draws.append(dict(bb=rect, gradient=(rect, spec, lut, next_z())))
+        elif t == "image":
+            g = it["generator"]
+            assert g["name"] == "checkerboard" and len(g["args"]) == 3
+            key = tuple(g["args"])
+            if key not in images:
+                border, size, count = key
+                n = 2 * border + size * count
+                yy, xx = np.mgrid[0:n, 0:n]
+                on = (((xx - border) % (2 * size)) < size) ^ (((yy - border) % (2 * size)) < size)
+                v = np.where(on, 255, 127).astype(np.uint8)
+                pix = np.stack([v, v, v, np.full_like(v, 255)], axis=2)                          # B, G, R, A
+                edge = (yy < border) | (yy >= n - border) | (xx < border) | (xx >= n - border)
+                pix[edge] = (0, 0, 255, 255)
+                tex = TextureRef(f"image_{len(images)}", pot(n), pot(n), G.GL_RGBA8, G.GL_LINEAR, pixels=None)
+                full = np.zeros((tex.h, tex.w, 4), np.uint8)
+                full[:n, :n] = pix
+                tex.pixels, tex.upload_format = full, G.GL_BGRA
+                frame.static_textures.append(tex)
+                images[key] = (tex, frame.gpu_cache.push([[0.0, 0.0, float(n), float(n)], [0.0, 0.0, 0.0, 0.0]]))
+            tex, res = images[key]
+            brush = [[1.0, 1.0, 1.0, 1.0], [0.0, 0.0, 0.0, 0.0], [-1.0, -1.0, 0.0, 0.0]]               # ImageBrushData: white, no tiling
+            segs = None
+            if it["clips"]:
+                assert len(it["clips"]) == 1 and it["clips"][0]["mode"] == "clip"
+                c = it["clips"][0]
+                crect = _abs_rect(c["rect"], c["origin"])
+                rad = [[r[0] + 1.0, r[1] + 1.0] for r in c["radii"]] if perturb == "radius+1" else c["radii"]
+                rad = tuple((_au(r[0]), _au(r[1])) for r in ensure_no_corner_overlap(tuple(tuple(r) for r in rad), (crect[2] - crect[0], crect[3] - crect[1])))
+                assert (rect[2] - rect[0]) * (rect[3] - rect[1]) >= MIN_BRUSH_SPLIT_AREA, "a small brush gets one mask over the prim: not restated"
+                segs = build_segments(rect, [(rect, "clip", False), (big, "clip", False)] + rounded_rect_items(crect, rad, "clip"))
+                assert len(segs) > 1
+                for sg in segs:
+                    brush += [[sg[0] - rect[0], sg[1] - rect[1], sg[2] - rect[0], sg[3] - rect[1]], [0.0, 0.0, 0.0, 0.0]]
+                draws.append(dict(bb=rect, image=(rect, frame.gpu_cache.push(brush), tex, res, segs, crect, rad, next_z())))
+            else:
+                draws.append(dict(bb=rect, image=(rect, frame.gpu_cache.push(brush), tex, res, None, None, None, next_z())))
+        else:
+            raise NotImplementedError(t)
+
+    # -- pass 0: the corner masks of segmented images (R8 alpha target) and the indirect quad tasks (RGBA8 colour target)
+    first = []
+    mask_task = {}
+    minst, fast_all = [], True
+    mx = my = 4
+    shelf = 0
+    for di, d in enumerate(draws):
+        if "image" in d and d["image"][4] is not None:
+            rect, _, _, _, segs, crect, rad, _ = d["image"]
+            fast_all &= all(r == rad[0] for r in rad) and rad[0][0] == rad[0][1]
+            for si, sg in enumerate(segs):
+                if not sg[4]:
+                    continue
+                so = (float(np.floor(sg[0])), float(np.floor(sg[1])))
+                tw, th = int(np.ceil(sg[2]) - so[0]), int(np.ceil(sg[3]) - so[1])
+                if mx + tw + 4 > 1024:
+                    mx, my, shelf = 4, my + shelf + 4, 0
+                task = (float(mx), float(my), float(mx + tw), float(my + th))
+                minst.append(scenes.clip_rect_instance(task, so, 1.0, (crect[0], crect[1]), (crect[2] - crect[0], crect[3] - crect[1]), rad, 0))
+                mask_task[(di, si)] = frame.add_render_task(task, 1.0, so)
+                mx, shelf = mx + tw + 4, max(shelf, th)
+    t_masks = None
+    if minst:
+        t_masks = TextureRef("reftest_clip_masks", 1024, pot(my + shelf + 4), G.GL_R8, G.GL_LINEAR, render_target=True)
+        tg_m = Target(t_masks, "alpha", clear_color=(1.0, 1.0, 1.0, 1.0))
+        tg_m.steps.append(Step("cs_clip_rectangle FAST_PATH" if fast_all else "cs_clip_rectangle", "CLIP_RECT", np.concatenate(minst), None, "none"))
+        first.append(tg_m)
+    t_prims = None
+    if prim_tasks:
+        px = py = 0
+        shelf = 0
+        for pt in prim_tasks:
+            tw, th = pt["size"]
+            if px + tw > 2048:
+                px, py, shelf = 0, py + shelf, 0
+            pt["task_rect"] = (float(px), float(py), float(px + tw), float(py + th))
+            px, shelf = px + tw, max(shelf, th)
+        t_prims = TextureRef("reftest_prim_tasks", 2048, pot(py + shelf), G.GL_RGBA8, G.GL_LINEAR, render_target=True)
+        tg_p = Target(t_prims, "color", clear_color=(0.0, 0.0, 0.0, 0.0))
+        pinst, fast, slow = [], [], []
+        for pt in prim_tasks:
+            tr, o = pt["task_rect"], pt["origin"]
+            addr = frame.add_render_task(tr, 1.0, o)
+            pinst.append(frame.quad_instance(pt["rect"], pt["clip"], pt["color"], 0, addr, quad_flags=QF_PRIM_TASK))
+            world = (o[0], o[1], o[0] + (tr[2] - tr[0]), o[1] + (tr[3] - tr[1]))
+            for clip_addr, is_fast in pt["masks"]:
+                m = frame.quad_instance(world, world, (1.0, 1.0, 1.0, 1.0), 0, addr, quad_flags=2, edge_flags=15)
+                (fast if is_fast else slow).append(m + [0, clip_addr, 0, 0])                      # MaskInstance: identity clip transform, ClipSpace::Raster
+        tg_p.steps.append(Step("ps_quad_textured", "PRIM_INSTANCES", np.array(pinst, dtype=np.int32), None, "none", textures={}))
+        if fast:
+            tg_p.steps.append(Step("ps_quad_mask FAST_PATH", "MASK", np.array(fast, dtype=np.int32), "Multiply", "none", textures={}))
+        if slow:
+            tg_p.steps.append(Step("ps_quad_mask", "MASK", np.array(slow, dtype=np.int32), "Multiply", "none", textures={}))
+        first.append(tg_p)
+    if first:
+        frame.passes.append(first)
+        frame.readback = [t.texture for t in first]
+
+    # -- the picture tiles: opaque batches front to back, alpha batches in display-list order
+    for target, task, (x0, y0, x1, y1) in tiles:
+        op, al = [], []                     # (shader key, textures, instance)
+        for di, d in enumerate(draws):
+            bb = d["bb"]
+            if not (bb[0] < x1 and bb[2] > x0 and bb[1] < y1 and bb[3] > y0):
+                continue
+            if "gradient" in d:
+                rect, spec, lut, zz = d["gradient"]
+                ph = frame.add_prim_header(rect, big, zz, spec, 0, task, (lut, 0, 0, 0))
+                op.append(("brush_linear_gradient", {}, frame.brush_instance(ph, CLIP_TASK_EMPTY)))
+            elif "image" in d:
+                rect, spec, tex, res, segs, _, _, zz = d["image"]
+                ph = frame.add_prim_header(rect, big, zz, spec, 0, task, (4 | (1 << 16), 0, 65535, 0))
+                if segs is None:
+                    op.append(("brush_image TEXTURE_2D", {0: tex}, frame.brush_instance(ph, CLIP_TASK_EMPTY, resource_address=res)))
+                else:
+                    for si, sg in enumerate(segs):
+                        if sg[4]:
+                            al.append(("brush_image ALPHA_PASS,TEXTURE_2D", {0: tex, 9: t_masks},
+                                       frame.brush_instance(ph, mask_task[(di, si)], segment=si, brush_flags=1, resource_address=res)))
+                        else:
+                            op.append(("brush_image TEXTURE_2D", {0: tex}, frame.brush_instance(ph, CLIP_TASK_EMPTY, segment=si, brush_flags=1, resource_address=res)))
+            else:
+                if d["direct"]:
+                    rect, cov, color, segs, zs = d["direct"]
+                    for si, zz in enumerate(zs):
+                        op.append(("ps_quad_textured", {}, frame.quad_instance(rect, cov, color, zz, task, quad_flags=QF_COMPOSITE | 1, segment=si, segments=segs)))
+                cov, color, seg_tasks, zs = d["composite"]
+                segs = [(r, prim_tasks[k]["task_rect"]) for r, k in seg_tasks]
+                for si, zz in enumerate(zs):
+                    al.append(("ps_quad_textured", {0: t_prims}, frame.quad_instance(cov, cov, color, zz, task, quad_flags=QF_COMPOSITE, segment=si, segments=segs)))
+
+        def batches(lst, blend, depth):
+            out, cur = [], None
+            for key, tex, inst in lst:
+                k = (key, tuple(sorted((s, t.name) for s, t in tex.items())))
+                if cur is None or cur[0] != k:
+                    cur = (k, key, tex, [])
+                    out.append(cur)
+                cur[3].append(inst)
+            return [Step(key, "PRIM_INSTANCES", np.array(inst, dtype=np.int32), blend, depth, textures=tex) for _, key, tex, inst in out]
+        target.opaque += batches(op[::-1], None, "opaque")
+        target.alpha += batches(al, "PremultipliedAlpha", "alpha")
+    return _finish(frame, tiles)
+
+
 WORKLOADS = {
     **{f"reftest-text-{n}": (lambda n=n, **kw: text_reftest(n, **kw)) for n in TEXT_REFTESTS},
     "large-blur-radius": large_blur_radius,
