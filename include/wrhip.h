@@ -250,7 +250,8 @@ void WrhipSetProfiling(int enabled);
  * fused with the next flush's setup stage (wr_setup_raster[_dense]_kernel: setup bytes and workgroups added), 8 = wr_setup_rows_kernel
  * (3 fused likewise), 9 = wr_span_rows_kernel (the cs_blur / cs_scale targets of a level, a wave per target row piece), 10 = wr_tile_rows_kernel
  * (picture targets of a few large gradient / image prims, likewise), 11 = wr_setup_tile_rows_kernel (10 fused with the next flush's setup stage), 12 = a thin launch of the raster kernel (13: the same with the next flush's setup stage in front, wr_setup_raster_thin_kernel) (wr_raster_kernel<fmt, false, 1, feat>:
- * small levels, several workgroups per bin).  algo_bytes: the launch's algorithmic bytes:
+ * small levels, several workgroups per bin), 14 = wr_tap_kernel (WrhipTapTexture: fmt of the tapped texture, feat 1 against an expected texture;
+ * algo_bytes: the rect's bytes, twice with an expected texture).  algo_bytes: the launch's algorithmic bytes:
  * raster launches count every destination pixel they own once (twice when the target's old content is loaded) plus
  * the source texels their draws can sample; the setup stage counts instance + descriptor + record bytes.  Returns the
  * number of entries written (<= max). */
@@ -274,6 +275,9 @@ void* WrhipGetTextureDevicePtr(GLuint tex, int32_t* width, int32_t* height,
                                int32_t* stride);
 /* Texture id of an FBO's colour attachment (fbo 0 = default framebuffer). */
 GLuint WrhipGetFramebufferTexture(GLuint fbo);
+/* Width and height of a texture's storage as recorded so far: a state query that submits nothing and waits for nothing
+ * (returns 0, leaving the outputs alone, for an unknown texture or one without storage). */
+int32_t WrhipGetTextureSize(GLuint tex, int32_t* width, int32_t* height);
 /* Name of the HIP device the context runs on, or NULL if none. */
 const char* WrhipDeviceName(void);
 /* Submit everything recorded so far to the context's HIP stream (pending draws, queued uploads, the
@@ -285,6 +289,41 @@ void WrhipFlush(void);
 int WrhipFlushHeld(void);
 /* The context's hipStream_t (NULL in the host simulation), e.g. for torch.cuda.ExternalStream. */
 void* WrhipGetStream(void);
+/* Texture taps: a reduction over a texture rect, enqueued on the context's stream behind whatever was issued before it and
+ * delivered to the host later -- a reftest harness or a frame loop checks every frame without a ReadPixels, which would stall
+ * the pipeline and copy the whole window.
+ *
+ * WrhipTapTexture(tex, x, y, w, h, expected) reduces the w x h rect at (x, y) of `tex` (GL_RGBA8 or GL_R8; the window is
+ * WrhipGetFramebufferTexture(0); rows as stored: row r of the rect is texture row y + r) and returns a ticket >= 0.
+ *   digest[j]  the sum over the rect's pixels, mod 2^64, of mix(k_i + C_j): i = r * w + c, k_i = (uint64)i << 32 | v_i, v_i the
+ *              pixel's four stored bytes as a little-endian word (its one byte for R8), C_0 = 0x9E3779B97F4A7C15,
+ *              C_1 = 0xD1B54A32D192ED03, mix(z): z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) * 0x94D049BB133111EB,
+ *              z ^ z >> 31.  Exact integer arithmetic: any restatement gives the same 128 bits.
+ *   hist[d]    with `expected` != 0 (a texture of the same format holding at least w x h pixels, compared from ITS origin): the
+ *              pixels whose largest absolute channel difference is d -- wrench's reftest measure; max_diff and differing are
+ *              its two summaries (taken from the bins on the host).  Without `expected` every pixel is in hist[0].
+ * The tap sees exactly the draws, clears, uploads, blits and composites issued before the call.  Recorded work is submitted as by
+ * WrhipFlushHeld: nothing is waited for, and raster launches that are held back for the next flush stay held back -- a tap of a
+ * texture they write is issued directly behind them whenever they leave (the next flush, WrhipFlushHeld, Finish, a readback).
+ * Later writes to either texture, deleting it or giving it new storage do not change the result.
+ * Returns -1 and sets GL_INVALID_VALUE, launching nothing, for an unknown texture or format, a rect that is empty or not inside
+ * `tex`, an `expected` of another format or too small, and while sharding is on (WrhipSetShard world > 1, WrhipSetTargetRows on
+ * `tex`).
+ *
+ * WrhipTapResultGet(ticket, out, wait): 0 and *out filled; 1 if the result has not arrived yet (wait == 0 only; wait != 0 first
+ * sends what the tap is parked behind, then waits for this ticket alone, not for the stream); -1 for a ticket that was never
+ * handed out or has been overwritten -- the ring holds the 64 newest. */
+typedef struct WrhipTapResult {
+  int32_t  status;        /* 0 ok */
+  uint32_t width, height; /* the rect actually reduced */
+  uint32_t format;        /* GL_RGBA8 or GL_R8 */
+  uint64_t digest[2];
+  uint32_t max_diff;      /* 0 without an expected texture */
+  uint32_t differing;     /* pixels with difference > 0 */
+  uint32_t hist[256];     /* hist[d] = pixels whose difference is exactly d; all in hist[0] without an expected texture */
+} WrhipTapResult;
+int32_t WrhipTapTexture(GLuint tex, int32_t x, int32_t y, int32_t w, int32_t h, GLuint expected);
+int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
 
 #ifdef __cplusplus
 }

@@ -617,6 +617,18 @@ struct Context {
   bool dense_text = false;             // WRHIP_DENSE_TEXT=1: text levels run the 128-VGPR build of their variant (wr_raster_dense_kernel: four waves
                                        // per SIMD; the default until the glyph walk read 32-byte glyph records -- since then the 168-VGPR
                                        // build, which does not spill, is the faster one: cfg3 97.6 vs 102.3 us, profiles/r04_g_dense_waves_ab.txt)
+  // Texture taps (WrhipTapTexture): a ring of tickets, each with a device slot the tap kernel reduces into, a pinned host slot the
+  // result is copied to on the stream, and an event recorded behind that copy.  Ticket n lives in slot n % TAP_RING until ticket
+  // n + TAP_RING takes it over.  A tap of a texture the held-back launches (Context::Tail) still have to write waits in
+  // `tap_parked`, its arguments resolved -- storage pointers, not names -- and is issued by tail_launched(), directly behind them.
+  static const int TAP_RING = 64;
+  struct TapSlot { uint64_t n = ~0ull; bool parked = false; wr_event_t ev; int32_t w = 0, h = 0; GLenum format = 0; };
+  struct TapParked { uint64_t n; WrTapArgs args; };
+  TapSlot tap_slot[TAP_RING];
+  uint64_t tap_next = 0;               // tickets handed out so far
+  WrhipTapResult* tap_dev = nullptr;   // TAP_RING device slots
+  WrhipTapResult* tap_host = nullptr;  // ... and their pinned host copies
+  std::vector<TapParked> tap_parked;
   int chain_grid = 0;                  // workgroups of a chained R8 launch (0: off -- the default; WRHIP_CHAIN=1 turns it on, WRHIP_CHAIN_GRID overrides)
   unsigned chain_base = 0;             // value of WrUnsupportedCounters::chain_arrive once every chained launch enqueued so far has run
 
@@ -648,6 +660,9 @@ struct Context {
     grad_tables = getenv("WRHIP_NO_GTAB") == nullptr;
     if (const char* e = getenv("WRHIP_RUNS_POOL_WORDS")) runs_pool_words = (size_t)atoll(e);
     wrrt::event_create(&ev_a); wrrt::event_create(&ev_b);
+    for (TapSlot& ts : tap_slot) wrrt::event_create_sync(&ts.ev);
+    tap_dev = (WrhipTapResult*)wrrt::dev_alloc(sizeof(WrhipTapResult) * TAP_RING);
+    tap_host = (WrhipTapResult*)wrrt::pinned_alloc(sizeof(WrhipTapResult) * TAP_RING);
     memset(&stats, 0, sizeof(stats));
     dcounters = (WrUnsupportedCounters*)wrrt::dev_alloc(sizeof(WrUnsupportedCounters));
     wrrt::memset8(dcounters, 0, sizeof(WrUnsupportedCounters), stream);
@@ -752,6 +767,7 @@ uint64_t get_time_value() {
 // Deferred work: flush
 void flush_all();
 void drain_tail();
+void tap_issue_parked();
 // every host-side wait for the stream: the held-back raster level goes out first
 void sync_stream();
 
@@ -1233,6 +1249,8 @@ Context::~Context() {
   wrrt::dev_free(dupload); wrrt::dev_free(dcounters);
   for (Scratch& S : scratch) { wrrt::dev_free(S.prims); wrrt::dev_free(S.recs); wrrt::dev_free(S.aux); wrrt::dev_free(S.vtab); wrrt::dev_free(S.qtab); wrrt::dev_free(S.masks); wrrt::dev_free(S.bin_ctr); wrrt::dev_free(S.mr_slots); wrrt::dev_free(S.mr_store); wrrt::dev_free(S.flat); }
   wrrt::pinned_free(staging);
+  for (TapSlot& ts : tap_slot) wrrt::event_destroy(ts.ev);
+  wrrt::dev_free(tap_dev); wrrt::pinned_free(tap_host);
   wrrt::event_destroy(ev_a); wrrt::event_destroy(ev_b);
   wrrt::event_destroy(ev_copy);
   for (RingFence& f : ring_fence) if (f.made) wrrt::event_destroy(f.ev);
@@ -1265,6 +1283,7 @@ void tail_launched() {
   T.refs.clear();
   T.held.clear();
   T.pending = false;
+  tap_issue_parked();      // (taps of what these launches wrote: directly behind them)
 }
 // The instantiated raster kernels: RGBA8 (+depth) x {0, TEX|GENERIC, +R8TEX, everything}, R8 x {0, GENERIC|BLUR, +CLIP}.
 // `SA` non-null: launch the fused setup + raster variant (only for the variants can_fuse() names).
@@ -1479,6 +1498,45 @@ void sync_scratch() {
   if (ctx->tail.pending) ctx->stats.scratch_grown_held++;
   HostTimer ht(&ctx->stats.host_wait_ns);
   wrrt::stream_sync(ctx->stream);
+}
+
+// ---- texture taps (WrhipTapTexture) -------------------------------------------------------------------------------------------
+// One tap on the stream, now: the slot zeroed, the kernel, the copy of the slot to its pinned host copy, the ticket's event.
+// Every step is enqueued through the submit thread; nothing here waits.
+void tap_issue(uint64_t n, const WrTapArgs& a) {
+  Context* c = ctx;
+  const int si = (int)(n % Context::TAP_RING);
+  Context::TapSlot& ts = c->tap_slot[si];
+  WrhipTapResult* d = c->tap_dev + si;
+  wrrt::memset8(d, 0, sizeof(WrhipTapResult), c->stream);
+  const int grid = (a.h + a.rows_per_wg - 1) / a.rows_per_wg;
+  prof_begin();
+  WR_LAUNCH(wr_tap_kernel, grid, 256, c->stream, a);
+  // (14: wr_tap_kernel; feat 1: against an expected texture, whose bytes are read as well)
+  prof_end(14, a.bpp == 4 ? WR_FMT_RGBA8 : WR_FMT_R8, 0, a.exp ? 1 : 0, (uint64_t)a.w * a.h * a.bpp * (a.exp ? 2 : 1), (uint64_t)grid);
+  c->stats.kernel_launches++;
+  wrrt::d2h(c->tap_host + si, d, sizeof(WrhipTapResult), c->stream);
+  wrrt::event_record(&ts.ev, c->stream);
+  c->stats.d2h_bytes += sizeof(WrhipTapResult);
+  ts.parked = false;
+}
+// The held-back launches have just been enqueued (tail_launched): the taps that waited for them follow, in the order they were made.
+// (a parked tap whose ticket has been overwritten since has no slot to deliver into, and nobody who could ask for it)
+void tap_issue_parked() {
+  Context* c = ctx;
+  if (c->tap_parked.empty()) return;
+  std::vector<Context::TapParked> parked;
+  parked.swap(c->tap_parked);
+  for (const Context::TapParked& p : parked)
+    if (c->tap_slot[p.n % Context::TAP_RING].n == p.n) tap_issue(p.n, p.args);
+}
+// ticket -> its ring slot, or null once TAP_RING newer tickets exist (tickets are the low 31 bits of the running count)
+Context::TapSlot* tap_find(int32_t ticket) {
+  Context* c = ctx;
+  if (ticket < 0) return nullptr;
+  Context::TapSlot& ts = c->tap_slot[ticket % Context::TAP_RING];
+  if (ts.n == ~0ull || (int32_t)(ts.n & 0x7FFFFFFFull) != ticket) return nullptr;
+  return &ts;
 }
 
 // Forwarded composites.  A target whose pending work is [full clear,] N draws of `composite FAST_PATH` that each copy a whole
@@ -3603,6 +3661,13 @@ GLuint WrhipGetFramebufferTexture(GLuint fbo) {
   Framebuffer* fb = ctx ? ctx->framebuffers.find(fbo) : nullptr;
   return fb ? fb->color_attachment : 0;
 }
+int32_t WrhipGetTextureSize(GLuint tex, int32_t* width, int32_t* height) {
+  Texture* t = ctx && tex ? ctx->textures.find(tex) : nullptr;
+  if (!t || !t->dptr) return 0;
+  if (width) *width = t->width;
+  if (height) *height = t->height;
+  return 1;
+}
 const char* WrhipDeviceName(void) { return g_rt_ok ? g_device_name : nullptr; }
 void WrhipFlush(void) {
   if (!ctx) return;
@@ -3637,6 +3702,70 @@ int WrhipFlushHeld(void) {
 #endif
   if (early_fb) return 2;
   return ctx->tail.pending ? 1 : 0;
+}
+// A tap: see include/wrhip.h.  Arguments are checked before anything is flushed or launched.
+int32_t WrhipTapTexture(GLuint tex, int32_t x, int32_t y, int32_t w, int32_t h, GLuint expected) {
+  if (!ctx) return -1;
+  Context* c = ctx;
+  Texture* t = tex ? c->textures.find(tex) : nullptr;
+  Texture* e = expected ? c->textures.find(expected) : nullptr;
+  bool ok = t && t->dptr && (t->internal_format == GL_RGBA8 || t->internal_format == GL_R8) && (!expected || (e && e->dptr));
+  ok = ok && w >= 1 && h >= 1 && x >= 0 && y >= 0 && x <= t->width - w && y <= t->height - h;
+  ok = ok && (!e || (e->internal_format == t->internal_format && e->width >= w && e->height >= h));
+  ok = ok && c->shard_world <= 1 && t->own_y0 == t->own_y1;      // (sharded targets hold a strip of the frame each: out of scope)
+  if (!ok) { c->last_error = GL_INVALID_VALUE; return -1; }
+  // what was recorded so far goes out the way WrhipFlushHeld sends it: this flush's raster launches stay held back, queued uploads
+  // (to `tex` or `expected`, say) are scattered
+  flush_all();
+  flush_uploads(3700);
+  WrTapArgs a;
+  a.src = (const uint8_t*)t->dptr + (size_t)y * t->stride + (size_t)x * t->bpp;
+  a.exp = e ? (const uint8_t*)e->dptr : nullptr;
+  a.src_stride = t->stride; a.exp_stride = e ? e->stride : 0;
+  a.bpp = t->bpp; a.w = w; a.h = h;
+  // (a workgroup per 8 KB of rect rows, whole rows -- and no more than 1024 workgroups: each ends in three atomics on the slot)
+  a.rows_per_wg = std::max(1, std::min(h, (int)((8192 + (size_t)w * t->bpp - 1) / ((size_t)w * t->bpp))));
+  a.rows_per_wg = std::max(a.rows_per_wg, (h + 1023) / 1024);
+  const uint64_t n = c->tap_next++;
+  const int si = (int)(n % Context::TAP_RING);
+  a.digest = (unsigned long long*)&c->tap_dev[si].digest[0];
+  a.hist = (unsigned*)&c->tap_dev[si].hist[0];
+  Context::TapSlot& ts = c->tap_slot[si];
+  ts.n = n; ts.w = w; ts.h = h; ts.format = t->internal_format;
+  if (c->tail.pending && (t->tail_ref || (e && e->tail_ref))) {
+    // the held-back launches write (or read) one of the two: the tap waits for them to leave, and does not make them.  Both
+    // textures now count as the tail's, so that a host-side write to either, its deletion or new storage sends the tail -- and
+    // this tap behind it -- first (sync_texture_for_write); draws and clears recorded from here on follow it on the stream anyway.
+    ts.parked = true;
+    c->tap_parked.push_back(Context::TapParked{n, a});
+    if (!t->tail_ref) { t->tail_ref = true; c->tail.refs.push_back(tex); }
+    if (e && !e->tail_ref) { e->tail_ref = true; c->tail.refs.push_back(expected); }
+  } else {
+    tap_issue(n, a);
+  }
+  return (int32_t)(n & 0x7FFFFFFFull);
+}
+int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait) {
+  if (!ctx || !out) return -1;
+  Context* c = ctx;
+  Context::TapSlot* ts = tap_find(ticket);
+  if (!ts) return -1;
+  if (ts->parked) {
+    if (!wait) return 1;
+    drain_tail();            // what it is parked behind goes out (as after a WrhipFlushHeld with nothing recorded), the tap with it
+    if (ts->parked) tap_issue_parked();
+  }
+  if (wait) { HostTimer ht(&c->stats.host_wait_ns); wrrt::event_sync(&ts->ev); }
+  else if (!wrrt::event_query(&ts->ev)) return 1;
+  WrhipTapResult r;
+  memcpy(&r, c->tap_host + (ts - c->tap_slot), sizeof(r));
+  r.status = 0; r.width = (uint32_t)ts->w; r.height = (uint32_t)ts->h; r.format = ts->format;
+  // (the two summaries of the histogram are taken here, from the 256 bins the device counted)
+  r.max_diff = 0;
+  for (uint32_t d = 1; d < 256; d++) if (r.hist[d]) r.max_diff = d;
+  r.differing = (uint32_t)((uint64_t)ts->w * ts->h - r.hist[0]);
+  *out = r;
+  return 0;
 }
 void* WrhipGetStream(void) {
 #ifdef WRHIP_HOSTSIM

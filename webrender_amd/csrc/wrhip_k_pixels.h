@@ -100,6 +100,107 @@ __global__ void wr_blit_kernel(WrBlitArgs a) {
 }
 #endif
 
+// WrhipTapTexture (include/wrhip.h): two order-free 64-bit sums over the pixels of a texture rect -- pixel i = r * w + c of the rect
+// with stored value v contributes mix(((u64)i << 32 | v) + C_j), mix = the splitmix64 finaliser -- and, against an expected
+// texture, the histogram of per-pixel differences (the largest absolute channel difference: wrench's reftest measure).
+// A read-only stream: a 256-thread workgroup per run of rows (WrTapArgs::rows_per_wg), 16-byte loads from the first 16-byte
+// boundary of a row on where the expected row is aligned there too, single pixels before it, behind the last whole piece and
+// wherever the two rows' alignments differ.  The sums stay in registers (a wave reduction, the four waves' sums added in LDS, then
+// one 64-bit atomic per workgroup and word); differences are counted in an LDS histogram (equal pixels, the usual case, in a register instead) that leaves with one
+// atomic per bin in use.  Integer sums commute: the result does not depend on the order the workgroups run in.
+WR_DEVICE unsigned long long wr_tap_mix(unsigned long long z) {
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+struct WrTapAcc { unsigned long long d0, d1; unsigned n0; };
+WR_DEVICE uint32_t wr_tap_absdiff(uint32_t a, uint32_t b) { return a > b ? a - b : b - a; }
+// pixel `i` of the rect: value v, expected e (== v when nothing is expected); hist: the workgroup's 256 bins
+WR_DEVICE void wr_tap_px(WrTapAcc& A, unsigned* hist, unsigned long long i, uint32_t v, uint32_t e) {
+  const unsigned long long k = (i << 32) | v;
+  A.d0 += wr_tap_mix(k + 0x9E3779B97F4A7C15ull);
+  A.d1 += wr_tap_mix(k + 0xD1B54A32D192ED03ull);
+  if (v == e) { A.n0++; return; }
+  uint32_t d = wr_tap_absdiff(v & 0xFF, e & 0xFF);       // (R8 values have no more than this byte)
+  d = (uint32_t)wr_imax((int)d, (int)wr_tap_absdiff((v >> 8) & 0xFF, (e >> 8) & 0xFF));
+  d = (uint32_t)wr_imax((int)d, (int)wr_tap_absdiff((v >> 16) & 0xFF, (e >> 16) & 0xFF));
+  d = (uint32_t)wr_imax((int)d, (int)wr_tap_absdiff(v >> 24, e >> 24));
+  atomicAdd(&hist[d], 1u);
+}
+WR_DEVICE uint32_t wr_tap_load(const uint8_t* p, int bpp) {
+  if (bpp == 1) return p[0];
+  uint32_t v;
+  __builtin_memcpy(&v, p, 4);
+  return v;
+}
+// row r of the rect, thread t of nt
+WR_DEVICE void wr_tap_row(const WrTapArgs& a, int r, int t, int nt, WrTapAcc& A, unsigned* hist) {
+  const uint8_t* ps = a.src + (size_t)r * a.src_stride;
+  const uint8_t* pe = a.exp ? a.exp + (size_t)r * a.exp_stride : nullptr;
+  const unsigned long long i0 = (unsigned long long)r * (unsigned)a.w;
+  const int bpp = a.bpp, ppv = 16 / bpp;
+  // [0, head) single pixels, [head, tail0) 16-byte pieces, [tail0, w) single pixels
+  int head = a.w;
+  if (((uintptr_t)ps & (uintptr_t)(bpp - 1)) == 0) {
+    const int h16 = (int)(((16 - ((uintptr_t)ps & 15)) & 15) / bpp);
+    if (h16 < a.w && (!pe || (((uintptr_t)pe + (size_t)h16 * bpp) & 15) == 0)) head = h16;
+  }
+  const int nvec = (a.w - head) / ppv, tail0 = head + nvec * ppv;
+  for (int c = t; c < nvec; c += nt) {
+    const int p = head + c * ppv;
+    const wr_u4 sv = wr_load16(ps + (size_t)p * bpp);
+    const wr_u4 ev = pe ? wr_load16(pe + (size_t)p * bpp) : sv;
+    const uint32_t sw[4] = {sv.x, sv.y, sv.z, sv.w}, ew[4] = {ev.x, ev.y, ev.z, ev.w};
+    if (bpp == 4) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) wr_tap_px(A, hist, i0 + (unsigned)(p + k), sw[k], ew[k]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 16; k++) wr_tap_px(A, hist, i0 + (unsigned)(p + k), (sw[k >> 2] >> (8 * (k & 3))) & 0xFF, (ew[k >> 2] >> (8 * (k & 3))) & 0xFF);
+    }
+  }
+  const int nscalar = head + (a.w - tail0);
+  for (int q = t; q < nscalar; q += nt) {
+    const int p = q < head ? q : tail0 + (q - head);
+    const uint32_t v = wr_tap_load(ps + (size_t)p * bpp, bpp);
+    wr_tap_px(A, hist, i0 + (unsigned)p, v, pe ? wr_tap_load(pe + (size_t)p * bpp, bpp) : v);
+  }
+}
+#ifndef WR_INST_ONLY      /* (not a template: defined by wrhip.hip alone, not by the instantiation units wrhip_inst.hip) */
+__global__ void __launch_bounds__(256) wr_tap_kernel(WrTapArgs a) {
+  const int r0 = (int)blockIdx.x * a.rows_per_wg, r1 = wr_imin(a.h, r0 + a.rows_per_wg);
+  WrTapAcc A = {0ull, 0ull, 0u};
+#ifdef WRHIP_HOSTSIM
+  // (threads run one after the other: each adds what it saw straight to the slot)
+  for (int r = r0; r < r1; r++) wr_tap_row(a, r, (int)threadIdx.x, (int)blockDim.x, A, a.hist);
+  atomicAdd(&a.digest[0], A.d0); atomicAdd(&a.digest[1], A.d1);
+  atomicAdd(&a.hist[0], A.n0);
+#else
+  __shared__ unsigned lh[256];
+  __shared__ unsigned long long ld[2];
+  lh[threadIdx.x] = 0u;
+  if (threadIdx.x < 2) ld[threadIdx.x] = 0ull;
+  __syncthreads();
+  for (int r = r0; r < r1; r++) wr_tap_row(a, r, (int)threadIdx.x, 256, A, lh);
+  for (int o = 32; o > 0; o >>= 1) {
+    A.d0 += __shfl_down(A.d0, o);
+    A.d1 += __shfl_down(A.d1, o);
+    A.n0 += __shfl_down(A.n0, o);
+  }
+  // (the waves' sums meet in LDS: atomics on ONE address run one after the other chip-wide, 11-13 ns each -- at one per wave
+  // and word the 17 k of a 4K window took 220 us against 29 us this way)
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(&ld[0], A.d0); atomicAdd(&ld[1], A.d1);
+    if (A.n0) atomicAdd(&lh[0], A.n0);
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) atomicAdd(&a.digest[threadIdx.x], ld[threadIdx.x]);
+  const unsigned n = lh[threadIdx.x];
+  if (n) atomicAdd(&a.hist[threadIdx.x], n);
+#endif
+}
+#endif
+
 // A solid colour on a general quad, one row at a time: the row's span from the edge instances of its run (aa_span / aa_edge /
 // aa_dist, rasterize.h:480-562) -- the two edge sums are what costs (Edge::nextRow, one add per row: wr_accum), so they are
 // evaluated once per lane-row and shared by the row's pixels.

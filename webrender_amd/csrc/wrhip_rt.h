@@ -75,6 +75,7 @@ static inline void event_create(wr_event_t* e) { e->t = 0; }
 static inline void event_destroy(wr_event_t) {}
 static inline void event_record(wr_event_t*, wr_stream_t) {}
 static inline void event_sync(wr_event_t*) {}
+static inline bool event_query(wr_event_t*) { return true; }
 static inline void stream_wait_event(wr_stream_t, wr_event_t*) {}
 static inline void event_create_sync(wr_event_t* e) { e->t = 0; }
 static inline float event_elapsed_ms(wr_event_t*, wr_event_t*) { return 0.f; }
@@ -245,6 +246,15 @@ static inline void event_create(wr_event_t* e) { WR_HIP_CHECK(hipEventCreate(e))
 static inline void event_destroy(wr_event_t e) { wrq::drain(); WR_HIP_CHECK(hipEventDestroy(e)); }
 static inline void event_record(wr_event_t* e, wr_stream_t s) { const wr_event_t ev = *e; wrq::run([=] { WR_HIP_CHECK(hipEventRecord(ev, s)); }); }
 static inline void event_sync(wr_event_t* e) { wrq::drain(); WR_HIP_CHECK(hipEventSynchronize(*e)); }
+// has everything enqueued ahead of the event's last record completed?  (never blocks on the device: the submit ring is drained so
+// that the record itself has been made)
+static inline bool event_query(wr_event_t* e) {
+  wrq::drain();
+  const hipError_t r = hipEventQuery(*e);
+  if (r == hipErrorNotReady) { (void)hipGetLastError(); return false; }
+  WR_HIP_CHECK(r);
+  return true;
+}
 // ordering-only events (no timestamps) and cross-stream waits
 static inline void event_create_sync(wr_event_t* e) { WR_HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming)); }
 static inline void stream_wait_event(wr_stream_t s, wr_event_t* e) { const wr_event_t ev = *e; wrq::run([=] { WR_HIP_CHECK(hipStreamWaitEvent(s, ev, 0)); }); }

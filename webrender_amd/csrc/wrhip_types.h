@@ -680,6 +680,19 @@ struct WrBlitArgs {
   int32_t invert_x, composite;         // Composite(): X flips (linear only), premultiplied-over blend instead of a copy (RGBA8 <- RGBA8)
 };
 
+// WrhipTapTexture: a digest of a texture rect and, against `exp`, the histogram of per-pixel differences (wr_tap_kernel).
+// `src` / `exp` point at the first pixel of the rect (exp: at its texture's origin, or null); the two sums and the 256 bins are
+// the head of the ticket's device slot (the layout WrhipTapResult gives them), zeroed on the stream before the launch.
+struct WrTapArgs {
+  const uint8_t* src; const uint8_t* exp;
+  int32_t src_stride, exp_stride;      // bytes
+  int32_t bpp;                         // 4: RGBA8, 1: R8
+  int32_t w, h;                        // the rect
+  int32_t rows_per_wg;                 // workgroup b reduces rows [b * rows_per_wg, ...)
+  unsigned long long* digest;          // [2]
+  unsigned* hist;                      // [256]
+};
+
 // CompositeYUV (composite.h:1160-1386): the destination rows of linear_convert_yuv, four pixels (one chunk of linear_row_yuv) per
 // thread.  Everything that is constant along a row -- the planes' x coordinates in 1/128 texel x 2^8 fixed point, their steps, where
 // the half-resolution fast path (upscaleYUV42R8) starts and ends -- is worked out once on the host, as the reference does per row.

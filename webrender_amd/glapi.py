@@ -132,10 +132,13 @@ EXTRA_SIGNATURES = {
     "WrhipSetTargetRows": (None, [u32, i32, i32]),
     "WrhipGetTextureDevicePtr": (P, [u32, P, P, P]),
     "WrhipGetFramebufferTexture": (u32, [u32]),
+    "WrhipGetTextureSize": (i32, [u32, P, P]),
     "WrhipDeviceName": (c_char_p, []),
     "WrhipFlush": (None, []),
     "WrhipFlushHeld": (i32, []),
     "WrhipGetStream": (P, []),
+    "WrhipTapTexture": (i32, [u32, i32, i32, i32, i32, u32]),
+    "WrhipTapResultGet": (i32, [i32, P, i32]),
 }
 
 
@@ -149,6 +152,11 @@ class WrhipStats(C.Structure):
 
 class WrhipKernelStat(C.Structure):
     _fields_ = [(n, i32) for n in ("kind", "fmt", "depth", "feat")] + [(n, u64) for n in ("launches", "ns", "algo_bytes", "workgroups")]
+
+
+class WrhipTapResult(C.Structure):
+    _fields_ = [("status", i32), ("width", u32), ("height", u32), ("format", u32), ("digest", u64 * 2),
+                ("max_diff", u32), ("differing", u32), ("hist", u32 * 256)]
 
 
 def _as_ptr(x):
@@ -217,6 +225,28 @@ class GL:
         s = WrhipStats()
         self.WrhipGetStats(C.byref(s))
         return {n: getattr(s, n) for n, _ in s._fields_}
+
+    def tap_texture(self, tex, rect=None, expected=0):
+        """Enqueue a tap (include/wrhip.h, WrhipTapTexture) of `rect` = (x, y, w, h) of texture id `tex` -- None: all of it --
+        against texture id `expected` (0: digest only).  Returns the ticket, or -1 (GL_INVALID_VALUE is then set)."""
+        if rect is None:
+            w, h = i32(0), i32(0)
+            if not self.WrhipGetTextureSize(tex, C.byref(w), C.byref(h)):
+                return self.WrhipTapTexture(tex, 0, 0, 0, 0, expected)
+            rect = (0, 0, w.value, h.value)
+        return self.WrhipTapTexture(tex, *[int(v) for v in rect], expected)
+
+    def tap_result(self, ticket, wait=True):
+        """The result of a tap as a dict (digest: two ints, hist: 256 ints), None if it has not arrived (wait=False only).
+        A ticket the ring no longer holds raises KeyError."""
+        r = WrhipTapResult()
+        rc = self.WrhipTapResultGet(ticket, C.byref(r), 1 if wait else 0)
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise KeyError(f"tap ticket {ticket} is unknown or has been overwritten")
+        return {"status": r.status, "width": r.width, "height": r.height, "format": r.format, "digest": (int(r.digest[0]), int(r.digest[1])),
+                "max_diff": r.max_diff, "differing": r.differing, "hist": list(r.hist)}
 
 
 def repo_root():

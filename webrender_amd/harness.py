@@ -142,3 +142,29 @@ def render_streamed(backend_path, frames):
         stats["gl_error"] = int(err)
     r.destroy()
     return px, stats
+
+
+def render_streamed_tapped(backend_path, frames):
+    """render_streamed with every frame looked at: after each frame's render the window is tapped (GL.tap_texture: a digest taken
+    on the device, in stream order behind that frame) -- still nothing between the frames that drains the held-back raster launches,
+    no Finish, no readback.  The results are fetched after the one Finish at the end.  Returns the final window (RGBA8), the
+    backend's statistics and the list of per-frame tap results (GL.tap_result dicts, frame 0 first).  libwrhip only."""
+    gl = GL(backend_path)
+    assert gl.is_wrhip, "render_streamed_tapped: taps are a libwrhip addition"
+    w, h = frames[0].width, frames[0].height
+    r = Renderer(gl, w, h)
+    window = gl.WrhipGetFramebufferTexture(0)
+    tickets = []
+    for f in frames:
+        assert (f.width, f.height) == (w, h), "render_streamed_tapped: one window size"
+        r.render(f)
+        tickets.append(gl.tap_texture(window))
+    r.finish()
+    err = gl.GetError()
+    assert all(t >= 0 for t in tickets), tickets
+    taps = [gl.tap_result(t) for t in tickets]
+    px = r.read_pixels()
+    stats = gl.stats()
+    stats["gl_error"] = int(err)
+    r.destroy()
+    return px, stats, taps
