@@ -278,13 +278,15 @@ WR_DEVICE void wr_quad_row_edges(const WrQuadRec& Q, int si, int y, WrQuadRowCac
     if (C) *C = L;
     return;
   }
+  // (the z / w slots are in use: perspective, or a second varying -- brush_mix_blend, brush_yuv_image, ps_quad_mask's vClipLocalPos.w)
+  const bool zw = Q.pad || Q.base_kind == WR_PK_MIX_BLEND || Q.base_kind == WR_PK_YUV || (Q.base_kind == WR_PK_QUAD_MASK && Q.clip.proj != 0);
   const int dy = C ? y - C->y : 0;
   if (C && C->si == si && dy > 0 && dy <= 8) {
     L = *C;
     for (int i = 0; i < dy; i++) {
       L.xl = L.xl + S.ls; L.xr = L.xr + S.rs;
       L.lu = L.lu + S.luvs[0]; L.lv = L.lv + S.luvs[1]; L.ru = L.ru + S.ruvs[0]; L.rv = L.rv + S.ruvs[1];
-      if (Q.pad || Q.base_kind == WR_PK_MIX_BLEND || Q.base_kind == WR_PK_YUV) {
+      if (zw) {
         L.wl = L.wl + Q.persp.lws[si]; L.wr = L.wr + Q.persp.rws[si];
         L.zl = L.zl + Q.persp.lzs[si]; L.zr = L.zr + Q.persp.rzs[si];
       }
@@ -294,7 +296,7 @@ WR_DEVICE void wr_quad_row_edges(const WrQuadRec& Q, int si, int y, WrQuadRowCac
     L.lu = wr_accum(S.luv[0], S.luvs[0], y - S.lrow); L.lv = wr_accum(S.luv[1], S.luvs[1], y - S.lrow);
     L.ru = wr_accum(S.ruv[0], S.ruvs[0], y - S.rrow); L.rv = wr_accum(S.ruv[1], S.ruvs[1], y - S.rrow);
     L.wl = L.wr = L.zl = L.zr = 0.0f;
-    if (Q.pad || Q.base_kind == WR_PK_MIX_BLEND || Q.base_kind == WR_PK_YUV) {
+    if (zw) {
       L.wl = wr_accum(Q.persp.lw[si], Q.persp.lws[si], y - S.lrow); L.wr = wr_accum(Q.persp.rw[si], Q.persp.rws[si], y - S.rrow);
       L.zl = wr_accum(Q.persp.lz[si], Q.persp.lzs[si], y - S.lrow); L.zr = wr_accum(Q.persp.rz[si], Q.persp.rzs[si], y - S.rrow);
     }
@@ -425,7 +427,7 @@ __device__ __noinline__ WrGrad4 wr_gradient_row4(const WrPrim* Pp, const WrGradR
 __device__ __noinline__ WrWide wr_filter_pixel(const WrPrim* Pp, const WrFilterRec* Fp, const WrDrawDesc* D, int x, int y, const WrRuns* runs);
 __device__ __noinline__ WrWide wr_filter_eval(const WrPrim* Pp, const WrFilterRec* Fp, const WrDrawDesc* D, float cu, float cv);
 __device__ __noinline__ WrWide wr_gradient_main(const WrGradRec* Gp, const WrDrawDesc* D, float lu, float lv);
-__device__ __noinline__ WrWide wr_quad_mask_pixel(const WrPrim* Pp, const WrClipRec* Cp, const WrDrawDesc* D, int x, int y, const WrRuns* runs);
+__device__ __noinline__ WrWide wr_quad_mask_pixel(const WrPrim* Pp, const WrClipRec* Cp, const WrDrawDesc* D, int x, int y, const WrRuns* runs, const float* wrow);
 __device__ __noinline__ WrWide wr_yuv_pixel(const WrPrim* Pp, const WrYuvRec* Yp, const WrDrawDesc* D, int x, int y, const WrRuns* runs, const float* row);
 WR_DEVICE void wr_yuv_main_sample(const WrTexDesc& t, int pl, float cu, float cv, float (&fs)[3]);
 WR_DEVICE WrWide wr_yuv_main_rgb(const WrYuvRec& Y, const float (&fs)[3], bool clamp01);
@@ -639,7 +641,11 @@ __device__ __noinline__ unsigned long long wr_quad_tex_pixel_rgba8(const WrPrim*
     }
     else if (Q.base_kind == WR_PK_GRADIENT) src = wr_gradient_row4(&Pl, &Q.grad, D, x, y, runs).v[0];
     else if (Q.base_kind == WR_PK_FILTER) src = wr_filter_pixel(&Pl, &Q.filt, D, x, y, runs);
-    else src = wr_quad_mask_pixel(&Pl, &Q.clip, D, x, y, runs);
+    else {
+      // (a projective clip transform: vClipLocalPos.w of the two edges on this row, from the walk's z slots)
+      const float wrow[2] = {E.zl, E.zr};
+      src = wr_quad_mask_pixel(&Pl, &Q.clip, D, x, y, runs, Q.clip.proj ? wrow : nullptr);
+    }
   } else if (Q.base_kind == WR_PK_TEX_REPEAT && Pl.dual && Pl.blend == WR_BLEND_DUAL_SRC) {
     // the dual-source REPETITION key on an anti-aliased (or rotated) prim: no span shader under this key, every pixel runs main() --
     // the repeated uv of wr_repeat_dual_pixel from this row's edge interpolants -- and the blend takes both colours and the coverage
@@ -2117,7 +2123,9 @@ WR_DEVICE float wr_clip_dist(const WrClipRec& C, float px, float py) {
 
 // ps_quad_mask fragment (ps_quad.glsl:399-415, ps_quad_mask.glsl:167-200): one pixel of main(), which
 // runs four pixels at a time -- fwidth() of the chunk is |lane1 - lane0| in x plus in y (glsl.h:765-768).
-__device__ __noinline__ WrWide wr_quad_mask_pixel(const WrPrim* Pp, const WrClipRec* Cp, const WrDrawDesc* D, int x, int y, const WrRuns* runs = nullptr) {
+// `wrow`: a row of a general quad under a projective clip transform (C.proj) -- vClipLocalPos.w of the left and right edge on this row.
+__device__ __noinline__ WrWide wr_quad_mask_pixel(const WrPrim* Pp, const WrClipRec* Cp, const WrDrawDesc* D, int x, int y, const WrRuns* runs = nullptr,
+                                                  const float* wrow = nullptr) {
   const WrPrim& P = *Pp;
   const WrClipRec& C = *Cp;
   const WrTexRow r = wr_tex_row(P, D->tex[0], y, runs, x);   // span == 0 for this kind: interpolants only (of the depth run holding x)
@@ -2126,8 +2134,22 @@ __device__ __noinline__ WrWide wr_quad_mask_pixel(const WrPrim* Pp, const WrClip
   wr_tex_tail_uv(P, r, n0, f0x, f0y);
   wr_tex_tail_uv(P, r, n0 + 1, f1x, f1y);
   wr_tex_tail_uv(P, r, n, qx, qy);
-  const float wv = C.w;
-  f0x = f0x / wv; f0y = f0y / wv; f1x = f1x / wv; f1y = f1y / wv; qx = qx / wv; qy = qy / wv;   // vClipLocalPos.xy / vClipLocalPos.w
+  float w0 = C.w, w1 = C.w, wq = C.w;
+  if (C.proj) {
+    // a projective clip transform: .w is a varying like .xy -- the same walk on its edges (init_interp lane, one step per chunk,
+    // restarted at depth runs), divided per pixel and for lanes 0 / 1 of the chunk (fwidth of the divided position)
+    WrPrim P2 = P;
+    P2.uvL0[0] = wrow ? wrow[0] : C.wv[0]; P2.uvLs[0] = wrow ? 0.0f : C.wv[1];
+    P2.uvR0[0] = wrow ? wrow[1] : C.wv[2]; P2.uvRs[0] = wrow ? 0.0f : C.wv[3];
+    P2.uvL0[1] = P2.uvLs[1] = P2.uvR0[1] = P2.uvRs[1] = 0.0f;
+    P2.rows_linear = 0;
+    const WrTexRow r2 = wr_tex_row(P2, D->tex[0], y, runs, x);
+    float unused;
+    wr_tex_tail_uv(P2, r2, n0, w0, unused);
+    wr_tex_tail_uv(P2, r2, n0 + 1, w1, unused);
+    wr_tex_tail_uv(P2, r2, n, wq, unused);
+  }
+  f0x = f0x / w0; f0y = f0y / w0; f1x = f1x / w1; f1y = f1y / w1; qx = qx / wq; qy = qy / wq;   // vClipLocalPos.xy / vClipLocalPos.w
   return wr_quad_mask_eval(C, f0x, f0y, f1x, f1y, qx, qy);
 }
 // ... from clip_local_pos of the pixel (qx, qy) and of lanes 0 / 1 of its chunk (fwidth) on

@@ -622,7 +622,7 @@ struct WrVsOut {
   float u2[4], v2[4];  // a second interpolated vec2 varying (WR_PK_BOX_SHADOW: vLocalPos.xy)
   float u3[4], v3[4];  // a third one (WR_PK_YUV: vUv_V)
   int tail_clamp;      // fragment main(): clamps uv to uv_bounds
-  int tail_modulate;   // fragment main(): multiplies texel by colour
+  int tail_modulate;   // fragment main(): multiplies texel by colour (2: and takes .rrrr of the product -- an image mask)
   int blend_override;  // swgl_blendDropShadow / swgl_blendSubpixelText: WrBlend key replacing the draw's (0 = none)
   wf4 blend_color;     // ... and its constant colour (swgl_BlendColorRGBA8)
   int dual; float dual_swz;   // brush_image DUAL_SOURCE_BLENDING (WrPrim::dual / dual_swz)
@@ -848,6 +848,11 @@ WR_DEVICE void wr_vs_ps_quad_textured(const WrDrawDesc& d, const uint8_t* arena,
     for (int i = 0; i < 4; i++) C->bounds[i] = 0.0f;
     C->params[0] = C->params[1] = C->params[2] = 0.0f;
     C->fast = fast ? 1 : 0; C->mode = mode; C->w = cw[0];
+    // (a projective clip transform -- a clip under a 3-D transform seen from the raster space, render_target.rs:1339-1359: w goes
+    // along as a varying of its own, parked in the side record at once)
+    C->proj = (cw[1] != cw[0] || cw[2] != cw[0] || cw[3] != cw[0]) ? 1 : 0;
+    for (int n = 0; n < 4; n++) C->wv[n] = cw[n];
+    C->pad_[0] = C->pad_[1] = C->pad_[2] = 0;
     if (fast) {
       const float hx = 0.5f * (c0.z - c0.x), hy = 0.5f * (c0.w - c0.y), radius = c1.x;
       for (int n = 0; n < 4; n++) { o.u[n] = o.u[n] - (hx + c0.x) * cw[n]; o.v[n] = o.v[n] - (hy + c0.y) * cw[n]; }
@@ -875,16 +880,24 @@ WR_DEVICE void wr_vs_ps_quad_textured(const WrDrawDesc& d, const uint8_t* arena,
     // (QF_IS_MASK is not asked for: the batcher sets it on image masks only, render_target.rs:1272; a rounded-rect mask instance
     // carries APPLY_RENDER_TASK_CLIP or nothing, :1391-1395, and the flag changes nothing here -- pattern_fragment returns
     // vec4(alpha), of which ps_quad.glsl:411-413's .rrrr is the identity)
-    o.kind = (cw[1] != cw[0] || cw[2] != cw[0] || cw[3] != cw[0]) ? WR_PK_UNSUPPORTED : WR_PK_QUAD_MASK;   // affine clip transforms
+    o.kind = WR_PK_QUAD_MASK;
     o.color = prim_color; o.has_color = 0;
     o.tex_slot = WR_S_GPU_BUFFER_F;
     return;
   }
   if (textured) {
-    o.kind = (quad_flags & 16) ? WR_PK_UNSUPPORTED : WR_PK_TEX_RGBA8;
+    o.kind = WR_PK_TEX_RGBA8;
     o.color = wf4{1.f, 1.f, 1.f, 1.f};
     o.has_color = 1;   // swgl_commitTextureLinearColorRGBA8(..., v_color)
     o.tail_clamp = 1; o.tail_modulate = 1;
+    if (quad_flags & 16) {
+      // QF_IS_MASK on a textured quad -- an image mask (render_target.rs:1258-1331): swgl_drawSpanRGBA8 commits nothing for it
+      // (ps_quad_textured.glsl:49-60), every pixel runs main(): the clamped texture() sample times v_color, then .rrrr
+      // (ps_quad.glsl:406-416).  RGBA8 masks, and R8 ones (texture() of an R8 sampler is (r, 0, 0, 1))
+      const int mf = d.tex[WR_S_COLOR0].format;
+      o.kind = (mf == WR_FMT_RGBA8 || mf == WR_FMT_R8) ? WR_PK_TEX_FS : WR_PK_UNSUPPORTED;
+      o.has_color = 0; o.tail_modulate = 2;
+    }
     o.uv_bounds = wf4{(seg_uv.x + 0.5f) / tsx, (seg_uv.y + 0.5f) / tsy, (seg_uv.z - 0.5f) / tsx, (seg_uv.w - 0.5f) / tsy};
     o.tex_slot = WR_S_COLOR0;
   } else {
@@ -2686,7 +2699,8 @@ WR_DEVICE void wr_quad_build_rowtab(const WrTargetDesc* Tp, const WrPrim* Pp, Wr
   const int rows = P.y1 - P.y0;
   if (!T.qtab || !T.qtab_ctl || (T.qtab_pad & 1u) || rows < WR_QTAB_MIN_ROWS || Q.nseg <= 0) return;
   const bool yuv = P.kind == WR_PK_TEX_QUAD && Q.base_kind == WR_PK_YUV;
-  const bool zw = Q.pad != 0 || (P.kind == WR_PK_TEX_QUAD && Q.base_kind == WR_PK_MIX_BLEND) || yuv;
+  const bool zw = Q.pad != 0 || (P.kind == WR_PK_TEX_QUAD && Q.base_kind == WR_PK_MIX_BLEND) || yuv ||
+                  (P.kind == WR_PK_TEX_QUAD && Q.base_kind == WR_PK_QUAD_MASK && Q.clip.proj != 0);
   const int stride = yuv ? 14 : (zw ? 10 : (P.kind == WR_PK_TEX_QUAD ? 6 : 2));
   float* tab = (float*)wr_pool_words(T, (unsigned long long)rows * (unsigned long long)stride);
   if (!tab) return;
@@ -2812,7 +2826,7 @@ WR_DEVICE void wr_finish_prim(const WrDrawDesc& d, int draw_index, const WrVsOut
     // (and brush_opacity, brush_blend, brush_linear_gradient: main() on the perspective-correct varying)
     const bool ptex = ((d.shader == WR_SH_PS_QUAD_TEXTURED || o.persp_div >= 0.0f) && (o.kind == WR_PK_TEX_RGBA8 || o.kind == WR_PK_TEX_FS)) ||
                       ((d.shader == WR_SH_PS_TEXT_RUN || d.shader == WR_SH_PS_TEXT_RUN_DUAL) && (o.kind == WR_PK_TEX_R8 || o.kind == WR_PK_TEX_RGBA8)) ||      /* (the GLYPH_TRANSFORM keys never reach here with a projective transform: their vertex stage reports it) */
-                      o.kind == WR_PK_FILTER || o.kind == WR_PK_MIX_BLEND || (o.kind == WR_PK_QUAD_MASK && auxp->clip.w == 1.0f) ||
+                      o.kind == WR_PK_FILTER || o.kind == WR_PK_MIX_BLEND || (o.kind == WR_PK_QUAD_MASK && auxp->clip.w == 1.0f && !auxp->clip.proj) ||      /* (a projective prim under a projective clip transform: a third varying divided by the prim's w -- reported) */
                       (o.kind == WR_PK_YUV && inside && wr_yuv_persp_ok(o, auxp->yuv)) || (o.kind == WR_PK_TEX_REPEAT && o.persp_div >= 0.0f) || (o.kind == WR_PK_GRADIENT && (d.shader == WR_SH_BRUSH_LINEAR_GRADIENT || d.shader == WR_SH_BRUSH_LINEAR_GRADIENT_ALPHA ||
                                                                               d.shader == WR_SH_PS_QUAD_RADIAL_GRADIENT || d.shader == WR_SH_PS_QUAD_CONIC_GRADIENT));
     if (!(o.kind == WR_PK_SOLID || ptex)) { atomicAdd(&cnt->perspective_prims, 1u); return; }
@@ -2936,6 +2950,11 @@ WR_DEVICE void wr_finish_prim(const WrDrawDesc& d, int draw_index, const WrVsOut
       }
       if (!wr_quad_walk(sx, sy, qu, qv, cx0, cy0, cx1, cy1, aa, o.aa_edges, auxp->quad, bx0, by0, bx1, by1, z4, w4, true, qu2, qv2)) return;
     }
+    else if (o.kind == WR_PK_QUAD_MASK && base.clip.proj) {
+      // ps_quad_mask under a projective clip transform: vClipLocalPos.w rides in the walk's z slots
+      const float none[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (!wr_quad_walk(sx, sy, qu, qv, cx0, cy0, cx1, cy1, aa, o.aa_edges, auxp->quad, bx0, by0, bx1, by1, base.clip.wv, none, true)) return;
+    }
     else if (o.kind == WR_PK_MIX_BLEND) {
       // brush_mix_blend's second varying (v_src_uv) rides in the walk's z / w slots
       if (!wr_quad_walk(sx, sy, qu, qv, cx0, cy0, cx1, cy1, aa, o.aa_edges, auxp->quad, bx0, by0, bx1, by1, o.u2, o.v2, true)) return;
@@ -2969,6 +2988,7 @@ WR_DEVICE void wr_finish_prim(const WrDrawDesc& d, int draw_index, const WrVsOut
     if (o.has_color) { P.flags |= WR_PF_HAS_COLOR; wr_pack_color(o.color, P.color); }
     if (o.tail_clamp) P.flags |= WR_PF_TAIL_CLAMP;
     if (o.tail_modulate) P.flags |= WR_PF_TAIL_MODULATE;
+    if (o.tail_modulate == 2) P.flags |= WR_PF_TAIL_RRRR;
     P.tex_slot = o.tex_slot;
     P.uv_bounds[0] = o.uv_bounds.x; P.uv_bounds[1] = o.uv_bounds.y; P.uv_bounds[2] = o.uv_bounds.z; P.uv_bounds[3] = o.uv_bounds.w;
     P.fcolor[0] = o.color.x; P.fcolor[1] = o.color.y; P.fcolor[2] = o.color.z; P.fcolor[3] = o.color.w;
@@ -3029,6 +3049,7 @@ WR_DEVICE void wr_finish_prim(const WrDrawDesc& d, int draw_index, const WrVsOut
     if (o.has_color) { P.flags |= WR_PF_HAS_COLOR; wr_pack_color(o.color, P.color); }
     if (o.tail_clamp) P.flags |= WR_PF_TAIL_CLAMP;
     if (o.tail_modulate) P.flags |= WR_PF_TAIL_MODULATE;
+    if (o.tail_modulate == 2) P.flags |= WR_PF_TAIL_RRRR;
     P.tex_slot = o.tex_slot;
     P.uv_bounds[0] = o.uv_bounds.x; P.uv_bounds[1] = o.uv_bounds.y;
     P.uv_bounds[2] = o.uv_bounds.z; P.uv_bounds[3] = o.uv_bounds.w;
@@ -3061,6 +3082,14 @@ WR_DEVICE void wr_finish_prim(const WrDrawDesc& d, int draw_index, const WrVsOut
       M.sL0[0] = wr_pick4(o.u2, tl) + dy0 * l2u; M.sL0[1] = wr_pick4(o.v2, tl) + dy0 * l2v;
       M.sR0[0] = wr_pick4(o.u2, tr) + dy0 * r2u; M.sR0[1] = wr_pick4(o.v2, tr) + dy0 * r2v;
       M.sLs[0] = l2u; M.sLs[1] = l2v; M.sRs[0] = r2u; M.sRs[1] = r2v;
+    }
+    if (o.kind == WR_PK_QUAD_MASK && auxp->clip.proj) {
+      // vClipLocalPos.w on the two edges: the vertex values make way for the edge interpolants (WrClipRec::wv)
+      WrClipRec& C = auxp->clip;
+      const float w4[4] = {C.wv[0], C.wv[1], C.wv[2], C.wv[3]};
+      const float lws = (wr_pick4(w4, bl) - wr_pick4(w4, tl)) * yScale, rws = (wr_pick4(w4, br) - wr_pick4(w4, tr)) * yScale;
+      C.wv[0] = wr_pick4(w4, tl) + dy0 * lws; C.wv[1] = lws;
+      C.wv[2] = wr_pick4(w4, tr) + dy0 * rws; C.wv[3] = rws;
     }
     if (o.kind == WR_PK_SVG_FILTER) {
       WrSvgRec& M = auxp->svg;
@@ -3914,6 +3943,7 @@ WR_DEVICE WrWide wr_tex_tail_texel(const WrPrim& P, const WrTexDesc& t, float cu
     tr = float((p >> 16) & 0xFF) * (1.0f / 255.0f); ta = float(p >> 24) * (1.0f / 255.0f);
   }
   if (P.flags & WR_PF_TAIL_MODULATE) { tr = P.fcolor[0] * tr; tg = P.fcolor[1] * tg; tb = P.fcolor[2] * tb; ta = P.fcolor[3] * ta; }
+  if (P.flags & WR_PF_TAIL_RRRR) { tg = tr; tb = tr; ta = tr; }      // output_color.rrrr
   WrWide s;
   uint32_t pc[2];
   wr_pack_color(wf4{tr, tg, tb, ta}, pc);

@@ -332,6 +332,8 @@ enum WrPrimFlags {
   WR_PF_HAS_COLOR = 32,   // textured: modulate by colour (applyColor)
   WR_PF_TAIL_CLAMP = 64,     // main(): clamp uv to uv_bounds before sampling
   WR_PF_TAIL_MODULATE = 128, // main(): multiply texel by fcolor
+  WR_PF_TAIL_RRRR = 256,     // main(): ... then output_color.rrrr (ps_quad.glsl:411-413, QF_IS_MASK on a textured quad: an image mask).
+                             // WrPrim::flags only -- WrRec::kbf carries the low eight bits, and no path that reads a WrRec alone draws such a prim
   WR_PF_MASKED = 8,          // non-solid prim under swgl_clipMask: src = muldiv255(src, mask) ahead of the blend
                              // (blend.h:458-460; shares its bit with WR_PF_CLEAR_COLOR -- clears are never masked)
 };
@@ -439,7 +441,15 @@ struct WrClipRec {
   float center_radius[4][4];  // vClipCenter_Radius_{TL,TR,BR,BL}
   float plane[4][3];        // vClipPlane_{TL,TR,BR,BL}
   float bounds[4];          // vTransformBounds
+  // ps_quad_mask under a projective clip transform: vClipLocalPos.w varies over the prim -- a third interpolated varying.  wv: the four
+  // vertex values as the vertex stage leaves them; once an axis-aligned prim is set up, its edge interpolants (as WrPrim::uv*):
+  // [0] left edge at the first row, [1] its per-row slope, [2] / [3] the right edge's.  On a general quad the run edges travel in the
+  // walk's z slots (WrPerspRec::lz / rz: free, the prim itself is not projective).
+  int32_t proj;             // w is not one constant (then `w` above is vertex 0's)
+  float wv[4];
+  int32_t pad_[3];
 };
+static_assert(sizeof(WrClipRec) <= 184, "WrClipRec lives in WrQuadRec's union beside WrYuvRec: it must not grow WrAux");
 
 // cs_clip_box_shadow flat varyings (cs_clip_box_shadow.glsl:7-14) + the second
 // interpolated varying (vLocalPos.xy; vUv lives in WrPrim's uv interpolants)

@@ -97,11 +97,13 @@ class TextureRef:
 class Step:
     """One DrawElementsInstanced with its GL state."""
 
-    def __init__(self, shader, desc, instances, blend=None, depth="none", textures=None):
+    def __init__(self, shader, desc, instances, blend=None, depth="none", textures=None, scissor=None):
         self.shader, self.desc, self.instances = shader, desc, instances
         self.blend = blend          # None (blend off) or Device.BLEND_MODES key
         self.depth = depth          # "opaque" | "alpha" | "none"
         self.textures = textures or {}   # slot -> TextureRef
+        self.scissor = scissor      # None, or (x, y, w, h) in target pixels: this draw alone is scissored to it (the
+                                    # *_with_scissor batches of a clip in another coordinate system, renderer/mod.rs:2335-2377)
 
 
 class Target:

@@ -28,6 +28,7 @@ class Renderer:
         self.textures = {}       # TextureRef.name -> device.Texture
         self.data_tex = {}       # sampler name -> (device.Texture, rows)
         self.frame_count = 0
+        self._scissor = None     # (x, y, w, h) the bound target is scissored to, None: scissor test off
         d = self.device
         # dummy 1x1 white texture bound for TextureSource::Invalid/Dummy
         # (renderer/mod.rs:1063-1090 dummy cache texture)
@@ -126,7 +127,20 @@ class Renderer:
         vao = d.create_vao(desc)
         d.bind_program(prog, projection)
         self._bind_step_textures(step)
+        sc = step.scissor
+        if sc is None:
+            d.draw_instanced_batch(vao, step.instances)
+            return
+        # a batch drawn under a scissor of its own (mod.rs:2335-2377: enable_scissor, set_scissor_rect, draw, disable_scissor);
+        # what the target was scissored to before is back afterwards
+        prev = self._scissor
+        self.gl.Enable(G.GL_SCISSOR_TEST)
+        self.gl.SetScissor(int(sc[0]), int(sc[1]), int(sc[2]), int(sc[3]))
         d.draw_instanced_batch(vao, step.instances)
+        if prev is None:
+            self.gl.Disable(G.GL_SCISSOR_TEST)
+        else:
+            self.gl.SetScissor(*prev)
 
     def draw_picture_cache_target(self, target, valid_rect=None):
         """Renderer::draw_picture_cache_target + draw_alpha_batch_container (renderer/mod.rs:2669-2968).  `valid_rect`: the
@@ -145,7 +159,8 @@ class Renderer:
         uses_scissor = valid_rect is not None and tuple(valid_rect) != (0, 0, tex.width, tex.height)
         if uses_scissor:
             self.gl.Enable(G.GL_SCISSOR_TEST)
-            self.gl.SetScissor(valid_rect[0], valid_rect[1], valid_rect[2] - valid_rect[0], valid_rect[3] - valid_rect[1])
+            self._scissor = (valid_rect[0], valid_rect[1], valid_rect[2] - valid_rect[0], valid_rect[3] - valid_rect[1])
+            self.gl.SetScissor(*self._scissor)
         if target.opaque:
             d.set_blend(False)
             d.enable_depth(G.GL_LEQUAL)
@@ -167,6 +182,7 @@ class Renderer:
         d.disable_depth()
         if uses_scissor:
             self.gl.Disable(G.GL_SCISSOR_TEST)
+            self._scissor = None
         d.invalidate_depth_target()
 
     def draw_offscreen_target(self, target):

@@ -1685,10 +1685,13 @@ def filter_grid(width=1024, height=1024, n=72, seed=71, atlas=1024, tile_filter=
 # ps_quad_mask: rounded-rectangle clips applied to quads.  The quad pattern is drawn first
 # (ps_quad_textured, solid colour), then one MaskInstance per clip multiplies the same pixels by the
 # clip's coverage (renderer: set_blend_mode_multiply; quad.rs / gpu_types.rs:618-624).
-def quad_masks(width=1024, height=1024, n=90, seed=81, tile_filter=None, fractional=True, only=None, rotate=False, perspective=False):
+def quad_masks(width=1024, height=1024, n=90, seed=81, tile_filter=None, fractional=True, only=None, rotate=False, perspective=False,
+               clip_projective=False, size=(48, 360)):
+    """size: the prims' smallest and largest extent.  clip_projective: two of every three clips live under a projective clip transform (a clip under a 3-D transform seen from the
+    raster space, render_target.rs:1339-1359): vClipLocalPos.w varies over the prim, within [0.5, 2] at its corners."""
     from .frame import QF_APPLY_DEVICE_CLIP
     QF_IS_MASK = 16
-    rng, rects = random_rects(n, width, height, 48, 360, seed, fractional)
+    rng, rects = random_rects(n, width, height, size[0], size[1], seed, fractional)
     rgb = rng.integers(0, 256, size=(n, 3), dtype=np.uint8)
     alpha = np.round(rng.uniform(0.4, 1.0, size=n) * 255).astype(np.uint8)
     colors = premultiply(np.concatenate([rgb, alpha[:, None]], axis=1))
@@ -1712,6 +1715,20 @@ def quad_masks(width=1024, height=1024, n=90, seed=81, tile_filter=None, fractio
             addr = frame.gpu_buffer_f.push([list(cr), rad[0:4], rad[4:8], [mode, 0.0, 0.0, 0.0]])
             clips.append((addr, False))
     tids = [0] * n
+    ctids = [0] * n      # clip transform ids (the MaskInstance's first clip word)
+    if clip_projective:
+        crng = np.random.default_rng(seed + 7919)        # (a generator of its own: the default scene draws what it always drew)
+        for i in range(n):
+            if i % 3 == 0:
+                continue
+            x0, y0, x1, y1 = [float(v) for v in rects[i]]
+            cx, cy = (x0 + x1) / 2, (y0 + y1) / 2
+            th = float(crng.uniform(-0.25, 0.25))
+            a = np.array([[np.cos(th), -np.sin(th)], [np.sin(th), np.cos(th)]], np.float64)
+            m = projective_about(a, cx, cy, float(np.hypot(x1 - x0, y1 - y0)) * 0.5, crng, strength=(0.2, 0.45))
+            wc = [float((m @ np.array([px_, py_, 0.0, 1.0]))[3]) for px_ in (x0, x1) for py_ in (y0, y1)]
+            assert all(0.5 <= w_ <= 2.0 for w_ in wc) and max(wc) - min(wc) > 0.05, wc
+            ctids[i] = frame.add_transform(m.T.astype(np.float32), np.linalg.inv(m).T.astype(np.float32), axis_aligned=False)
     bounds = np.array(rects, np.float64)
     if rotate:       # quads (and the clips that live in their space) under a rotation / skew
         for i in range(n):
@@ -1749,9 +1766,141 @@ def quad_masks(width=1024, height=1024, n=90, seed=81, tile_filter=None, fractio
                 m = frame.quad_instance(rects[i], big, (1.0, 1.0, 1.0, 1.0), int(i + 1), task,
                                     quad_flags=QF_APPLY_DEVICE_CLIP | QF_IS_MASK)
             addr, fast = clips[i]
-            inst = np.array([m + [0, addr, int(i % 4 == 1), 0]], dtype=np.int32)     # clip transform 0 (identity), address, space
+            inst = np.array([m + [ctids[i], addr, int(i % 4 == 1), 0]], dtype=np.int32)     # clip transform (0: identity), address, space
             target.alpha.append(Step("ps_quad_mask FAST_PATH" if fast else "ps_quad_mask", "MASK", inst,
                                      "Multiply", "alpha", textures={}))
+        targets.append(target)
+        rect = (float(x0), float(y0), float(x1), float(y1))
+        clip = (float(x0), float(y0), float(min(x1, width)), float(min(y1, height)))
+        frame.composite_tiles.append(CompositeTile(tex, rect, clip, opaque=True))
+    frame.passes.append(targets)
+    return frame
+
+
+# Image masks (ClipItemKind::Image, CSS mask-image; render_target.rs:1258-1331).  The quad pattern is drawn first, then one
+# ps_quad_textured instance per visible mask tile multiplies the same pixels by the mask: QuadFlags::IS_MASK (with
+# APPLY_RENDER_TASK_CLIP in the prim's own coordinate system), EdgeAaSegmentMask::empty(), white base colour, and ONE segment that
+# carries the tile's rect and its uv rect.  The fragment stage takes .rrrr of colour x texel (ps_quad.glsl:406-416) and swgl has
+# no span shader for it (ps_quad_textured.glsl:49-60): every pixel runs main().  A clip in another coordinate system is drawn
+# under a scissor (image_mask_instances_with_scissor, renderer/mod.rs:2335-2377).
+def mask_image_atlas(rng, size=384, count=12):
+    """`count` mask images of 20x20 .. 64x64 texels shelf-packed into a size x size atlas of INDEPENDENT random channels (bytes in
+    B, G, R, A order -- no grey, no premultiplication: .rrrr differs from any other swizzle nearly everywhere); the last image
+    touches the atlas's last row and column.  -> pixels, [(x0, y0, x1, y1) texels]"""
+    pix = rng.integers(0, 256, size=(size, size, 4), dtype=np.uint8)
+    srcs = []
+    x = y = shelf = 0
+    for i in range(count - 1):
+        w, h = int(rng.integers(20, 65)), int(rng.integers(20, 65))
+        if x + w > size:
+            x, y, shelf = 0, y + shelf, 0
+        assert y + h <= size - 66, "mask_image_atlas: atlas too small"
+        srcs.append((x, y, x + w, y + h))
+        x += w + 2
+        shelf = max(shelf, h + 2)
+    w, h = int(rng.integers(20, 65)), int(rng.integers(20, 65))
+    srcs.append((size - w, size - h, size, size))
+    return pix, srcs
+
+
+def image_masks(width=1024, height=1024, n=60, seed=501, rotate=False, perspective=False, nearest=False, scissor=False, tiled=False,
+                tile_filter=None, only=None, size=(48, 360), atlas=384, atlas_edit=None, masks=True, r8=False, mask_edge_flags=0):
+    """perspective: True, or "clip" (every third transformed prim is cut by the near plane).  scissor: every other mask is drawn
+    under a scissor that cuts it (and the 64-px bins) at odd pixels.  tiled: every mask is split into 2x2 tiles (visible_mask_tiles),
+    one instance each.  atlas_edit: a function of the atlas pixels (B, G, R, A bytes) applied before the upload; masks=False
+    leaves the mask steps out (both for the tests' own checks of what the scene shows).  r8: the atlas is an R8 texture holding the
+    red channel.  mask_edge_flags: the mask instances' edge flags (the batcher passes EdgeAaSegmentMask::empty(); 15 asks for
+    swgl_antiAlias on all four edges, the route plain textured quads take when they are anti-aliased)."""
+    from .frame import QF_IS_MASK
+    rng, rects = random_rects(n, width, height, size[0], size[1], seed, True)
+    rgb = rng.integers(0, 256, size=(n, 3), dtype=np.uint8)
+    alpha = np.round(rng.uniform(0.4, 1.0, size=n) * 255).astype(np.uint8)
+    colors = premultiply(np.concatenate([rgb, alpha[:, None]], axis=1))
+    frame = Frame(width, height, (1.0, 1.0, 1.0, 1.0))
+    pix, srcs = mask_image_atlas(rng, atlas)
+    if atlas_edit is not None:
+        pix = np.ascontiguousarray(atlas_edit(pix.copy()))
+    # (a name of its own per content: a Renderer keeps textures by name from frame to frame)
+    name = f"mask_image_atlas_{seed}_{'nearest' if nearest else 'linear'}{'_r8' if r8 else ''}"
+    if r8:       # an R8 mask texture: texture() gives (r, 0, 0, 1), of which .rrrr is the mask all the same
+        t_atlas = TextureRef(name, atlas, atlas, G.GL_R8, G.GL_NEAREST if nearest else G.GL_LINEAR,
+                             pixels=np.ascontiguousarray(pix[..., 2]), upload_format=G.GL_RED)
+    else:
+        t_atlas = TextureRef(name, atlas, atlas, G.GL_RGBA8, G.GL_NEAREST if nearest else G.GL_LINEAR, pixels=pix,
+                             upload_format=G.GL_BGRA)
+    frame.static_textures.append(t_atlas)
+    rects = np.array(rects, np.float64)
+    prims = []
+    for i in range(n):
+        src = srcs[int(rng.integers(0, len(srcs))) if i % 5 else len(srcs) - 1]     # (every fifth: the image in the atlas's corner)
+        sw, sh = src[2] - src[0], src[3] - src[1]
+        if i % 4 == 3:       # minified: the prim is smaller than its mask image
+            sc = float(rng.uniform(0.35, 0.9))
+            rects[i, 2], rects[i, 3] = rects[i, 0] + sw * sc, rects[i, 1] + sh * sc * float(rng.uniform(0.8, 1.2))
+        x0, y0, x1, y1 = [float(v) for v in rects[i]]
+        inset = float(rng.uniform(0.0, min(x1 - x0, y1 - y0) * 0.2)) if i % 3 else 0.0     # the mask need not cover the prim
+        mr = (x0 + inset, y0 + inset, x1 - inset * 0.5, y1 - inset)
+        # mask tiles: (tile rect, uv rect in texels)
+        if tiled:
+            fx, fy = float(rng.uniform(0.3, 0.7)), float(rng.uniform(0.3, 0.7))
+            ux, uy = src[0] + max(1, min(sw - 1, int(round(sw * fx)))), src[1] + max(1, min(sh - 1, int(round(sh * fy))))
+            px_, py_ = mr[0] + (mr[2] - mr[0]) * (ux - src[0]) / sw, mr[1] + (mr[3] - mr[1]) * (uy - src[1]) / sh
+            tiles = [((mr[0], mr[1], px_, py_), (src[0], src[1], ux, uy)), ((px_, mr[1], mr[2], py_), (ux, src[1], src[2], uy)),
+                     ((mr[0], py_, px_, mr[3]), (src[0], uy, ux, src[3])), ((px_, py_, mr[2], mr[3]), (ux, uy, src[2], src[3]))]
+        else:
+            tiles = [(mr, src)]
+        prims.append((mr, tiles))
+    tids = [0] * n
+    bounds = rects.copy()
+    if rotate or perspective:       # quads (and the masks that live in their space) under a rotation / skew / projective transform
+        for i in range(n):
+            if i % 3 != 2:
+                x0, y0, x1, y1 = rects[i]
+                diag = float(np.hypot(x1 - x0, y1 - y0))
+                tids[i] = rotation_about(frame, rng, (x0 + x1) / 2, (y0 + y1) / 2, i, diag * 0.5 if perspective else None,
+                                         strength=(1.1, 2.6) if (perspective == "clip" and i % 3 == 0) else (0.15, 0.6))
+                bounds[i] = rotated_bounds(tuple(float(v) for v in rects[i]))
+                if perspective:
+                    rr = diag * 1.4 + 4
+                    bounds[i] = ((x0 + x1) / 2 - rr, (y0 + y1) / 2 - rr, (x0 + x1) / 2 + rr, (y0 + y1) / 2 + rr)
+    targets = []
+    for (tx, ty, ox, oy) in tile_grid(width, height):
+        if tile_filter is not None and not tile_filter(tx, ty):
+            continue
+        x0, y0, x1, y1 = ox, oy, ox + TILE_W, oy + TILE_H
+        hit = np.nonzero((bounds[:, 0] < x1) & (bounds[:, 2] > x0) & (bounds[:, 1] < y1) & (bounds[:, 3] > y0))[0]
+        tex = TextureRef(f"tile_{tx}_{ty}", TILE_W, TILE_H, G.GL_RGBA8, G.GL_LINEAR, render_target=True, with_depth=True)
+        target = Target(tex, "picture_tile", clear_color=(1.0, 1.0, 1.0, 1.0), clear_depth=True)
+        task = frame.add_render_task((0.0, 0.0, float(TILE_W), float(TILE_H)), 1.0, (float(ox), float(oy)))
+        for i in hit:
+            if only is not None and i not in only:
+                continue
+            big = (-BIG, -BIG, BIG, BIG)
+            if tids[i]:
+                q = frame.quad_instance(rects[i], big, colors[i], int(i + 1), task, transform_id=tids[i], quad_flags=0, edge_flags=15)
+            else:
+                q = frame.quad_instance(rects[i], big, colors[i], int(i + 1), task)
+            target.alpha.append(Step("ps_quad_textured", "PRIM_INSTANCES", np.array([q], dtype=np.int32),
+                                     "PremultipliedAlpha", "alpha", textures={}))
+            if not masks:
+                continue
+            mr, tiles = prims[i]
+            inst = [frame.quad_instance(mr, mr, (1.0, 1.0, 1.0, 1.0), int(i + 1), task, transform_id=tids[i],
+                                        quad_flags=QF_IS_MASK | (0 if tids[i] else QF_APPLY_DEVICE_CLIP), edge_flags=mask_edge_flags, segment=0,
+                                        segments=[(trect, tuple(float(v) for v in uv))])
+                    for trect, uv in tiles]
+            sc = None
+            if scissor and i % 2 == 0:
+                # a scissor inside the prim's box, in tile pixels, on odd coordinates (no multiple of the 64-px bin)
+                bx0, by0, bx1, by1 = bounds[i] if tids[i] else rects[i]
+                sx0, sy0 = int(bx0 + (bx1 - bx0) * 0.22 - ox) | 1, int(by0 + (by1 - by0) * 0.15 - oy) | 1
+                sx1, sy1 = int(bx0 + (bx1 - bx0) * 0.81 - ox) | 1, int(by0 + (by1 - by0) * 0.9 - oy) | 1
+                sx0, sy0, sx1, sy1 = max(sx0, 1), max(sy0, 1), min(sx1, TILE_W - 1), min(sy1, TILE_H - 1)
+                if sx1 <= sx0 or sy1 <= sy0:
+                    continue            # (the scissor leaves nothing of this mask in this tile)
+                sc = (sx0, sy0, sx1 - sx0, sy1 - sy0)
+            target.alpha.append(Step("ps_quad_textured", "PRIM_INSTANCES", np.array(inst, dtype=np.int32), "Multiply", "alpha",
+                                     textures={0: t_atlas}, scissor=sc))
         targets.append(target)
         rect = (float(x0), float(y0), float(x1), float(y1))
         clip = (float(x0), float(y0), float(min(x1, width)), float(min(y1, height)))
