@@ -2430,14 +2430,14 @@ WR_DEVICE WrRowVals wr_clip_row_vals_wave(const WrPrim& P, int y, int lane, cons
 // the prim and the row only, so the raster stage evaluates it once per wave with the 16 row-owning lanes (next to the row
 // interpolants) and hands it round; a 4-pixel group in a solid phase then costs a compare and a constant.
 struct WrClipRow { float w, aa_range, stx, sty; int n12, n34, corners; };     // n12 = n1 | n2 << 16, n34 likewise, corners = (start + 1) | (end + 1) << 8
-WR_DEVICE WrClipRow wr_clip_row_setup(const WrPrim& P, const WrClipRec& C, const WrRowVals& rv) {
+// `wv`: vLocalPos.w of the row (C.w; under a projective transform the row's own value, WrRowW)
+WR_DEVICE WrClipRow wr_clip_row_setup(const WrPrim& P, const WrClipRec& C, const WrRowVals& rv, const float wv) {
   WrClipRow cr;
   const float su = rv.s[0], sv = rv.s[1];
   const float ou = rv.o[0], ov = rv.o[1];
   const int len = P.x1 - P.x0, span = len >= 4 ? (len & ~3) : 0;
   const float lx0 = ou, lx1 = lx0 + su;
   const float ly0 = ov, ly1 = ly0 + sv;
-  const float wv = C.w;
   const float w = 1.0f / wv;
   const float p0x = lx0 * w, p0y = ly0 * w, p1x = lx1 * w, p1y = ly1 * w;
   const float stx = (su * 4.0f) * w, sty = (sv * 4.0f) * w;
@@ -2501,9 +2501,10 @@ WR_DEVICE WrClipRow wr_clip_row_setup(const WrPrim& P, const WrClipRec& C, const
   cr.n12 = n1 | (n2 << 16); cr.n34 = n3 | (n4 << 16); cr.corners = (start_corner + 1) | ((end_corner + 1) << 8);
   return cr;
 }
+WR_DEVICE WrClipRow wr_clip_row_setup(const WrPrim& P, const WrClipRec& C, const WrRowVals& rv) { return wr_clip_row_setup(P, C, rv, C.w); }
 
 // one pixel (n = x - P.x0) of a cs_clip_rectangle row
-WR_DEVICE uint32_t wr_clip_rect_px(const WrPrim& P, const WrClipRec& C, const WrRowVals& rv, const WrClipRow& cr, int n) {
+WR_DEVICE uint32_t wr_clip_rect_px(const WrPrim& P, const WrClipRec& C, const WrRowVals& rv, const WrClipRow& cr, int n, const float wv) {
   const float su = rv.s[0], sv = rv.s[1];
   const float ou = rv.o[0], ov = rv.o[1];
   const int len = P.x1 - P.x0, span = len >= 4 ? (len & ~3) : 0;
@@ -2511,7 +2512,6 @@ WR_DEVICE uint32_t wr_clip_rect_px(const WrPrim& P, const WrClipRec& C, const Wr
   // the four SIMD lanes of vLocalPos.xy at the span start (init_interp)
   const float lx0 = ou, lx1 = lx0 + su, lx2 = lx1 + su, lx3 = lx2 + su;
   const float ly0 = ov, ly1 = ly0 + sv, ly2 = ly1 + sv, ly3 = ly2 + sv;
-  const float wv = C.w;
   const float w = cr.w, aa_range = cr.aa_range, stx = cr.stx, sty = cr.sty;
   const int n1 = cr.n12 & 0xFFFF, n2 = cr.n12 >> 16, n3 = cr.n34 & 0xFFFF, n4 = cr.n34 >> 16;
   const int start_corner = (cr.corners & 0xFF) - 1, end_corner = (cr.corners >> 8) - 1;
@@ -2572,6 +2572,64 @@ WR_DEVICE uint32_t wr_clip_rect_px(const WrPrim& P, const WrClipRec& C, const Wr
   const float fin = ((1.0f - alpha) - alpha) * mode + alpha;
   return uint32_t(wr_round_pixel(wv > 0.0f ? fin : 0.0f)) & 0xFFFF;
 }
+WR_DEVICE uint32_t wr_clip_rect_px(const WrPrim& P, const WrClipRec& C, const WrRowVals& rv, const WrClipRow& cr, int n) { return wr_clip_rect_px(P, C, rv, cr, n, C.w); }
+
+WR_DEVICE float wr_sel4(float a0, float a1, float a2, float a3, int i) { return i == 0 ? a0 : (i == 1 ? a1 : (i == 2 ? a2 : a3)); }
+
+// ---- cs_clip_* under a projective clip or prim transform (WrClipRec::proj, WrBoxRec::proj) ----
+// vLocalPos.w is a varying like .xy: its left / right edge values on a row are the row-by-row sums of its edge interpolants (wv[]), and
+// the row's origin and step come out of them as the other varyings' do (rasterize.h:1011-1016).  Both span shaders begin with
+// `if (swgl_interpStep(vLocalPos).w != 0.0) return;` -- interp_step is the step of a 4-pixel chunk --, so the decision is the ROW's:
+// where w does not move along the row the span rasteriser runs with the row's own w, elsewhere every chunk of the row runs main().
+struct WrRowW { float o, s; };
+WR_DEVICE WrRowW wr_proj_row_w(const WrPrim& P, const float (&wv)[4], int y) {
+  WrRowW rw;
+  const int k = y - P.y0;
+  const float Lw = wr_accum(wv[0], wv[1], k), Rw = wr_accum(wv[2], wv[3], k);
+  float stepScale = 1.0f / (P.xr - P.xl);
+  if (!wr_isfinite(stepScale)) stepScale = 0.0f;
+  const float start = float(P.x0) + 0.5f - P.xl;
+  rw.s = (Rw - Lw) * stepScale;
+  rw.o = Lw + rw.s * start;
+  return rw;
+}
+WR_DEVICE bool wr_proj_row_steps(const WrRowW& rw) { return rw.s * 4.0f != 0.0f; }
+// One varying of pixel n of a row that main() walks from its first chunk on: the lane's start value (init_interp: o, + s, + s, + s),
+// then one `+= interp_step` per chunk (step_interp_inputs).
+WR_DEVICE float wr_main_walk(float o, float s, int lane, int m) {
+  const float l1 = o + s, l2 = l1 + s, l3 = l2 + s;
+  return wr_accum(wr_sel4(o, l1, l2, l3, lane), (s * 4.0f) * 1.0f, m);
+}
+// cs_clip_rectangle main() (cs_clip_rectangle.glsl:170-199) on pixel n of such a row: vLocalPos.xy / vLocalPos.w per lane, the AA range
+// from lanes 0 / 1 of the pixel's chunk (fwidth of the divided position), 0 where w <= 0
+WR_DEVICE uint32_t wr_clip_rect_main_px(const WrClipRec& C, const WrRowVals& rv, const WrRowW& rw, int n) {
+  const int lane = n & 3, m = n >> 2;
+  const float w0 = wr_main_walk(rw.o, rw.s, 0, m), w1 = wr_main_walk(rw.o, rw.s, 1, m), wq = wr_main_walk(rw.o, rw.s, lane, m);
+  const float f0x = wr_main_walk(rv.o[0], rv.s[0], 0, m) / w0, f0y = wr_main_walk(rv.o[1], rv.s[1], 0, m) / w0;
+  const float f1x = wr_main_walk(rv.o[0], rv.s[0], 1, m) / w1, f1y = wr_main_walk(rv.o[1], rv.s[1], 1, m) / w1;
+  const float qx = wr_main_walk(rv.o[0], rv.s[0], lane, m) / wq, qy = wr_main_walk(rv.o[1], rv.s[1], lane, m) / wq;
+  const float far = 1.0f / (fabsf(f1x - f0x) + fabsf(f1y - f0y));
+  const float dist = wr_clip_dist(C, qx, qy);
+  const float alpha = wr_clamp(0.5f - dist * far, 0.0f, 1.0f);
+  const float fin = ((1.0f - alpha) - alpha) * C.mode + alpha;
+  return uint32_t(wr_round_pixel(wq > 0.0f ? fin : 0.0f)) & 0xFFFF;
+}
+// four pixels (x .. x + 3) of row y of a projective cs_clip_rectangle prim, everything from the prim (the bin raster's route: rows outside
+// the mask-row store, WRHIP_NO_MASK_ROWS)
+__device__ __noinline__ WrRow4 wr_clip_rect_proj_row4(const WrPrim* Pp, const WrClipRec* Cp, int x, int y) {
+  const WrPrim& P = *Pp;
+  const WrRowVals rv = wr_clip_row_vals(P, y);
+  const WrRowW rw = wr_proj_row_w(P, Cp->wv, y);
+  const int len = P.x1 - P.x0;
+  WrRow4 out;
+  if (wr_proj_row_steps(rw)) {
+    for (int i = 0; i < 4; i++) { const int n = x + i - P.x0; out.v[i] = (n < 0 || n >= len) ? 0u : wr_clip_rect_main_px(*Cp, rv, rw, n); }
+    return out;
+  }
+  const WrClipRow cr = wr_clip_row_setup(P, *Cp, rv, rw.o);
+  for (int i = 0; i < 4; i++) out.v[i] = wr_clip_rect_px(P, *Cp, rv, cr, x + i - P.x0, rw.o);
+  return out;
+}
 __device__ __noinline__ WrRow4 wr_clip_rect_row4(const WrPrim* Pp, const WrClipRec* Cp, WrRowVals rv, WrClipRow cr, int x, int y) {
   WrRow4 out;
 #pragma unroll
@@ -2606,12 +2664,23 @@ WR_DEVICE float wr_box_shade(const WrBoxRec& B, const WrTexDesc& t, float ul, fl
   return (alpha - B.mode) * in + B.mode;
 }
 
-WR_DEVICE float wr_sel4(float a0, float a1, float a2, float a3, int i) { return i == 0 ? a0 : (i == 1 ? a1 : (i == 2 ? a2 : a3)); }
-
 // Four horizontally adjacent pixels (x .. x+3) of row y: one span-level setup and
 // one walk of the nine-patch state machine serve all four.
 // row interpolants of a cs_clip_box_shadow prim: c = 0,1 vUv; 2,3 vLocalPos.xy
-__device__ __noinline__ WrRow4 wr_box_shadow_row4(const WrPrim* Pp, const WrBoxRec* Bp, WrRowVals rv, WrBoxRow br, int x, int y) {
+// cs_clip_box_shadow main() (cs_clip_box_shadow.glsl:123-138) on pixel n of a row along which vLocalPos.w steps (see WrRowW): vUv and
+// vLocalPos.xy divided by the lane's own w, 0 where it is <= 0
+WR_DEVICE uint32_t wr_box_shadow_main_px(const WrBoxRec& B, const WrRowVals& rv, const WrRowW& rw, int n) {
+  const WrTexDesc t{B.ptr, int(B.wh & 0xFFFF), int(B.wh >> 16), B.stride, (int16_t)B.format, (int16_t)B.linear, float(B.wh & 0xFFFF), float(B.wh >> 16)};
+  const int lane = n & 3, m = n >> 2;
+  const float wq = wr_main_walk(rw.o, rw.s, lane, m);
+  float v4[4];
+#pragma unroll
+  for (int c = 0; c < 4; c++) v4[c] = wr_main_walk(rv.o[c], rv.s[c], lane, m) / wq;
+  const float r = wr_box_shade(B, t, v4[0], v4[1], v4[2], v4[3]);
+  return uint32_t(wr_round_pixel(wq > 0.0f ? r : 0.0f)) & 0xFFFF;
+}
+// `wv`: vLocalPos.w of the row (B.w; under a projective transform the row's own value)
+WR_DEVICE WrRow4 wr_box_shadow_row4_w(const WrPrim* Pp, const WrBoxRec* Bp, const WrRowVals& rv, const WrBoxRow& br, int x, int y, const float wv) {
   const WrPrim& P = *Pp;
   const WrBoxRec& B = *Bp;
   WrRow4 out;
@@ -2641,13 +2710,13 @@ __device__ __noinline__ WrRow4 wr_box_shadow_row4(const WrPrim* Pp, const WrBoxR
       if (span > 0) a = a + (s4[c] * 4.0f) * (float(span) * 0.25f);
       v4[c] = wr_accum(a, (s4[c] * 4.0f) * 1.0f, m);
     }
-    const float r = wr_box_shade(B, t, v4[0] / B.w, v4[1] / B.w, v4[2] / B.w, v4[3] / B.w);
-    out.v[i] = uint32_t(wr_round_pixel(B.w > 0.0f ? r : 0.0f)) & 0xFFFF;
+    const float r = wr_box_shade(B, t, v4[0] / wv, v4[1] / wv, v4[2] / wv, v4[3] / wv);
+    out.v[i] = uint32_t(wr_round_pixel(wv > 0.0f ? r : 0.0f)) & 0xFFFF;
   }
   // ---- span pixels
   const int first = n0 < 0 ? 0 : n0, last = (n0 + 3 < span - 1) ? n0 + 3 : span - 1;    // my pixels inside [0, span)
   if (first > last) return out;
-  float w = B.w;
+  float w = wv;
   if (w <= 0.0f) return out;                 // swgl_commitSolidR8(0.0): zeros
   w = 1.0f / w;
   float cur[4][4], st[4];        // uv_linear.x, uv_linear.y, local_pos.x, local_pos.y lanes; per-chunk steps
@@ -2778,6 +2847,24 @@ __device__ __noinline__ WrRow4 wr_box_shadow_row4(const WrPrim* Pp, const WrBoxR
     }
   }
   return out;
+}
+
+__device__ __noinline__ WrRow4 wr_box_shadow_row4(const WrPrim* Pp, const WrBoxRec* Bp, WrRowVals rv, WrBoxRow br, int x, int y) {
+  return wr_box_shadow_row4_w(Pp, Bp, rv, br, x, y, Bp->w);
+}
+// four pixels (x .. x + 3) of row y of a projective cs_clip_box_shadow prim, everything from the prim (the bin raster's route)
+__device__ __noinline__ WrRow4 wr_box_shadow_proj_row4(const WrPrim* Pp, const WrBoxRec* Bp, int x, int y) {
+  const WrPrim& P = *Pp;
+  const WrRowVals rv = wr_box_row_vals(P, *Bp, y);
+  const WrRowW rw = wr_proj_row_w(P, Bp->wv, y);
+  const int len = P.x1 - P.x0;
+  if (wr_proj_row_steps(rw)) {
+    WrRow4 out;
+    for (int i = 0; i < 4; i++) { const int n = x + i - P.x0; out.v[i] = (n < 0 || n >= len) ? 0u : wr_box_shadow_main_px(*Bp, rv, rw, n); }
+    return out;
+  }
+  const WrBoxRow br = wr_box_row_setup(P, *Bp, rv, rw.o);      // (xc / vrow are the caller's shortcut: not used here)
+  return wr_box_shadow_row4_w(Pp, Bp, rv, br, x, y, rw.o);
 }
 
 // the one value of the row's u-clamped run (WrBoxRow::xc): stepx is exactly 0 there, so whichever filter the run takes,

@@ -529,6 +529,21 @@ WR_DEVICE void wr_apply_prim(uint32_t (&plo)[4 * R], uint32_t (&phi)[4 * R], uin
   }
   if ((FEAT & WR_FEAT_CLIP) && FMT == WR_FMT_R8 && kind == WR_PK_BOX_SHADOW) {
     const bool anyx = cx[0] || cx[1] || cx[2] || cx[3];
+    if (Ap->box.proj) {
+      // a projective clip or prim transform: the row's w decides between the span shader and main() (WrRowW); none of the shortcuts
+      // below holds (they assume one w), and every group asks the prim for its row
+#pragma unroll
+      for (int j = 0; j < R; j++) {
+        if (!cy[j] || !anyx) continue;
+        const WrRow4 r4 = wr_box_shadow_proj_row4(Pp, &Ap->box, px, py + 4 * j);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int q = 4 * j + i;
+          if (cx[i]) plo[q] = wr_blend_r8(blend, plo[q], r4.v[i]);
+        }
+      }
+      return;
+    }
 #ifndef WRHIP_HOSTSIM
     const WrRowVals mine = wr_box_row_vals(*Pp, Ap->box, wy0 + ((px - wx0) >> 2));   // lane (l & 15) owns strip row (l & 15)
     WrBoxRow mine_br = wr_box_row_setup(*Pp, Ap->box, mine);
@@ -574,6 +589,19 @@ WR_DEVICE void wr_apply_prim(uint32_t (&plo)[4 * R], uint32_t (&phi)[4 * R], uin
   }
   if ((FEAT & WR_FEAT_CLIP) && FMT == WR_FMT_R8 && kind == WR_PK_CLIP_RECT) {
     const bool anyx = cx[0] || cx[1] || cx[2] || cx[3];
+    if (Ap->clip.proj) {      // (as for cs_clip_box_shadow above)
+#pragma unroll
+      for (int j = 0; j < R; j++) {
+        if (!cy[j] || !anyx) continue;
+        const WrRow4 r4 = wr_clip_rect_proj_row4(Pp, &Ap->clip, px, py + 4 * j);
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+          const int q = 4 * j + i;
+          if (cx[i]) plo[q] = wr_blend_r8(blend, plo[q], r4.v[i]);
+        }
+      }
+      return;
+    }
 #ifndef WRHIP_HOSTSIM
     const WrRowVals mine = wr_clip_row_vals(*Pp, wy0 + ((px - wx0) >> 2));
     const WrClipRow mine_cr = wr_clip_row_setup(*Pp, Ap->clip, mine);

@@ -9,10 +9,14 @@
 WR_DEVICE void wr_fill_lanes(uint8_t* dst, int a, int b, uint32_t v, int lane, int stride = 64) {      // lane: + 64 * part
   for (int n = a + lane; n < b; n += stride) dst[n] = (uint8_t)v;
 }
+__device__ __noinline__ void wr_box_shadow_main_row(const WrPrim* Pp, const WrBoxRec* Bp, WrRowVals rv, float ow, float sw, int n0, int stride, uint8_t* dst);
+__device__ __noinline__ void wr_clip_rect_proj_row(const WrPrim* Pp, const WrClipRec* Cp, float ox, float sx, float oy, float sy, int y, int n0, int stride, uint8_t* dst);
 // cs_clip_box_shadow (cs_clip_box_shadow.glsl:150-324): the walk of wr_box_shadow_row4 over the whole row
+// `wv`: vLocalPos.w of the row (B.w; under a projective transform the row's own value)
 WR_DEVICE void wr_box_shadow_row_lanes(const WrPrim& P, const WrBoxRec& B, const WrRowVals& rv, const WrBoxRow& br, int lane, uint8_t* dst,
-                                       int part = 0, int parts = 1) {
+                                       int part, int parts, const float wv, const float wstep = 0.0f) {
   const int wl = lane + 64 * part, ws = 64 * parts;      // this wave's share of a run: pixels wl, wl + ws, ..
+  if (wstep * 4.0f != 0.0f) { wr_box_shadow_main_row(&P, &B, rv, wv, wstep, wl, ws, dst); return; }      // (WrRowW: the row has no sectors)
   const WrTexDesc t{B.ptr, int(B.wh & 0xFFFF), int(B.wh >> 16), B.stride, (int16_t)B.format, (int16_t)B.linear, float(B.wh & 0xFFFF), float(B.wh >> 16)};
   float o4[4], s4[4];
 #pragma unroll
@@ -34,11 +38,11 @@ WR_DEVICE void wr_box_shadow_row_lanes(const WrPrim& P, const WrBoxRec& B, const
       if (span > 0) a = a + (s4[c] * 4.0f) * (float(span) * 0.25f);
       v4[c] = wr_accum(a, (s4[c] * 4.0f) * 1.0f, m);
     }
-    const float r = wr_box_shade(B, t, v4[0] / B.w, v4[1] / B.w, v4[2] / B.w, v4[3] / B.w);
-    dst[n] = (uint8_t)(uint32_t(wr_round_pixel(B.w > 0.0f ? r : 0.0f)) & 0xFFFF);
+    const float r = wr_box_shade(B, t, v4[0] / wv, v4[1] / wv, v4[2] / wv, v4[3] / wv);
+    dst[n] = (uint8_t)(uint32_t(wr_round_pixel(wv > 0.0f ? r : 0.0f)) & 0xFFFF);
   }
   if (span <= 0) return;
-  float w = B.w;
+  float w = wv;
   if (w <= 0.0f) { wr_fill_lanes(dst, 0, span, 0, wl, ws); return; }      // swgl_commitSolidR8(0.0)
   w = 1.0f / w;
   float cur[4][4], st[4];
@@ -201,13 +205,15 @@ WR_DEVICE void wr_clip_rect_row_lanes(const WrPrim* Pp, const WrClipRec* Cp, int
 #else
   const WrRowVals rv = wr_clip_row_vals_wave(P, y, lane, tabs);      // (y is wave-uniform here)
 #endif
-  const WrClipRow cr = wr_clip_row_setup(P, *Cp, rv);
   const int len = P.x1 - P.x0, span = len >= 4 ? (len & ~3) : 0, S = span >> 2;
+  const float wv = Cp->w;
+  const WrClipRow cr = wr_clip_row_setup(P, *Cp, rv, wv);
   const int n2 = cr.n12 >> 16, n4 = cr.n34 >> 16;
   const int b1 = cr.n12 & 0xFFFF, b2 = b1 + n2, b3 = b2 + (cr.n34 & 0xFFFF), b4 = b3 + n4;
   const float mode = Cp->mode;
-  if (!(Cp->w > 0.0f)) {                        // (degenerate w: every pixel through the general function)
-    for (int n = wl; n < len; n += ws) dst[n] = (uint8_t)wr_clip_rect_px(P, *Cp, rv, cr, n);
+  if (!(wv > 0.0f)) {                           // (degenerate w: every pixel through the general function)
+    if (Cp->proj) { wr_clip_rect_proj_row(Pp, Cp, rv.o[0], rv.s[0], rv.o[1], rv.s[1], y, wl, ws, dst); return; }      // (C.w of such a prim is -1: wr_vs_cs_clip_rect)
+    for (int n = wl; n < len; n += ws) dst[n] = (uint8_t)wr_clip_rect_px(P, *Cp, rv, cr, n, wv);
     return;
   }
   // the solid phases [0, b1) clear, [b2, b3) opaque, [b4, S) clear: constants, a chunk per lane
@@ -223,8 +229,35 @@ WR_DEVICE void wr_clip_rect_row_lanes(const WrPrim* Pp, const WrClipRec* Cp, int
   const int na = 4 * n2, nb = 4 * n4, nt = len - span;
   for (int p = wl; p < na + nb + nt; p += ws) {
     const int n = p < na ? 4 * b1 + p : (p < na + nb ? 4 * b3 + (p - na) : span + (p - na - nb));
-    dst[n] = (uint8_t)wr_clip_rect_px(P, *Cp, rv, cr, n);
+    dst[n] = (uint8_t)wr_clip_rect_px(P, *Cp, rv, cr, n, wv);
   }
+}
+// One row of a cs_clip_rectangle prim under a projective clip or prim transform (WrRowW), for the whole wave (pixels n0, n0 + stride, .. are
+// this lane's): the row's w from its edge sums (the walk: such a prim has no row-sum tables); then, where w steps along the row, the row
+// has no phases -- main() on every pixel, a pixel per lane, one division per varying and lane; any other row is the span rasteriser's
+// with the row's own w, again a pixel per lane.  Out of line, behind the branch for a w that is not positive (the vertex stage leaves
+// -1 in WrClipRec::w of these prims): the rows of every other prim keep their registers -- with the branch at the top of the row loop
+// the kernel's frame grew from 48 to 80 bytes, here it stays.
+__device__ __noinline__ void wr_clip_rect_proj_row(const WrPrim* Pp, const WrClipRec* Cp, float ox, float sx, float oy, float sy, int y, int n0, int stride, uint8_t* dst) {
+  WrRowVals rv;
+  rv.o[0] = ox; rv.s[0] = sx; rv.o[1] = oy; rv.s[1] = sy; rv.o[2] = rv.o[3] = rv.s[2] = rv.s[3] = 0.0f;
+  const WrRowW rw = wr_proj_row_w(*Pp, Cp->wv, y);
+  const int len = Pp->x1 - Pp->x0;
+  if (wr_proj_row_steps(rw)) {
+    for (int n = n0; n < len; n += stride) dst[n] = (uint8_t)wr_clip_rect_main_px(*Cp, rv, rw, n);
+    return;
+  }
+  const WrClipRow cr = wr_clip_row_setup(*Pp, *Cp, rv, rw.o);
+  for (int n = n0; n < len; n += stride) dst[n] = (uint8_t)wr_clip_rect_px(*Pp, *Cp, rv, cr, n, rw.o);
+}
+// cs_clip_box_shadow under such a transform: the row's w (out of line: two row-sum walks), and a row along which it steps -- main() on
+// every pixel, a pixel per lane.  The other rows are the nine-patch walk of wr_box_shadow_row_lanes with the row's own w (as a callee
+// of this kernel a second copy of that walk takes 350-460 bytes of frame).
+__device__ __noinline__ WrRowW wr_box_shadow_proj_w(const WrPrim* Pp, const WrBoxRec* Bp, int y) { return wr_proj_row_w(*Pp, Bp->wv, y); }
+__device__ __noinline__ void wr_box_shadow_main_row(const WrPrim* Pp, const WrBoxRec* Bp, WrRowVals rv, float ow, float sw, int n0, int stride, uint8_t* dst) {
+  WrRowW rw; rw.o = ow; rw.s = sw;
+  const int len = Pp->x1 - Pp->x0;
+  for (int n = n0; n < len; n += stride) dst[n] = (uint8_t)wr_box_shadow_main_px(*Bp, rv, rw, n);
 }
 #if defined(WR_ROWS_TIMING) && !defined(WRHIP_HOSTSIM)
 __device__ unsigned long long wr_rows_times[4096 * 8];      // debug build: phase timestamps of the first item of the launch's first 4096 waves
@@ -295,17 +328,30 @@ WR_DEVICE void wr_mask_rows_body(const WrTargetDesc* __restrict__ targets, int b
     uint32_t my_off = rows_at + uint32_t(y - Pp->y0) * sl.pitch;
     WrRowVals brv;
     WrBoxRow bbr;
+    float bwv = 0.0f, bws = 0.0f;
     if (Pp->kind == WR_PK_BOX_SHADOW) {
       // the rows of a nine-patch's middle band are identical: a row whose key equals the key of the prim's middle row (left
       // in the slot by the setup stage) points at that row's bytes instead of being evaluated (wr_box_row_key)
       const int yc = Pp->y0 + (nrows >> 1);
+      bwv = aux[sl.prim].box.w;
+      if (!(bwv > 0.0f) && aux[sl.prim].box.proj) {
+        // a projective clip or prim transform (the vertex stage leaves -1 in WrBoxRec::w: no row has a valid key, so none stands for
+        // another -- two rows with different w are not the same row): the row's own w, and whether it steps along the row
+        const WrRowW rw = wr_box_shadow_proj_w(Pp, &aux[sl.prim].box, y);
+#ifdef WRHIP_HOSTSIM
+        bwv = rw.o; bws = rw.s;
+#else
+        bwv = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rw.o)));      // (wave-uniform)
+        bws = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, rw.s)));
+#endif
+      }
 #ifdef WRHIP_HOSTSIM
       brv = wr_box_row_vals(*Pp, aux[sl.prim].box, y, tabs);
 #else
       brv = wr_box_row_vals_wave(*Pp, aux[sl.prim].box, y, lane, tabs);
 #endif
       WR_RT(3);
-      bbr = wr_box_row_setup(*Pp, aux[sl.prim].box, brv);
+      bbr = wr_box_row_setup(*Pp, aux[sl.prim].box, brv, bwv);
       WR_RT(4);
       if (y != yc && wr_box_keys_equal(wr_box_row_key(*Pp, aux[sl.prim].box, brv, bbr), slots[si].key)) {
         if (lane == 0 && part == 0) ((uint32_t*)pbase)[y - Pp->y0] = rows_at + uint32_t(yc - Pp->y0) * sl.pitch;
@@ -320,7 +366,7 @@ WR_DEVICE void wr_mask_rows_body(const WrTargetDesc* __restrict__ targets, int b
     }
     uint8_t* dst = pbase + my_off + (Pp->x0 & 3);
     WR_RT(5);
-    if (Pp->kind == WR_PK_BOX_SHADOW) wr_box_shadow_row_lanes(*Pp, aux[sl.prim].box, brv, bbr, lane, dst, part, parts);
+    if (Pp->kind == WR_PK_BOX_SHADOW) wr_box_shadow_row_lanes(*Pp, aux[sl.prim].box, brv, bbr, lane, dst, part, parts, bwv, bws);
     else wr_clip_rect_row_lanes(Pp, &aux[sl.prim].clip, y, lane, dst, part, parts, tabs);
     WR_RT(6);
 #if defined(WR_ROWS_TIMING) && !defined(WRHIP_HOSTSIM)

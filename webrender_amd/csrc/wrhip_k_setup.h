@@ -2155,8 +2155,12 @@ WR_DEVICE void wr_vs_cs_clip_rect(const WrDrawDesc& d, const uint8_t* arena, int
   o.color = wf4{0, 0, 0, 0};
   o.uv_bounds = wf4{0, 0, 0, 0};
   o.tex_slot = WR_S_COLOR0;
-  // perspective-varying w is not handled by the span rasteriser either (:226-228 falls back to main()): "next"
-  o.kind = (lw[1] == lw[0] && lw[2] == lw[0] && lw[3] == lw[0]) ? WR_PK_CLIP_RECT : WR_PK_UNSUPPORTED;
+  // a projective clip or prim transform: .w is a varying like .xy; the span rasteriser declines every row along which it steps (:225-227)
+  // and main() divides per pixel (wr_clip_rect_main_px)
+  C.proj = (lw[1] == lw[0] && lw[2] == lw[0] && lw[3] == lw[0]) ? 0 : 1;
+  if (C.proj) C.w = -1.0f;      // (no positive w: nothing that assumes ONE w -- shortcuts, the rows kernel's phases -- applies; the values are wv's)
+  C.wv[0] = lw[0]; C.wv[1] = lw[1]; C.wv[2] = lw[2]; C.wv[3] = lw[3];
+  o.kind = WR_PK_CLIP_RECT;
 }
 
 // cs_clip_box_shadow.glsl:59-119 (vertex stage)
@@ -2206,8 +2210,11 @@ WR_DEVICE void wr_vs_cs_clip_box_shadow(const WrDrawDesc& d, const uint8_t* aren
   o.color = wf4{0, 0, 0, 0};
   o.uv_bounds = wf4{0, 0, 0, 0};
   o.tex_slot = WR_S_COLOR0;
-  const bool affine = lw[1] == lw[0] && lw[2] == lw[0] && lw[3] == lw[0];
-  o.kind = (affine && tex.format == WR_FMT_R8 && tex.ptr) ? WR_PK_BOX_SHADOW : WR_PK_UNSUPPORTED;
+  // (a projective clip or prim transform: as cs_clip_rectangle's vertex stage; cs_clip_box_shadow.glsl:152-154, wr_box_shadow_main_px)
+  B.proj = (lw[1] == lw[0] && lw[2] == lw[0] && lw[3] == lw[0]) ? 0 : 1;
+  if (B.proj) B.w = -1.0f;      // (as WrClipRec::w; also, no row of the prim has a valid key -- wr_box_row_key -- so none stands for another)
+  B.wv[0] = lw[0]; B.wv[1] = lw[1]; B.wv[2] = lw[2]; B.wv[3] = lw[3];
+  o.kind = (tex.format == WR_FMT_R8 && tex.ptr) ? WR_PK_BOX_SHADOW : WR_PK_UNSUPPORTED;
 }
 
 // composite.glsl:73-159
@@ -3083,8 +3090,8 @@ WR_DEVICE void wr_finish_prim(const WrDrawDesc& d, int draw_index, const WrVsOut
       M.sR0[0] = wr_pick4(o.u2, tr) + dy0 * r2u; M.sR0[1] = wr_pick4(o.v2, tr) + dy0 * r2v;
       M.sLs[0] = l2u; M.sLs[1] = l2v; M.sRs[0] = r2u; M.sRs[1] = r2v;
     }
-    if (o.kind == WR_PK_QUAD_MASK && auxp->clip.proj) {
-      // vClipLocalPos.w on the two edges: the vertex values make way for the edge interpolants (WrClipRec::wv)
+    if ((o.kind == WR_PK_QUAD_MASK || o.kind == WR_PK_CLIP_RECT) && auxp->clip.proj) {
+      // vClipLocalPos.w / vLocalPos.w on the two edges: the vertex values make way for the edge interpolants (WrClipRec::wv)
       WrClipRec& C = auxp->clip;
       const float w4[4] = {C.wv[0], C.wv[1], C.wv[2], C.wv[3]};
       const float lws = (wr_pick4(w4, bl) - wr_pick4(w4, tl)) * yScale, rws = (wr_pick4(w4, br) - wr_pick4(w4, tr)) * yScale;
@@ -3119,6 +3126,12 @@ WR_DEVICE void wr_finish_prim(const WrDrawDesc& d, int draw_index, const WrVsOut
       B.lpL0[0] = wr_pick4(o.u2, tl) + dy0 * l2u; B.lpL0[1] = wr_pick4(o.v2, tl) + dy0 * l2v;
       B.lpR0[0] = wr_pick4(o.u2, tr) + dy0 * r2u; B.lpR0[1] = wr_pick4(o.v2, tr) + dy0 * r2v;
       B.lpLs[0] = l2u; B.lpLs[1] = l2v; B.lpRs[0] = r2u; B.lpRs[1] = r2v;
+      if (B.proj) {
+        const float w4[4] = {B.wv[0], B.wv[1], B.wv[2], B.wv[3]};
+        const float lws = (wr_pick4(w4, bl) - wr_pick4(w4, tl)) * yScale, rws = (wr_pick4(w4, br) - wr_pick4(w4, tr)) * yScale;
+        B.wv[0] = wr_pick4(w4, tl) + dy0 * lws; B.wv[1] = lws;
+        B.wv[2] = wr_pick4(w4, tr) + dy0 * rws; B.wv[3] = rws;
+      }
     }
   }
   if (blend_override) {     // the prim's colour slot carries swgl_BlendColorRGBA8 (its own colour is 1: no modulation)
@@ -4671,12 +4684,13 @@ struct WrBoxRow {
                                // middle column -- every pixel of it samples the same texel, so it has ONE value,
   uint32_t vrow;               // ... this one (wr_box_row_finish evaluates a single pixel of the run)
 };
-WR_DEVICE WrBoxRow wr_box_row_setup(const WrPrim& P, const WrBoxRec& B, const WrRowVals& rv) {
+// `wv`: vLocalPos.w of the row (B.w; under a projective transform the row's own value)
+WR_DEVICE WrBoxRow wr_box_row_setup(const WrPrim& P, const WrBoxRec& B, const WrRowVals& rv, const float wv) {
   WrBoxRow br;
   br.ss_se = br.os01 = br.os23 = 0; br.xc = 0; br.vrow = 0;
   const int len = P.x1 - P.x0, span = len >= 4 ? (len & ~3) : 0;
-  if (span <= 0 || !(B.w > 0.0f)) return br;
-  const float w = 1.0f / B.w;
+  if (span <= 0 || !(wv > 0.0f)) return br;
+  const float w = 1.0f / wv;
   float cur[4][1], st[4];
 #pragma unroll
   for (int c = 0; c < 4; c++) { cur[c][0] = rv.o[c] * w; st[c] = (rv.s[c] * 4.0f) * w; }
@@ -4730,6 +4744,7 @@ WR_DEVICE WrBoxRow wr_box_row_setup(const WrPrim& P, const WrBoxRec& B, const Wr
   }
   return br;
 }
+WR_DEVICE WrBoxRow wr_box_row_setup(const WrPrim& P, const WrBoxRec& B, const WrRowVals& rv) { return wr_box_row_setup(P, B, rv, B.w); }
 
 // Row key of a cs_clip_box_shadow prim on an axis-aligned transform (v and local y constant along the row: s[1] == s[3] == 0).
 // Everything wr_box_shadow_row_lanes computes from the row's v / local y goes through (a) the span lengths of
@@ -4901,8 +4916,9 @@ WR_DEVICE void wr_setup_body(const WrDrawDesc* __restrict__ draws, int n_draws,
         // [row map: rows x u32, padded to 16 B][rows x pitch bytes][row-sum tables: WrAccTabs]
         const unsigned long long map16 = ((unsigned long long)mr_rows * 4 + 15) >> 4;
         mr_n16 = map16 + (((unsigned long long)mr_rows * mr_pitch + 15) >> 4);
-        mr_tabs16 = uint32_t(mr_n16);
-        mr_n16 += WR_ACCTABS_N16;
+        // (a clip under a projective transform takes the walk instead: its rows are wr_clip_rect_proj_row's, which reads no tables; a box
+        // shadow's eight sums have theirs, its w sums -- a ninth and a tenth -- are walked)
+        if (!(P.kind == WR_PK_CLIP_RECT && aux[gid].clip.proj)) { mr_tabs16 = uint32_t(mr_n16); mr_n16 += WR_ACCTABS_N16; }
       }
     }
     // gradient tables' can_merge bitmap (WrGradRec::merge): here, ONCE, after the vertex stage's registers are dead (at its four
@@ -4951,7 +4967,7 @@ WR_DEVICE void wr_setup_body(const WrDrawDesc* __restrict__ draws, int n_draws,
   }
   int mr_slot = -1;
   wr_mask_rows_reserve(mr_T, mr_rows, mr_pitch, mr_n16, mr_tabs16, gid, V.draw(P.draw).target, recs, mr_slot);
-  if (mr_slot >= 0) {
+  if (mr_slot >= 0 && mr_tabs16 != 0) {
     // The prim has its rows: its row-sum tables (one walk over the prim's rows per interpolant that needs one, here, instead of one
     // per ROW in the rows kernel), then -- for a box shadow -- the key of its middle row, which the rows kernel compares every row's
     // key with.  (After the reservation: the wave's lanes get here together.)

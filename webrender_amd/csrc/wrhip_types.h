@@ -436,7 +436,7 @@ struct WrBlurRec {
 struct WrClipRec {
   int32_t fast;             // FAST_PATH program
   float mode;               // vClipMode.x
-  float w;                  // vLocalPos.w (constant: affine transforms only)
+  float w;                  // vLocalPos.w (one constant unless `proj`)
   float params[3];          // vClipParams (fast path)
   float center_radius[4][4];  // vClipCenter_Radius_{TL,TR,BR,BL}
   float plane[4][3];        // vClipPlane_{TL,TR,BR,BL}
@@ -445,6 +445,7 @@ struct WrClipRec {
   // vertex values as the vertex stage leaves them; once an axis-aligned prim is set up, its edge interpolants (as WrPrim::uv*):
   // [0] left edge at the first row, [1] its per-row slope, [2] / [3] the right edge's.  On a general quad the run edges travel in the
   // walk's z slots (WrPerspRec::lz / rz: free, the prim itself is not projective).
+  // cs_clip_rectangle under a projective clip or prim transform (vLocalPos.w, always an axis-aligned task rect): the same.
   int32_t proj;             // w is not one constant (then `w` above is vertex 0's)
   float wv[4];
   int32_t pad_[3];
@@ -464,6 +465,10 @@ struct WrBoxRec {
   float uv_noclamp[4];      // vUvBounds_NoClamp
   float bounds[4];          // vTransformBounds
   float lpL0[2], lpLs[2], lpR0[2], lpRs[2];   // edge interpolants of vLocalPos.xy (as WrPrim::uv*)
+  // a projective clip or prim transform: vLocalPos.w is not one constant (then `w` above is vertex 0's) -- wv as WrClipRec::wv
+  int32_t proj;
+  float wv[4];
+  int32_t pad_[3];
 };
 
 // Anti-aliased axis-aligned quad (aa_span / aa_dist, rasterize.h:480-562; DO_AA, blend.h:433-446):

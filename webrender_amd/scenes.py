@@ -780,10 +780,37 @@ def prim_clip_tasks(rng, rects, atlas=1024, fractional=False):
     return out
 
 
+def clip_task_pass(frame, t_mask, rects, clip_tasks, kind, seed=98):
+    """The pass that draws the clip tasks of prim_clip_tasks / masked_rects instead of an uploaded atlas: per task a rounded clip of
+    the prim's rect (cs_clip_rectangle, the FAST_PATH and the general key in turn, every fifth one clip-out) whose clip node is a
+    mask_transform of `kind` about the rect's centre -> the alpha target."""
+    trng = np.random.default_rng(seed)
+    tgt = Target(t_mask, "alpha", clear_color=(1.0, 1.0, 1.0, 1.0))
+    fast, slow = [], []
+    for i, ct in enumerate(clip_tasks):
+        if ct is None:
+            continue
+        x0, y0, x1, y1 = (float(v) for v in rects[i])
+        w, h = x1 - x0, y1 - y0
+        tid = mask_transform(frame, trng, kind, i, (x0 + x1) / 2, (y0 + y1) / 2, 0.5 * float(np.hypot(w, h)) + 24.0)
+        if len(fast) <= len(slow):
+            r = float(trng.integers(2, max(3, int(min(w, h) / 2))))
+            fast.append(clip_rect_instance(ct[0], ct[1], 1.0, (x0, y0), (w, h), ((r, r),) * 4, int(i % 5 == 0), tids=(tid, 0)))
+        else:
+            radii = tuple((float(trng.uniform(0, w / 2)), float(trng.uniform(0, h / 2))) for _ in range(4))
+            slow.append(clip_rect_instance(ct[0], ct[1], 1.0, (x0, y0), (w, h), radii, int(i % 5 == 0), tids=(tid, 0)))
+    if fast:
+        tgt.steps.append(Step("cs_clip_rectangle FAST_PATH", "CLIP_RECT", np.concatenate(fast), None, "none"))
+    if slow:
+        tgt.steps.append(Step("cs_clip_rectangle", "CLIP_RECT", np.concatenate(slow), None, "none"))
+    return tgt
+
+
 def masked_rects(width=1024, height=1024, n=150, seed=12, atlas=1024, fractional=False, tile_filter=None, force_aa=False, rotate=False,
-                 perspective=False):
+                 perspective=False, clip_transform=None):
     """`force_aa`: BRUSH_FLAG_FORCE_AA + all edge flags on every prim; `rotate`: every other prim under a rotation about its
-    centre (anti-aliased by brush.glsl:150-170) -- masked solids on the general-quad walk."""
+    centre (anti-aliased by brush.glsl:150-170) -- masked solids on the general-quad walk.  `clip_transform`: the masks are not an
+    uploaded atlas but drawn by a pass of their own (clip_task_pass) under clip transforms of that kind."""
     rng, rects = random_rects(n, width, height, 16, 200, seed, fractional)
     rgb = rng.integers(0, 256, size=(n, 3), dtype=np.uint8)
     alpha = np.round(rng.uniform(0.3, 1.0, size=n) * 255).astype(np.uint8)
@@ -823,6 +850,10 @@ def masked_rects(width=1024, height=1024, n=150, seed=12, atlas=1024, fractional
                 m = projective_about(a, cx, cy, hyp * 0.5, rng)
             tids[i] = frame.add_transform(m.T.astype(np.float32), np.linalg.inv(m).T.astype(np.float32), axis_aligned=False)
             grow[i] = (0.9 if perspective else 0.25) * hyp + 2
+    if clip_transform is not None:
+        frame.static_textures.remove(t_mask)
+        t_mask = TextureRef("clip_mask_atlas", atlas, atlas, G.GL_R8, G.GL_LINEAR, render_target=True)
+        frame.passes.append([clip_task_pass(frame, t_mask, rects, clip_tasks, clip_transform)])
     targets = []
     for (tx, ty, ox, oy) in tile_grid(width, height):
         if tile_filter is not None and not tile_filter(tx, ty):
@@ -858,7 +889,42 @@ CLIP_RECT_DTYPE = np.dtype([
     ("corners", "<f4", (8, 4))])      # [rect, radii] x TL, TR, BL, BR  (ClipMaskInstanceRect, gpu_types.rs:207-228)
 
 
-def clip_rect_instance(task_rect, screen_origin, dps, local_pos, size, radii, mode, sub_rect=None):
+MASK_TRANSFORM_KINDS = ("affine", "projective", "rows", "behind")
+
+
+def mask_transform(frame, trng, kind, k, cx, cy, rr):
+    """A spatial node for legacy clip-mask instance `k` (ClipMaskInstanceCommon's clip_transform_id / prim_transform_id), about
+    (cx, cy) -> transform id, 0 for `kind` None.  "affine": rotations (0.3 rad, 90 degrees, any angle) and a skew; "projective":
+    projective_about at its default strength (w > 0 inside radius rr); "rows": w varies with y alone (pm[3, 1] = 0.4 / rr, no
+    rotation), so that every target row has one w; "behind": projective_about with a strength above 1 (part of the mask at w <= 0);
+    "mix": all of these and the identity in turn.  Every value is drawn from `trng`."""
+    if kind == "mix":
+        kind = (None,) + MASK_TRANSFORM_KINDS
+        kind = kind[k % len(kind)]
+    if kind is None:
+        return 0
+    assert kind in MASK_TRANSFORM_KINDS, kind
+    th = (0.3, np.pi / 2, float(trng.uniform(0, 2 * np.pi)), 0.0)[k % 4]
+    sk = float(trng.uniform(0.15, 0.4)) * (1 if k % 8 < 4 else -1) if k % 4 == 3 else 0.0
+    c, sn = np.cos(th), np.sin(th)
+    a = np.array([[c, -sn + sk * c], [sn, c + sk * sn]], np.float64)
+    if kind == "affine":
+        m = np.eye(4)
+        m[:2, :2] = a
+        m[:2, 3] = np.array([cx, cy]) - a @ np.array([cx, cy])
+    elif kind == "rows":
+        tneg, tpos, pm = np.eye(4), np.eye(4), np.eye(4)
+        tneg[:2, 3] = (-cx, -cy); tpos[:2, 3] = (cx, cy)
+        pm[3, 1] = (0.4 if k % 2 else -0.4) / rr
+        m = tpos @ pm @ tneg
+        pm[3, 1] = -pm[3, 1]            # (the inverse in closed form: its w row has an exact 0 in x, which a numerical inverse need not)
+        return frame.add_transform(m.T.astype(np.float32), (tpos @ pm @ tneg).T.astype(np.float32), axis_aligned=False)
+    else:
+        m = projective_about(a, cx, cy, rr * (1.0 + abs(sk)), trng, **({"strength": (1.3, 1.8)} if kind == "behind" else {}))
+    return frame.add_transform(m.T.astype(np.float32), np.linalg.inv(m).T.astype(np.float32), axis_aligned=False)
+
+
+def clip_rect_instance(task_rect, screen_origin, dps, local_pos, size, radii, mode, sub_rect=None, tids=(0, 0)):
     """ClipData::rounded_rect (prim_store/mod.rs:816-878): rect at the origin of
     the clip's local space, corner rects + (outer radius, inner radius 0).
     radii = ((tlw,tlh),(trw,trh),(blw,blh),(brw,brh))."""
@@ -868,7 +934,7 @@ def clip_rect_instance(task_rect, screen_origin, dps, local_pos, size, radii, mo
     inst["area"][0] = sub_rect or (0.0, 0.0, tw, th)
     inst["origins"][0] = (task_rect[0], task_rect[1], screen_origin[0], screen_origin[1])
     inst["dps"][0] = dps
-    inst["tids"][0] = (0, 0)
+    inst["tids"][0] = tids
     inst["lpos"][0] = local_pos
     inst["lrect"][0] = (0.0, 0.0, w, h)
     inst["mode"][0] = float(mode)
@@ -888,13 +954,24 @@ def _pinned_to_corner(atlas, x, y, shelf, tw, th):
     return px, py
 
 
-def clip_masks(n=24, atlas=1024, seed=31, dps=1.0, window=(256, 256), pin_corner=False):
+def clip_masks(n=24, atlas=1024, seed=31, dps=1.0, window=(256, 256), pin_corner=False, clip_transform=None, prim_transform=None,
+               transform_seed=97, task_sizes=None, program=None):
     """`n` rounded-rect mask tasks in one R8 alpha target: even tasks have a
     uniform radius (FAST_PATH program), odd ones four different elliptical
     corners (general program); a third of them clip-out; some are followed by a
     second clip multiplied on top (draw_clip_batch_list, renderer/mod.rs:3564-3640).
-    pin_corner: the last task sits against the atlas's right and bottom edges (its rect ends at (atlas, atlas))."""
+    pin_corner: the last task sits against the atlas's right and bottom edges (its rect ends at (atlas, atlas)).
+    clip_transform / prim_transform: a kind of mask_transform -- every instance's clip / prim spatial node is one of that kind about the
+    clip's centre (in local / in world space), drawn from a generator of their own (transform_seed): the rest of the frame is what it
+    is without them.  task_sizes: [(tw, th)] -- task k is that large whatever its clip's size (its origin is the clip's top left
+    corner, less a few pixels); program: "fast" / "general" -- every first clip of a task is of that program."""
     rng = np.random.default_rng(seed)
+    trng = np.random.default_rng(transform_seed)
+
+    def nodes(k, lpos, w, h):
+        rr = 0.5 * float(np.hypot(w, h)) + 24.0
+        return (mask_transform(frame, trng, clip_transform, k, lpos[0] + w / 2, lpos[1] + h / 2, rr),
+                mask_transform(frame, trng, prim_transform, k + 1, lpos[0] + w / 2, lpos[1] + h / 2, rr))
     frame = Frame(window[0], window[1], (1.0, 1.0, 1.0, 1.0))
     t_mask = TextureRef("clip_masks", atlas, atlas, G.GL_R8, G.GL_LINEAR, render_target=True)
     tgt = Target(t_mask, "alpha", clear_color=(1.0, 1.0, 1.0, 1.0))
@@ -908,6 +985,8 @@ def clip_masks(n=24, atlas=1024, seed=31, dps=1.0, window=(256, 256), pin_corner
         lpos = (float(rng.uniform(0, 500)), float(rng.uniform(0, 500)))
         tw = int(np.ceil(w * dps)) + int(rng.integers(-12, 13))
         th = int(np.ceil(h * dps)) + int(rng.integers(-12, 13))
+        if task_sizes is not None:
+            tw, th = task_sizes[k % len(task_sizes)]
         if x + tw + 4 > atlas:
             x, y, shelf = 4, y + shelf + 4, 0
         if pin_corner and k == n - 1:
@@ -918,23 +997,26 @@ def clip_masks(n=24, atlas=1024, seed=31, dps=1.0, window=(256, 256), pin_corner
         so = (float(np.floor(lpos[0] * dps)) + float(rng.integers(-8, 9)),
               float(np.floor(lpos[1] * dps)) + float(rng.integers(-8, 9)))
         mode = 1 if k % 3 == 2 else 0
-        if k % 2 == 0:
+        tids = nodes(k, lpos, w, h)
+        if (k % 2 == 0) if program is None else program == "fast":
             r = float(rng.integers(0, int(min(w, h) / 2)))
             radii = ((r, r),) * 4
-            (fast0 if True else fast1).append(clip_rect_instance(task, so, dps, lpos, (w, h), radii, mode))
+            (fast0 if True else fast1).append(clip_rect_instance(task, so, dps, lpos, (w, h), radii, mode, tids=tids))
         else:
             mx, my = w / 2, h / 2
             radii = tuple((float(rng.uniform(0, mx)), float(rng.uniform(0, my))) for _ in range(4))
             if k % 7 == 1:
                 radii = ((0.0, 0.0),) + radii[1:]
-            slow0.append(clip_rect_instance(task, so, dps, lpos, (w, h), radii, mode))
+            slow0.append(clip_rect_instance(task, so, dps, lpos, (w, h), radii, mode, tids=tids))
         if k % 4 == 1:       # a second, smaller clip on the same task, multiplied in
             r2 = float(rng.integers(2, 20))
             inst2 = clip_rect_instance(task, so, dps, (lpos[0] + 7.25, lpos[1] + 5.5), (w * 0.8, h * 0.7),
-                                       ((r2, r2),) * 4, 0)
+                                       ((r2, r2),) * 4, 0, tids=nodes(k + 2, (lpos[0] + 7.25, lpos[1] + 5.5), w * 0.8, h * 0.7))
             fast1.append(inst2)
-    tgt.steps.append(Step("cs_clip_rectangle FAST_PATH", "CLIP_RECT", np.concatenate(fast0), None, "none"))
-    tgt.steps.append(Step("cs_clip_rectangle", "CLIP_RECT", np.concatenate(slow0), None, "none"))
+    if fast0:
+        tgt.steps.append(Step("cs_clip_rectangle FAST_PATH", "CLIP_RECT", np.concatenate(fast0), None, "none"))
+    if slow0:
+        tgt.steps.append(Step("cs_clip_rectangle", "CLIP_RECT", np.concatenate(slow0), None, "none"))
     if fast1:
         tgt.steps.append(Step("cs_clip_rectangle FAST_PATH", "CLIP_RECT", np.concatenate(fast1), "Multiply", "none"))
     frame.passes.append([tgt])
@@ -967,9 +1049,12 @@ def blurred_shadow_tile(size, radius, sigma, rng):
     return np.clip(img * 255.0 + 0.5, 0, 255).astype(np.uint8)
 
 
-def box_shadow_masks(n=16, atlas=1024, seed=41, dps=1.0, window=(256, 256), pin_corner=False):
-    """pin_corner: the last task sits against the atlas's right and bottom edges (its rect ends at (atlas, atlas))."""
+def box_shadow_masks(n=16, atlas=1024, seed=41, dps=1.0, window=(256, 256), pin_corner=False, clip_transform=None, prim_transform=None,
+                     transform_seed=97, task_sizes=None):
+    """pin_corner: the last task sits against the atlas's right and bottom edges (its rect ends at (atlas, atlas)).
+    clip_transform / prim_transform, task_sizes: as clip_masks', about the centre of the shadow's rect."""
     rng = np.random.default_rng(seed)
+    trng = np.random.default_rng(transform_seed)
     frame = Frame(window[0], window[1], (1.0, 1.0, 1.0, 1.0))
     cache = np.zeros((512, 512), np.uint8)
     tiles = []
@@ -998,6 +1083,8 @@ def box_shadow_masks(n=16, atlas=1024, seed=41, dps=1.0, window=(256, 256), pin_
             lpos = (float(np.floor(lpos[0])), float(np.floor(lpos[1])))
         tw = int(np.ceil(w * dps)) + int(rng.integers(-10, 11))
         th = int(np.ceil(h * dps)) + int(rng.integers(-10, 11))
+        if task_sizes is not None:
+            tw, th = task_sizes[k % len(task_sizes)]
         if x + tw + 4 > atlas:
             x, y, shelf = 4, y + shelf + 4, 0
         if pin_corner and k == n - 1:
@@ -1010,7 +1097,9 @@ def box_shadow_masks(n=16, atlas=1024, seed=41, dps=1.0, window=(256, 256), pin_
         inst["area"][k] = (0.0, 0.0, tw, th)
         inst["origins"][k] = (task[0], task[1], so[0], so[1])
         inst["dps"][k] = dps
-        inst["tids"][k] = (0, 0)
+        rr = 0.5 * float(np.hypot(w, h)) + 24.0
+        inst["tids"][k] = (mask_transform(frame, trng, clip_transform, k, lpos[0] + w / 2, lpos[1] + h / 2, rr),
+                           mask_transform(frame, trng, prim_transform, k + 1, lpos[0] + w / 2, lpos[1] + h / 2, rr))
         inst["res"][k] = (addr % 1024, addr // 1024)
         inst["src_size"][k] = (src_local, src_local)
         inst["mode"][k] = 1 if k % 3 == 2 else 0
