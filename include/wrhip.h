@@ -251,7 +251,8 @@ void WrhipSetProfiling(int enabled);
  * (3 fused likewise), 9 = wr_span_rows_kernel (the cs_blur / cs_scale targets of a level, a wave per target row piece), 10 = wr_tile_rows_kernel
  * (picture targets of a few large gradient / image prims, likewise), 11 = wr_setup_tile_rows_kernel (10 fused with the next flush's setup stage), 12 = a thin launch of the raster kernel (13: the same with the next flush's setup stage in front, wr_setup_raster_thin_kernel) (wr_raster_kernel<fmt, false, 1, feat>:
  * small levels, several workgroups per bin), 14 = wr_tap_kernel (WrhipTapTexture: fmt of the tapped texture, feat 1 against an expected texture;
- * algo_bytes: the rect's bytes, twice with an expected texture).  algo_bytes: the launch's algorithmic bytes:
+ * algo_bytes: the rect's bytes, twice with an expected texture), 15 = wr_grab_pack_kernel (WrhipGrabTexture: fmt of the grabbed texture,
+ * feat 1 in delta mode; algo_bytes: bytes read plus bytes written, as far as they are known at the launch).  algo_bytes: the launch's algorithmic bytes:
  * raster launches count every destination pixel they own once (twice when the target's old content is loaded) plus
  * the source texels their draws can sample; the setup stage counts instance + descriptor + record bytes.  Returns the
  * number of entries written (<= max). */
@@ -324,6 +325,55 @@ typedef struct WrhipTapResult {
 } WrhipTapResult;
 int32_t WrhipTapTexture(GLuint tex, int32_t x, int32_t y, int32_t w, int32_t h, GLuint expected);
 int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
+/* Texture grabs: the taps' sibling that delivers the pixels -- whole rects, or only the 64 x 64 blocks of a rect that changed since
+ * the previous grab of it -- in stream order, behind held-back launches, through tickets, without a Finish or a ReadPixels.
+ *
+ * WrhipGrabTexture(tex, rects, nrects, flags) enqueues a grab of `nrects` rects (x, y, w, h each) of `tex` (GL_RGBA8 or GL_R8; the
+ * window is WrhipGetFramebufferTexture(0)) and returns a ticket >= 0.  Pixels are the stored bytes (RGBA8 textures hold B, G, R,
+ * A); row r of a rect is texture row y + r.
+ * Ordering is the taps': the grab sees exactly what was issued before the call; recorded work is submitted as by WrhipFlushHeld;
+ * nothing is waited for; raster launches that are held back stay held back, and a grab of a texture they write is issued directly
+ * behind them whenever they leave.  Later writes to the texture, new storage for it or deleting it do not change the result.
+ * Full mode (no WRHIP_GRAB_DELTA): 1 to 16 rects, each non-empty and inside `tex`; they may overlap.  FLIP_ROWS and SWAP_RB apply
+ *   to every rect.  WrhipGrabResultGet copies them to `dst`: one rect as h rows of w * bpp bytes at `dst_stride` (0: tight); several
+ *   rects one after another, each tight (`dst_stride` must be 0).
+ * Delta mode (WRHIP_GRAB_DELTA): one rect, neither FLIP_ROWS nor SWAP_RB.  The library keeps one retained copy of the rect in HBM
+ *   per texture, valid until the texture gets new storage or is deleted, a delta grab names another rect, or WRHIP_GRAB_KEY is
+ *   passed.  Blocks are 64 x 64 pixels, aligned to the rect's origin, edge blocks cut to the rect.  A block is sent when any stored
+ *   byte of it differs from the retained copy, and every block is sent when there is no valid retained copy (a keyframe); the
+ *   same grab brings the retained copy up to date.  In WrhipGrabResultGet `dst` is the caller's own image of the rect (h rows at
+ *   `dst_stride`, 0: tight): the sent blocks are patched into it and nothing else is touched.
+ * Returns -1 and sets GL_INVALID_VALUE, launching nothing, for an unknown texture or format, no rects or more than 16, a rect that
+ * is empty or not inside `tex`, an unknown flag, DELTA with several rects or with FLIP_ROWS / SWAP_RB, KEY without DELTA, SWAP_RB on
+ * GL_R8, and while sharding is on (WrhipSetShard world > 1, WrhipSetTargetRows on `tex`).  Returns -1 with GL_OUT_OF_MEMORY when the
+ * pinned host memory of the ticket ring would exceed WRHIP_GRAB_PINNED_MAX bytes (environment; default 512 MB): every one of the 8
+ * ring entries keeps a device and a pinned slot as large as the largest grab it carried (a delta grab: all blocks of the rect).
+ *
+ * WrhipGrabResultGet(ticket, info, dst, dst_stride, wait): 0 with *info filled and, unless `dst` is NULL, the pixels delivered; 1 if
+ * the result has not arrived yet (wait == 0 only; wait != 0 first sends what the grab is parked behind, then waits for this ticket
+ * alone, not for the stream); -1 for a ticket that was never handed out or has been overwritten -- the ring holds the 8 newest --
+ * and, with GL_INVALID_VALUE, for a `dst_stride` below a row's bytes or a non-zero one with several rects.  A result may be fetched
+ * any number of times while its ticket lives.  `bytes` counts what crossed to the host: WRHIP_GRAB_HEADER bytes and the payload --
+ * the rects' bytes in full mode, blocks * (16 + 64 * 64 * bpp) in delta mode (a 16-byte record and the block at a fixed pitch);
+ * WrhipStats::d2h_bytes grows by it when the result is first fetched.
+ * Not routed through grabs: Finish, GetColorBuffer, ReadPixels.  Not supported: scaling, other formats, sharded targets. */
+#define WRHIP_GRAB_FLIP_ROWS 1u   /* full mode: deliver the rect's last row first */
+#define WRHIP_GRAB_SWAP_RB   2u   /* full mode, RGBA8 only: bytes 0 and 2 of every pixel exchanged */
+#define WRHIP_GRAB_DELTA     4u   /* only the 64x64 blocks that differ from the previous DELTA grab of this texture and rect */
+#define WRHIP_GRAB_KEY       8u   /* with DELTA: ignore the retained copy, send every block */
+#define WRHIP_GRAB_MAX_RECTS 16
+#define WRHIP_GRAB_HEADER    16u  /* bytes that cross with every grab ahead of its payload (the payload's byte count) */
+typedef struct WrhipGrabInfo {
+  int32_t  status;                 /* 0 ok */
+  uint32_t format, flags;          /* GL_RGBA8 or GL_R8; flags as given */
+  int32_t  nrects, rects[WRHIP_GRAB_MAX_RECTS][4];   /* x, y, w, h as given */
+  uint32_t keyframe;               /* DELTA: 1 if there was no valid retained copy (every block sent) */
+  uint32_t blocks, blocks_total;   /* DELTA: blocks sent / blocks of the rect */
+  int32_t  damage[4];              /* DELTA: x, y, w, h (relative to the rect) bounding the sent blocks, each cut to the rect; 0,0,0,0 if none */
+  uint64_t bytes;                  /* bytes that crossed to the host for this ticket (header + payload) */
+} WrhipGrabInfo;
+int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint32_t flags);
+int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64_t dst_stride, int32_t wait);
 
 #ifdef __cplusplus
 }

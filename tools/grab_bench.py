@@ -1,0 +1,260 @@
+#!/usr/bin/env python3
+"""Measurements of texture grabs (include/wrhip.h, WrhipGrabTexture) on the MI355X: DESIGN.md section 6.2.
+
+  pack       wr_grab_pack_kernel on the 3840 x 2160 RGBA8 window (hipEvents, WrhipSetProfiling(1)): full mode, a keyframe delta,
+             a delta with nothing changed, a delta with ~2 % of the blocks changed
+  transport  33.2 MB from the device slot to the pinned host slot: wr_grab_push_kernel at 8 / 32 / 128 workgroups against
+             hipMemcpyAsync, grab call to arrival on the host clock (the pack's time is in it; `pack` says how much that is)
+  stream     cfg2 at 4K streamed -- one native replay call per frame from a Python loop, one Finish at the end --, frames/s:
+             no grab, a tap per frame, a full grab per frame, a delta grab per frame (identical frames), a ReadPixels per frame
+  ab         plain bench.py against another build of the library (WRHIP_LIB_PATH), alternated, no grab issued
+
+Every section runs three alternated rounds.  Needs the GPU: there is no fallback.
+  python tools/grab_bench.py [--sections pack,transport,stream] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import time
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from webrender_amd import glapi, scenes, glconst as G      # noqa: E402
+from webrender_amd.renderer import Renderer                # noqa: E402
+from webrender_amd.harness import record_scene, ScenePlayer  # noqa: E402
+
+W, H = 3840, 2160
+ROUNDS = 3
+LINES = []
+
+
+def say(s=""):
+    print(s, flush=True)
+    LINES.append(s)
+
+
+def kernel_stats(gl, kind):
+    arr = (glapi.WrhipKernelStat * 64)()
+    n = gl.WrhipGetKernelStats(arr, 64)
+    return [arr[i] for i in range(n) if arr[i].kind == kind]
+
+
+class Window:
+    """A context with a 4K window of noise"""
+
+    def __init__(self, lib):
+        self.gl = glapi.GL(lib)
+        self.r = Renderer(self.gl, W, H)
+        self.tex = self.gl.WrhipGetFramebufferTexture(0)
+        self.upload(0, 0, np.random.default_rng(1).integers(0, 256, (H, W, 4), dtype=np.uint8))
+        self.r.finish()
+
+    def upload(self, x, y, px):
+        gl = self.gl
+        gl.ActiveTexture(G.GL_TEXTURE0)
+        gl.BindTexture(G.GL_TEXTURE_2D, self.tex)
+        gl.TexSubImage2D(G.GL_TEXTURE_2D, 0, x, y, px.shape[1], px.shape[0], G.GL_BGRA, G.GL_UNSIGNED_BYTE, np.ascontiguousarray(px))
+
+    def grab(self, flags=0, wait=True):
+        t = self.gl.grab_texture(self.tex, None, flags)
+        assert t >= 0, self.gl.GetError()
+        info = glapi.WrhipGrabInfo()
+        if wait:
+            assert self.gl.WrhipGrabResultGet(t, C.byref(info), None, 0, 1) == 0
+        return info
+
+    def close(self):
+        self.r.destroy()
+
+
+def section_pack(lib):
+    say(f"## pack: wr_grab_pack_kernel, {W}x{H} RGBA8 window, hipEvents (WrhipSetProfiling(1)), us per launch")
+    w = Window(lib)
+    gl = w.gl
+    for flags in (0, glapi.GRAB_DELTA):          # (untimed: code objects, slots, the retained copy)
+        for _ in range(8):
+            w.grab(flags)
+    rng = np.random.default_rng(2)
+    nblocks = (W // 64) * ((H + 63) // 64)
+    some = rng.choice(nblocks, size=max(1, nblocks // 50), replace=False)          # ~2 % of the blocks
+    patches = [rng.integers(0, 256, (16, 16, 4), dtype=np.uint8) for _ in range(2)]
+    gl.WrhipSetProfiling(1)
+    rows = {}
+    for rnd in range(ROUNDS):
+        for name, flags, n in (("full", 0, 30), ("delta keyframe", glapi.GRAB_DELTA | glapi.GRAB_KEY, 30), ("delta unchanged", glapi.GRAB_DELTA, 30),
+                               ("delta ~2% changed", glapi.GRAB_DELTA, 10)):
+            if name == "delta unchanged":
+                w.grab(glapi.GRAB_DELTA)
+            gl.WrhipResetStats()
+            blocks = []
+            for k in range(n):
+                if name == "delta ~2% changed":
+                    for b in some:
+                        w.upload(int(b % (W // 64)) * 64 + 5, int(b // (W // 64)) * 64 + 3, patches[(k + rnd) & 1])
+                    gl.WrhipFlush()
+                blocks.append(w.grab(flags).blocks)
+            ks = kernel_stats(gl, 15)
+            assert len(ks) == 1 and ks[0].launches == n and ks[0].feat == (1 if flags & glapi.GRAB_DELTA else 0), [(k.kind, k.feat, k.launches) for k in ks]
+            rows.setdefault(name, []).append((ks[0].ns / n / 1e3, ks[0].workgroups // n, int(np.median(blocks))))
+    gl.WrhipSetProfiling(0)
+    for name, v in rows.items():
+        say(f"  {name:20s} " + "  ".join(f"{us:8.1f}" for us, _, _ in v) + f"   us   ({v[0][1]} workgroups; blocks sent {v[0][2]} of {nblocks})")
+    say("  (beside: wr_tap_kernel 28.9 / 32.4 us for 33.2 / 66.4 MB read; the 6.1 TB/s copy ceiling gives 10.9 us for 33.2 MB read + 33.2 MB written)")
+    w.close()
+
+
+def section_transport(lib):
+    say("## transport: the window (33.2 MB at 4K), device slot -> pinned host slot, grab call to arrival (host clock, median of 20; the pack is in it), GB/s")
+    variants = [("push kernel, 8 workgroups", "kernel", "8"), ("push kernel, 32 workgroups", "kernel", "32"),
+                ("push kernel, 128 workgroups", "kernel", "128"), ("hipMemcpyAsync", "memcpy", "32")]
+    rows = {}
+    for rnd in range(ROUNDS):
+        for name, mode, wgs in variants:
+            os.environ["WRHIP_GRAB_FULL_PUSH"] = mode
+            os.environ["WRHIP_GRAB_PUSH_WGS"] = wgs
+            w = Window(lib)          # (the two variables are read by a context's first grab)
+            for _ in range(10):
+                w.grab(0)
+            ts = []
+            for _ in range(20):
+                t0 = time.perf_counter()
+                info = w.grab(0)
+                ts.append(time.perf_counter() - t0)
+            rows.setdefault(name, []).append((float(np.median(ts)), int(info.bytes)))
+            w.close()
+    os.environ.pop("WRHIP_GRAB_FULL_PUSH", None)
+    os.environ.pop("WRHIP_GRAB_PUSH_WGS", None)
+    for name, v in rows.items():
+        say(f"  {name:30s} " + "  ".join(f"{b / t / 1e9:6.1f} GB/s ({t * 1e6:6.0f} us)" for t, b in v))
+
+
+def section_stream(lib, frames):
+    say(f"## stream: cfg2 {W}x{H} streamed, one native replay call per frame from a Python loop, one Finish at the end; {frames} frames per region, frames/s")
+    frame = scenes.make_workload("cfg2", width=W, height=H)
+    assert (frame.width, frame.height) == (W, H)
+    rec, _ = record_scene(lib, frame)
+    p = ScenePlayer(lib, rec)
+    sym = lambda name, res, *args: C.CFUNCTYPE(res, *args)(p.symbol(name))
+    finish = sym("Finish", None)
+    window = sym("WrhipGetFramebufferTexture", C.c_uint32, C.c_uint32)(0)
+    tap = sym("WrhipTapTexture", C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32)
+    grab = sym("WrhipGrabTexture", C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_uint32)
+    grab_get = sym("WrhipGrabResultGet", C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
+    read_pixels = sym("ReadPixels", None, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, C.c_void_p)
+    get_stats = sym("WrhipGetStats", None, C.c_void_p)
+    reset_stats = sym("WrhipResetStats", None)
+    rect = (C.c_int32 * 4)(0, 0, W, H)
+    host = np.zeros((H, W, 4), np.uint8)
+    info = glapi.WrhipGrabInfo()
+    one = rec.stream
+
+    def run(kind, n):
+        waiting = []
+
+        def fetch(wait):
+            while waiting:
+                rc = grab_get(waiting[0], C.byref(info), host.ctypes.data if kind != "full grab, info only" else None, 0, 1 if wait else 0)
+                if rc == 1:
+                    return
+                assert rc == 0, rc
+                waiting.pop(0)
+                wait = False
+        for _ in range(n):
+            p.rp.exec(one)
+            if kind == "tap":
+                assert tap(window, 0, 0, W, H, 0) >= 0
+            elif kind.startswith("full grab") or kind == "delta grab":
+                if len(waiting) == 8:
+                    fetch(True)
+                t = grab(window, C.addressof(rect), 1, glapi.GRAB_DELTA if kind == "delta grab" else 0)
+                assert t >= 0
+                waiting.append(t)
+                fetch(False)
+            elif kind == "ReadPixels":
+                read_pixels(0, 0, W, H, G.GL_BGRA, G.GL_UNSIGNED_BYTE, host.ctypes.data)
+        finish()
+        while waiting:
+            fetch(True)
+
+    kinds = ["no grab", "tap", "full grab", "full grab, info only", "delta grab", "ReadPixels"]
+    rows, carried = {}, {}
+    for k in kinds:
+        run(k, 10)
+    for rnd in range(ROUNDS):
+        for k in kinds:
+            n = frames if k != "ReadPixels" else max(20, frames // 4)
+            reset_stats()
+            t0 = time.perf_counter()
+            run(k, n)
+            dt = time.perf_counter() - t0
+            st = glapi.WrhipStats()
+            get_stats(C.byref(st))
+            rows.setdefault(k, []).append(n / dt)
+            carried.setdefault(k, []).append((int(st.setup_carried), n))
+    for k in kinds:
+        say(f"  {k:22s} " + "  ".join(f"{v:9.1f}" for v in rows[k]) + f"   frames/s   (setup_carried {carried[k][0][0]} of {carried[k][0][1]} flushes)")
+    say("  (full grab / delta grab / ReadPixels deliver into the caller's 33.2 MB image; ReadPixels as GL_BGRA, no CPU swizzle; 'info only' fetches with dst == NULL)")
+
+
+def section_ab(other, steps, warmup):
+    say(f"## ab: bench.py --gpus 1 --steps {steps} --warmup {warmup} (cfg2), this library against {os.path.basename(other)}, alternated, frames/s")
+    rows = {"parent": [], "this": []}
+    for rnd in range(ROUNDS):
+        for name in ("parent", "this"):
+            env = dict(os.environ)
+            if name == "parent":
+                env["WRHIP_LIB_PATH"] = os.path.abspath(other)
+            else:
+                env.pop("WRHIP_LIB_PATH", None)
+            out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)],
+                                 env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+            if out.returncode != 0:
+                say(f"  {name}: bench.py exited with {out.returncode}: {out.stderr[-400:]}")
+                return
+            res = [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")][-1]
+            rows[name].append(float(res["value"]))
+            print(f"  ({name}, round {rnd}: {res['value']})", file=sys.stderr, flush=True)
+    for name, v in rows.items():
+        say(f"  {name:8s} " + "  ".join(f"{x:10.1f}" for x in v) + f"   {res.get('unit', '')}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sections", default="pack,transport,stream")
+    ap.add_argument("--frames", type=int, default=200)
+    ap.add_argument("--ab", default=None, metavar="LIB", help="another build of libwrhip.so to run bench.py against")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--size", default=None, metavar="WxH", help="another window size (the figures of DESIGN.md are for the default, 3840x2160)")
+    args = ap.parse_args()
+    global ROUNDS, W, H
+    ROUNDS = args.rounds
+    if args.size:
+        W, H = (int(v) for v in args.size.split("x"))
+    lib = glapi.wrhip_path()
+    w = Window(lib)
+    say(f"# grab_bench: {w.gl.WrhipDeviceName().decode() if w.gl.WrhipDeviceName() else 'no device'}; {ROUNDS} alternated rounds per line")
+    w.close()
+    try:
+        for s in args.sections.split(","):
+            if s == "pack":
+                section_pack(lib)
+            elif s == "transport":
+                section_transport(lib)
+            elif s == "stream":
+                section_stream(lib, args.frames)
+        if args.ab:
+            section_ab(args.ab, args.steps, args.warmup)
+    finally:
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write("\n".join(LINES) + "\n")
+
+
+if __name__ == "__main__":
+    main()

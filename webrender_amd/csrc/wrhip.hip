@@ -238,6 +238,12 @@ struct Texture {
   bool pending_read = false, pending_write = false;
   int pending_target = -1;   // index into Context::work when pending_write
   bool tail_ref = false;     // read or written by the deferred last raster level (Context::Tail)
+  // WrhipGrabTexture, delta mode: the retained copy of rect grab_rect (pool storage, rows of a multiple of 16 bytes) that the next
+  // delta grab of that rect compares against; not valid: the next one is a keyframe
+  void* grab_keep = nullptr;
+  size_t grab_keep_size = 0;
+  int grab_rect[4] = {0, 0, 0, 0};
+  bool grab_valid = false;
   // RGBA32I data textures: does any transform id in them carry TRANSFORM_NON_AXIS_ALIGNED (bit 23,
   // transform.glsl:22-29)?  Read as sPrimitiveHeadersI (2 texels per prim, id in .z of the first) and as
   // sGpuBufferI (ps_quad header, id in .x); maintained on upload.  A draw is only declared
@@ -629,6 +635,28 @@ struct Context {
   WrhipTapResult* tap_dev = nullptr;   // TAP_RING device slots
   WrhipTapResult* tap_host = nullptr;  // ... and their pinned host copies
   std::vector<TapParked> tap_parked;
+  // Texture grabs (WrhipGrabTexture): the taps' ticket ring with pixels in it.  A ticket's device slot is packed on the draw stream
+  // (wr_grab_pack_kernel) and carried to its pinned host slot on `grab_stream`, behind ev_pack and ahead of the ticket's event `ev`;
+  // the next pack into the slot waits for `ev` on the draw stream.  Slots grow to the largest grab they carried.  Stream and events
+  // are made by the first grab: a context that never grabs has none of this.
+  static const int GRAB_RING = 8;
+  struct GrabSlot {
+    uint64_t n = ~0ull; bool parked = false, counted = false;
+    wr_event_t ev, ev_pack;
+    uint8_t* dev = nullptr; uint8_t* host = nullptr; size_t cap = 0;
+    GLenum format = 0; uint32_t flags = 0; int bpp = 0, nrects = 0; int32_t rects[WR_GRAB_MAX_RECTS][4];
+    bool keyframe = false; uint32_t blocks_total = 0;
+  };
+  struct GrabParked { uint64_t n; WrGrabArgs args; };
+  GrabSlot grab_slot[GRAB_RING];
+  uint64_t grab_next = 0;
+  std::vector<GrabParked> grab_parked;
+  std::vector<std::pair<void*, size_t>> grab_keep_dead;      // retained copies replaced while a parked grab may still name them
+  wr_stream_t grab_stream;
+  bool grab_ready = false;
+  size_t grab_pinned_max = (size_t)512 << 20;      // WRHIP_GRAB_PINNED_MAX, bytes
+  int grab_push_wgs = 32;                          // WRHIP_GRAB_PUSH_WGS: workgroups of wr_grab_push_kernel
+  bool grab_full_kernel = false;                   // WRHIP_GRAB_FULL_PUSH=kernel: full grabs cross by the push kernel too (default: a plain copy)
   int chain_grid = 0;                  // workgroups of a chained R8 launch (0: off -- the default; WRHIP_CHAIN=1 turns it on, WRHIP_CHAIN_GRID overrides)
   unsigned chain_base = 0;             // value of WrUnsupportedCounters::chain_arrive once every chained launch enqueued so far has run
 
@@ -768,6 +796,8 @@ uint64_t get_time_value() {
 void flush_all();
 void drain_tail();
 void tap_issue_parked();
+void grab_issue_parked();
+void grab_forget(struct Texture& t, bool release);
 // every host-side wait for the stream: the held-back raster level goes out first
 void sync_stream();
 
@@ -1002,6 +1032,7 @@ void pool_free(void* p, size_t n) {
 
 void free_texture_storage(Texture& t) {
   sync_texture_for_write(t);
+  grab_forget(t, true);
   flush_uploads(967);   // queued rows may target this storage
   if (t.dptr) {
     pool_free(t.dptr, t.dsize);
@@ -1036,6 +1067,7 @@ void set_tex_storage(Texture& t, GLenum external_format, GLsizei width, GLsizei 
                      GLsizei stride = 0) {
   GLenum internal_format = remap_internal_format(external_format);
   sync_texture_for_write(t);
+  grab_forget(t, false);      // (new storage: the next delta grab is a keyframe)
   if (t.width != width || t.height != height || t.internal_format != internal_format) {
     t.internal_format = internal_format; t.width = width; t.height = height;
   }
@@ -1243,7 +1275,7 @@ Context::~Context() {
   flush_all();
   flush_uploads(1206);
   sync_stream();
-  for (Texture* t : textures.objects) if (t) { if (t->dptr) wrrt::dev_free(t->dptr); t->dptr = nullptr; free(t->hmirror); t->hmirror = nullptr; }
+  for (Texture* t : textures.objects) if (t) { if (t->dptr) wrrt::dev_free(t->dptr); t->dptr = nullptr; free(t->hmirror); t->hmirror = nullptr; if (t->grab_keep) wrrt::dev_free(t->grab_keep); t->grab_keep = nullptr; }
   for (auto& kv : pool) wrrt::dev_free(kv.second);
   pool.clear();
   wrrt::dev_free(dupload); wrrt::dev_free(dcounters);
@@ -1251,6 +1283,12 @@ Context::~Context() {
   wrrt::pinned_free(staging);
   for (TapSlot& ts : tap_slot) wrrt::event_destroy(ts.ev);
   wrrt::dev_free(tap_dev); wrrt::pinned_free(tap_host);
+  if (grab_ready) {
+    wrrt::stream_sync(grab_stream);
+    for (GrabSlot& gs : grab_slot) { wrrt::event_destroy(gs.ev); wrrt::event_destroy(gs.ev_pack); wrrt::dev_free(gs.dev); wrrt::pinned_free(gs.host); }
+    wrrt::stream_destroy(grab_stream);
+  }
+  for (auto& kd : grab_keep_dead) wrrt::dev_free(kd.first);
   wrrt::event_destroy(ev_a); wrrt::event_destroy(ev_b);
   wrrt::event_destroy(ev_copy);
   for (RingFence& f : ring_fence) if (f.made) wrrt::event_destroy(f.ev);
@@ -1284,6 +1322,7 @@ void tail_launched() {
   T.held.clear();
   T.pending = false;
   tap_issue_parked();      // (taps of what these launches wrote: directly behind them)
+  grab_issue_parked();     // (... and grabs)
 }
 // The instantiated raster kernels: RGBA8 (+depth) x {0, TEX|GENERIC, +R8TEX, everything}, R8 x {0, GENERIC|BLUR, +CLIP}.
 // `SA` non-null: launch the fused setup + raster variant (only for the variants can_fuse() names).
@@ -1537,6 +1576,87 @@ Context::TapSlot* tap_find(int32_t ticket) {
   Context::TapSlot& ts = c->tap_slot[ticket % Context::TAP_RING];
   if (ts.n == ~0ull || (int32_t)(ts.n & 0x7FFFFFFFull) != ticket) return nullptr;
   return &ts;
+}
+
+// ---- texture grabs (WrhipGrabTexture) -----------------------------------------------------------------------------------------
+void grab_init() {
+  Context* c = ctx;
+  if (c->grab_ready) return;
+  wrrt::stream_create(&c->grab_stream);
+  for (Context::GrabSlot& gs : c->grab_slot) { wrrt::event_create_sync(&gs.ev); wrrt::event_create_sync(&gs.ev_pack); }
+  if (const char* e = getenv("WRHIP_GRAB_PINNED_MAX")) c->grab_pinned_max = (size_t)atoll(e);
+  if (const char* e = getenv("WRHIP_GRAB_PUSH_WGS")) c->grab_push_wgs = std::max(1, std::min(atoi(e), 1024));
+  if (const char* e = getenv("WRHIP_GRAB_FULL_PUSH")) c->grab_full_kernel = strcmp(e, "kernel") == 0;
+  c->grab_ready = true;
+}
+// One grab, now: the pack on the draw stream -- behind the transport of the slot's previous ticket --, the transport on the grab
+// stream behind the pack, the ticket's event behind the transport.  Enqueued through the submit thread; nothing here waits.
+void grab_issue(uint64_t n, const WrGrabArgs& a) {
+  Context* c = ctx;
+  Context::GrabSlot& gs = c->grab_slot[n % Context::GRAB_RING];
+  wrrt::stream_wait_event(c->stream, &gs.ev);
+  if (a.delta && !a.keyframe) wrrt::memset8(a.slot, 0, WR_GRAB_HEADER, c->stream);      // (the count the changed blocks add to)
+  int rows = 0;
+  uint64_t rect_bytes = 0;
+  for (int i = 0; i < a.nrects; i++) { rows += a.rects[i][3]; rect_bytes += (uint64_t)a.rects[i][2] * a.rects[i][3] * a.bpp; }
+  const int grid = a.delta ? a.bx * a.by : (rows + a.rows_per_wg - 1) / a.rows_per_wg;
+  prof_begin();
+  WR_LAUNCH(wr_grab_pack_kernel, grid, 256, c->stream, a);
+  // (15: wr_grab_pack_kernel; feat 1: delta.  Bytes read plus bytes written: the rect twice in full mode; a keyframe reads the rect
+  // and writes entries and retained copy; any other delta reads rect and retained copy -- what its changed blocks then write is not
+  // known here and is not counted)
+  prof_end(15, a.bpp == 4 ? WR_FMT_RGBA8 : WR_FMT_R8, 0, a.delta ? 1 : 0, a.delta && a.keyframe ? 2 * rect_bytes + a.payload : 2 * rect_bytes, (uint64_t)grid);
+  c->stats.kernel_launches++;
+  WrGrabPushArgs pa;
+  pa.src = gs.dev; pa.dst = gs.host; pa.capacity = (uint32_t)gs.cap;
+#ifdef WRHIP_HOSTSIM
+  WR_LAUNCH(wr_grab_push_kernel, 1, 256, c->stream, pa);
+#else
+  wrrt::event_record(&gs.ev_pack, c->stream);
+  wrrt::stream_wait_event(c->grab_stream, &gs.ev_pack);
+  if (a.delta || c->grab_full_kernel) WR_LAUNCH(wr_grab_push_kernel, c->grab_push_wgs, 256, c->grab_stream, pa);
+  else wrrt::d2h(gs.host, gs.dev, (size_t)WR_GRAB_HEADER + a.payload, c->grab_stream);
+  wrrt::event_record(&gs.ev, c->grab_stream);
+#endif
+  gs.parked = false;
+}
+// tail_launched(): the grabs that waited for the held-back launches follow them, in the order they were made
+void grab_issue_parked() {
+  Context* c = ctx;
+  if (c->grab_parked.empty()) return;
+  std::vector<Context::GrabParked> parked;
+  parked.swap(c->grab_parked);
+  // (a parked grab whose ticket has been overwritten since has no slot to deliver into.  If it was a delta grab it would also have
+  // brought its texture's retained copy up to date: the next grab of that copy sends every block instead, or, if there is none
+  // in the list, the copy stops being valid)
+  std::vector<const uint8_t*> stale;
+  for (Context::GrabParked& p : parked) {
+    Context::GrabSlot& gs = c->grab_slot[p.n % Context::GRAB_RING];
+    auto st = std::find(stale.begin(), stale.end(), (const uint8_t*)p.args.keep);
+    if (gs.n != p.n) { if (p.args.delta && st == stale.end()) stale.push_back(p.args.keep); continue; }
+    if (p.args.delta && st != stale.end()) { p.args.keyframe = 1; gs.keyframe = true; stale.erase(st); }
+    grab_issue(p.n, p.args);
+  }
+  for (const uint8_t* k : stale)
+    for (Texture* t : c->textures.objects) if (t && t->grab_keep == k) t->grab_valid = false;
+  for (auto& kd : c->grab_keep_dead) pool_free(kd.first, kd.second);
+  c->grab_keep_dead.clear();
+}
+// The retained copy of `t` is no longer valid (new storage, deletion); release: its memory goes back to the pool -- which hands it
+// out again in stream order -- unless a parked grab was given it and has not been enqueued yet.
+void grab_forget(Texture& t, bool release) {
+  t.grab_valid = false;
+  if (!release || !t.grab_keep) return;
+  if (ctx->grab_parked.empty()) pool_free(t.grab_keep, t.grab_keep_size);
+  else ctx->grab_keep_dead.push_back(std::make_pair(t.grab_keep, t.grab_keep_size));
+  t.grab_keep = nullptr; t.grab_keep_size = 0;
+}
+Context::GrabSlot* grab_find(int32_t ticket) {
+  Context* c = ctx;
+  if (ticket < 0) return nullptr;
+  Context::GrabSlot& gs = c->grab_slot[ticket % Context::GRAB_RING];
+  if (gs.n == ~0ull || (int32_t)(gs.n & 0x7FFFFFFFull) != ticket) return nullptr;
+  return &gs;
 }
 
 // Forwarded composites.  A target whose pending work is [full clear,] N draws of `composite FAST_PATH` that each copy a whole
@@ -3765,6 +3885,156 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait) {
   for (uint32_t d = 1; d < 256; d++) if (r.hist[d]) r.max_diff = d;
   r.differing = (uint32_t)((uint64_t)ts->w * ts->h - r.hist[0]);
   *out = r;
+  return 0;
+}
+// A grab: see include/wrhip.h.  Arguments are checked before anything is flushed or launched.
+int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint32_t flags) {
+  if (!ctx) return -1;
+  Context* c = ctx;
+  Texture* t = tex ? c->textures.find(tex) : nullptr;
+  const bool delta = (flags & WRHIP_GRAB_DELTA) != 0;
+  bool ok = t && t->dptr && (t->internal_format == GL_RGBA8 || t->internal_format == GL_R8);
+  ok = ok && rects && nrects >= 1 && nrects <= WRHIP_GRAB_MAX_RECTS;
+  ok = ok && (flags & ~(WRHIP_GRAB_FLIP_ROWS | WRHIP_GRAB_SWAP_RB | WRHIP_GRAB_DELTA | WRHIP_GRAB_KEY)) == 0;
+  ok = ok && (delta ? nrects == 1 && !(flags & (WRHIP_GRAB_FLIP_ROWS | WRHIP_GRAB_SWAP_RB)) : !(flags & WRHIP_GRAB_KEY));
+  ok = ok && (!(flags & WRHIP_GRAB_SWAP_RB) || t->internal_format == GL_RGBA8);
+  uint64_t payload = 0;
+  for (int i = 0; ok && i < nrects; i++) {
+    const int32_t x = rects[4 * i], y = rects[4 * i + 1], w = rects[4 * i + 2], h = rects[4 * i + 3];
+    ok = w >= 1 && h >= 1 && x >= 0 && y >= 0 && x <= t->width - w && y <= t->height - h;
+    if (ok) payload += (uint64_t)w * h * t->bpp;
+  }
+  ok = ok && c->shard_world <= 1 && t->own_y0 == t->own_y1;      // (sharded targets hold a strip of the frame each: out of scope)
+  if (!ok) { c->last_error = GL_INVALID_VALUE; return -1; }
+  grab_init();
+  const int bx = (rects[2] + WR_GRAB_BLOCK - 1) / WR_GRAB_BLOCK, by = (rects[3] + WR_GRAB_BLOCK - 1) / WR_GRAB_BLOCK;
+  if (delta) payload = (uint64_t)bx * by * WR_GRAB_ENTRY(t->bpp);
+  // the pinned memory of the ring with this grab's slot grown to hold it
+  const int si = (int)(c->grab_next % Context::GRAB_RING);
+  Context::GrabSlot& gs = c->grab_slot[si];
+  const uint64_t need = (WR_GRAB_HEADER + payload + 15) & ~(uint64_t)15;
+  uint64_t pinned = 0;
+  for (const Context::GrabSlot& o : c->grab_slot) pinned += &o == &gs ? std::max<uint64_t>(o.cap, need) : o.cap;
+  if (pinned > c->grab_pinned_max || need > 0xFFFFFFF0ull) { out_of_memory(); return -1; }
+  // what was recorded so far goes out the way WrhipFlushHeld sends it: this flush's raster launches stay held back
+  flush_all();
+  flush_uploads(3760);
+  if (gs.cap < need) {
+    // (the slot's previous ticket may still be crossing: a grab larger than any before it waits for that, once per slot)
+    if (gs.n != ~0ull && !gs.parked) { HostTimer ht(&c->stats.host_wait_ns); wrrt::event_sync(&gs.ev); }
+    uint8_t* nd = (uint8_t*)wrrt::try_dev_alloc((size_t)need);
+    if (!nd) { out_of_memory(); return -1; }
+    wrrt::dev_free(gs.dev); wrrt::pinned_free(gs.host);
+    gs.n = ~0ull; gs.parked = false;
+    gs.dev = nd; gs.host = (uint8_t*)wrrt::pinned_alloc((size_t)need); gs.cap = (size_t)need;
+  }
+  WrGrabArgs a;
+  memset(&a, 0, sizeof(a));
+  a.tex = (const uint8_t*)t->dptr; a.tex_stride = t->stride; a.bpp = t->bpp;
+  a.slot = gs.dev;
+  a.nrects = nrects;
+  memcpy(a.rects, rects, sizeof(int32_t) * 4 * nrects);
+  a.flip = (flags & WRHIP_GRAB_FLIP_ROWS) ? 1 : 0; a.swap_rb = (flags & WRHIP_GRAB_SWAP_RB) ? 1 : 0;
+  a.payload = (uint32_t)payload;
+  a.rows_per_wg = 1;
+  bool keyframe = false;
+  if (delta) {
+    const int32_t w = rects[2], h = rects[3];
+    const int keep_stride = (w * t->bpp + 15) & ~15;
+    const size_t keep_need = (size_t)keep_stride * h;
+    keyframe = !(t->grab_keep && t->grab_valid && memcmp(t->grab_rect, rects, sizeof(t->grab_rect)) == 0) || (flags & WRHIP_GRAB_KEY);
+    if (!t->grab_keep || t->grab_keep_size < keep_need) {
+      grab_forget(*t, true);
+      size_t actual = 0;
+      t->grab_keep = pool_alloc(keep_need, &actual);
+      t->grab_keep_size = actual;
+      if (!t->grab_keep) { out_of_memory(); return -1; }
+    }
+    memcpy(t->grab_rect, rects, sizeof(t->grab_rect));
+    t->grab_valid = true;
+    a.delta = 1; a.keyframe = keyframe ? 1 : 0;
+    a.keep = (uint8_t*)t->grab_keep; a.keep_stride = keep_stride;
+    a.bx = bx; a.by = by;
+  } else {
+    // (a workgroup per 8 KB of rows, as the taps have it, and no more than 4096 workgroups)
+    int rows = 0;
+    for (int i = 0; i < nrects; i++) rows += rects[4 * i + 3];
+    const uint64_t row_bytes = std::max<uint64_t>(1, payload / (uint64_t)rows);
+    a.rows_per_wg = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)rows, (8192 + row_bytes - 1) / row_bytes));
+    a.rows_per_wg = std::max(a.rows_per_wg, (rows + 4095) / 4096);
+  }
+  const uint64_t n = c->grab_next++;
+  gs.n = n; gs.counted = false;
+  gs.format = t->internal_format; gs.flags = flags; gs.bpp = t->bpp; gs.nrects = nrects;
+  memcpy(gs.rects, rects, sizeof(int32_t) * 4 * nrects);
+  gs.keyframe = keyframe; gs.blocks_total = delta ? (uint32_t)(bx * by) : 0;
+  if (c->tail.pending && t->tail_ref) {
+    // the held-back launches write (or read) the texture: the grab waits for them to leave, and does not make them (see WrhipTapTexture)
+    gs.parked = true;
+    c->grab_parked.push_back(Context::GrabParked{n, a});
+  } else {
+    grab_issue(n, a);
+  }
+  return (int32_t)(n & 0x7FFFFFFFull);
+}
+int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64_t dst_stride, int32_t wait) {
+  if (!ctx || !info) return -1;
+  Context* c = ctx;
+  Context::GrabSlot* gs = grab_find(ticket);
+  if (!gs) return -1;
+  const bool delta = (gs->flags & WRHIP_GRAB_DELTA) != 0;
+  const int bpp = gs->bpp;
+  const int64_t tight = (int64_t)gs->rects[0][2] * bpp;
+  if (dst && dst_stride != 0 && (gs->nrects > 1 || dst_stride < tight)) { c->last_error = GL_INVALID_VALUE; return -1; }
+  if (gs->parked) {
+    if (!wait) return 1;
+    drain_tail();            // what it is parked behind goes out (as after a WrhipFlushHeld with nothing recorded), the grab with it
+    if (gs->parked) grab_issue_parked();
+  }
+  if (wait) { HostTimer ht(&c->stats.host_wait_ns); wrrt::event_sync(&gs->ev); }
+  else if (!wrrt::event_query(&gs->ev)) return 1;
+  uint32_t payload;
+  memcpy(&payload, gs->host, 4);
+  payload = (uint32_t)std::min<uint64_t>(payload, gs->cap - WR_GRAB_HEADER);
+  const uint8_t* src = gs->host + WR_GRAB_HEADER;
+  WrhipGrabInfo r;
+  memset(&r, 0, sizeof(r));
+  r.format = gs->format; r.flags = gs->flags; r.nrects = gs->nrects;
+  memcpy(r.rects, gs->rects, sizeof(int32_t) * 4 * gs->nrects);
+  r.bytes = (uint64_t)WR_GRAB_HEADER + payload;
+  if (!delta) {
+    for (int i = 0; i < gs->nrects; i++) {
+      const size_t row = (size_t)gs->rects[i][2] * bpp;
+      const int h = gs->rects[i][3];
+      if (dst) {
+        const size_t ds = gs->nrects == 1 && dst_stride ? (size_t)dst_stride : row;
+        // (tight rects leave as one copy: they follow each other in `dst` as they do in the slot)
+        if (ds == row) big_memcpy(dst, src, row * h);      // (a 4K window: 33 MB, the copy pool's threads share it)
+        else for (int y = 0; y < h; y++) memcpy((uint8_t*)dst + (size_t)y * ds, src + (size_t)y * row, row);
+        dst = (uint8_t*)dst + row * h;
+      }
+      src += row * h;
+    }
+  } else {
+    const size_t entry = WR_GRAB_ENTRY(bpp), pitch = (size_t)WR_GRAB_BLOCK * bpp;
+    const int rw = gs->rects[0][2], rh = gs->rects[0][3];
+    const size_t ds = dst_stride ? (size_t)dst_stride : (size_t)tight;
+    r.keyframe = gs->keyframe ? 1 : 0;
+    r.blocks = (uint32_t)(payload / entry); r.blocks_total = gs->blocks_total;
+    int x0 = rw, y0 = rh, x1 = 0, y1 = 0;
+    for (uint32_t e = 0; e < r.blocks; e++) {
+      int32_t rec[4];
+      memcpy(rec, src + e * entry, 16);
+      if (rec[0] < 0 || rec[1] < 0 || rec[2] < 1 || rec[3] < 1 || rec[2] > WR_GRAB_BLOCK || rec[3] > WR_GRAB_BLOCK || rec[0] > rw - rec[2] || rec[1] > rh - rec[3]) { r.status = 1; continue; }
+      x0 = std::min(x0, rec[0]); y0 = std::min(y0, rec[1]); x1 = std::max(x1, rec[0] + rec[2]); y1 = std::max(y1, rec[1] + rec[3]);
+      if (dst)
+        for (int y = 0; y < rec[3]; y++)
+          memcpy((uint8_t*)dst + (size_t)(rec[1] + y) * ds + (size_t)rec[0] * bpp, src + e * entry + 16 + (size_t)y * pitch, (size_t)rec[2] * bpp);
+    }
+    if (x1 > x0 && y1 > y0) { r.damage[0] = x0; r.damage[1] = y0; r.damage[2] = x1 - x0; r.damage[3] = y1 - y0; }
+  }
+  if (!gs->counted) { c->stats.d2h_bytes += r.bytes; gs->counted = true; }
+  *info = r;
   return 0;
 }
 void* WrhipGetStream(void) {

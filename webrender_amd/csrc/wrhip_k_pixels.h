@@ -201,6 +201,178 @@ __global__ void __launch_bounds__(256) wr_tap_kernel(WrTapArgs a) {
 }
 #endif
 
+// WrhipGrabTexture (include/wrhip.h): the pixels themselves, packed into the ticket's device slot (layout: WrGrabArgs).
+// Full mode is the tap kernel's walk with a store behind every load: a 256-thread workgroup per run of rows of the rects laid end
+// to end, 16-byte loads and stores from the source row's first 16-byte boundary on where the (tight) destination row is aligned
+// there too, single pixels before it, behind the last whole piece and wherever the two disagree.  Rows are flipped and R and B
+// exchanged on the way.
+// Delta mode gives every 64 x 64 block of the rect a workgroup: a thread holds the block's 16-byte pieces it is responsible for in
+// registers (four for RGBA8, one for R8; pieces count from the block's left edge, so that the retained copy and the slot entry --
+// both the library's own, both 16-byte aligned there -- take whole stores whatever the texture's alignment is), compares them with
+// the retained copy, and the block leaves -- record, pixels, retained copy -- only if a lane of it saw a difference: a ballot per
+// wave, one LDS word per workgroup.  Its entry is the next free one (one atomic per CHANGED block on the slot's byte count), or its
+// own index on a keyframe, where nothing is compared and nothing is counted.
+WR_DEVICE void wr_grab_st16(void* p, const wr_u4& v) {
+#ifdef WRHIP_HOSTSIM
+  __builtin_memcpy(p, &v, 16);
+#else
+  typedef uint32_t wr_gu4 __attribute__((ext_vector_type(4)));
+  *(__attribute__((address_space(1))) wr_gu4*)p = wr_gu4{v.x, v.y, v.z, v.w};
+#endif
+}
+WR_DEVICE void wr_grab_st4(void* p, uint32_t v) {
+#ifdef WRHIP_HOSTSIM
+  __builtin_memcpy(p, &v, 4);
+#else
+  *(__attribute__((address_space(1))) uint32_t*)p = v;
+#endif
+}
+WR_DEVICE uint32_t wr_grab_swap(uint32_t v) { return (v & 0xFF00FF00u) | ((v & 0xFFu) << 16) | ((v >> 16) & 0xFFu); }
+// row g of the rects' rows laid end to end, thread t of nt
+WR_DEVICE void wr_grab_row(const WrGrabArgs& a, int g, int t, int nt) {
+  const int bpp = a.bpp, ppv = 16 / bpp;
+  size_t off = 0;
+  int i = 0, r = g;
+  for (; i < a.nrects - 1 && r >= a.rects[i][3]; i++) { r -= a.rects[i][3]; off += (size_t)a.rects[i][2] * a.rects[i][3] * bpp; }
+  const int w = a.rects[i][2], h = a.rects[i][3];
+  const uint8_t* ps = a.tex + (size_t)(a.rects[i][1] + r) * a.tex_stride + (size_t)a.rects[i][0] * bpp;
+  uint8_t* pd = a.slot + WR_GRAB_HEADER + off + (size_t)(a.flip ? h - 1 - r : r) * w * bpp;
+  // [0, head) single pixels, [head, tail0) 16-byte pieces, [tail0, w) single pixels
+  int head = w;
+  const int h16 = (int)(((16 - ((uintptr_t)ps & 15)) & 15) / bpp);
+  if (h16 < w && (((uintptr_t)pd + (size_t)h16 * bpp) & 15) == 0) head = h16;
+  const int nvec = (w - head) / ppv, tail0 = head + nvec * ppv;
+  for (int c = t; c < nvec; c += nt) {
+    const int p = head + c * ppv;
+    wr_u4 v = wr_load16(ps + (size_t)p * bpp);
+    if (a.swap_rb) { v.x = wr_grab_swap(v.x); v.y = wr_grab_swap(v.y); v.z = wr_grab_swap(v.z); v.w = wr_grab_swap(v.w); }
+    wr_grab_st16(pd + (size_t)p * bpp, v);
+  }
+  const int nscalar = head + (w - tail0);
+  for (int q = t; q < nscalar; q += nt) {
+    const int p = q < head ? q : tail0 + (q - head);
+    if (bpp == 4) {
+      const uint32_t v = wr_load4(ps + (size_t)p * 4);
+      wr_grab_st4(pd + (size_t)p * 4, a.swap_rb ? wr_grab_swap(v) : v);
+    } else {
+      pd[p] = ps[p];
+    }
+  }
+}
+// delta: the geometry of block b, and piece `piece` of it (row-major, 64 * bpp / 16 pieces per block row)
+struct WrGrabBlock { const uint8_t* ps; uint8_t* pk; int x0, y0, bw, bh; };
+WR_DEVICE WrGrabBlock wr_grab_block(const WrGrabArgs& a, int b) {
+  WrGrabBlock B;
+  B.x0 = (b % a.bx) * WR_GRAB_BLOCK; B.y0 = (b / a.bx) * WR_GRAB_BLOCK;
+  B.bw = wr_imin(WR_GRAB_BLOCK, a.rects[0][2] - B.x0); B.bh = wr_imin(WR_GRAB_BLOCK, a.rects[0][3] - B.y0);
+  B.ps = a.tex + (size_t)(a.rects[0][1] + B.y0) * a.tex_stride + (size_t)(a.rects[0][0] + B.x0) * a.bpp;
+  B.pk = a.keep + (size_t)B.y0 * a.keep_stride + (size_t)B.x0 * a.bpp;
+  return B;
+}
+// -> the piece's pixels inside the block (0: none of it is), `v`: their bytes, zero beyond them; r, o: its row and byte offset in it
+WR_DEVICE int wr_grab_piece(const WrGrabArgs& a, const WrGrabBlock& B, int piece, wr_u4& v, int& r, int& o) {
+  const int bpp = a.bpp, ppv = 16 / bpp, ppr = WR_GRAB_BLOCK / ppv;
+  r = piece / ppr;
+  const int px0 = (piece % ppr) * ppv;
+  o = px0 * bpp;
+  const int n = r < B.bh ? wr_imax(0, wr_imin(ppv, B.bw - px0)) : 0;
+  if (n == 0) return 0;
+  const uint8_t* p = B.ps + (size_t)r * a.tex_stride + o;
+  if (n == ppv && ((uintptr_t)p & 15) == 0) { v = wr_load16(p); return n; }
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  if (bpp == 4) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) if (k < n) w[k] = wr_load4(p + 4 * k);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; k++) if (k < n) w[k >> 2] |= (uint32_t)p[k] << (8 * (k & 3));
+  }
+  v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+  return n;
+}
+WR_DEVICE bool wr_grab_differs(const wr_u4& v, const wr_u4& e) { return ((v.x ^ e.x) | (v.y ^ e.y) | (v.z ^ e.z) | (v.w ^ e.w)) != 0u; }
+// the entry's record and where its pixels start
+WR_DEVICE uint8_t* wr_grab_entry(const WrGrabArgs& a, const WrGrabBlock& B, unsigned index, bool write_record) {
+  uint8_t* e = a.slot + WR_GRAB_HEADER + (size_t)index * WR_GRAB_ENTRY(a.bpp);
+  if (write_record) wr_grab_st16(e, wr_u4{(uint32_t)B.x0, (uint32_t)B.y0, (uint32_t)B.bw, (uint32_t)B.bh});
+  return e + 16;
+}
+#ifndef WR_INST_ONLY
+__global__ void __launch_bounds__(256) wr_grab_pack_kernel(WrGrabArgs a) {
+  const int t = (int)threadIdx.x;
+  // (what the host knows of the slot's byte count is written here: everything in full mode and on a keyframe)
+  if ((!a.delta || a.keyframe) && blockIdx.x == 0 && t == 0) wr_grab_st16(a.slot, wr_u4{a.payload, 0u, 0u, 0u});
+  if (!a.delta) {
+    int rows = 0;
+    for (int i = 0; i < a.nrects; i++) rows += a.rects[i][3];
+    const int g0 = (int)blockIdx.x * a.rows_per_wg, g1 = wr_imin(rows, g0 + a.rows_per_wg);
+    for (int g = g0; g < g1; g++) wr_grab_row(a, g, t, (int)blockDim.x);
+    return;
+  }
+  const int b = (int)blockIdx.x;
+  const WrGrabBlock B = wr_grab_block(a, b);
+  const int pieces = WR_GRAB_BLOCK * WR_GRAB_BLOCK * a.bpp / 16, pitch = WR_GRAB_BLOCK * a.bpp;
+  const unsigned entry_bytes = (unsigned)WR_GRAB_ENTRY(a.bpp);
+#ifdef WRHIP_HOSTSIM
+  // (threads run one after the other: the first walks the block twice)
+  if (t != 0) return;
+  bool diff = a.keyframe != 0;
+  wr_u4 v; int r, o;
+  for (int piece = 0; piece < pieces && !diff; piece++)
+    if (wr_grab_piece(a, B, piece, v, r, o)) diff = wr_grab_differs(v, wr_load16(B.pk + (size_t)r * a.keep_stride + o));
+  if (!diff) return;
+  const unsigned index = a.keyframe ? (unsigned)b : atomicAdd((unsigned*)a.slot, entry_bytes) / entry_bytes;
+  uint8_t* px = wr_grab_entry(a, B, index, true);
+  for (int piece = 0; piece < pieces; piece++)
+    if (wr_grab_piece(a, B, piece, v, r, o)) { wr_grab_st16(px + (size_t)r * pitch + o, v); wr_grab_st16(B.pk + (size_t)r * a.keep_stride + o, v); }
+#else
+  __shared__ unsigned lw[2];           // [0]: a lane saw a difference; [1]: the entry the block takes
+  wr_u4 v[4];
+  int n[4], r[4], o[4];
+  bool diff = false;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    n[k] = 0;
+    const int piece = k * 256 + t;
+    if (piece >= pieces) continue;
+    n[k] = wr_grab_piece(a, B, piece, v[k], r[k], o[k]);
+    if (n[k] && !a.keyframe) diff = diff || wr_grab_differs(v[k], wr_load16(B.pk + (size_t)r[k] * a.keep_stride + o[k]));
+  }
+  unsigned index = (unsigned)b;
+  if (!a.keyframe) {
+    if (t == 0) lw[0] = 0u;
+    __syncthreads();
+    if (__ballot(diff) != 0ull && (t & 63) == 0) lw[0] = 1u;
+    __syncthreads();
+    if (lw[0] == 0u) return;
+    if (t == 0) lw[1] = atomicAdd((unsigned*)a.slot, entry_bytes) / entry_bytes;
+    __syncthreads();
+    index = lw[1];
+  }
+  uint8_t* px = wr_grab_entry(a, B, index, t == 0);
+#pragma unroll
+  for (int k = 0; k < 4; k++)
+    if (n[k]) { wr_grab_st16(px + (size_t)r[k] * pitch + o[k], v[k]); wr_grab_st16(B.pk + (size_t)r[k] * a.keep_stride + o[k], v[k]); }
+#endif
+}
+// The slot's header and as many bytes as its count word says, device slot -> pinned host slot, 16 bytes per store.  A small grid on
+// the grab stream: the link, not the chip, bounds it, and the raster launches of the following frames keep the CUs.
+__global__ void __launch_bounds__(256) wr_grab_push_kernel(WrGrabPushArgs a) {
+  const uint32_t payload = wr_load4(a.src);
+  unsigned long long n16 = ((unsigned long long)WR_GRAB_HEADER + payload + 15ull) >> 4;
+  if (n16 > (unsigned long long)(a.capacity >> 4)) n16 = a.capacity >> 4;
+  const unsigned long long step = (unsigned long long)gridDim.x * blockDim.x;
+  unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i + 3 * step < n16; i += 4 * step) {
+    const wr_u4 v0 = wr_load16(a.src + 16 * i), v1 = wr_load16(a.src + 16 * (i + step));
+    const wr_u4 v2 = wr_load16(a.src + 16 * (i + 2 * step)), v3 = wr_load16(a.src + 16 * (i + 3 * step));
+    wr_grab_st16(a.dst + 16 * i, v0); wr_grab_st16(a.dst + 16 * (i + step), v1);
+    wr_grab_st16(a.dst + 16 * (i + 2 * step), v2); wr_grab_st16(a.dst + 16 * (i + 3 * step), v3);
+  }
+  for (; i < n16; i += step) wr_grab_st16(a.dst + 16 * i, wr_load16(a.src + 16 * i));
+}
+#endif
+
 // A solid colour on a general quad, one row at a time: the row's span from the edge instances of its run (aa_span / aa_edge /
 // aa_dist, rasterize.h:480-562) -- the two edge sums are what costs (Edge::nextRow, one add per row: wr_accum), so they are
 // evaluated once per lane-row and shared by the row's pixels.

@@ -708,6 +708,35 @@ struct WrTapArgs {
   unsigned* hist;                      // [256]
 };
 
+// WrhipGrabTexture: the pixels of up to 16 texture rects, or the changed 64 x 64 blocks of one, packed into the ticket's device slot
+// (wr_grab_pack_kernel) and carried to its pinned host copy on the grab stream (wr_grab_push_kernel, or a plain copy).
+// A slot, on the device and on the host: a 16-byte header -- word 0: the payload's bytes -- and the payload behind it.
+//   full   the rects one after another, each tight (w * bpp bytes per row), rows flipped / R and B exchanged on the way
+//   delta  entries of WR_GRAB_ENTRY(bpp) bytes: a 16-byte record (x, y, w, h of the block, relative to the rect) and the block's
+//          rows at a pitch of 64 * bpp; `keep` is the retained copy of the rect (rows of keep_stride bytes, a multiple of 16)
+#define WR_GRAB_HEADER 16
+#define WR_GRAB_BLOCK 64
+#define WR_GRAB_ENTRY(bpp) (16 + WR_GRAB_BLOCK * WR_GRAB_BLOCK * (bpp))
+#define WR_GRAB_MAX_RECTS 16
+struct WrGrabArgs {
+  const uint8_t* tex;                  // the texture's storage (its origin)
+  uint8_t* slot;                       // the ticket's device slot
+  uint8_t* keep;                       // delta: the retained copy
+  int32_t tex_stride, keep_stride;     // bytes
+  int32_t bpp;                         // 4: RGBA8, 1: R8
+  int32_t delta, keyframe;             // keyframe: every block is sent, entry i is block i (nothing is compared, no atomic)
+  int32_t flip, swap_rb;               // full mode
+  int32_t nrects;
+  int32_t rows_per_wg;                 // full: workgroup b packs rows [b * rows_per_wg, ...) of the rects' rows laid end to end
+  int32_t bx, by;                      // delta: blocks across and down
+  uint32_t payload;                    // full, and a keyframe: the payload's bytes (known on the host)
+  int32_t rects[WR_GRAB_MAX_RECTS][4]; // x, y, w, h
+};
+struct WrGrabPushArgs {
+  const uint8_t* src; uint8_t* dst;    // device slot -> pinned host slot
+  uint32_t capacity;                   // of either, bytes (a multiple of 16): the count read from the slot is held to it
+};
+
 // CompositeYUV (composite.h:1160-1386): the destination rows of linear_convert_yuv, four pixels (one chunk of linear_row_yuv) per
 // thread.  Everything that is constant along a row -- the planes' x coordinates in 1/128 texel x 2^8 fixed point, their steps, where
 // the half-resolution fast path (upscaleYUV42R8) starts and ends -- is worked out once on the host, as the reference does per row.

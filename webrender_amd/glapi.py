@@ -139,6 +139,8 @@ EXTRA_SIGNATURES = {
     "WrhipGetStream": (P, []),
     "WrhipTapTexture": (i32, [u32, i32, i32, i32, i32, u32]),
     "WrhipTapResultGet": (i32, [i32, P, i32]),
+    "WrhipGrabTexture": (i32, [u32, P, i32, u32]),
+    "WrhipGrabResultGet": (i32, [i32, P, P, C.c_int64, i32]),
 }
 
 
@@ -157,6 +159,16 @@ class WrhipKernelStat(C.Structure):
 class WrhipTapResult(C.Structure):
     _fields_ = [("status", i32), ("width", u32), ("height", u32), ("format", u32), ("digest", u64 * 2),
                 ("max_diff", u32), ("differing", u32), ("hist", u32 * 256)]
+
+
+# WrhipGrabTexture flags, and the bytes that cross ahead of every grab's payload (include/wrhip.h)
+GRAB_FLIP_ROWS, GRAB_SWAP_RB, GRAB_DELTA, GRAB_KEY = 1, 2, 4, 8
+GRAB_MAX_RECTS, GRAB_HEADER, GRAB_BLOCK = 16, 16, 64
+
+
+class WrhipGrabInfo(C.Structure):
+    _fields_ = [("status", i32), ("format", u32), ("flags", u32), ("nrects", i32), ("rects", (i32 * 4) * GRAB_MAX_RECTS),
+                ("keyframe", u32), ("blocks", u32), ("blocks_total", u32), ("damage", i32 * 4), ("bytes", u64)]
 
 
 def _as_ptr(x):
@@ -188,7 +200,10 @@ class GL:
             setattr(self, name, self._wrap(name, fn, args))
         if self.is_wrhip:
             for name, (res, args) in EXTRA_SIGNATURES.items():
-                fn = getattr(self._dll, name)
+                # (WRHIP_LIB_PATH may name an older build, for A/B runs: an addition it lacks is an AttributeError where it is used)
+                fn = getattr(self._dll, name, None)
+                if fn is None:
+                    continue
                 fn.restype, fn.argtypes = res, args
                 setattr(self, name, fn)
 
@@ -247,6 +262,53 @@ class GL:
             raise KeyError(f"tap ticket {ticket} is unknown or has been overwritten")
         return {"status": r.status, "width": r.width, "height": r.height, "format": r.format, "digest": (int(r.digest[0]), int(r.digest[1])),
                 "max_diff": r.max_diff, "differing": r.differing, "hist": list(r.hist)}
+
+
+    def grab_texture(self, tex, rects=None, flags=0):
+        """Enqueue a grab (include/wrhip.h, WrhipGrabTexture) of texture id `tex`: `rects` is None (all of it), one rect
+        (x, y, w, h) or a list of rects.  Returns the ticket, or -1 (GL_INVALID_VALUE / GL_OUT_OF_MEMORY is then set)."""
+        if rects is None:
+            w, h = i32(0), i32(0)
+            if not self.WrhipGetTextureSize(tex, C.byref(w), C.byref(h)):
+                w = h = i32(0)
+            rects = [(0, 0, w.value, h.value)]
+        elif len(rects) == 4 and not hasattr(rects[0], "__len__"):
+            rects = [rects]
+        flat = [int(v) for r in rects for v in r]
+        arr = (i32 * max(1, len(flat)))(*flat)
+        return self.WrhipGrabTexture(tex, C.addressof(arr), len(rects), flags)
+
+    def grab_result(self, ticket, wait=True, into=None):
+        """The result of a grab: (info dict, pixels).  Full mode: one array per rect ((h, w, 4) stored B, G, R, A bytes, or (h, w)
+        for R8) -- the array itself for a single rect, a list for several.  Delta mode: the caller's image `into` of the rect (a
+        C-contiguous uint8 array of the rect's shape; None: a fresh one of zeros) with the sent blocks patched in.  None if the
+        result has not arrived (wait=False only); a ticket the ring no longer holds raises KeyError."""
+        import numpy as np
+        r = WrhipGrabInfo()
+        rc = self.WrhipGrabResultGet(ticket, C.byref(r), None, 0, 1 if wait else 0)
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise KeyError(f"grab ticket {ticket} is unknown or has been overwritten")
+        rects = [tuple(r.rects[i]) for i in range(r.nrects)]
+        bpp = 1 if r.format == 0x8229 else 4          # GL_R8
+        shape = lambda w, h: (h, w) if bpp == 1 else (h, w, 4)
+        if r.flags & GRAB_DELTA:
+            out = np.zeros(shape(*rects[0][2:]), np.uint8) if into is None else into
+            assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.shape == shape(*rects[0][2:]), "grab_result: `into` is not the rect's image"
+            pixels, buf = out, out
+        else:
+            buf = np.empty(sum(w * h * bpp for _, _, w, h in rects), np.uint8)
+            parts, at = [], 0
+            for _, _, w, h in rects:
+                parts.append(buf[at:at + w * h * bpp].reshape(shape(w, h)))
+                at += w * h * bpp
+            pixels = parts[0] if len(parts) == 1 else parts
+        rc = self.WrhipGrabResultGet(ticket, C.byref(r), buf.ctypes.data, 0, 1)
+        assert rc == 0, rc
+        info = {"status": r.status, "format": r.format, "flags": r.flags, "rects": rects, "keyframe": r.keyframe, "blocks": r.blocks,
+                "blocks_total": r.blocks_total, "damage": tuple(r.damage), "bytes": int(r.bytes)}
+        return info, pixels
 
 
 def repo_root():

@@ -168,3 +168,50 @@ def render_streamed_tapped(backend_path, frames):
     stats["gl_error"] = int(err)
     r.destroy()
     return px, stats, taps
+
+
+def render_streamed_grabbed(backend_path, frames, delta=False, rect=None):
+    """render_streamed_tapped with the pixels: after each frame's render `rect` of the window (None: all of it) is grabbed
+    (GL.grab_texture: packed on the device in stream order behind that frame, carried to the host on the library's second
+    stream) -- still nothing between the frames that drains the held-back raster launches.  Results are fetched in order as they
+    arrive, and the oldest is waited for (that ticket alone) only when the ring of 8 would otherwise lose it, so any number of
+    frames goes through.  delta=True: delta grabs, patched one after the other into one host image.
+    Returns the final window (RGBA8), the backend's statistics, the host's image of the rect after every frame's grab (stored
+    bytes, B, G, R, A) and the grabs' info dicts.  libwrhip only."""
+    from . import glapi
+    gl = GL(backend_path)
+    assert gl.is_wrhip, "render_streamed_grabbed: grabs are a libwrhip addition"
+    w, h = frames[0].width, frames[0].height
+    r = Renderer(gl, w, h)
+    window = gl.WrhipGetFramebufferTexture(0)
+    rect = (0, 0, w, h) if rect is None else tuple(rect)
+    host = np.zeros((rect[3], rect[2], 4), np.uint8)
+    waiting, images, infos = [], [], []
+
+    def fetch(wait):
+        while waiting:
+            res = gl.grab_result(waiting[0], wait=wait, into=host if delta else None)
+            if res is None:
+                return
+            waiting.pop(0)
+            infos.append(res[0])
+            images.append(host.copy() if delta else res[1])
+            wait = False
+    for f in frames:
+        assert (f.width, f.height) == (w, h), "render_streamed_grabbed: one window size"
+        r.render(f)
+        if len(waiting) == 8:
+            fetch(True)
+        t = gl.grab_texture(window, rect, glapi.GRAB_DELTA if delta else 0)
+        assert t >= 0, (t, gl.GetError())
+        waiting.append(t)
+        fetch(False)
+    r.finish()
+    err = gl.GetError()
+    while waiting:
+        fetch(True)
+    px = r.read_pixels()
+    stats = gl.stats()
+    stats["gl_error"] = int(err)
+    r.destroy()
+    return px, stats, images, infos
