@@ -252,7 +252,7 @@ void WrhipSetProfiling(int enabled);
  * (picture targets of a few large gradient / image prims, likewise), 11 = wr_setup_tile_rows_kernel (10 fused with the next flush's setup stage), 12 = a thin launch of the raster kernel (13: the same with the next flush's setup stage in front, wr_setup_raster_thin_kernel) (wr_raster_kernel<fmt, false, 1, feat>:
  * small levels, several workgroups per bin), 14 = wr_tap_kernel (WrhipTapTexture: fmt of the tapped texture, feat 1 against an expected texture;
  * algo_bytes: the rect's bytes, twice with an expected texture), 15 = wr_grab_pack_kernel (WrhipGrabTexture: fmt of the grabbed texture,
- * feat 1 in delta mode; algo_bytes: bytes read plus bytes written, as far as they are known at the launch).  algo_bytes: the launch's algorithmic bytes:
+ * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta; algo_bytes: bytes read plus bytes written, as far as they are known at the launch).  algo_bytes: the launch's algorithmic bytes:
  * raster launches count every destination pixel they own once (twice when the target's old content is loaded) plus
  * the source texels their draws can sample; the setup stage counts instance + descriptor + record bytes.  Returns the
  * number of entries written (<= max). */
@@ -343,8 +343,11 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  *   byte of it differs from the retained copy, and every block is sent when there is no valid retained copy (a keyframe); the
  *   same grab brings the retained copy up to date.  In WrhipGrabResultGet `dst` is the caller's own image of the rect (h rows at
  *   `dst_stride`, 0: tight): the sent blocks are patched into it and nothing else is touched.
+ * Packed delta mode (WRHIP_GRAB_DELTA | WRHIP_GRAB_PACKED, with or without KEY): a delta grab whose sent blocks are written in the
+ *   lossless packed form below.  Retained copy, block comparison and keyframe rules are the plain delta grab's, and plain and packed
+ *   delta grabs of one texture and rect may alternate without a keyframe: PACKED changes only how a sent block is written.
  * Returns -1 and sets GL_INVALID_VALUE, launching nothing, for an unknown texture or format, no rects or more than 16, a rect that
- * is empty or not inside `tex`, an unknown flag, DELTA with several rects or with FLIP_ROWS / SWAP_RB, KEY without DELTA, SWAP_RB on
+ * is empty or not inside `tex`, an unknown flag, DELTA with several rects or with FLIP_ROWS / SWAP_RB, KEY or PACKED without DELTA, SWAP_RB on
  * GL_R8, and while sharding is on (WrhipSetShard world > 1, WrhipSetTargetRows on `tex`).  Returns -1 with GL_OUT_OF_MEMORY when the
  * pinned host memory of the ticket ring would exceed WRHIP_GRAB_PINNED_MAX bytes (environment; default 512 MB): every one of the 8
  * ring entries keeps a device and a pinned slot as large as the largest grab it carried (a delta grab: all blocks of the rect).
@@ -354,13 +357,43 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  * alone, not for the stream); -1 for a ticket that was never handed out or has been overwritten -- the ring holds the 8 newest --
  * and, with GL_INVALID_VALUE, for a `dst_stride` below a row's bytes or a non-zero one with several rects.  A result may be fetched
  * any number of times while its ticket lives.  `bytes` counts what crossed to the host: WRHIP_GRAB_HEADER bytes and the payload --
- * the rects' bytes in full mode, blocks * (16 + 64 * 64 * bpp) in delta mode (a 16-byte record and the block at a fixed pitch);
- * WrhipStats::d2h_bytes grows by it when the result is first fetched.
+ * the rects' bytes in full mode, blocks * (16 + 64 * 64 * bpp) in delta mode (a 16-byte record and the block at a fixed pitch), the
+ * sum of the entries' sizes in packed delta mode, where `blocks` counts the entries and `damage` bounds them;
+ * WrhipStats::d2h_bytes grows by it when the ticket is first fetched, by this call or by WrhipGrabPayloadGet.  A delta payload that
+ * does not parse (status 1) is delivered as far as its entries are good ones: the library's own kernels never write such a one.
+ *
+ * WrhipGrabPayloadGet(ticket, dst, capacity, bytes, wait): the bytes that crossed, of a grab of any mode, as they lie in the pinned
+ * slot -- the 16-byte header (word 0: the payload's bytes), then the payload --, for a consumer that forwards them.  0 with *bytes =
+ * header + payload and the first min(capacity, *bytes) of them copied to `dst` (which may be NULL with capacity 0); 1: not arrived
+ * (wait == 0 only); -1: a dead ticket.  Parking and `wait` are WrhipGrabResultGet's.
+ *
+ * WrhipGrabDecode(payload, bytes, format, flags, rect_w, rect_h, dst, dst_stride, damage, blocks): a pure host function -- no
+ * context, no GPU -- that patches a delta payload (`payload`: its header; `flags`: the grab's, PACKED or not; `format`: GL_RGBA8 or
+ * GL_R8) into the caller's image `dst` of the rect (rows of `dst_stride` bytes, 0: tight; NULL: only checked) and returns 0 with the
+ * entries' bounding box and number (either may be NULL), or -1 for a malformed payload, having written nothing.
+ * WrhipGrabResultGet decodes through the same code (webrender_amd/csrc/wr_grab_codec.h, which a program can include on its own).
+ *
+ * THE PACKED PAYLOAD (a contract: one content has one encoding, only the order of the entries is free).
+ *   A sequence of entries, each starting on 16 bytes and a multiple of 16 bytes long: a 16-byte record, then a body.  The record is
+ *   four little-endian 32-bit words:  0: x of the block, relative to the rect;  1: y likewise;  2: w | h << 8 | mode << 16, w and h
+ *   in 1..64 (the block cut to the rect);  3: aux.
+ *   The block's pixels in row-major order over the CUT block are p_0 .. p_{w*h-1}; a pixel's value is its 4 stored bytes as a word
+ *   (RGBA8) or its byte (R8).  Pixel i starts a run if i = 0 or value(p_i) != value(p_{i-1}) -- the first pixel of a row is compared
+ *   with the last pixel of the row above.  n is the number of run starts.
+ *     mode 0 RAW    neither of the others applies.  aux 0.  Body: 64 rows at a pitch of 64 * bpp, as in a plain delta entry; the
+ *                   bytes beyond the cut block are zero.
+ *     mode 1 SOLID  n = 1.  aux: the value (R8: the byte, zero-extended).  No body.
+ *     mode 2 RUNS   n > 1 and 16 + align16(8 * h + n * bpp) < 16 + 4096 * bpp.  aux: n.  Body: h words of 64 bits, one per block
+ *                   row, bit c set when pixel (r, c) starts a run, bits at c >= w zero; then the n start values in order (n * bpp
+ *                   bytes); then zero bytes to the next multiple of 16.
+ *   A tie between RUNS and RAW goes to RAW: a full RGBA8 block is RUNS up to n = 3964 and RAW from 3965, a full R8 block RUNS up
+ *   to n = 3568 and RAW from 3569.  No entry is larger than a plain delta entry, so slots are sized as for a plain delta grab.
  * Not routed through grabs: Finish, GetColorBuffer, ReadPixels.  Not supported: scaling, other formats, sharded targets. */
 #define WRHIP_GRAB_FLIP_ROWS 1u   /* full mode: deliver the rect's last row first */
 #define WRHIP_GRAB_SWAP_RB   2u   /* full mode, RGBA8 only: bytes 0 and 2 of every pixel exchanged */
 #define WRHIP_GRAB_DELTA     4u   /* only the 64x64 blocks that differ from the previous DELTA grab of this texture and rect */
 #define WRHIP_GRAB_KEY       8u   /* with DELTA: ignore the retained copy, send every block */
+#define WRHIP_GRAB_PACKED    32u  /* with DELTA: sent blocks as SOLID / RUNS / RAW entries (the packed payload above); 16 is no flag */
 #define WRHIP_GRAB_MAX_RECTS 16
 #define WRHIP_GRAB_HEADER    16u  /* bytes that cross with every grab ahead of its payload (the payload's byte count) */
 typedef struct WrhipGrabInfo {
@@ -374,6 +407,8 @@ typedef struct WrhipGrabInfo {
 } WrhipGrabInfo;
 int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint32_t flags);
 int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64_t dst_stride, int32_t wait);
+int32_t WrhipGrabPayloadGet(int32_t ticket, void* dst, uint64_t capacity, uint64_t* bytes, int32_t wait);
+int32_t WrhipGrabDecode(const void* payload, uint64_t bytes, uint32_t format, uint32_t flags, int32_t rect_w, int32_t rect_h, void* dst, int64_t dst_stride, int32_t damage[4], uint32_t* blocks);
 
 #ifdef __cplusplus
 }

@@ -2,11 +2,14 @@
 """Measurements of texture grabs (include/wrhip.h, WrhipGrabTexture) on the MI355X: DESIGN.md section 6.2.
 
   pack       wr_grab_pack_kernel on the 3840 x 2160 RGBA8 window (hipEvents, WrhipSetProfiling(1)): full mode, a keyframe delta,
-             a delta with nothing changed, a delta with ~2 % of the blocks changed
+             a delta with nothing changed, a delta with ~2 % of the blocks changed; the three delta lines again with
+             WRHIP_GRAB_PACKED (wr_grab_pack_runs_kernel); all of it on a window of noise (every block RAW) and on the cfg2 frame
   transport  33.2 MB from the device slot to the pinned host slot: wr_grab_push_kernel at 8 / 32 / 128 workgroups against
              hipMemcpyAsync, grab call to arrival on the host clock (the pack's time is in it; `pack` says how much that is)
   stream     cfg2 at 4K streamed -- one native replay call per frame from a Python loop, one Finish at the end --, frames/s:
-             no grab, a tap per frame, a full grab per frame, a delta grab per frame (identical frames), a ReadPixels per frame
+             no grab, a tap per frame, a full grab per frame, a delta grab per frame (identical frames), a ReadPixels per frame;
+             then cfg2 frames of different seeds in turn: no grab, a delta grab per frame, a packed delta grab per frame, with the
+             bytes per frame that crossed
   ab         plain bench.py against another build of the library (WRHIP_LIB_PATH), alternated, no grab issued
 
 Every section runs three alternated rounds.  Needs the GPU: there is no fallback.
@@ -43,13 +46,16 @@ def kernel_stats(gl, kind):
 
 
 class Window:
-    """A context with a 4K window of noise"""
+    """A context with a 4K window of noise, or of the cfg2 frame"""
 
-    def __init__(self, lib):
+    def __init__(self, lib, content="noise"):
         self.gl = glapi.GL(lib)
         self.r = Renderer(self.gl, W, H)
         self.tex = self.gl.WrhipGetFramebufferTexture(0)
-        self.upload(0, 0, np.random.default_rng(1).integers(0, 256, (H, W, 4), dtype=np.uint8))
+        if content == "noise":
+            self.upload(0, 0, np.random.default_rng(1).integers(0, 256, (H, W, 4), dtype=np.uint8))
+        else:
+            self.r.render(scenes.make_workload(content, width=W, height=H))
         self.r.finish()
 
     def upload(self, x, y, px):
@@ -70,11 +76,12 @@ class Window:
         self.r.destroy()
 
 
-def section_pack(lib):
-    say(f"## pack: wr_grab_pack_kernel, {W}x{H} RGBA8 window, hipEvents (WrhipSetProfiling(1)), us per launch")
-    w = Window(lib)
+def section_pack(lib, content="noise"):
+    say(f"## pack: wr_grab_pack_kernel / wr_grab_pack_runs_kernel, {W}x{H} RGBA8 window of {content}, hipEvents (WrhipSetProfiling(1)), us per launch")
+    w = Window(lib, content)
     gl = w.gl
-    for flags in (0, glapi.GRAB_DELTA):          # (untimed: code objects, slots, the retained copy)
+    DP = glapi.GRAB_DELTA | glapi.GRAB_PACKED
+    for flags in (0, glapi.GRAB_DELTA, DP):          # (untimed: code objects, slots, the retained copy)
         for _ in range(8):
             w.grab(flags)
     rng = np.random.default_rng(2)
@@ -85,24 +92,29 @@ def section_pack(lib):
     rows = {}
     for rnd in range(ROUNDS):
         for name, flags, n in (("full", 0, 30), ("delta keyframe", glapi.GRAB_DELTA | glapi.GRAB_KEY, 30), ("delta unchanged", glapi.GRAB_DELTA, 30),
-                               ("delta ~2% changed", glapi.GRAB_DELTA, 10)):
-            if name == "delta unchanged":
+                               ("delta ~2% changed", glapi.GRAB_DELTA, 10),
+                               ("packed keyframe", DP | glapi.GRAB_KEY, 30), ("packed unchanged", DP, 30), ("packed ~2% changed", DP, 10)):
+            if name.endswith("unchanged"):
                 w.grab(glapi.GRAB_DELTA)
             gl.WrhipResetStats()
-            blocks = []
+            blocks, crossed = [], []
             for k in range(n):
-                if name == "delta ~2% changed":
+                if name.endswith("~2% changed"):
                     for b in some:
                         w.upload(int(b % (W // 64)) * 64 + 5, int(b // (W // 64)) * 64 + 3, patches[(k + rnd) & 1])
                     gl.WrhipFlush()
-                blocks.append(w.grab(flags).blocks)
+                info = w.grab(flags)
+                blocks.append(info.blocks)
+                crossed.append(info.bytes)
             ks = kernel_stats(gl, 15)
-            assert len(ks) == 1 and ks[0].launches == n and ks[0].feat == (1 if flags & glapi.GRAB_DELTA else 0), [(k.kind, k.feat, k.launches) for k in ks]
-            rows.setdefault(name, []).append((ks[0].ns / n / 1e3, ks[0].workgroups // n, int(np.median(blocks))))
+            feat = 2 if flags & glapi.GRAB_PACKED else 1 if flags & glapi.GRAB_DELTA else 0
+            assert len(ks) == 1 and ks[0].launches == n and ks[0].feat == feat, [(k.kind, k.feat, k.launches) for k in ks]
+            rows.setdefault(name, []).append((ks[0].ns / n / 1e3, ks[0].workgroups // n, int(np.median(blocks)), int(np.median(crossed))))
     gl.WrhipSetProfiling(0)
     for name, v in rows.items():
-        say(f"  {name:20s} " + "  ".join(f"{us:8.1f}" for us, _, _ in v) + f"   us   ({v[0][1]} workgroups; blocks sent {v[0][2]} of {nblocks})")
-    say("  (beside: wr_tap_kernel 28.9 / 32.4 us for 33.2 / 66.4 MB read; the 6.1 TB/s copy ceiling gives 10.9 us for 33.2 MB read + 33.2 MB written)")
+        say(f"  {name:20s} " + "  ".join(f"{us:8.1f}" for us, _, _, _ in v) + f"   us   ({v[0][1]} workgroups; blocks sent {v[0][2]} of {nblocks}; {v[0][3]} bytes crossed)")
+    if content == "noise":
+        say("  (beside: wr_tap_kernel 28.9 / 32.4 us for 33.2 / 66.4 MB read; the 6.1 TB/s copy ceiling gives 10.9 us for 33.2 MB read + 33.2 MB written)")
     w.close()
 
 
@@ -136,6 +148,9 @@ def section_stream(lib, frames):
     frame = scenes.make_workload("cfg2", width=W, height=H)
     assert (frame.width, frame.height) == (W, H)
     rec, _ = record_scene(lib, frame)
+    # (the changing stream's frames are recorded here too: a recording makes and destroys a context of its own, which must not
+    # happen while the player's is the library's current one)
+    streams = [record_scene(lib, scenes.make_workload("cfg2", width=W, height=H, seed=sd))[0].stream for sd in (1, 2, 3, 4)]
     p = ScenePlayer(lib, rec)
     sym = lambda name, res, *args: C.CFUNCTYPE(res, *args)(p.symbol(name))
     finish = sym("Finish", None)
@@ -198,6 +213,55 @@ def section_stream(lib, frames):
         say(f"  {k:22s} " + "  ".join(f"{v:9.1f}" for v in rows[k]) + f"   frames/s   (setup_carried {carried[k][0][0]} of {carried[k][0][1]} flushes)")
     say("  (full grab / delta grab / ReadPixels deliver into the caller's 33.2 MB image; ReadPixels as GL_BGRA, no CPU swizzle; 'info only' fetches with dst == NULL)")
 
+    # frames that change: cfg2 of four seeds in turn (recorded one by one above; the window and its tiles are the same objects in each)
+    say(f"## changing stream: cfg2 {W}x{H} of seeds 1..4 in turn, one grab per frame, {frames} frames per region")
+    modes = {"no grab": None, "delta grab": glapi.GRAB_DELTA, "packed delta grab": glapi.GRAB_DELTA | glapi.GRAB_PACKED}
+
+    def run_changing(flags, n):
+        waiting, crossed, blocks = [], [], []
+
+        def fetch(wait):
+            while waiting:
+                rc = grab_get(waiting[0], C.byref(info), host.ctypes.data, 0, 1 if wait else 0)
+                if rc == 1:
+                    return
+                assert rc == 0 and info.status == 0, (rc, info.status)
+                waiting.pop(0)
+                crossed.append(int(info.bytes))
+                blocks.append(int(info.blocks))
+                wait = False
+        for k in range(n):
+            p.rp.exec(streams[k % len(streams)])
+            if flags is not None:
+                if len(waiting) == 8:
+                    fetch(True)
+                t = grab(window, C.addressof(rect), 1, flags)
+                assert t >= 0
+                waiting.append(t)
+                fetch(False)
+        finish()
+        while waiting:
+            fetch(True)
+        # (the four recordings must address the same objects for the replay to draw them: every frame then differs from the one before)
+        assert flags is None or (len(blocks) == n and min(blocks[1:]) > 0), f"frames that did not change: blocks per frame {blocks}"
+        return crossed, blocks
+
+    check = np.zeros((H, W, 4), np.uint8)
+    for name, flags in modes.items():
+        run_changing(flags, 12)
+        if flags is not None:          # (the patched image is the window)
+            read_pixels(0, 0, W, H, G.GL_BGRA, G.GL_UNSIGNED_BYTE, check.ctypes.data)
+            assert np.array_equal(check, host), f"{name}: the patched image is not the window"
+    crows = {}
+    for rnd in range(ROUNDS):
+        for name, flags in modes.items():
+            t0 = time.perf_counter()
+            crossed, blocks = run_changing(flags, frames)
+            dt = time.perf_counter() - t0
+            crows.setdefault(name, []).append((frames / dt, float(np.mean(crossed[1:])) if crossed else 0.0, float(np.mean(blocks[1:])) if blocks else 0.0))
+    for name, v in crows.items():
+        say(f"  {name:22s} " + "  ".join(f"{fps:9.1f}" for fps, _, _ in v) + "   frames/s   " + (f"({v[0][1] / 1e6:7.3f} MB and {v[0][2]:6.1f} blocks per frame crossed)" if v[0][1] else ""))
+
 
 def section_ab(other, steps, warmup):
     say(f"## ab: bench.py --gpus 1 --steps {steps} --warmup {warmup} (cfg2), this library against {os.path.basename(other)}, alternated, frames/s")
@@ -243,7 +307,8 @@ def main():
     try:
         for s in args.sections.split(","):
             if s == "pack":
-                section_pack(lib)
+                section_pack(lib, "noise")
+                section_pack(lib, "cfg2")
             elif s == "transport":
                 section_transport(lib)
             elif s == "stream":

@@ -1,0 +1,179 @@
+// The payload of a delta grab (include/wrhip.h, WrhipGrabTexture) on the host: walking its entries, checking them, patching them into
+// an image of the rect -- and, for the host simulation and for programs that want a payload to feed the decoder, the encoding of one
+// block.  Plain C++: no HIP, no library state, nothing but this file is needed (tools/grab_codec_check.cpp includes it alone).
+//
+// A payload: a 16-byte header (word 0: the bytes of the entries behind it) and the entries.
+//   plain   entries of 16 + 64 * 64 * bpp bytes: a record x, y, w, h (four little-endian words; the block relative to the rect, cut
+//           to it) and the block's rows at a pitch of 64 * bpp
+//   packed  (WRHIP_GRAB_PACKED) entries of a multiple of 16 bytes: a record x, y, w | h << 8 | mode << 16, aux and a body
+//           RAW   0  aux 0; the body of a plain entry, bytes outside the cut block zero
+//           SOLID 1  aux: the one value of the block; no body
+//           RUNS  2  aux: n, the run starts; h words of 64 bits (bit c of word r: pixel (r, c) starts a run), the n values, zeros
+//                    to the next multiple of 16
+//           Pixel i of the cut block in row-major order starts a run if i == 0 or its value differs from pixel i - 1's.  One run
+//           start: SOLID; otherwise RUNS if that entry is smaller than a RAW one, else RAW.
+#ifndef WR_GRAB_CODEC_H
+#define WR_GRAB_CODEC_H
+#include <stddef.h>
+#include <stdint.h>
+#include <string.h>
+
+#define WR_GC_HEADER 16
+#define WR_GC_BLOCK 64
+enum { WR_GC_RAW = 0, WR_GC_SOLID = 1, WR_GC_RUNS = 2 };
+
+struct WrGrabEntry {
+  int32_t x, y, w, h;      // the block, relative to the rect
+  int32_t mode;            // WR_GC_*; RAW for a plain entry
+  uint32_t aux;
+  size_t size;             // of the whole entry, record included
+};
+
+static inline size_t wr_gc_raw_size(int bpp) { return 16 + (size_t)WR_GC_BLOCK * WR_GC_BLOCK * bpp; }
+static inline size_t wr_gc_runs_size(int h, uint32_t n, int bpp) { return 16 + (((size_t)8 * h + (size_t)n * bpp + 15) & ~(size_t)15); }
+// the mode the rule gives a cut block of h rows with n run starts
+static inline int wr_gc_mode(int h, uint32_t n, int bpp) {
+  if (n == 1) return WR_GC_SOLID;
+  return wr_gc_runs_size(h, n, bpp) < wr_gc_raw_size(bpp) ? WR_GC_RUNS : WR_GC_RAW;
+}
+static inline uint32_t wr_gc_load32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+static inline void wr_gc_store32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
+static inline uint64_t wr_gc_load64(const uint8_t* p) { return (uint64_t)wr_gc_load32(p) | (uint64_t)wr_gc_load32(p + 4) << 32; }
+
+// The entry at `p`, of which `avail` bytes belong to the payload, against a rect of rw x rh: false if its record or its body is
+// not one the format allows or does not fit.  Everything wr_gc_patch relies on is checked here.
+static inline bool wr_gc_entry(const uint8_t* p, size_t avail, int bpp, bool packed, int rw, int rh, WrGrabEntry* E, bool checked = false) {
+  if (avail < 16) return false;
+  const uint32_t w0 = wr_gc_load32(p), w1 = wr_gc_load32(p + 4), w2 = wr_gc_load32(p + 8), w3 = wr_gc_load32(p + 12);
+  uint32_t w, h, mode = WR_GC_RAW, aux = 0;
+  if (packed) { w = w2 & 0xFFu; h = (w2 >> 8) & 0xFFu; mode = w2 >> 16; aux = w3; }
+  else { w = w2; h = w3; }
+  if (w < 1 || h < 1 || w > WR_GC_BLOCK || h > WR_GC_BLOCK || mode > WR_GC_RUNS) return false;
+  if (w > (uint32_t)rw || h > (uint32_t)rh || w0 > (uint32_t)rw - w || w1 > (uint32_t)rh - h) return false;
+  E->x = (int32_t)w0; E->y = (int32_t)w1; E->w = (int32_t)w; E->h = (int32_t)h; E->mode = (int32_t)mode; E->aux = aux;
+  if (mode == WR_GC_SOLID) { E->size = 16; return true; }
+  if (mode == WR_GC_RAW) { E->size = wr_gc_raw_size(bpp); return E->size <= avail; }
+  const uint32_t n = aux;
+  if (n < 1 || n > w * h) return false;
+  E->size = wr_gc_runs_size((int)h, n, bpp);
+  if (E->size > avail) return false;
+  if (checked) return true;      // (an entry this function has passed before: its record and size are all the caller is after)
+  // the bitmap: no bit at a column >= w, the first pixel starts a run, as many bits as values
+  const uint64_t beyond = w == 64 ? 0ull : ~0ull << w;
+  uint32_t bits = 0;
+  for (uint32_t r = 0; r < h; r++) {
+    const uint64_t m = wr_gc_load64(p + 16 + 8 * r);
+    if (m & beyond) return false;
+    bits += (uint32_t)__builtin_popcountll(m);
+  }
+  return bits == n && (p[16] & 1u) != 0;
+}
+
+// n pixels of one value
+static inline void wr_gc_fill(uint8_t* d, const uint8_t* v, int n, int bpp) {
+  if (bpp == 1) { memset(d, v[0], (size_t)n); return; }
+  uint32_t w;
+  memcpy(&w, v, 4);
+  for (int i = 0; i < n; i++) memcpy(d + 4 * (size_t)i, &w, 4);
+}
+// A checked entry's pixels into the image of the rect (`dst`, rows of `ds` bytes); runs are filled whole, not pixel by pixel
+static inline void wr_gc_patch(const uint8_t* p, const WrGrabEntry& E, int bpp, uint8_t* dst, size_t ds) {
+  uint8_t* d0 = dst + (size_t)E.y * ds + (size_t)E.x * bpp;
+  if (E.mode == WR_GC_RAW) {
+    for (int r = 0; r < E.h; r++) memcpy(d0 + (size_t)r * ds, p + 16 + (size_t)r * WR_GC_BLOCK * bpp, (size_t)E.w * bpp);
+    return;
+  }
+  if (E.mode == WR_GC_SOLID) {
+    uint8_t v[4];
+    wr_gc_store32(v, E.aux);
+    for (int r = 0; r < E.h; r++) wr_gc_fill(d0 + (size_t)r * ds, v, E.w, bpp);
+    return;
+  }
+  const uint8_t* lit = p + 16 + 8 * (size_t)E.h;
+  const uint8_t* cur = lit;      // (the first pixel starts a run: never read before it is set)
+  for (int r = 0; r < E.h; r++) {
+    const uint64_t m = wr_gc_load64(p + 16 + 8 * (size_t)r);
+    uint8_t* d = d0 + (size_t)r * ds;
+    for (int c = 0; c < E.w;) {
+      if ((m >> c) & 1ull) { cur = lit; lit += bpp; }
+      const uint64_t above = c == 63 ? 0ull : (m >> (c + 1)) << (c + 1);      // (the starts right of c: none at a column >= w)
+      const int e = above ? __builtin_ctzll(above) : E.w;
+      wr_gc_fill(d + (size_t)c * bpp, cur, e - c, bpp);
+      c = e;
+    }
+  }
+}
+
+// A whole payload (`payload`: its header; `bytes`: what the caller holds of it) patched into `dst`: 0, with the bounding box of the
+// entries' blocks and their number, or -1 for a malformed one -- nothing is written then: every entry is checked before the first
+// is patched.
+static inline int wr_gc_decode(const void* payload, uint64_t bytes, int bpp, bool packed, int rw, int rh, void* dst, int64_t dst_stride,
+                               int32_t damage[4], uint32_t* blocks) {
+  if (!payload || bytes < WR_GC_HEADER || (bpp != 1 && bpp != 4) || rw < 1 || rh < 1) return -1;
+  const int64_t tight = (int64_t)rw * bpp;
+  if (dst && dst_stride != 0 && dst_stride < tight) return -1;
+  const uint8_t* p = (const uint8_t*)payload;
+  const uint64_t count = wr_gc_load32(p);
+  if (count > bytes - WR_GC_HEADER) return -1;
+  p += WR_GC_HEADER;
+  int x0 = rw, y0 = rh, x1 = 0, y1 = 0;
+  uint32_t n = 0;
+  WrGrabEntry E;
+  for (size_t at = 0; at < count; at += E.size, n++) {
+    if (!wr_gc_entry(p + at, (size_t)(count - at), bpp, packed, rw, rh, &E)) return -1;
+    x0 = E.x < x0 ? E.x : x0; y0 = E.y < y0 ? E.y : y0;
+    x1 = E.x + E.w > x1 ? E.x + E.w : x1; y1 = E.y + E.h > y1 ? E.y + E.h : y1;
+  }
+  if (dst) {
+    const size_t ds = dst_stride ? (size_t)dst_stride : (size_t)tight;
+    for (size_t at = 0; at < count; at += E.size) {
+      wr_gc_entry(p + at, (size_t)(count - at), bpp, packed, rw, rh, &E, true);
+      wr_gc_patch(p + at, E, bpp, (uint8_t*)dst, ds);
+    }
+  }
+  if (damage) {
+    damage[0] = damage[1] = damage[2] = damage[3] = 0;
+    if (x1 > x0 && y1 > y0) { damage[0] = x0; damage[1] = y0; damage[2] = x1 - x0; damage[3] = y1 - y0; }
+  }
+  if (blocks) *blocks = n;
+  return 0;
+}
+
+// The packed entry of one cut block (w x h pixels at `px`, rows of `stride` bytes) at (x, y) of the rect, written to `out` (room
+// for wr_gc_raw_size(bpp) bytes): -> its size.  Serial; the device's kernel (wr_grab_pack_runs_kernel) writes the same bytes.
+static inline size_t wr_gc_encode_block(const uint8_t* px, size_t stride, int x, int y, int w, int h, int bpp, uint8_t* out) {
+  uint32_t n = 0;
+  uint64_t bitmap[WR_GC_BLOCK];
+  const uint8_t* prev = nullptr;
+  for (int r = 0; r < h; r++) {
+    bitmap[r] = 0;
+    for (int c = 0; c < w; c++) {
+      const uint8_t* q = px + (size_t)r * stride + (size_t)c * bpp;
+      if (!prev || memcmp(q, prev, (size_t)bpp) != 0) { bitmap[r] |= 1ull << c; n++; }
+      prev = q;
+    }
+  }
+  const int mode = wr_gc_mode(h, n, bpp);
+  uint32_t aux = 0;
+  if (mode == WR_GC_SOLID) { uint8_t v[4] = {0, 0, 0, 0}; memcpy(v, px, (size_t)bpp); aux = wr_gc_load32(v); }
+  if (mode == WR_GC_RUNS) aux = n;
+  wr_gc_store32(out, (uint32_t)x); wr_gc_store32(out + 4, (uint32_t)y);
+  wr_gc_store32(out + 8, (uint32_t)w | (uint32_t)h << 8 | (uint32_t)mode << 16); wr_gc_store32(out + 12, aux);
+  if (mode == WR_GC_SOLID) return 16;
+  if (mode == WR_GC_RAW) {
+    const size_t pitch = (size_t)WR_GC_BLOCK * bpp;
+    memset(out + 16, 0, pitch * WR_GC_BLOCK);
+    for (int r = 0; r < h; r++) memcpy(out + 16 + (size_t)r * pitch, px + (size_t)r * stride, (size_t)w * bpp);
+    return wr_gc_raw_size(bpp);
+  }
+  const size_t size = wr_gc_runs_size(h, n, bpp);
+  memset(out + 16, 0, size - 16);
+  uint8_t* lit = out + 16 + 8 * (size_t)h;
+  for (int r = 0; r < h; r++) {
+    wr_gc_store32(out + 16 + 8 * (size_t)r, (uint32_t)bitmap[r]); wr_gc_store32(out + 20 + 8 * (size_t)r, (uint32_t)(bitmap[r] >> 32));
+    for (int c = 0; c < w; c++)
+      if ((bitmap[r] >> c) & 1ull) { memcpy(lit, px + (size_t)r * stride + (size_t)c * bpp, (size_t)bpp); lit += bpp; }
+  }
+  return size;
+}
+#endif

@@ -24,6 +24,7 @@
 #include "wrhip_glenum.h"
 #include "wrhip_types.h"
 #include "wrhip_rt.h"
+#include "wr_grab_codec.h"
 #include "wrhip_kernels.h"
 #ifndef WRHIP_HOSTSIM
 // (the raster kernel instantiations live in wrhip_inst.hip, one translation unit per group, so their device compiles run in
@@ -1595,17 +1596,20 @@ void grab_issue(uint64_t n, const WrGrabArgs& a) {
   Context* c = ctx;
   Context::GrabSlot& gs = c->grab_slot[n % Context::GRAB_RING];
   wrrt::stream_wait_event(c->stream, &gs.ev);
-  if (a.delta && !a.keyframe) wrrt::memset8(a.slot, 0, WR_GRAB_HEADER, c->stream);      // (the count the changed blocks add to)
+  // (the count the changed blocks add to; a packed keyframe counts too: its entries differ in size)
+  if (a.delta && (!a.keyframe || a.packed)) wrrt::memset8(a.slot, 0, WR_GRAB_HEADER, c->stream);
   int rows = 0;
   uint64_t rect_bytes = 0;
   for (int i = 0; i < a.nrects; i++) { rows += a.rects[i][3]; rect_bytes += (uint64_t)a.rects[i][2] * a.rects[i][3] * a.bpp; }
   const int grid = a.delta ? a.bx * a.by : (rows + a.rows_per_wg - 1) / a.rows_per_wg;
   prof_begin();
-  WR_LAUNCH(wr_grab_pack_kernel, grid, 256, c->stream, a);
-  // (15: wr_grab_pack_kernel; feat 1: delta.  Bytes read plus bytes written: the rect twice in full mode; a keyframe reads the rect
+  if (a.packed) WR_LAUNCH(wr_grab_pack_runs_kernel, grid, 256, c->stream, a);
+  else WR_LAUNCH(wr_grab_pack_kernel, grid, 256, c->stream, a);
+  // (15: wr_grab_pack_kernel; feat 1: delta, 2: packed delta, wr_grab_pack_runs_kernel -- the bytes of its keyframe's entries are
+  // not known here either.  Bytes read plus bytes written: the rect twice in full mode; a keyframe reads the rect
   // and writes entries and retained copy; any other delta reads rect and retained copy -- what its changed blocks then write is not
   // known here and is not counted)
-  prof_end(15, a.bpp == 4 ? WR_FMT_RGBA8 : WR_FMT_R8, 0, a.delta ? 1 : 0, a.delta && a.keyframe ? 2 * rect_bytes + a.payload : 2 * rect_bytes, (uint64_t)grid);
+  prof_end(15, a.bpp == 4 ? WR_FMT_RGBA8 : WR_FMT_R8, 0, a.packed ? 2 : a.delta ? 1 : 0, a.delta && a.keyframe && !a.packed ? 2 * rect_bytes + a.payload : 2 * rect_bytes, (uint64_t)grid);
   c->stats.kernel_launches++;
   WrGrabPushArgs pa;
   pa.src = gs.dev; pa.dst = gs.host; pa.capacity = (uint32_t)gs.cap;
@@ -3895,7 +3899,8 @@ int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint3
   const bool delta = (flags & WRHIP_GRAB_DELTA) != 0;
   bool ok = t && t->dptr && (t->internal_format == GL_RGBA8 || t->internal_format == GL_R8);
   ok = ok && rects && nrects >= 1 && nrects <= WRHIP_GRAB_MAX_RECTS;
-  ok = ok && (flags & ~(WRHIP_GRAB_FLIP_ROWS | WRHIP_GRAB_SWAP_RB | WRHIP_GRAB_DELTA | WRHIP_GRAB_KEY)) == 0;
+  ok = ok && (flags & ~(WRHIP_GRAB_FLIP_ROWS | WRHIP_GRAB_SWAP_RB | WRHIP_GRAB_DELTA | WRHIP_GRAB_KEY | WRHIP_GRAB_PACKED)) == 0;
+  ok = ok && (delta || !(flags & WRHIP_GRAB_PACKED));
   ok = ok && (delta ? nrects == 1 && !(flags & (WRHIP_GRAB_FLIP_ROWS | WRHIP_GRAB_SWAP_RB)) : !(flags & WRHIP_GRAB_KEY));
   ok = ok && (!(flags & WRHIP_GRAB_SWAP_RB) || t->internal_format == GL_RGBA8);
   uint64_t payload = 0;
@@ -3952,7 +3957,7 @@ int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint3
     }
     memcpy(t->grab_rect, rects, sizeof(t->grab_rect));
     t->grab_valid = true;
-    a.delta = 1; a.keyframe = keyframe ? 1 : 0;
+    a.delta = 1; a.keyframe = keyframe ? 1 : 0; a.packed = (flags & WRHIP_GRAB_PACKED) ? 1 : 0;
     a.keep = (uint8_t*)t->grab_keep; a.keep_stride = keep_stride;
     a.bx = bx; a.by = by;
   } else {
@@ -3977,6 +3982,37 @@ int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint3
   }
   return (int32_t)(n & 0x7FFFFFFFull);
 }
+// The ticket's bytes in its pinned slot: 0 with *payload their count behind the header, 1 if they have not arrived (wait == 0 only)
+static int32_t grab_arrived(Context::GrabSlot* gs, int32_t wait, uint32_t* payload) {
+  Context* c = ctx;
+  if (gs->parked) {
+    if (!wait) return 1;
+    drain_tail();            // what it is parked behind goes out (as after a WrhipFlushHeld with nothing recorded), the grab with it
+    if (gs->parked) grab_issue_parked();
+  }
+  if (wait) { HostTimer ht(&c->stats.host_wait_ns); wrrt::event_sync(&gs->ev); }
+  else if (!wrrt::event_query(&gs->ev)) return 1;
+  memcpy(payload, gs->host, 4);
+  *payload = (uint32_t)std::min<uint64_t>(*payload, gs->cap - WR_GRAB_HEADER);
+  return 0;
+}
+int32_t WrhipGrabPayloadGet(int32_t ticket, void* dst, uint64_t capacity, uint64_t* bytes, int32_t wait) {
+  if (!ctx || !bytes) return -1;
+  Context* c = ctx;
+  Context::GrabSlot* gs = grab_find(ticket);
+  if (!gs) return -1;
+  uint32_t payload;
+  if (grab_arrived(gs, wait, &payload)) return 1;
+  *bytes = (uint64_t)WR_GRAB_HEADER + payload;
+  if (dst && capacity) big_memcpy(dst, gs->host, (size_t)std::min<uint64_t>(capacity, *bytes));
+  if (!gs->counted) { c->stats.d2h_bytes += *bytes; gs->counted = true; }
+  return 0;
+}
+int32_t WrhipGrabDecode(const void* payload, uint64_t bytes, uint32_t format, uint32_t flags, int32_t rect_w, int32_t rect_h, void* dst,
+                        int64_t dst_stride, int32_t damage[4], uint32_t* blocks) {
+  if ((format != GL_RGBA8 && format != GL_R8) || !(flags & WRHIP_GRAB_DELTA)) return -1;
+  return wr_gc_decode(payload, bytes, format == GL_RGBA8 ? 4 : 1, (flags & WRHIP_GRAB_PACKED) != 0, rect_w, rect_h, dst, dst_stride, damage, blocks);
+}
 int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64_t dst_stride, int32_t wait) {
   if (!ctx || !info) return -1;
   Context* c = ctx;
@@ -3986,16 +4022,8 @@ int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64
   const int bpp = gs->bpp;
   const int64_t tight = (int64_t)gs->rects[0][2] * bpp;
   if (dst && dst_stride != 0 && (gs->nrects > 1 || dst_stride < tight)) { c->last_error = GL_INVALID_VALUE; return -1; }
-  if (gs->parked) {
-    if (!wait) return 1;
-    drain_tail();            // what it is parked behind goes out (as after a WrhipFlushHeld with nothing recorded), the grab with it
-    if (gs->parked) grab_issue_parked();
-  }
-  if (wait) { HostTimer ht(&c->stats.host_wait_ns); wrrt::event_sync(&gs->ev); }
-  else if (!wrrt::event_query(&gs->ev)) return 1;
   uint32_t payload;
-  memcpy(&payload, gs->host, 4);
-  payload = (uint32_t)std::min<uint64_t>(payload, gs->cap - WR_GRAB_HEADER);
+  if (grab_arrived(gs, wait, &payload)) return 1;
   const uint8_t* src = gs->host + WR_GRAB_HEADER;
   WrhipGrabInfo r;
   memset(&r, 0, sizeof(r));
@@ -4016,21 +4044,35 @@ int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64
       src += row * h;
     }
   } else {
-    const size_t entry = WR_GRAB_ENTRY(bpp), pitch = (size_t)WR_GRAB_BLOCK * bpp;
+    // the entries one after the other, each checked (wr_grab_codec.h) before it is patched in.  A plain entry that is not one is
+    // passed over; behind a packed one nothing can be found any more: the walk ends there.  Either way: status 1
+    const bool packed = (gs->flags & WRHIP_GRAB_PACKED) != 0;
+    const size_t entry = WR_GRAB_ENTRY(bpp);
     const int rw = gs->rects[0][2], rh = gs->rects[0][3];
     const size_t ds = dst_stride ? (size_t)dst_stride : (size_t)tight;
     r.keyframe = gs->keyframe ? 1 : 0;
-    r.blocks = (uint32_t)(payload / entry); r.blocks_total = gs->blocks_total;
+    r.blocks = packed ? 0 : (uint32_t)(payload / entry); r.blocks_total = gs->blocks_total;
     int x0 = rw, y0 = rh, x1 = 0, y1 = 0;
-    for (uint32_t e = 0; e < r.blocks; e++) {
-      int32_t rec[4];
-      memcpy(rec, src + e * entry, 16);
-      if (rec[0] < 0 || rec[1] < 0 || rec[2] < 1 || rec[3] < 1 || rec[2] > WR_GRAB_BLOCK || rec[3] > WR_GRAB_BLOCK || rec[0] > rw - rec[2] || rec[1] > rh - rec[3]) { r.status = 1; continue; }
-      x0 = std::min(x0, rec[0]); y0 = std::min(y0, rec[1]); x1 = std::max(x1, rec[0] + rec[2]); y1 = std::max(y1, rec[1] + rec[3]);
-      if (dst)
-        for (int y = 0; y < rec[3]; y++)
-          memcpy((uint8_t*)dst + (size_t)(rec[1] + y) * ds + (size_t)rec[0] * bpp, src + e * entry + 16 + (size_t)y * pitch, (size_t)rec[2] * bpp);
+    WrGrabEntry E;
+    std::vector<std::pair<size_t, WrGrabEntry>> found;      // packed: where the walk found the entries, for the copy pool
+    for (size_t at = 0; packed ? at < payload : at + entry <= payload; at += packed ? E.size : entry) {
+      if (!wr_gc_entry(src + at, payload - at, bpp, packed, rw, rh, &E)) {
+        r.status = 1;
+        if (packed) break;
+        continue;
+      }
+      if (packed) r.blocks++;
+      x0 = std::min(x0, E.x); y0 = std::min(y0, E.y); x1 = std::max(x1, E.x + E.w); y1 = std::max(y1, E.y + E.h);
+      if (dst && packed) found.push_back(std::make_pair(at, E));
+      else if (dst) wr_gc_patch(src + at, E, bpp, (uint8_t*)dst, ds);
     }
+    // (the blocks of a packed payload are decoded side by side once there are enough of them: 256 blocks write 4 MB of RGBA8)
+    const size_t nf = found.size();
+    auto patch = [&](int part, int parts) {
+      for (size_t i = nf * part / parts; i < nf * (part + 1) / parts; i++) wr_gc_patch(src + found[i].first, found[i].second, bpp, (uint8_t*)dst, ds);
+    };
+    if (nf >= 256) copy_pool().run(patch);
+    else if (nf) patch(0, 1);
     if (x1 > x0 && y1 > y0) { r.damage[0] = x0; r.damage[1] = y0; r.damage[2] = x1 - x0; r.damage[3] = y1 - y0; }
   }
   if (!gs->counted) { c->stats.d2h_bytes += r.bytes; gs->counted = true; }

@@ -355,6 +355,131 @@ __global__ void __launch_bounds__(256) wr_grab_pack_kernel(WrGrabArgs a) {
     if (n[k]) { wr_grab_st16(px + (size_t)r[k] * pitch + o[k], v[k]); wr_grab_st16(B.pk + (size_t)r[k] * a.keep_stride + o[k], v[k]); }
 #endif
 }
+// WRHIP_GRAB_PACKED: the delta path with every sent block written as a packed entry (wr_grab_codec.h; the contract is in
+// include/wrhip.h).  Geometry, piece ownership and the compare with the retained copy are wr_grab_pack_kernel's.  A block that is
+// sent is staged in LDS at the pitch of a plain entry, zeros beyond the cut block, and then looked at in raster order: thread t has
+// the 16 pixels of row t / 4 from column 16 * (t & 3) on, so that the predecessor of its first pixel -- the pixel to the left, or the
+// last valid one of the row above -- is one LDS read.  The run starts a thread found are 16 bits of the row's bitmap word and a
+// count; the counts are scanned across the wave by lane shifts and across the four waves through four LDS words, which gives n and
+// where each thread's values go among the n.  n decides the mode and the entry's size, ONE returning atomic on the slot's byte count
+// takes the entry (keyframes too: entries differ in size, so entry i is not block i), and what leaves for the slot leaves as
+// 16-byte stores: a RUNS body is put together in a second LDS buffer and copied out, a RAW body is the registers the pieces were
+// loaded into.  32 KB of LDS per workgroup.
+#ifndef WRHIP_HOSTSIM
+typedef uint32_t wr_lu4 __attribute__((ext_vector_type(4)));
+typedef uint16_t __attribute__((may_alias)) wr_u16a;
+template <int BPP> WR_DEVICE uint32_t wr_grab_staged(const wr_lu4* stage, int r, int c) {
+  return BPP == 4 ? ((const uint32_t*)stage)[r * WR_GRAB_BLOCK + c] : (uint32_t)((const uint8_t*)stage)[r * WR_GRAB_BLOCK + c];
+}
+template <int BPP> WR_DEVICE void wr_grab_pack_runs(const WrGrabArgs& a, const WrGrabBlock& B, int t, wr_lu4* stage, wr_lu4* outb, unsigned* lw) {
+  constexpr int NP = BPP == 4 ? 4 : 1;          // 16-byte pieces of the block per thread
+  wr_u4 v[NP];
+  int n[NP], r[NP], o[NP];
+  bool diff = false;
+#pragma unroll
+  for (int k = 0; k < NP; k++) {
+    const int piece = k * 256 + t;
+    v[k] = wr_u4{0u, 0u, 0u, 0u};
+    n[k] = wr_grab_piece(a, B, piece, v[k], r[k], o[k]);
+    if (n[k] && !a.keyframe) diff = diff || wr_grab_differs(v[k], wr_load16(B.pk + (size_t)r[k] * a.keep_stride + o[k]));
+    stage[piece] = wr_lu4{v[k].x, v[k].y, v[k].z, v[k].w};
+  }
+  // lw[0]: the block is sent; lw[1..4]: the waves' run starts; lw[5]: the entry's offset in the payload
+  if (t == 0) lw[0] = a.keyframe ? 1u : 0u;
+  __syncthreads();
+  if (__ballot(diff) != 0ull && (t & 63) == 0) lw[0] = 1u;
+  __syncthreads();
+  if (lw[0] == 0u) return;
+#pragma unroll
+  for (int k = 0; k < NP; k++)
+    if (n[k]) wr_grab_st16(B.pk + (size_t)r[k] * a.keep_stride + o[k], v[k]);
+  // this thread's 16 pixels in raster order, and which of them start a run
+  const int row = t >> 2, c0 = (t & 3) * 16;
+  uint32_t px[16];
+  if (BPP == 4) {
+#pragma unroll
+    for (int q = 0; q < 4; q++) { const wr_lu4 w = stage[4 * t + q]; px[4 * q] = w.x; px[4 * q + 1] = w.y; px[4 * q + 2] = w.z; px[4 * q + 3] = w.w; }
+  } else {
+    const wr_lu4 w = stage[t];
+    const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int j = 0; j < 16; j++) px[j] = (ww[j >> 2] >> (8 * (j & 3))) & 0xFFu;
+  }
+  uint32_t prev = 0u;
+  if (c0 > 0) prev = wr_grab_staged<BPP>(stage, row, c0 - 1);
+  else if (row > 0) prev = wr_grab_staged<BPP>(stage, row - 1, B.bw - 1);
+  bool has_prev = t != 0;
+  unsigned m = 0u;
+#pragma unroll
+  for (int j = 0; j < 16; j++) {
+    const bool valid = row < B.bh && c0 + j < B.bw;
+    if (valid && (!has_prev || px[j] != prev)) m |= 1u << j;
+    prev = px[j]; has_prev = true;
+  }
+  const unsigned cnt = (unsigned)__popc(m);
+  const int lane = t & 63, wave = t >> 6;
+  unsigned inc = cnt;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { const unsigned u = __shfl_up(inc, d); if (lane >= d) inc += u; }
+  if (lane == 63) lw[1 + wave] = inc;
+  __syncthreads();
+  unsigned before = 0u, total = 0u;
+#pragma unroll
+  for (int w = 0; w < 4; w++) { const unsigned s = lw[1 + w]; if (w < wave) before += s; total += s; }
+  // the mode (include/wrhip.h): one run start is SOLID; RUNS if that is smaller than RAW
+  const unsigned raw = (unsigned)WR_GRAB_ENTRY(BPP);
+  const unsigned body = (8u * (unsigned)B.bh + total * BPP + 15u) & ~15u;
+  const unsigned mode = total == 1u ? 1u : (16u + body < raw ? 2u : 0u);
+  const unsigned size = mode == 1u ? 16u : mode == 2u ? 16u + body : raw;
+  if (t == 0) lw[5] = atomicAdd((unsigned*)a.slot, size);
+  if (mode == 2u) {
+    uint8_t* ob = (uint8_t*)outb;
+    if (row < B.bh) ((wr_u16a*)ob)[4 * row + (t & 3)] = (uint16_t)m;
+    unsigned at = 8u * (unsigned)B.bh + (before + inc - cnt) * BPP;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      if (!((m >> j) & 1u)) continue;
+      if (BPP == 4) *(uint32_t*)(ob + at) = px[j]; else ob[at] = (uint8_t)px[j];
+      at += BPP;
+    }
+    const unsigned end = 8u * (unsigned)B.bh + total * BPP;
+    if (t < 16 && end + (unsigned)t < body) ob[end + t] = 0;
+  }
+  __syncthreads();
+  uint8_t* e = a.slot + WR_GRAB_HEADER + lw[5];
+  if (t == 0) wr_grab_st16(e, wr_u4{(uint32_t)B.x0, (uint32_t)B.y0, (uint32_t)B.bw | (uint32_t)B.bh << 8 | mode << 16, mode == 1u ? px[0] : mode == 2u ? total : 0u});
+  if (mode == 2u) {
+    for (unsigned p = (unsigned)t; p < body / 16u; p += 256u) { const wr_lu4 w = outb[p]; wr_grab_st16(e + 16 + 16 * (size_t)p, wr_u4{w.x, w.y, w.z, w.w}); }
+  } else if (mode == 0u) {
+#pragma unroll
+    for (int k = 0; k < NP; k++) wr_grab_st16(e + 16 + 16 * (size_t)(k * 256 + t), v[k]);
+  }
+}
+#endif
+__global__ void __launch_bounds__(256) wr_grab_pack_runs_kernel(WrGrabArgs a) {
+  const int t = (int)threadIdx.x;
+  const WrGrabBlock B = wr_grab_block(a, (int)blockIdx.x);
+#ifdef WRHIP_HOSTSIM
+  // (threads run one after the other: the first does it all, through the serial encoder of wr_grab_codec.h)
+  if (t != 0) return;
+  const int pieces = WR_GRAB_BLOCK * WR_GRAB_BLOCK * a.bpp / 16;
+  bool diff = a.keyframe != 0;
+  wr_u4 v; int r, o;
+  for (int piece = 0; piece < pieces && !diff; piece++)
+    if (wr_grab_piece(a, B, piece, v, r, o)) diff = wr_grab_differs(v, wr_load16(B.pk + (size_t)r * a.keep_stride + o));
+  if (!diff) return;
+  uint8_t entry[WR_GRAB_ENTRY(4)];
+  const unsigned size = (unsigned)wr_gc_encode_block(B.ps, (size_t)a.tex_stride, B.x0, B.y0, B.bw, B.bh, a.bpp, entry);
+  __builtin_memcpy(a.slot + WR_GRAB_HEADER + atomicAdd((unsigned*)a.slot, size), entry, size);
+  for (int piece = 0; piece < pieces; piece++)
+    if (wr_grab_piece(a, B, piece, v, r, o)) wr_grab_st16(B.pk + (size_t)r * a.keep_stride + o, v);
+#else
+  __shared__ wr_lu4 stage[1024], outb[1024];
+  __shared__ unsigned lw[8];
+  if (a.bpp == 4) wr_grab_pack_runs<4>(a, B, t, stage, outb, lw);
+  else wr_grab_pack_runs<1>(a, B, t, stage, outb, lw);
+#endif
+}
 // The slot's header and as many bytes as its count word says, device slot -> pinned host slot, 16 bytes per store.  A small grid on
 // the grab stream: the link, not the chip, bounds it, and the raster launches of the following frames keep the CUs.
 __global__ void __launch_bounds__(256) wr_grab_push_kernel(WrGrabPushArgs a) {

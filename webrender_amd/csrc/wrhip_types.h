@@ -714,6 +714,7 @@ struct WrTapArgs {
 //   full   the rects one after another, each tight (w * bpp bytes per row), rows flipped / R and B exchanged on the way
 //   delta  entries of WR_GRAB_ENTRY(bpp) bytes: a 16-byte record (x, y, w, h of the block, relative to the rect) and the block's
 //          rows at a pitch of 64 * bpp; `keep` is the retained copy of the rect (rows of keep_stride bytes, a multiple of 16)
+//   packed delta  entries of varying size, none larger than a plain one: wr_grab_codec.h
 #define WR_GRAB_HEADER 16
 #define WR_GRAB_BLOCK 64
 #define WR_GRAB_ENTRY(bpp) (16 + WR_GRAB_BLOCK * WR_GRAB_BLOCK * (bpp))
@@ -725,6 +726,7 @@ struct WrGrabArgs {
   int32_t tex_stride, keep_stride;     // bytes
   int32_t bpp;                         // 4: RGBA8, 1: R8
   int32_t delta, keyframe;             // keyframe: every block is sent, entry i is block i (nothing is compared, no atomic)
+  int32_t packed;                      // delta: entries are packed (wr_grab_pack_runs_kernel; a keyframe's take an atomic each too)
   int32_t flip, swap_rb;               // full mode
   int32_t nrects;
   int32_t rows_per_wg;                 // full: workgroup b packs rows [b * rows_per_wg, ...) of the rects' rows laid end to end

@@ -141,6 +141,8 @@ EXTRA_SIGNATURES = {
     "WrhipTapResultGet": (i32, [i32, P, i32]),
     "WrhipGrabTexture": (i32, [u32, P, i32, u32]),
     "WrhipGrabResultGet": (i32, [i32, P, P, C.c_int64, i32]),
+    "WrhipGrabPayloadGet": (i32, [i32, P, u64, P, i32]),
+    "WrhipGrabDecode": (i32, [P, u64, u32, u32, i32, i32, P, C.c_int64, P, P]),
 }
 
 
@@ -162,7 +164,7 @@ class WrhipTapResult(C.Structure):
 
 
 # WrhipGrabTexture flags, and the bytes that cross ahead of every grab's payload (include/wrhip.h)
-GRAB_FLIP_ROWS, GRAB_SWAP_RB, GRAB_DELTA, GRAB_KEY = 1, 2, 4, 8
+GRAB_FLIP_ROWS, GRAB_SWAP_RB, GRAB_DELTA, GRAB_KEY, GRAB_PACKED = 1, 2, 4, 8, 32
 GRAB_MAX_RECTS, GRAB_HEADER, GRAB_BLOCK = 16, 16, 64
 
 
@@ -309,6 +311,34 @@ class GL:
         info = {"status": r.status, "format": r.format, "flags": r.flags, "rects": rects, "keyframe": r.keyframe, "blocks": r.blocks,
                 "blocks_total": r.blocks_total, "damage": tuple(r.damage), "bytes": int(r.bytes)}
         return info, pixels
+
+    def grab_payload(self, ticket, wait=True):
+        """The bytes of a grab as they crossed to the host (include/wrhip.h, WrhipGrabPayloadGet): the 16-byte header, then the
+        payload.  None if they have not arrived (wait=False only); a ticket the ring no longer holds raises KeyError."""
+        n = u64(0)
+        rc = self.WrhipGrabPayloadGet(ticket, None, 0, C.byref(n), 1 if wait else 0)
+        if rc == 1:
+            return None
+        if rc != 0:
+            raise KeyError(f"grab ticket {ticket} is unknown or has been overwritten")
+        buf = C.create_string_buffer(n.value)
+        rc = self.WrhipGrabPayloadGet(ticket, buf, n.value, C.byref(n), 1)
+        assert rc == 0 and n.value == len(buf), (rc, n.value)
+        return buf.raw
+
+    def grab_decode(self, payload, fmt, flags, into):
+        """Patch a delta payload (grab_payload's bytes; `flags`: the grab's, GRAB_PACKED or not) into `into`, the caller's image of
+        the rect (a C-contiguous uint8 array, (h, w, 4) for GL_RGBA8, (h, w) for GL_R8): (damage, blocks).  A pure host function
+        (WrhipGrabDecode); a malformed payload raises ValueError and leaves `into` as it was."""
+        import numpy as np
+        bpp = 1 if fmt == 0x8229 else 4          # GL_R8
+        assert into.dtype == np.uint8 and into.flags["C_CONTIGUOUS"] and into.ndim == (2 if bpp == 1 else 3), "grab_decode: `into` is not an image of the rect"
+        damage, blocks = (i32 * 4)(), u32(0)
+        src = (C.c_char * len(payload)).from_buffer_copy(payload)
+        rc = self.WrhipGrabDecode(src, len(payload), fmt, flags, into.shape[1], into.shape[0], into.ctypes.data, 0, damage, C.byref(blocks))
+        if rc != 0:
+            raise ValueError("grab_decode: malformed payload")
+        return tuple(damage), blocks.value
 
 
 def repo_root():

@@ -170,12 +170,13 @@ def render_streamed_tapped(backend_path, frames):
     return px, stats, taps
 
 
-def render_streamed_grabbed(backend_path, frames, delta=False, rect=None):
+def render_streamed_grabbed(backend_path, frames, delta=False, rect=None, packed=False):
     """render_streamed_tapped with the pixels: after each frame's render `rect` of the window (None: all of it) is grabbed
     (GL.grab_texture: packed on the device in stream order behind that frame, carried to the host on the library's second
     stream) -- still nothing between the frames that drains the held-back raster launches.  Results are fetched in order as they
     arrive, and the oldest is waited for (that ticket alone) only when the ring of 8 would otherwise lose it, so any number of
-    frames goes through.  delta=True: delta grabs, patched one after the other into one host image.
+    frames goes through.  delta=True: delta grabs, patched one after the other into one host image; packed=True (with delta):
+    their blocks cross in the packed form (glapi.GRAB_PACKED).
     Returns the final window (RGBA8), the backend's statistics, the host's image of the rect after every frame's grab (stored
     bytes, B, G, R, A) and the grabs' info dicts.  libwrhip only."""
     from . import glapi
@@ -202,7 +203,7 @@ def render_streamed_grabbed(backend_path, frames, delta=False, rect=None):
         r.render(f)
         if len(waiting) == 8:
             fetch(True)
-        t = gl.grab_texture(window, rect, glapi.GRAB_DELTA if delta else 0)
+        t = gl.grab_texture(window, rect, (glapi.GRAB_DELTA if delta else 0) | (glapi.GRAB_PACKED if packed else 0))
         assert t >= 0, (t, gl.GetError())
         waiting.append(t)
         fetch(False)
