@@ -52,7 +52,7 @@ MENU = [
     lambda: scenes.filter_grid(n=30, seed=71, **W),
 ]
 
-# menu entries whose held-back raster launches offer no carrier: none of them has a variant of the fused setup kernel (can_fuse in
+# menu entries whose held-back raster launches offer no carrier: none of them has a variant of the fused setup kernel (pick_variant in
 # wrhip.hip -- the general-quad, shading and filter feature sets), so the flush after one of them runs its setup stage on its own
 NO_CARRIER = {6, 10, 13, 14}
 

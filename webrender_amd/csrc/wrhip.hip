@@ -19,6 +19,7 @@
 #include <condition_variable>
 #include <atomic>
 #include <functional>
+#include <utility>
 
 #include "../../include/wrhip.h"
 #include "wrhip_glenum.h"
@@ -26,13 +27,16 @@
 #include "wrhip_rt.h"
 #include "wr_grab_codec.h"
 #include "wrhip_kernels.h"
-#ifndef WRHIP_HOSTSIM
-// (the raster kernel instantiations live in wrhip_inst.hip, one translation unit per group, so their device compiles run in
-// parallel: here they are only launched)
+// The list of raster kernel instantiations: launch_raster() dispatches from it, and a static_assert holds pick_variant() to it.
 #include "wrhip_inst.h"
+#ifndef WRHIP_HOSTSIM
+// (they live in wrhip_inst.hip, one translation unit per group, so their device compiles run in parallel: here they are only launched)
 #define WR_INST_DECLARE(K, SIG, ...) extern template __global__ void K<__VA_ARGS__> SIG;
 WR_INST_ALL(WR_INST_DECLARE)
 #undef WR_INST_DECLARE
+#endif
+#ifndef WR_THIN_MAX_BINS
+#define WR_THIN_MAX_BINS 256      // a launch of at most this many bins leaves most of the chip idle: it goes out thin (pick_variant)
 #endif
 
 namespace {
@@ -457,6 +461,20 @@ struct TargetWork {
 
 const size_t MAX_TEXTURE_UNITS = 16;
 
+// WrhipKernelStat::kind (include/wrhip.h documents the values; bench.py and tools/grab_bench.py read them)
+enum WrKind { WR_KIND_SCATTER = 0, WR_KIND_SETUP = 1, WR_KIND_RASTER = 2, WR_KIND_MASK_ROWS = 3, WR_KIND_CHAIN = 4, WR_KIND_DENSE = 5, WR_KIND_SETUP_RASTER = 6, WR_KIND_SETUP_DENSE = 7,
+              WR_KIND_SETUP_ROWS = 8, WR_KIND_SPAN_ROWS = 9, WR_KIND_TILE_ROWS = 10, WR_KIND_SETUP_TILE_ROWS = 11, WR_KIND_THIN = 12, WR_KIND_SETUP_THIN = 13, WR_KIND_TAP = 14, WR_KIND_GRAB = 15 };
+// (WrhipStats::raster_ns: the launches that write target pixels -- not the stages ahead of them, nor taps and grabs)
+constexpr bool kind_is_raster(WrKind k) { return !(k == WR_KIND_SCATTER || k == WR_KIND_SETUP || k == WR_KIND_MASK_ROWS || k == WR_KIND_SETUP_ROWS || k == WR_KIND_TAP || k == WR_KIND_GRAB); }
+// The switches pick_variant() looks at, read once per context (Context()).
+struct Switches {
+  bool thin_r8 = true;       // WRHIP_NO_THIN=1: small launches keep the 4-wave workgroup shape
+  int thin_parts = 4;        // workgroups per bin of a thin R8 launch (WRHIP_THIN_PARTS = 1, 2, 4, 8, 16): 16 / parts waves each, so that a wave shares its SIMD with fewer others
+  int chain_grid = 0;        // workgroups of a chained R8 launch (0: off -- the default; WRHIP_CHAIN=1 turns it on, WRHIP_CHAIN_GRID overrides)
+  bool fuse_small = false;   // WRHIP_FUSE_SMALL=1: a small textured colour launch carries the setup stage as a 4-wave launch instead of going out thin
+  bool fuse_thin = true;     // WRHIP_NO_FUSE_THIN=1: the thin colour launch leaves without the setup stage (nothing else in its place)
+};
+
 struct Context {
   int32_t references = 1;
   ObjectStore<Query> queries;
@@ -619,8 +637,7 @@ struct Context {
   size_t last_qtab_cap = 0;
   uint64_t last_qctl_v = 0;            // ... its virtual ring address: once the ring may reuse it (ring_safe beyond it, a new ring) it is dropped unread
   bool cell_raster = true;             // WRHIP_NO_CELLS=1: rect-only bins always take the pixel walk
-  bool thin_r8 = true;                 // WRHIP_NO_THIN=1: small R8 launches keep the 4-wave workgroup shape
-  int thin_parts = 4;                  // workgroups per bin of a thin launch (WRHIP_THIN_PARTS = 1, 2, 4, 8, 16): 16 / parts waves each, so that a wave shares its SIMD with fewer others
+  Switches sw;                         // what the choice of a launch's kernel variant depends on (pick_variant)
   bool dense_text = false;             // WRHIP_DENSE_TEXT=1: text levels run the 128-VGPR build of their variant (wr_raster_dense_kernel: four waves
                                        // per SIMD; the default until the glyph walk read 32-byte glyph records -- since then the 168-VGPR
                                        // build, which does not spill, is the faster one: cfg3 97.6 vs 102.3 us, profiles/r04_g_dense_waves_ab.txt)
@@ -658,7 +675,6 @@ struct Context {
   size_t grab_pinned_max = (size_t)512 << 20;      // WRHIP_GRAB_PINNED_MAX, bytes
   int grab_push_wgs = 32;                          // WRHIP_GRAB_PUSH_WGS: workgroups of wr_grab_push_kernel
   bool grab_full_kernel = false;                   // WRHIP_GRAB_FULL_PUSH=kernel: full grabs cross by the push kernel too (default: a plain copy)
-  int chain_grid = 0;                  // workgroups of a chained R8 launch (0: off -- the default; WRHIP_CHAIN=1 turns it on, WRHIP_CHAIN_GRID overrides)
   unsigned chain_base = 0;             // value of WrUnsupportedCounters::chain_arrive once every chained launch enqueued so far has run
 
   Context() {
@@ -671,15 +687,20 @@ struct Context {
     setup_on_stream = getenv("WRHIP_SETUP_STREAM") && atoi(getenv("WRHIP_SETUP_STREAM")) != 0;
     copy_overlap = getenv("WRHIP_NO_COPY_STREAM") == nullptr;
     forward_composites = getenv("WRHIP_NO_FORWARD") == nullptr;
-    thin_r8 = getenv("WRHIP_NO_THIN") == nullptr;
-    if (const char* e = getenv("WRHIP_THIN_PARTS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) thin_parts = v; }
+    sw.thin_r8 = getenv("WRHIP_NO_THIN") == nullptr;
+    if (const char* e = getenv("WRHIP_THIN_PARTS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) sw.thin_parts = v; }
+    // A small textured colour launch is worth more as a THIN launch (four workgroups per bin: a quarter of the rows per wave, four
+    // times the waves) than as the 4-wave carrier of the setup stage: transforms-simple, 256 bins of eleven rotated rects, 241 us
+    // fused (round 5).  Since then the thin launch carries it itself (wr_setup_raster_thin_kernel).
+    sw.fuse_small = getenv("WRHIP_FUSE_SMALL") != nullptr;
+    sw.fuse_thin = getenv("WRHIP_NO_FUSE_THIN") == nullptr;
     dense_text = getenv("WRHIP_DENSE_TEXT") != nullptr;
     // Chained thin R8 levels (wr_raster_chain_kernel) are OFF unless WRHIP_CHAIN=1: measured on cfg4 (profiles/r03_e_chain_ab.txt),
     // the five chained levels take 144 us in one launch against ~100 us + four kernel boundaries apart -- a grid barrier that has
     // to write back and invalidate the XCDs' L2s (the levels run on all eight) costs about what a kernel boundary costs.
     // (grid: half the CUs -- two contexts' chained launches may meet on the chip and every workgroup of both has to be resident)
-    if (thin_r8 && getenv("WRHIP_CHAIN") && atoi(getenv("WRHIP_CHAIN")) > 0)
-      chain_grid = getenv("WRHIP_CHAIN_GRID") ? atoi(getenv("WRHIP_CHAIN_GRID")) : wrrt::cu_count() / 2;
+    if (sw.thin_r8 && getenv("WRHIP_CHAIN") && atoi(getenv("WRHIP_CHAIN")) > 0)
+      sw.chain_grid = getenv("WRHIP_CHAIN_GRID") ? atoi(getenv("WRHIP_CHAIN_GRID")) : wrrt::cu_count() / 2;
     cell_raster = getenv("WRHIP_NO_CELLS") == nullptr;
     fuse_scatter = getenv("WRHIP_NO_FUSE_SCATTER") == nullptr;
     mask_rows = getenv("WRHIP_NO_MASK_ROWS") == nullptr;
@@ -804,7 +825,7 @@ void sync_stream();
 
 void flush_uploads(size_t extra_end = 0, bool may_defer = false);
 void prof_begin(wr_stream_t* on = nullptr);
-void prof_end(int kind, int fmt, int depth, int feat, uint64_t algo_bytes, uint64_t workgroups, wr_stream_t* on = nullptr);
+void prof_end(WrKind kind, int fmt, int depth, int feat, uint64_t algo_bytes, uint64_t workgroups, wr_stream_t* on = nullptr);
 
 const size_t STAGING_BYTES_DEFAULT = size_t(96) << 20;
 // WRHIP_STAGING_BYTES: another ring size (tests/test_hostsim_parity.py wraps a few-MB ring many times per run)
@@ -959,7 +980,7 @@ void flush_uploads(size_t why, bool may_defer) {
       if (dbg) fprintf(stderr, "scatter launch of its own (flush_uploads called from line %zu): %zu segments, may_defer %d scatter_first %d pending %d\n", why, nseg, (int)may_defer, (int)c->scatter_first, (int)c->ps.valid);
       prof_begin();
       WR_LAUNCH(wr_upload_kernel, (int)nseg * parts, 256, c->stream, (const WrUploadSeg*)(c->dupload + seg_off), (int)nseg, parts);
-      prof_end(0, 0, 0, 0, up_bytes, nseg * parts);
+      prof_end(WR_KIND_SCATTER, 0, 0, 0, up_bytes, nseg * parts);
       c->stats.kernel_launches++;
     }
     c->useg.clear();
@@ -974,7 +995,7 @@ void launch_pending_scatter() {
   if (!c->ps.valid) return;
   prof_begin();
   WR_LAUNCH(wr_upload_kernel, c->ps.nseg * c->ps.parts, 256, c->stream, (const WrUploadSeg*)(c->dupload + c->ps.seg_off), c->ps.nseg, c->ps.parts);
-  prof_end(0, 0, 0, 0, c->ps.bytes, (uint64_t)c->ps.nseg * c->ps.parts);
+  prof_end(WR_KIND_SCATTER, 0, 0, 0, c->ps.bytes, (uint64_t)c->ps.nseg * c->ps.parts);
   c->stats.kernel_launches++;
   c->ps.valid = false;
 }
@@ -1303,7 +1324,7 @@ Context::~Context() {
 // vertex + bin + raster launches covering every selected target at once.
 // While profiling, every launch is bracketed by its own event pair and waited for (measurement runs only).
 void prof_begin(wr_stream_t* on) { if (ctx->profiling) wrrt::event_record(&ctx->ev_a, on ? *on : ctx->stream); }
-void prof_end(int kind, int fmt, int depth, int feat, uint64_t algo_bytes, uint64_t workgroups, wr_stream_t* on) {
+void prof_end(WrKind kind, int fmt, int depth, int feat, uint64_t algo_bytes, uint64_t workgroups, wr_stream_t* on) {
   Context* c = ctx;
   if (!c->profiling) return;
   wrrt::event_record(&c->ev_b, on ? *on : c->stream);
@@ -1313,7 +1334,7 @@ void prof_end(int kind, int fmt, int depth, int feat, uint64_t algo_bytes, uint6
   for (WrhipKernelStat& e : c->kstats) if (e.kind == kind && e.fmt == fmt && e.depth == depth && e.feat == feat) k = &e;
   if (!k) { c->kstats.push_back(WrhipKernelStat{kind, fmt, depth, feat, 0, 0, 0, 0}); k = &c->kstats.back(); }
   k->launches++; k->ns += ns; k->algo_bytes += algo_bytes; k->workgroups += workgroups;
-  if (kind == 2 || kind == 4 || kind == 5 || kind == 6 || kind == 7 || kind == 9 || kind == 10 || kind == 11 || kind == 12 || kind == 13) c->stats.raster_ns += ns;
+  if (kind_is_raster(kind)) c->stats.raster_ns += ns;
 }
 
 void tail_launched() {
@@ -1325,76 +1346,142 @@ void tail_launched() {
   tap_issue_parked();      // (taps of what these launches wrote: directly behind them)
   grab_issue_parked();     // (... and grabs)
 }
-// The instantiated raster kernels: RGBA8 (+depth) x {0, TEX|GENERIC, +R8TEX, everything}, R8 x {0, GENERIC|BLUR, +CLIP}.
-// `SA` non-null: launch the fused setup + raster variant (only for the variants can_fuse() names).
-#ifndef WR_THIN_MAX_BINS
-#define WR_THIN_MAX_BINS 256
-#endif
-bool can_fuse(const Context::Held& H) {
-  if (H.row_n > 0) return H.row_mode == 2;     // (tile rows carry it: wr_setup_tile_rows_kernel; a span-rows launch is too short to hide a setup stage behind)
-  if (H.mr_rows > 0) return true;          // (the mask-rows launch ahead of an R8 raster launch: wr_setup_rows_kernel)
-  // a small textured colour launch is worth more as a THIN launch (four workgroups per bin: a quarter of the rows per wave, four
-  // times the waves) than as the carrier of the setup stage: transforms-simple, 256 bins of eleven rotated rects, 241 us fused
-  // (round 5, later: the thin launch carries it itself -- wr_setup_raster_thin_kernel; WRHIP_NO_FUSE_THIN=1: it leaves without)
-  static const bool thin_first = getenv("WRHIP_FUSE_SMALL") == nullptr;
-  static const bool fuse_thin = getenv("WRHIP_NO_FUSE_THIN") == nullptr;
-  if (thin_first && ctx->thin_r8 && H.fmt == WR_FMT_RGBA8 && !H.depth && H.nb <= WR_THIN_MAX_BINS && H.feat == (WR_FEAT_TEX | WR_FEAT_GENERIC)) return fuse_thin;
-  return H.fmt == WR_FMT_RGBA8 && (H.feat == 0 || H.feat == (WR_FEAT_TEX | WR_FEAT_GENERIC) ||
-                                   H.feat == (WR_FEAT_TEX | WR_FEAT_GENERIC | WR_FEAT_R8TEX));
+// ---- which kernel a held-back launch goes out as --------------------------------------------------------------------------------
+// pick_variant() is the one place that decides it.  Which launch may carry the next flush's setup stage (flush_work), which launches
+// chain (launch_held), the kernel, grid and block launch_raster() issues and the kind it reports are all read from its answer;
+// launch_raster() turns the answer into a launch by looking it up in wrhip_inst.h's WR_INST_ALL, and the static_assert below keeps
+// every answer inside that list.  A new variant: an entry in wrhip_inst.h and a branch in pick_variant().
+//
+// The feature sets that are instantiated, besides the empty one (a level's set is rounded up to one of them).  RGBA8: IMAGE -- images,
+// composites, anything on the per-pixel path; TEXT -- ... and glyphs / masked solids; ALL -- ... and everything else a colour target
+// can hold.  R8: BLUR -- blur / scale passes, clip masks evaluated by the rows kernel; CLIP -- ... and clip masks evaluated in the bins.
+enum { WR_FS_IMAGE = WR_FEAT_TEX | WR_FEAT_GENERIC, WR_FS_TEXT = WR_FS_IMAGE | WR_FEAT_R8TEX, WR_FS_ALL = WR_FS_TEXT | WR_FEAT_BLUR | WR_FEAT_SHADE,
+       WR_FS_BLUR = WR_FEAT_GENERIC | WR_FEAT_BLUR, WR_FS_CLIP = WR_FS_BLUR | WR_FEAT_CLIP };
+constexpr int round_feat(int fmt, int feat) {
+  if (fmt == WR_FMT_R8) return feat == 0 ? 0 : !(feat & WR_FEAT_CLIP) ? WR_FS_BLUR : WR_FS_CLIP;
+  return feat == 0 ? 0 : !(feat & ~WR_FS_IMAGE) ? WR_FS_IMAGE : !(feat & ~WR_FS_TEXT) ? WR_FS_TEXT : WR_FS_ALL;
 }
-// `chain_n` >= 2: H is the first of chain_n consecutive thin R8 launches of one variant (chainable()); they go out as one
-// wr_raster_chain_kernel launch.
-bool chainable(const Context::Held& H) {
-  return ctx->chain_grid > 0 && H.row_n == 0 && H.fmt == WR_FMT_R8 && H.nb <= WR_THIN_MAX_BINS && (H.feat == 0 || H.feat == (WR_FEAT_GENERIC | WR_FEAT_BLUR));
+// (named like the kernels, so that an entry of WR_INST_ALL names its family)
+enum class Family { wr_raster_kernel, wr_setup_raster_kernel, wr_raster_dense_kernel, wr_setup_raster_dense_kernel, wr_setup_raster_thin_kernel, wr_span_rows_kernel, wr_tile_rows_kernel, wr_setup_tile_rows_kernel };
+constexpr uint32_t inst_key(Family k, int fmt, bool depth, int r, int feat) { return (uint32_t)k << 20 | (uint32_t)fmt << 16 | (uint32_t)depth << 12 | (uint32_t)r << 8 | (uint32_t)feat; }
+// k<fmt, depth, r, feat>: the kernel (the row kernels are no templates); grid, block: its workgroups -- a carried setup stage's come on
+// top -- and the threads of each; kind: what it is reported as.  carries: the next flush's setup stage goes out in front of this launch.
+// mask_rows: wr_mask_rows_kernel (mr_grid workgroups) goes ahead of it -- and is then the one that carries, as wr_setup_rows_kernel.
+// chains: consecutive launches like this one may leave as one wr_raster_chain_kernel<feat> launch.
+struct Variant {
+  Family k = Family::wr_raster_kernel; int fmt = 0; bool depth = false; int r = 4, feat = 0;
+  int grid = 0, block = 256; WrKind kind = WR_KIND_RASTER;
+  bool carries = false, mask_rows = false, chains = false; int mr_grid = 0;
+};
+// `carry`: the launch is asked to carry the next flush's setup stage (Variant::carries: whether it does).  `have_mask_rows`: the
+// flush's mask-row store exists (Scratch::mr_ctl), so a launch with mr_rows > 0 has its rows kernel.
+constexpr Variant pick_variant(const Context::Held& H, const Switches& sw, bool carry, bool have_mask_rows) {
+  Variant V;
+  V.fmt = H.fmt;
+  if (H.row_n > 0) {
+    // the row targets of a level: one wave per (target row, 256-pixel piece), four waves per workgroup.  Tile rows carry a setup
+    // stage; a span-rows launch is too short to hide one behind
+    V.grid = std::max(1, std::min((H.row_items + 3) / 4, 16384));
+    V.carries = carry && H.row_mode == 2;
+    V.k = H.row_mode != 2 ? Family::wr_span_rows_kernel : V.carries ? Family::wr_setup_tile_rows_kernel : Family::wr_tile_rows_kernel;
+    V.kind = H.row_mode != 2 ? WR_KIND_SPAN_ROWS : V.carries ? WR_KIND_SETUP_TILE_ROWS : WR_KIND_TILE_ROWS;
+    return V;
+  }
+  V.depth = H.fmt == WR_FMT_RGBA8 && H.depth; V.feat = H.feat; V.grid = H.nb;
+  if (H.mr_rows > 0 && have_mask_rows) {
+    // the cs_clip_* prims of this launch's targets, row by row (one wave per row), ahead of the bins that blend them
+    V.mask_rows = true; V.mr_grid = std::max(1, std::min((H.mr_rows + 3) / 4, 4096));
+    V.carries = carry; carry = false;          // (the raster launch that follows is the plain one)
+  }
+  // Small launches leave most of the chip idle and are bound by one wave's critical path: there a bin's sixteen strips go to several
+  // workgroups of waves of 64 x 4 pixels (R = 1) instead of one workgroup of four waves of 64 x 16.
+  const bool small = sw.thin_r8 && !V.depth && H.nb <= WR_THIN_MAX_BINS;
+  if (H.fmt != WR_FMT_RGBA8) {
+    // (small mask launches: blur / down-scale passes of a few dozen bins)
+    const bool light = H.feat == 0 || H.feat == WR_FS_BLUR;
+    V.chains = sw.chain_grid > 0 && H.nb <= WR_THIN_MAX_BINS && light;
+    if (small && light) { V.r = 1; V.grid = H.nb * sw.thin_parts; V.block = 1024 / sw.thin_parts; V.kind = WR_KIND_THIN; }
+    return V;
+  }
+  if (H.dense && H.feat == WR_FS_TEXT) {
+    // (glyph levels: the 128-VGPR instantiation of the same body, plain or with the next flush's setup stage in front)
+    V.k = carry ? Family::wr_setup_raster_dense_kernel : Family::wr_raster_dense_kernel; V.kind = carry ? WR_KIND_SETUP_DENSE : WR_KIND_DENSE;
+    V.carries = V.carries || carry; return V;
+  }
+  // (small colour launches without depth -- a picture's blur chain: cs_scale halvings and cs_blur passes down to a single bin -- four
+  // workgroups per bin; wrench large-blur-radius: 139 us for the one-bin blur passes)
+  const bool thin = small && (H.feat == WR_FS_IMAGE || H.feat == WR_FS_ALL);
+  if (carry && thin && H.feat == WR_FS_IMAGE && !sw.fuse_small) {
+    // worth more thin than as the 4-wave carrier (Switches::fuse_small): the thin launch carries the setup stage itself, or nothing does
+    if (sw.fuse_thin) { V.k = Family::wr_setup_raster_thin_kernel; V.r = 1; V.grid = H.nb * 4; V.kind = WR_KIND_SETUP_THIN; V.carries = true; return V; }
+  } else if (carry && (H.feat == 0 || H.feat == WR_FS_IMAGE || H.feat == WR_FS_TEXT)) {
+    V.k = Family::wr_setup_raster_kernel; V.kind = WR_KIND_SETUP_RASTER; V.carries = true; return V;
+  }
+  if (thin) { V.r = 1; V.grid = H.nb * 4; V.kind = WR_KIND_THIN; }
+  return V;
 }
+// Every variant pick_variant() can return is built: over both formats, depth, the rounded feature sets, dense, a bin count on each
+// side of WR_THIN_MAX_BINS, the row modes, mask rows, carry, and every switch both ways.  (One evaluation per setting of the
+// switches: a single one would exceed the compilers' constexpr step limits.)
+// (what launch_raster() can launch: wrhip_inst.h's list, and the thin mask launches -- small kernels that are built with this file)
+#define WR_INST_LAUNCHABLE(X) WR_INST_ALL(X) X(wr_raster_kernel, WR_SIG_PLAIN, WR_FMT_R8, false, 1, 0) X(wr_raster_kernel, WR_SIG_PLAIN, WR_FMT_R8, false, 1, WR_FS_BLUR)
+constexpr bool variant_is_built(const Variant& V) {
+  if (V.k == Family::wr_span_rows_kernel || V.k == Family::wr_tile_rows_kernel || V.k == Family::wr_setup_tile_rows_kernel) return true;
+  if (V.chains && V.feat != 0 && V.feat != WR_FS_BLUR) return false;          // (wr_raster_chain_kernel<0>, <WR_FS_BLUR>)
+#define WR_INST_CASE(K, SIG, FMT, DEPTH, R, FEAT) case inst_key(Family::K, FMT, DEPTH, R, FEAT):
+  switch (inst_key(V.k, V.fmt, V.depth, V.r, V.feat)) { WR_INST_LAUNCHABLE(WR_INST_CASE) return true; default: return false; }
+#undef WR_INST_CASE
+}
+constexpr bool selectable_are_built(int s) {
+  const Switches sw{(s & 1) != 0, (s & 2) ? 16 : 4, (s & 4) ? 8 : 0, (s & 8) != 0, (s & 16) != 0};
+  const int sets[2][4] = {{0, WR_FS_IMAGE, WR_FS_TEXT, WR_FS_ALL}, {0, WR_FS_BLUR, WR_FS_CLIP, WR_FS_CLIP}};
+  for (int r8 = 0; r8 < 2; r8++) for (int fi = 0; fi < 4; fi++) for (int depth = 0; depth < 2 - r8; depth++) for (int dense = 0; dense < 2; dense++)
+    for (int nb = WR_THIN_MAX_BINS; nb <= WR_THIN_MAX_BINS + 1; nb++) for (int mode = 0; mode < 3; mode++) for (int mr = 0; mr < 2; mr++)
+      for (int carry = 0; carry < 2; carry++) for (int have = 0; have < 2; have++) {
+        const Context::Held H{r8 ? WR_FMT_R8 : WR_FMT_RGBA8, depth, sets[r8][fi], nb, 0, 0, mr * 9, dense, 0, mode ? 1 : 0, mode ? 7 : 0, mode};
+        const Variant V = pick_variant(H, sw, carry != 0, have != 0);
+        if (!variant_is_built(V) || (V.carries && !carry)) return false;
+      }
+  return true;
+}
+template <int S> constexpr bool selectable_are_built_v = selectable_are_built(S);
+template <int... S> constexpr bool all_selectable_are_built(std::integer_sequence<int, S...>) { return (selectable_are_built_v<S> && ...); }
+static_assert(all_selectable_are_built(std::make_integer_sequence<int, 32>{}), "pick_variant() can return a variant that wrhip_inst.h does not instantiate");
+
+// One held-back launch.  `SA` non-null: it carries the next flush's setup stage (flush_work chose it because pick_variant() says it
+// does).  `chain_n` >= 2: H is the first of chain_n consecutive launches that chain (launch_held); they go out as one launch.
 void launch_raster(const Context::Held& H, const WrTargetDesc* targets, int n_targets, const WrDrawDesc* draws, Context::Scratch& S,
                    const WrSetupArgs* SA = nullptr, int n_setup_blocks = 0, int chain_n = 1, uint64_t setup_bytes = 0) {
   Context* c = ctx;
-#define WR_K(FMT, DEPTH, FEAT)                                                                                          \
-  do {                                                                                                                  \
-    WR_LAUNCH((wr_raster_kernel<FMT, DEPTH, 4, FEAT>), H.nb, 256, c->stream, targets, n_targets, draws,                 \
-              (const WrPrim*)S.prims, (const WrRec*)S.recs, (const WrAux*)S.aux, (const float*)S.vtab, S.masks, H.off); \
-  } while (0)
-#define WR_KF(DEPTH, FEAT)                                                                                              \
-  do {                                                                                                                  \
-    WR_LAUNCH((wr_setup_raster_kernel<WR_FMT_RGBA8, DEPTH, 4, FEAT>), n_setup_blocks + SA->up_blocks + H.nb, 256, c->stream, *SA,        \
-              n_setup_blocks, targets, n_targets, draws, (const WrPrim*)S.prims, (const WrRec*)S.recs,                  \
-              (const WrAux*)S.aux, (const float*)S.vtab, S.masks, H.off);                                               \
-  } while (0)
+  const Variant V = pick_variant(H, c->sw, SA != nullptr, S.mr_ctl != nullptr);
+  const int front = SA ? n_setup_blocks + SA->up_blocks : 0;      // (the workgroups of a carried setup stage and upload scatter)
   if (H.row_n > 0) {
-    // the span-rows targets of a level: one wave per (target row, 256-pixel piece), four waves per workgroup
-    const int wgs = std::max(1, std::min((H.row_items + 3) / 4, 16384));
     static const bool dbg_rows = getenv("WRHIP_DEBUG_ROWS") != nullptr;
-    if (dbg_rows) fprintf(stderr, "span rows (mode %d): targets [%d, %d) items %d workgroups %d\n", H.row_mode, H.row_t0, H.row_t0 + H.row_n, H.row_items, wgs);
+    if (dbg_rows) fprintf(stderr, "span rows (mode %d): targets [%d, %d) items %d workgroups %d\n", H.row_mode, H.row_t0, H.row_t0 + H.row_n, H.row_items, V.grid);
     prof_begin();
-    const bool rows_fused = SA != nullptr && H.row_mode == 2;
-    if (rows_fused) WR_LAUNCH(wr_setup_tile_rows_kernel, n_setup_blocks + SA->up_blocks + wgs, 256, c->stream, *SA, n_setup_blocks, targets, H.row_t0, H.row_n, draws, (const WrPrim*)S.prims, (const WrAux*)S.aux);
-    else if (H.row_mode == 2) WR_LAUNCH(wr_tile_rows_kernel, wgs, 256, c->stream, targets, H.row_t0, H.row_n, draws, (const WrPrim*)S.prims, (const WrAux*)S.aux);
-    else WR_LAUNCH(wr_span_rows_kernel, wgs, 256, c->stream, targets, H.row_t0, H.row_n, draws, (const WrPrim*)S.prims, (const WrAux*)S.aux);
-    prof_end(rows_fused ? 11 : (H.row_mode == 2 ? 10 : 9), H.fmt, 0, 0, H.algo_bytes + (rows_fused ? setup_bytes : 0), (uint64_t)wgs + (rows_fused ? n_setup_blocks : 0));
+    if (V.k == Family::wr_setup_tile_rows_kernel) WR_LAUNCH(wr_setup_tile_rows_kernel, front + V.grid, 256, c->stream, *SA, n_setup_blocks, targets, H.row_t0, H.row_n, draws, (const WrPrim*)S.prims, (const WrAux*)S.aux);
+    else if (V.k == Family::wr_tile_rows_kernel) WR_LAUNCH(wr_tile_rows_kernel, V.grid, 256, c->stream, targets, H.row_t0, H.row_n, draws, (const WrPrim*)S.prims, (const WrAux*)S.aux);
+    else WR_LAUNCH(wr_span_rows_kernel, V.grid, 256, c->stream, targets, H.row_t0, H.row_n, draws, (const WrPrim*)S.prims, (const WrAux*)S.aux);
+    prof_end(V.kind, H.fmt, 0, 0, H.algo_bytes + (V.carries ? setup_bytes : 0), (uint64_t)V.grid + (V.carries ? n_setup_blocks : 0));
     c->stats.kernel_launches++; c->stats.raster_launches++; c->stats.row_launches++;
     return;
   }
-  const int F5 = WR_FEAT_TEX | WR_FEAT_GENERIC, F7 = F5 | WR_FEAT_R8TEX, FA = F7 | WR_FEAT_BLUR | WR_FEAT_SHADE;
-  if (H.mr_rows > 0 && S.mr_ctl) {
-    // the cs_clip_* prims of this launch's targets, row by row (one wave per row), ahead of the bins that blend them
-    const int wgs = std::max(1, std::min((H.mr_rows + 3) / 4, 4096));
+  if (V.mask_rows) {
+    const WrKind kind = V.carries ? WR_KIND_SETUP_ROWS : WR_KIND_MASK_ROWS;
     prof_begin();
-    const bool rows_fused = SA != nullptr;
-    if (SA) {
-      WR_LAUNCH(wr_setup_rows_kernel, n_setup_blocks + SA->up_blocks + wgs, 256, c->stream, *SA, n_setup_blocks, targets, H.off, H.off + H.nb,
+    if (V.carries)
+      WR_LAUNCH(wr_setup_rows_kernel, front + V.mr_grid, 256, c->stream, *SA, n_setup_blocks, targets, H.off, H.off + H.nb,
                 (const WrPrim*)S.prims, (const WrAux*)S.aux, S.mr_ctl, (const WrMaskSlot*)S.mr_slots, S.mr_store);
-      SA = nullptr;                          // (the raster launch that follows is the plain one)
-    } else
-    WR_LAUNCH(wr_mask_rows_kernel, wgs, 256, c->stream, targets, H.off, H.off + H.nb, (const WrPrim*)S.prims, (const WrAux*)S.aux,
-              S.mr_ctl, (const WrMaskSlot*)S.mr_slots, S.mr_store);
-    prof_end(rows_fused ? 8 : 3, H.fmt, 0, 0, rows_fused ? setup_bytes : 0, (uint64_t)wgs + (rows_fused ? n_setup_blocks : 0));      // (8: wr_setup_rows_kernel)
+    else
+      WR_LAUNCH(wr_mask_rows_kernel, V.mr_grid, 256, c->stream, targets, H.off, H.off + H.nb, (const WrPrim*)S.prims, (const WrAux*)S.aux,
+                S.mr_ctl, (const WrMaskSlot*)S.mr_slots, S.mr_store);
+    prof_end(kind, H.fmt, 0, 0, V.carries ? setup_bytes : 0, (uint64_t)V.mr_grid + (V.carries ? n_setup_blocks : 0));
     if (c->profiling) {          // bytes this launch evaluated: the kernel's running count, read back (profiling syncs per launch anyway)
       unsigned long long parts[32], seen = 0;
       wrrt::d2h(parts, S.mr_ctl + 32, sizeof(parts), c->stream);
       wrrt::stream_sync(c->stream);
       for (unsigned long long v : parts) seen += v;
-      for (WrhipKernelStat& e : c->kstats) if (e.kind == (rows_fused ? 8 : 3) && e.fmt == H.fmt) e.algo_bytes += seen - S.mr_seen;
+      for (WrhipKernelStat& e : c->kstats) if (e.kind == kind && e.fmt == H.fmt) e.algo_bytes += seen - S.mr_seen;
       S.mr_seen = seen;
     }
     c->stats.kernel_launches++;
@@ -1405,7 +1492,7 @@ void launch_raster(const Context::Held& H, const WrTargetDesc* targets, int n_ta
     ch.n = chain_n;
     int widest = 0; uint64_t bytes = 0;
     for (int i = 0; i < chain_n; i++) { ch.first[i] = (&H)[i].off; ch.count[i] = (&H)[i].nb; widest = std::max(widest, (&H)[i].nb); bytes += (&H)[i].algo_bytes; }
-    const int grid = std::max(1, std::min(widest, c->chain_grid));
+    const int grid = std::max(1, std::min(widest, c->sw.chain_grid));
     // arrivals at the barrier after level l: the workgroups that have a bin at level l or later (the others have left)
     for (int l = 0; l + 1 < chain_n; l++) {
       int part = 0;
@@ -1414,105 +1501,46 @@ void launch_raster(const Context::Held& H, const WrTargetDesc* targets, int n_ta
       ch.want[l] = c->chain_base;
     }
     prof_begin();
-    if (H.feat == 0)
+    if (V.feat == 0)
       WR_LAUNCH((wr_raster_chain_kernel<0>), grid, 1024, c->stream, targets, n_targets, draws, (const WrPrim*)S.prims, (const WrRec*)S.recs,
                 (const WrAux*)S.aux, (const float*)S.vtab, S.masks, ch, &c->dcounters->chain_arrive, c->dcounters);
     else
-      WR_LAUNCH((wr_raster_chain_kernel<WR_FEAT_GENERIC | WR_FEAT_BLUR>), grid, 1024, c->stream, targets, n_targets, draws, (const WrPrim*)S.prims,
+      WR_LAUNCH((wr_raster_chain_kernel<WR_FS_BLUR>), grid, 1024, c->stream, targets, n_targets, draws, (const WrPrim*)S.prims,
                 (const WrRec*)S.recs, (const WrAux*)S.aux, (const float*)S.vtab, S.masks, ch, &c->dcounters->chain_arrive, c->dcounters);
-    prof_end(4, H.fmt, chain_n, H.feat, bytes, (uint64_t)grid);
+    prof_end(WR_KIND_CHAIN, H.fmt, chain_n, V.feat, bytes, (uint64_t)grid);
     c->stats.kernel_launches++; c->stats.raster_launches++;
     return;
   }
+  // the entry of WR_INST_ALL that V names; WR_SIG_PLAIN / WR_SIG_FUSED: the kernel's argument list, without / with a setup stage
+  const bool fused = V.carries && !V.mask_rows;
   prof_begin();
-  uint64_t thin_wgs = 0;                 // a thin launch (R = 1 instantiation): its workgroups; reported as kind 12 (not mixed into the R = 4 rows)
-  const bool fused = SA != nullptr;      // (SA still set: this raster launch carries the next flush's setup stage)
-  static const bool thin_carrier = getenv("WRHIP_FUSE_SMALL") == nullptr;      // (can_fuse's thin_first)
-  if (H.dense && H.fmt == WR_FMT_RGBA8 && H.feat == F7) {
-    // (glyph levels: the 128-VGPR instantiation of the same body, plain or with the next flush's setup stage in front)
-#define WR_KD(DEPTH)                                                                                                         \
-  do {                                                                                                                       \
-    if (SA) WR_LAUNCH((wr_setup_raster_dense_kernel<WR_FMT_RGBA8, DEPTH, 4, WR_FEAT_TEX | WR_FEAT_GENERIC | WR_FEAT_R8TEX>), \
-                      n_setup_blocks + SA->up_blocks + H.nb, 256, c->stream, *SA, n_setup_blocks, targets, n_targets, draws,                 \
-                      (const WrPrim*)S.prims, (const WrRec*)S.recs, (const WrAux*)S.aux, (const float*)S.vtab, S.masks, H.off); \
-    else WR_LAUNCH((wr_raster_dense_kernel<WR_FMT_RGBA8, DEPTH, 4, WR_FEAT_TEX | WR_FEAT_GENERIC | WR_FEAT_R8TEX>), H.nb, 256, \
-                   c->stream, targets, n_targets, draws, (const WrPrim*)S.prims, (const WrRec*)S.recs, (const WrAux*)S.aux,  \
-                   (const float*)S.vtab, S.masks, H.off);                                                                    \
-  } while (0)
-    if (H.depth) WR_KD(true); else WR_KD(false);
-#undef WR_KD
+#define WR_LAUNCH_WR_SIG_PLAIN(...) WR_LAUNCH((__VA_ARGS__), V.grid, V.block, c->stream, targets, n_targets, draws, (const WrPrim*)S.prims, (const WrRec*)S.recs, (const WrAux*)S.aux, (const float*)S.vtab, S.masks, H.off)
+#define WR_LAUNCH_WR_SIG_FUSED(...) WR_LAUNCH((__VA_ARGS__), front + V.grid, V.block, c->stream, *SA, n_setup_blocks, targets, n_targets, draws, (const WrPrim*)S.prims, (const WrRec*)S.recs, (const WrAux*)S.aux, (const float*)S.vtab, S.masks, H.off)
+#define WR_INST_CASE(K, SIG, FMT, DEPTH, R, FEAT) case inst_key(Family::K, FMT, DEPTH, R, FEAT): WR_LAUNCH_##SIG(K<FMT, DEPTH, R, FEAT>); break;
+  switch (inst_key(V.k, V.fmt, V.depth, V.r, V.feat)) {
+    WR_INST_LAUNCHABLE(WR_INST_CASE)
+    default: c->last_error = GL_INVALID_OPERATION; return;      // (no such kernel: reported instead of drawn -- the static_assert above rules it out)
   }
-  else if (SA && H.fmt == WR_FMT_RGBA8 && !H.depth && c->thin_r8 && H.nb <= WR_THIN_MAX_BINS && H.feat == F5 && thin_carrier) {
-    // the thin colour launch with the next flush's setup stage in front (can_fuse)
-    thin_wgs = (uint64_t)H.nb * 4 + (uint64_t)n_setup_blocks;
-    WR_LAUNCH((wr_setup_raster_thin_kernel<WR_FMT_RGBA8, false, 1, WR_FEAT_TEX | WR_FEAT_GENERIC>), n_setup_blocks + SA->up_blocks + H.nb * 4, 256, c->stream, *SA,
-              n_setup_blocks, targets, n_targets, draws, (const WrPrim*)S.prims, (const WrRec*)S.recs, (const WrAux*)S.aux, (const float*)S.vtab, S.masks, H.off);
-  }
-  else if (SA) {
-    if (H.depth) {
-      if (H.feat == 0) WR_KF(true, 0); else if (H.feat == F5) WR_KF(true, WR_FEAT_TEX | WR_FEAT_GENERIC);
-      else WR_KF(true, WR_FEAT_TEX | WR_FEAT_GENERIC | WR_FEAT_R8TEX);
-    } else {
-      if (H.feat == 0) WR_KF(false, 0); else if (H.feat == F5) WR_KF(false, WR_FEAT_TEX | WR_FEAT_GENERIC);
-      else WR_KF(false, WR_FEAT_TEX | WR_FEAT_GENERIC | WR_FEAT_R8TEX);
-    }
-  }
-  else if (H.fmt == WR_FMT_RGBA8 && !H.depth && c->thin_r8 && H.nb <= WR_THIN_MAX_BINS && H.feat != 0 && H.feat != F7) {
-    thin_wgs = (uint64_t)H.nb * 4;
-    // Small colour launches without depth (a picture's blur chain: cs_scale halvings and cs_blur passes down to a single bin):
-    // as for the thin mask launches, a bin's sixteen strips go to four workgroups of four waves of 64 x 4 pixels instead of one
-    // workgroup of four waves of 64 x 16 (wrench large-blur-radius: 139 us for the one-bin blur passes)
-    if (H.feat == F5)
-      WR_LAUNCH((wr_raster_kernel<WR_FMT_RGBA8, false, 1, WR_FEAT_TEX | WR_FEAT_GENERIC>), H.nb * 4, 256, c->stream, targets, n_targets, draws,
-                (const WrPrim*)S.prims, (const WrRec*)S.recs, (const WrAux*)S.aux, (const float*)S.vtab, S.masks, H.off);
-    else
-      WR_LAUNCH((wr_raster_kernel<WR_FMT_RGBA8, false, 1, WR_FEAT_TEX | WR_FEAT_GENERIC | WR_FEAT_R8TEX | WR_FEAT_BLUR | WR_FEAT_SHADE>), H.nb * 4, 256, c->stream,
-                targets, n_targets, draws, (const WrPrim*)S.prims, (const WrRec*)S.recs, (const WrAux*)S.aux, (const float*)S.vtab, S.masks, H.off);
-  }
-  else if (H.fmt == WR_FMT_RGBA8) {
-    if (H.depth) {
-      if (H.feat == 0) WR_K(WR_FMT_RGBA8, true, 0); else if (H.feat == F5) WR_K(WR_FMT_RGBA8, true, WR_FEAT_TEX | WR_FEAT_GENERIC);
-      else if (H.feat == F7) WR_K(WR_FMT_RGBA8, true, WR_FEAT_TEX | WR_FEAT_GENERIC | WR_FEAT_R8TEX);
-      else WR_K(WR_FMT_RGBA8, true, WR_FEAT_TEX | WR_FEAT_GENERIC | WR_FEAT_R8TEX | WR_FEAT_BLUR | WR_FEAT_SHADE);
-    } else {
-      if (H.feat == 0) WR_K(WR_FMT_RGBA8, false, 0); else if (H.feat == F5) WR_K(WR_FMT_RGBA8, false, WR_FEAT_TEX | WR_FEAT_GENERIC);
-      else if (H.feat == F7) WR_K(WR_FMT_RGBA8, false, WR_FEAT_TEX | WR_FEAT_GENERIC | WR_FEAT_R8TEX);
-      else WR_K(WR_FMT_RGBA8, false, WR_FEAT_TEX | WR_FEAT_GENERIC | WR_FEAT_R8TEX | WR_FEAT_BLUR | WR_FEAT_SHADE);
-    }
-    (void)FA;
-  } else {
-    // Small mask launches (blur / down-scale passes of a few dozen bins) leave most of the chip idle and are bound by one
-    // wave's critical path: there a bin is given 16 waves of 64 x 4 pixels (4 px per lane) instead of 4 waves of 64 x 16.
-    const bool thin = c->thin_r8 && H.nb <= WR_THIN_MAX_BINS;
-    if (thin && (H.feat == 0 || H.feat == (WR_FEAT_GENERIC | WR_FEAT_BLUR))) thin_wgs = (uint64_t)H.nb * c->thin_parts;
-#define WR_K1(FEAT)                                                                                                     \
-  do {                                                                                                                  \
-    WR_LAUNCH((wr_raster_kernel<WR_FMT_R8, false, 1, FEAT>), H.nb * c->thin_parts, 1024 / c->thin_parts, c->stream, targets, n_targets, draws,          \
-              (const WrPrim*)S.prims, (const WrRec*)S.recs, (const WrAux*)S.aux, (const float*)S.vtab, S.masks, H.off); \
-  } while (0)
-    if (H.feat == 0) { if (thin) WR_K1(0); else WR_K(WR_FMT_R8, false, 0); }
-    else if (H.feat == (WR_FEAT_GENERIC | WR_FEAT_BLUR)) { if (thin) WR_K1(WR_FEAT_GENERIC | WR_FEAT_BLUR); else WR_K(WR_FMT_R8, false, WR_FEAT_GENERIC | WR_FEAT_BLUR); }
-    else WR_K(WR_FMT_R8, false, WR_FEAT_GENERIC | WR_FEAT_BLUR | WR_FEAT_CLIP);
-#undef WR_K1
-  }
-#undef WR_K
-#undef WR_KF
-  // (5: wr_raster_dense_kernel; 6 / 7: the same two with the next flush's setup stage in front, wr_setup_raster[_dense]_kernel)
-  prof_end(thin_wgs ? (fused ? 13 : 12) : fused ? (H.dense ? 7 : 6) : (H.dense ? 5 : 2), H.fmt, H.depth, H.feat, H.algo_bytes + (fused ? setup_bytes : 0),
-           thin_wgs ? thin_wgs : (uint64_t)H.nb + (fused ? n_setup_blocks : 0));
+#undef WR_INST_CASE
+#undef WR_LAUNCH_WR_SIG_FUSED
+#undef WR_LAUNCH_WR_SIG_PLAIN
+  // (a thin launch is reported apart from the R = 4 rows of its variant: WR_KIND_THIN)
+  prof_end(V.kind, V.fmt, V.depth, V.feat, H.algo_bytes + (fused ? setup_bytes : 0), (uint64_t)V.grid + (fused ? n_setup_blocks : 0));
   c->stats.kernel_launches++; c->stats.raster_launches++;
 #ifndef WRHIP_HOSTSIM
-  if (H.fmt == WR_FMT_RGBA8 && H.feat == 0 && c->cell_raster) c->stats.cell_bins += (uint64_t)H.nb;      // (wr_raster_body's CELLS instantiations)
+  if (V.fmt == WR_FMT_RGBA8 && V.feat == 0 && c->cell_raster) c->stats.cell_bins += (uint64_t)H.nb;      // (wr_raster_body's CELLS instantiations)
 #endif
 }
-// A flush's raster launches in order; runs of chainable() launches of one variant (only the first may have mask rows: its rows
+// A flush's raster launches in order; runs of launches of one variant that chain (only the first may have mask rows: its rows
 // launch goes ahead of the chain) leave as one launch.  `fuse_at`: the launch that carries the next flush's setup stage.
 void launch_held(const std::vector<Context::Held>& held, const WrTargetDesc* targets, int n_targets, const WrDrawDesc* draws, Context::Scratch& S,
                  int fuse_at = -1, const WrSetupArgs* SA = nullptr, int n_setup_blocks = 0, uint64_t setup_bytes = 0) {
+  const auto pick = [&](size_t i) { return pick_variant(held[i], ctx->sw, false, S.mr_ctl != nullptr); };
   for (size_t i = 0; i < held.size();) {
     size_t j = i + 1;
-    if (chainable(held[i]) && !(S.mr_ctl == nullptr && held[i].mr_rows > 0))
-      while (j < held.size() && j - i < WR_MAX_CHAIN && chainable(held[j]) && held[j].feat == held[i].feat && held[j].mr_rows == 0 && (int)j != fuse_at) j++;
+    const Variant Vi = pick(i);
+    if (Vi.chains && (held[i].mr_rows == 0 || Vi.mask_rows))
+      while (j < held.size() && j - i < WR_MAX_CHAIN && pick(j).chains && held[j].feat == held[i].feat && held[j].mr_rows == 0 && (int)j != fuse_at) j++;
     const bool fuse = (int)i == fuse_at;
     launch_raster(held[i], targets, n_targets, draws, S, fuse ? SA : nullptr, fuse ? n_setup_blocks : 0, (int)(j - i), fuse ? setup_bytes : 0);
     i = j;
@@ -1552,8 +1580,8 @@ void tap_issue(uint64_t n, const WrTapArgs& a) {
   const int grid = (a.h + a.rows_per_wg - 1) / a.rows_per_wg;
   prof_begin();
   WR_LAUNCH(wr_tap_kernel, grid, 256, c->stream, a);
-  // (14: wr_tap_kernel; feat 1: against an expected texture, whose bytes are read as well)
-  prof_end(14, a.bpp == 4 ? WR_FMT_RGBA8 : WR_FMT_R8, 0, a.exp ? 1 : 0, (uint64_t)a.w * a.h * a.bpp * (a.exp ? 2 : 1), (uint64_t)grid);
+  // (feat 1: against an expected texture, whose bytes are read as well)
+  prof_end(WR_KIND_TAP, a.bpp == 4 ? WR_FMT_RGBA8 : WR_FMT_R8, 0, a.exp ? 1 : 0, (uint64_t)a.w * a.h * a.bpp * (a.exp ? 2 : 1), (uint64_t)grid);
   c->stats.kernel_launches++;
   wrrt::d2h(c->tap_host + si, d, sizeof(WrhipTapResult), c->stream);
   wrrt::event_record(&ts.ev, c->stream);
@@ -1609,7 +1637,7 @@ void grab_issue(uint64_t n, const WrGrabArgs& a) {
   // not known here either.  Bytes read plus bytes written: the rect twice in full mode; a keyframe reads the rect
   // and writes entries and retained copy; any other delta reads rect and retained copy -- what its changed blocks then write is not
   // known here and is not counted)
-  prof_end(15, a.bpp == 4 ? WR_FMT_RGBA8 : WR_FMT_R8, 0, a.packed ? 2 : a.delta ? 1 : 0, a.delta && a.keyframe && !a.packed ? 2 * rect_bytes + a.payload : 2 * rect_bytes, (uint64_t)grid);
+  prof_end(WR_KIND_GRAB, a.bpp == 4 ? WR_FMT_RGBA8 : WR_FMT_R8, 0, a.packed ? 2 : a.delta ? 1 : 0, a.delta && a.keyframe && !a.packed ? 2 * rect_bytes + a.payload : 2 * rect_bytes, (uint64_t)grid);
   c->stats.kernel_launches++;
   WrGrabPushArgs pa;
   pa.src = gs.dev; pa.dst = gs.host; pa.capacity = (uint32_t)gs.cap;
@@ -2201,21 +2229,18 @@ void flush_work(const std::vector<int>& sel_in) {
     // the launch that will carry this flush's setup stage (if any): it also runs the batch's scatter, in its first workgroups
     int fuse_at = -1;
     if (n_prims > 0 && c->tail.pending && !c->setup_on_stream) {
-      // the launch that hides the setup stage best: the largest mask-rows launch if there is one, else the first raster
-      // launch the fused kernel has a variant for
-      int best_rows = 0;
-      for (size_t hi = 0; hi < c->tail.held.size(); hi++)
-        if (c->tail.held[hi].mr_rows > best_rows) { best_rows = c->tail.held[hi].mr_rows; fuse_at = (int)hi; }
-      // (... else the largest tile-rows launch: a wave per row piece of a few heavy prims, the long launch of such a flush -- behind
-      // the short rect pass of the same flush a setup stage would stick out)
-      if (fuse_at < 0) {
-        int best_items = 0;
-        for (size_t hi = 0; hi < c->tail.held.size(); hi++) {
-          const Context::Held& Hh = c->tail.held[hi];
-          if (Hh.row_n > 0 && Hh.row_mode == 2 && Hh.row_items > best_items && can_fuse(Hh)) { best_items = Hh.row_items; fuse_at = (int)hi; }
-        }
+      // the launch that hides the setup stage best, among those pick_variant() lets carry it: the largest mask-rows launch if there
+      // is one, else the largest tile-rows launch (a wave per row piece of a few heavy prims, the long launch of such a flush -- behind
+      // the short rect pass of the same flush a setup stage would stick out), else the first
+      const bool have_mask_rows = c->scratch[c->tail.set].mr_ctl != nullptr;
+      int64_t best = 0;
+      for (size_t hi = 0; hi < c->tail.held.size(); hi++) {
+        const Context::Held& Hh = c->tail.held[hi];
+        const Variant V = pick_variant(Hh, c->sw, true, have_mask_rows);
+        const int size = V.mask_rows ? Hh.mr_rows : Hh.row_items;
+        const int64_t rank = !V.carries ? 0 : size > 0 ? ((int64_t)(V.mask_rows ? 2 : 1) << 32) + size : 1;
+        if (rank > best) { best = rank; fuse_at = (int)hi; }
       }
-      for (size_t hi = 0; hi < c->tail.held.size() && fuse_at < 0; hi++) if (can_fuse(c->tail.held[hi])) fuse_at = (int)hi;
     }
     lap(1);      // arena staged
     flush_uploads(0, fuse_at >= 0);     // one DMA: queued texture uploads + this arena; then the scatter (its own launch, or the carrier's first workgroups)
@@ -2247,7 +2272,7 @@ void flush_work(const std::vector<int>& sel_in) {
         prof_begin(&c->setup_stream);
         WR_LAUNCH(wr_setup_kernel, n_setup_blocks, 256, c->setup_stream, ddraws, nd_arg, dinst, S.prims, S.recs, S.aux, n_prims,
                   dtargets, S.masks, S.vtab, c->dcounters, dblk);
-        prof_end(1, 0, 0, 0, setup_bytes, (uint64_t)n_setup_blocks, &c->setup_stream);
+        prof_end(WR_KIND_SETUP, 0, 0, 0, setup_bytes, (uint64_t)n_setup_blocks, &c->setup_stream);
         wrrt::event_record(&c->ev_setup, c->setup_stream);
         c->stats.kernel_launches += 1;
         drain_tail();                                            // the previous flush's raster launches, concurrently
@@ -2278,7 +2303,7 @@ void flush_work(const std::vector<int>& sel_in) {
         prof_begin();
         WR_LAUNCH(wr_setup_kernel, n_setup_blocks, 256, c->stream, ddraws, nd_arg, dinst, S.prims, S.recs, S.aux, n_prims,
                   dtargets, S.masks, S.vtab, c->dcounters, dblk);
-        prof_end(1, 0, 0, 0, setup_bytes, (uint64_t)n_setup_blocks);
+        prof_end(WR_KIND_SETUP, 0, 0, 0, setup_bytes, (uint64_t)n_setup_blocks);
         c->stats.kernel_launches += 1;
         drain_tail();        // (held-back launches the fused kernel has no variant for)
       }
@@ -2358,15 +2383,11 @@ void flush_work(const std::vector<int>& sel_in) {
     std::vector<Context::Held> launches;
     for (const Level& L : levels) {
       if (L.bins_rgba > 0) {
-        int f;
-        if (L.feat_rgba == 0) f = 0;
-        else if (!(L.feat_rgba & ~(WR_FEAT_TEX | WR_FEAT_GENERIC))) f = WR_FEAT_TEX | WR_FEAT_GENERIC;
-        else if (!(L.feat_rgba & ~(WR_FEAT_TEX | WR_FEAT_GENERIC | WR_FEAT_R8TEX))) f = WR_FEAT_TEX | WR_FEAT_GENERIC | WR_FEAT_R8TEX;
-        else f = WR_FEAT_TEX | WR_FEAT_GENERIC | WR_FEAT_R8TEX | WR_FEAT_BLUR | WR_FEAT_SHADE;
-        launches.push_back(Context::Held{WR_FMT_RGBA8, L.any_depth ? 1 : 0, f, L.bins_rgba, L.bin0, L.bytes_rgba, 0, (L.text && c->dense_text && f == (WR_FEAT_TEX | WR_FEAT_GENERIC | WR_FEAT_R8TEX)) ? 1 : 0});
+        const int f = round_feat(WR_FMT_RGBA8, L.feat_rgba);
+        launches.push_back(Context::Held{WR_FMT_RGBA8, L.any_depth ? 1 : 0, f, L.bins_rgba, L.bin0, L.bytes_rgba, 0, (L.text && c->dense_text && f == WR_FS_TEXT) ? 1 : 0});
       }
       if (L.bins_r8 > 0) {
-        const int f = L.feat_r8 == 0 ? 0 : (!(L.feat_r8 & WR_FEAT_CLIP) ? (WR_FEAT_GENERIC | WR_FEAT_BLUR) : (WR_FEAT_GENERIC | WR_FEAT_BLUR | WR_FEAT_CLIP));
+        const int f = round_feat(WR_FMT_R8, L.feat_r8);
         launches.push_back(Context::Held{WR_FMT_R8, 0, f, L.bins_r8, L.bin0 + L.bins_rgba, L.bytes_r8, (int)std::min<uint64_t>(L.mr_rows, WR_MR_MAX_ROWS)});
       }
       if (L.row_n > 0) {
