@@ -44,6 +44,27 @@ def test_streamed_new_static_texture(hostsim, oracle_gcc):
     check_streamed(hostsim, oracle_gcc, NEW_STATIC[1]())
 
 
+def test_streamed_setup_on_its_own_stream(hostsim):
+    """WRHIP_SETUP_STREAM=1 (off by default; host simulation only): every flush behind a held-back tail runs its setup stage as a
+    launch of its own on the second stream instead of in a held-back launch -- no setup stage is carried, and the window is the one
+    the same frames give without the variable.  The variable is read when the context is created: it is in place from before that
+    to after the last launch, and is then put back as it was found."""
+    _, make = GROWTH[0]          # (the smallest streamed case: 64, 64 and 129 rects)
+    want, _ = render_streamed(hostsim, make())
+    saved = os.environ.get("WRHIP_SETUP_STREAM")
+    os.environ["WRHIP_SETUP_STREAM"] = "1"
+    try:
+        got, st = render_streamed(hostsim, make())
+    finally:
+        if saved is None:
+            os.environ.pop("WRHIP_SETUP_STREAM", None)
+        else:
+            os.environ["WRHIP_SETUP_STREAM"] = saved
+    assert st["gl_error"] == 0, st
+    assert st["setup_carried"] == 0, st
+    assert np.array_equal(got, want), f"{int((got != want).sum())} bytes of the window differ; {st}"
+
+
 def stream_driver(lib, mode, **env):
     e = dict(os.environ, **{k: str(v) for k, v in env.items()})
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "stream_driver.py"), lib, mode], env=e, capture_output=True, text=True)

@@ -1361,6 +1361,36 @@ constexpr int round_feat(int fmt, int feat) {
   if (fmt == WR_FMT_R8) return feat == 0 ? 0 : !(feat & WR_FEAT_CLIP) ? WR_FS_BLUR : WR_FS_CLIP;
   return feat == 0 ? 0 : !(feat & ~WR_FS_IMAGE) ? WR_FS_IMAGE : !(feat & ~WR_FS_TEXT) ? WR_FS_TEXT : WR_FS_ALL;
 }
+// Shader classes that the flush plan and DrawElementsInstanced ask about.
+constexpr bool is_text_run(int sh) { return sh == WR_SH_PS_TEXT_RUN || sh == WR_SH_PS_TEXT_RUN_DUAL || sh == WR_SH_PS_TEXT_RUN_GT || sh == WR_SH_PS_TEXT_RUN_DUAL_GT; }
+constexpr bool is_clip_mask(int sh) { return sh == WR_SH_CS_CLIP_RECT || sh == WR_SH_CS_CLIP_RECT_FAST || sh == WR_SH_CS_CLIP_BOX_SHADOW; }
+constexpr bool is_brush_solid(int sh) { return sh == WR_SH_BRUSH_SOLID || sh == WR_SH_BRUSH_SOLID_ALPHA; }
+constexpr bool is_quad_prog(int sh) {
+  return sh == WR_SH_PS_QUAD_TEXTURED || sh == WR_SH_PS_QUAD_MASK || sh == WR_SH_PS_QUAD_MASK_FAST || sh == WR_SH_PS_QUAD_RADIAL_GRADIENT || sh == WR_SH_PS_QUAD_CONIC_GRADIENT;
+}
+constexpr bool is_gradient_prog(int sh) {
+  return sh == WR_SH_BRUSH_LINEAR_GRADIENT || sh == WR_SH_BRUSH_LINEAR_GRADIENT_ALPHA || sh == WR_SH_PS_QUAD_RADIAL_GRADIENT || sh == WR_SH_PS_QUAD_CONIC_GRADIENT ||
+         sh == WR_SH_CS_LINEAR_GRADIENT || sh == WR_SH_CS_RADIAL_GRADIENT || sh == WR_SH_CS_CONIC_GRADIENT;
+}
+// The prim families (WR_FEAT_*) a draw of this program can hold unless the host has verified it plain (WR_DF_SIMPLE: none).  A clip
+// mask that the rows kernel evaluates asks for WR_FEAT_BLUR instead: build_launches() knows which do.
+constexpr int shader_feat(int sh) {
+  if (sh == WR_SH_PS_CLEAR || sh == WR_SH_CLEAR_OP) return 0;
+  if (is_text_run(sh)) return WR_FEAT_R8TEX | WR_FEAT_TEX | WR_FEAT_GENERIC;
+  if (is_brush_solid(sh)) return WR_FEAT_R8TEX | WR_FEAT_GENERIC;      // masked / odd blend
+  if (sh == WR_SH_CS_BLUR_ALPHA || sh == WR_SH_CS_BLUR_COLOR) return WR_FEAT_BLUR;
+  if (is_clip_mask(sh)) return WR_FEAT_CLIP;
+  if (is_gradient_prog(sh)) return WR_FEAT_SHADE | WR_FEAT_GENERIC;
+  switch (sh) {
+    case WR_SH_BRUSH_BLEND: case WR_SH_BRUSH_BLEND_ALPHA: case WR_SH_BRUSH_MIX_BLEND: case WR_SH_BRUSH_MIX_BLEND_ALPHA:
+    case WR_SH_CS_SVG_FILTER: case WR_SH_CS_SVG_FILTER_NODE: case WR_SH_BRUSH_YUV: case WR_SH_BRUSH_YUV_ALPHA: case WR_SH_COMPOSITE_YUV:
+    case WR_SH_PS_QUAD_MASK: case WR_SH_PS_QUAD_MASK_FAST:
+    case WR_SH_CS_BORDER_SOLID: case WR_SH_CS_BORDER_SEGMENT: case WR_SH_CS_FAST_LINEAR_GRADIENT: case WR_SH_CS_LINE_DECORATION:
+    case WR_SH_BRUSH_IMAGE_REPEAT: case WR_SH_BRUSH_IMAGE_REPEAT_ALPHA: case WR_SH_BRUSH_IMAGE_REPEAT_DUAL:
+      return WR_FEAT_SHADE | WR_FEAT_GENERIC;
+    default: return WR_FEAT_TEX | WR_FEAT_GENERIC;
+  }
+}
 // (named like the kernels, so that an entry of WR_INST_ALL names its family)
 enum class Family { wr_raster_kernel, wr_setup_raster_kernel, wr_raster_dense_kernel, wr_setup_raster_dense_kernel, wr_setup_raster_thin_kernel, wr_span_rows_kernel, wr_tile_rows_kernel, wr_setup_tile_rows_kernel };
 constexpr uint32_t inst_key(Family k, int fmt, bool depth, int r, int feat) { return (uint32_t)k << 20 | (uint32_t)fmt << 16 | (uint32_t)depth << 12 | (uint32_t)r << 8 | (uint32_t)feat; }
@@ -1787,654 +1817,660 @@ static bool plan_forwarding(TargetWork& fb, const std::vector<int>& sel) {
   return true;
 }
 
-void flush_work(const std::vector<int>& sel_in) {
+// ---- a flush, phase by phase ----------------------------------------------------------------------------------------------------
+// What the phases of flush_work() hand to each other: one FlushPlan, built on its stack per flush.
+// One dependency level of the flush: its bins, split by target format, and its row targets.
+struct Level { int bin0 = 0, bins_rgba = 0, bins_r8 = 0, feat_rgba = 0, feat_r8 = 0; bool any_depth = false, text = false; uint64_t bytes_rgba = 0, bytes_r8 = 0, mr_rows = 0;
+               int row_t0 = -1, row_n = 0, row_items = 0, row_fmt = 0; uint64_t bytes_rows = 0;          // span-rows targets (rows_mode 1)
+               int trow_t0 = -1, trow_n = 0, trow_items = 0; uint64_t bytes_trows = 0; };                // tile-rows targets (rows_mode 2)
+struct InstSeg { size_t base; const uint8_t* src; size_t size; };
+struct FlushPlan {
+  std::vector<int> sel;                // indices into Context::work of the targets that are rasterised, in launch order
+  std::vector<int> forwarded_sel;      // ... of those that became write-throughs of their sources (plan_forwarding)
+  std::vector<char> rows_of;           // per Context::work index: 0 bins, 1 span rows, 2 tile rows
+  std::vector<Level> levels;
+  std::vector<int> target_level;
+  std::vector<size_t> flat_off;        // per target: offset of its flattened-depth-row table (words), or SIZE_MAX
+  size_t flat_words = 0;
+  std::vector<WrDrawDesc> draws;
+  std::vector<WrTargetDesc> targets;
+  std::vector<InstSeg> inst_segs;      // instance bytes of the selected targets, in arena order (copied at staging time)
+  size_t inst_bytes = 0;
+  int n_prims = 0, n_bins = 0, n_words = 0;      // (plan_targets' cursors, and so the totals once it is through)
+  size_t vtab_words = 0;
+  size_t gtab_words = 0;       // the pool's fixed head: the gradient-table copies of the WR_DF_GTAB draws (WrDrawDesc::gtab_base); the setup stage's
+                               // allocations start behind it
+  size_t qtab_need = 0;        // floats: rows x instances x 10 of the draws that may hold rotated / projected prims (WR_DF_XFORM)
+  bool runs_pool = false;
+  uint64_t mr_slots = 0, mr_rows = 0, mr_bytes = 0;      // bounds on what the cs_clip_* prims of this flush can reserve in the mask-row store
+  bool mr_on = false, mr_safe = false;
+  int n_row_targets = 0;
+  uint64_t algo_bytes = 0, pixels = 0;
+  // frame arena: [draws | targets | instance bytes | block table | qctl | mr_ctl] at `aoff` of the staging ring and of its HBM mirror
+  struct Arena {
+    size_t aoff = 0, off_draws = 0, off_targets = 0, off_inst = 0, off_blk = 0, off_qctl = 0, off_mrctl = 0, total = 0;
+    const uint8_t* dev(size_t off) const { return ctx->dupload + aoff + off; }
+    const WrDrawDesc* ddraws() const { return (const WrDrawDesc*)dev(off_draws); }
+    const WrTargetDesc* dtargets() const { return (const WrTargetDesc*)dev(off_targets); }
+    const uint8_t* dinst() const { return dev(off_inst); }
+    const int* dblk() const { return (const int*)dev(off_blk); }
+  } arena;
+  int n_targets() const { return (int)sel.size(); }
+  int nd() const { return (int)draws.size(); }
+  bool any_work() const { return n_bins > 0 || n_row_targets > 0; }
+};
+
+// Span-rows targets (wr_span_rows_kernel): every draw is a cs_blur / cs_scale pass or a clear, unblended, without depth --
+// the levels of a blur chain.  They get no bins; a wave per target row walks the target's few prims instead.
+bool span_rows_eligible(const TargetWork& w) {
   Context* c = ctx;
-  if (!c || c->work.empty() || sel_in.empty()) return;
-  HostTimer ht(&c->stats.host_flush_ns);
-  static const bool laps = getenv("WRHIP_DEBUG_LAPS") != nullptr;
-  auto lap_t = std::chrono::steady_clock::now();
-  auto lap = [&](int i) { if (laps) { const auto n = std::chrono::steady_clock::now(); c->lap_ns[i] += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(n - lap_t).count(); lap_t = n; } };
-  if (laps) c->lap_n++;
-  std::vector<int> sel(sel_in);
+  if (!c->span_rows || w.fwd_tex || w.forwarded_away || w.depth_tex) return false;
+  const Texture& t = c->textures[w.tex];
+  if (t.internal_format != GL_R8 && t.internal_format != GL_RGBA8) return false;
+  int nprim = 0; bool any = false;
+  for (const WrDrawDesc& d : w.draws) {
+    if (d.shader == WR_SH_CLEAR_OP) { if (d.flags & WR_DF_CLEAR_DEPTH) return false; nprim += 1; continue; }
+    if (d.shader != WR_SH_CS_BLUR_ALPHA && d.shader != WR_SH_CS_BLUR_COLOR && d.shader != WR_SH_CS_SCALE) return false;
+    if (d.blend != WR_BLEND_NONE || (d.flags & (WR_DF_DEPTH_TEST | WR_DF_DEPTH_WRITE | WR_DF_QUADS | WR_DF_SIMPLE | WR_DF_XFORM))) return false;
+    any = true; nprim += d.count;
+  }
+  return any && nprim <= 48;
+}
+// Tile-rows targets (wr_tile_rows_kernel): a picture target of a few large axis-aligned prims, at least one of them a linear
+// gradient or an image -- the kinds whose bin-raster variant runs at one wave per SIMD.  Solids only where the host has verified
+// them plain (WR_DF_SIMPLE), nothing that may sit on a general quad or ask for anti-aliasing, no depth that outlives the flush.
+bool tile_rows_eligible(const TargetWork& w) {
+  Context* c = ctx;
+  if (!c->tile_rows || w.forwarded_away) return false;
+  const Texture& t = c->textures[w.tex];
+  if (t.internal_format != GL_RGBA8) return false;
+  if (Texture* dt = w.depth_tex ? c->textures.find(w.depth_tex) : nullptr) {
+    if (dt->depth_materialized) return false;
+    if (w.depth_live && dt->depth_cleared && dt->depth_owner == w.tex) return false;      // (would have to be stored per pixel)
+  }
+  int nprim = 0; bool heavy = false;
+  for (const WrDrawDesc& d : w.draws) {
+    if (d.shader == WR_SH_CLEAR_OP) { nprim += 1; continue; }
+    const bool solid = is_brush_solid(d.shader) || d.shader == WR_SH_PS_QUAD_TEXTURED;
+    const bool shade = d.shader == WR_SH_BRUSH_IMAGE || d.shader == WR_SH_BRUSH_IMAGE_ALPHA || d.shader == WR_SH_BRUSH_LINEAR_GRADIENT ||
+                       d.shader == WR_SH_BRUSH_LINEAR_GRADIENT_ALPHA;
+    if (!solid && !shade) return false;
+    // (solids under a clip mask -- the corner segments of a rounded-rect clip, wrench large-clip-rect: 72 prims on two tiles are one
+    // serial walk per wave in the bin raster -- : the host has scanned such a draw for anti-aliasing requests (WR_DF_QUADS), so its
+    // prims are plain or masked solids)
+    const bool masked_solid = is_brush_solid(d.shader) && d.tex[WR_S_CLIP_MASK].ptr != nullptr && d.tex[WR_S_CLIP_MASK].format == WR_FMT_R8;
+    if (solid && !(d.flags & WR_DF_SIMPLE) && !masked_solid) return false;
+    if (d.flags & (WR_DF_QUADS | WR_DF_XFORM | WR_DF_TEX_RECT)) return false;
+    if (d.blend == WR_BLEND_UNSUPPORTED || d.blend == WR_BLEND_DUAL_SRC) return false;
+    if (d.query_slot >= 0) return false;
+    heavy = heavy || shade || (masked_solid && !(d.flags & WR_DF_SIMPLE));
+    nprim += d.count;
+  }
+  return heavy && nprim <= 128;
+}
+
+// Which targets are rasterised, and in which order.
+void select_targets(FlushPlan& P, const std::vector<int>& sel_in) {
+  Context* c = ctx;
+  std::vector<int>& sel = P.sel;
+  sel = sel_in;
   std::sort(sel.begin(), sel.end());
   sel.erase(std::unique(sel.begin(), sel.end()), sel.end());
   // forwarded composites: targets that turn into write-throughs of their sources leave the launch sequence
-  std::vector<GLuint> forwarded_dst;
   if (c->forward_composites) {
     for (int wi : sel) { TargetWork& w = c->work[wi]; w.fwd_tex = 0; w.forwarded_away = false; }
+    bool any_forwarded = false;
     for (int wi : sel) {
       TargetWork& w = c->work[wi];
       bool all_comp = !w.draws.empty();
       for (const WrDrawDesc& d : w.draws) if (d.shader != WR_SH_CLEAR_OP && d.shader != WR_SH_COMPOSITE_FAST) { all_comp = false; break; }
-      if (all_comp && plan_forwarding(w, sel)) forwarded_dst.push_back(w.tex);
+      if (all_comp && plan_forwarding(w, sel)) any_forwarded = true;
     }
-    if (!forwarded_dst.empty()) {
+    if (any_forwarded) {
       std::vector<int> keep;
       for (int wi : sel) if (!c->work[wi].forwarded_away) keep.push_back(wi);
-      // (the forwarded targets stay in sel_in's hazard bookkeeping below through `forwarded_sel`)
+      // (the forwarded targets stay in the hazard bookkeeping of retire_work() through `forwarded_sel`)
       sel.swap(keep);
     }
   }
-  std::vector<int> forwarded_sel;
-  for (int wi : sel_in) if (c->work[wi].forwarded_away) forwarded_sel.push_back(wi);
-  // Span-rows targets (wr_span_rows_kernel): every draw is a cs_blur / cs_scale pass or a clear, unblended, without depth --
-  // the levels of a blur chain.  They get no bins; a wave per target row walks the target's few prims instead.
-  auto rows_eligible = [&](const TargetWork& w) {
-    if (!c->span_rows || w.fwd_tex || w.forwarded_away || w.depth_tex) return false;
-    const Texture& t = c->textures[w.tex];
-    if (t.internal_format != GL_R8 && t.internal_format != GL_RGBA8) return false;
-    int nprim = 0; bool any = false;
-    for (const WrDrawDesc& d : w.draws) {
-      if (d.shader == WR_SH_CLEAR_OP) { if (d.flags & WR_DF_CLEAR_DEPTH) return false; nprim += 1; continue; }
-      if (d.shader != WR_SH_CS_BLUR_ALPHA && d.shader != WR_SH_CS_BLUR_COLOR && d.shader != WR_SH_CS_SCALE) return false;
-      if (d.blend != WR_BLEND_NONE || (d.flags & (WR_DF_DEPTH_TEST | WR_DF_DEPTH_WRITE | WR_DF_QUADS | WR_DF_SIMPLE | WR_DF_XFORM))) return false;
-      any = true; nprim += d.count;
-    }
-    return any && nprim <= 48;
-  };
-  // Tile-rows targets (wr_tile_rows_kernel): a picture target of a few large axis-aligned prims, at least one of them a linear
-  // gradient or an image -- the kinds whose bin-raster variant runs at one wave per SIMD.  Solids only where the host has verified
-  // them plain (WR_DF_SIMPLE), nothing that may sit on a general quad or ask for anti-aliasing, no depth that outlives the flush.
-  auto tile_rows_eligible = [&](const TargetWork& w) {
-    if (!c->tile_rows || w.forwarded_away) return false;
-    const Texture& t = c->textures[w.tex];
-    if (t.internal_format != GL_RGBA8) return false;
-    if (Texture* dt = w.depth_tex ? c->textures.find(w.depth_tex) : nullptr) {
-      if (dt->depth_materialized) return false;
-      if (w.depth_live && dt->depth_cleared && dt->depth_owner == w.tex) return false;      // (would have to be stored per pixel)
-    }
-    int nprim = 0; bool heavy = false;
-    for (const WrDrawDesc& d : w.draws) {
-      if (d.shader == WR_SH_CLEAR_OP) { nprim += 1; continue; }
-      const bool solid = d.shader == WR_SH_BRUSH_SOLID || d.shader == WR_SH_BRUSH_SOLID_ALPHA || d.shader == WR_SH_PS_QUAD_TEXTURED;
-      const bool shade = d.shader == WR_SH_BRUSH_IMAGE || d.shader == WR_SH_BRUSH_IMAGE_ALPHA || d.shader == WR_SH_BRUSH_LINEAR_GRADIENT ||
-                         d.shader == WR_SH_BRUSH_LINEAR_GRADIENT_ALPHA;
-      if (!solid && !shade) return false;
-      // (solids under a clip mask -- the corner segments of a rounded-rect clip, wrench large-clip-rect: 72 prims on two tiles are one
-      // serial walk per wave in the bin raster -- : the host has scanned such a draw for anti-aliasing requests (WR_DF_QUADS), so its
-      // prims are plain or masked solids)
-      const bool masked_solid = (d.shader == WR_SH_BRUSH_SOLID || d.shader == WR_SH_BRUSH_SOLID_ALPHA) && d.tex[WR_S_CLIP_MASK].ptr != nullptr &&
-                                d.tex[WR_S_CLIP_MASK].format == WR_FMT_R8;
-      if (solid && !(d.flags & WR_DF_SIMPLE) && !masked_solid) return false;
-      if (d.flags & (WR_DF_QUADS | WR_DF_XFORM | WR_DF_TEX_RECT)) return false;
-      if (d.blend == WR_BLEND_UNSUPPORTED || d.blend == WR_BLEND_DUAL_SRC) return false;
-      if (d.query_slot >= 0) return false;
-      heavy = heavy || shade || (masked_solid && !(d.flags & WR_DF_SIMPLE));
-      nprim += d.count;
-    }
-    return heavy && nprim <= 128;
-  };
-  std::vector<char> rows_of(c->work.size(), 0);
-  for (int wi : sel) rows_of[wi] = rows_eligible(c->work[wi]) ? 1 : (tile_rows_eligible(c->work[wi]) ? 2 : 0);
+  for (int wi : sel_in) if (c->work[wi].forwarded_away) P.forwarded_sel.push_back(wi);
+  P.rows_of.assign(c->work.size(), 0);
+  for (int wi : sel) P.rows_of[wi] = span_rows_eligible(c->work[wi]) ? 1 : (tile_rows_eligible(c->work[wi]) ? 2 : 0);
   // by dependency level, RGBA8 targets first inside a level, span-rows targets last, so each launch gets a contiguous bin / target range
   std::stable_sort(sel.begin(), sel.end(), [&](int a, int b) {
     const int la = c->work[a].level, lb = c->work[b].level;
     if (la != lb) return la < lb;
-    const int ka = rows_of[a] ? 1 + rows_of[a] : (c->textures[c->work[a].tex].internal_format == GL_R8 ? 1 : 0);
-    const int kb = rows_of[b] ? 1 + rows_of[b] : (c->textures[c->work[b].tex].internal_format == GL_R8 ? 1 : 0);
+    const int ka = P.rows_of[a] ? 1 + P.rows_of[a] : (c->textures[c->work[a].tex].internal_format == GL_R8 ? 1 : 0);
+    const int kb = P.rows_of[b] ? 1 + P.rows_of[b] : (c->textures[c->work[b].tex].internal_format == GL_R8 ? 1 : 0);
     return ka < kb;
   });
-  struct Level { int bin0 = 0, bins_rgba = 0, bins_r8 = 0, feat_rgba = 0, feat_r8 = 0; bool any_depth = false, text = false; uint64_t bytes_rgba = 0, bytes_r8 = 0, mr_rows = 0;
-                 int row_t0 = -1, row_n = 0, row_items = 0, row_fmt = 0; uint64_t bytes_rows = 0;          // span-rows targets (rows_mode 1)
-                 int trow_t0 = -1, trow_n = 0, trow_items = 0; uint64_t bytes_trows = 0; };                // tile-rows targets (rows_mode 2)
-  int n_row_targets = 0;
-  uint64_t mr_slots = 0, mr_rows = 0, mr_bytes = 0;      // bounds on what the cs_clip_* prims of this flush can reserve in the mask-row store
-  std::vector<Level> levels;
-  std::vector<int> target_level;
-  std::vector<size_t> flat_off;          // per target: offset of its flattened-depth-row table (words), or SIZE_MAX
-  size_t flat_words = 0;
-  const int n_targets = (int)sel.size();
-  std::vector<WrDrawDesc> draws;
-  std::vector<WrTargetDesc> targets(n_targets);
-  struct InstSeg { size_t base; const uint8_t* src; size_t size; };
-  std::vector<InstSeg> inst_segs;      // instance bytes of the selected targets, in arena order (copied at staging time)
-  size_t inst_bytes = 0;
-  int prim_cursor = 0, bin_cursor = 0, word_cursor = 0;
-  size_t vtab_cursor = 0;
-  size_t gtab_words = 0;       // the pool's fixed head: the gradient-table copies of the WR_DF_GTAB draws (WrDrawDesc::gtab_base); the setup stage's
-                               // allocations start behind it
-  size_t qtab_need = 0;        // floats: rows x instances x 10 of the draws that may hold rotated / projected prims (WR_DF_XFORM)
-  const bool no_qtab = !c->quad_rowtabs;
-  static const bool no_run_share = getenv("WRHIP_NO_RUN_SHARE") != nullptr;
-  const size_t runs_pool_words = c->runs_pool_words;
-  bool runs_pool = false;
-  uint64_t algo_bytes = 0, pixels = 0;
-  for (int oi = 0; oi < n_targets; oi++) {
-    TargetWork& w = c->work[sel[oi]];
-    Texture& t = c->textures[w.tex];
-    WrTargetDesc& T = targets[oi];
-    memset(&T, 0, sizeof(T));
-    if (levels.empty() || w.level != c->work[sel[oi - 1]].level) { levels.emplace_back(); levels.back().bin0 = bin_cursor; }
-    Level& L = levels.back();
-    target_level.push_back((int)levels.size() - 1);
-    T.color = t.dptr; T.width = t.width; T.height = t.height; T.stride = t.stride;
-    T.format = t.internal_format == GL_R8 ? WR_FMT_R8 : WR_FMT_RGBA8;
-    T.bins_x = (t.width + WR_BIN_W - 1) / WR_BIN_W; T.bins_y = (t.height + WR_BIN_H - 1) / WR_BIN_H;
-    // every target starts on a 64-prim boundary: a wave of the setup kernel then holds prims of one
-    // target and one mask word only (the slots in between are skipped as instance >= count)
-    prim_cursor = (prim_cursor + 63) & ~63;
-    T.first_bin = bin_cursor; T.first_prim = prim_cursor;
-    T.load_color = 1; T.init_color = 0; T.load_depth = 0; T.store_depth = 0;
-    Texture* dt = w.depth_tex ? c->textures.find(w.depth_tex) : nullptr;
-    T.init_depth = w.init_depth_set ? w.init_depth : (dt ? dt->depth_value : 0xFFFFFF);
-    if (dt && dt->depth_materialized && dt->dptr) { T.load_depth = 1; T.depth = (uint32_t*)dt->dptr; }
-    T.fwd_color = nullptr;
-    if (w.fwd_tex) {
-      Texture& ft = c->textures[w.fwd_tex];
-      c->stats.forwarded_targets++;
-      T.fwd_color = ft.dptr; T.fwd_stride = ft.stride; T.fwd_dx = w.fwd_dx; T.fwd_y0 = w.fwd_y0; T.fwd_ys = w.fwd_ys;
-      for (int k = 0; k < 4; k++) T.fwd_clip[k] = w.fwd_clip[k];
-    }
-    T.cells = c->cell_raster ? 1 : 0;
-    T.rows_mode = rows_of[sel[oi]];
-    T.y_begin = 0; T.y_end = t.height;
-    if (t.own_y1 > t.own_y0) {   // WrhipSetTargetRows: rows of this target owned by this process
-      T.y_begin = std::max(0, t.own_y0); T.y_end = std::min(t.height, t.own_y1);
-    } else if (c->shard_world > 1) {  // WrhipSetShard: contiguous strips of bin rows per rank
-      T.y_begin = (int)((int64_t)T.bins_y * c->shard_rank / c->shard_world) * WR_BIN_H;
-      T.y_end = std::min(t.height, (int)((int64_t)T.bins_y * (c->shard_rank + 1) / c->shard_world) * WR_BIN_H);
-    }
-    // (the target's instance bytes go from its snapshot straight into the staging ring when the arena is laid out: gathering
-    // them in one vector first was a second pass over 2.4 MB per cfg5 frame)
-    size_t inst_base = (inst_bytes + 15) & ~size_t(15);
-    inst_bytes = inst_base + w.inst.size();
-    if (!w.inst.empty()) inst_segs.push_back(InstSeg{inst_base, w.inst.data(), w.inst.size()});
-    bool any_kept = false;
-    T.dw_first = 0; T.dw_end = 0;
-    for (const WrDrawDesc& d0 : w.draws) {
-      WrDrawDesc d = d0;
-      d.target = oi;
-      d.inst_offset += inst_base;
-      // Leading full-target clears initialise the bins instead of loading HBM.
-      if (!any_kept && d.shader == WR_SH_CLEAR_OP && d.clip[0] <= 0 && d.clip[1] <= 0 && d.clip[2] >= t.width &&
-          d.clip[3] >= t.height) {
-        if (d.flags & WR_DF_CLEAR_COLOR) { T.load_color = 0; T.init_color = d.clear_color; }
-        if (d.flags & WR_DF_CLEAR_DEPTH) { T.init_depth = d.clear_depth; T.load_depth = 0; }
-        continue;
-      }
-      any_kept = true;
-      if (c->mask_rows && T.format == WR_FMT_R8 && !(d.flags & WR_DF_SIMPLE) &&
-          (d.shader == WR_SH_CS_CLIP_RECT || d.shader == WR_SH_CS_CLIP_RECT_FAST || d.shader == WR_SH_CS_CLIP_BOX_SHADOW)) {
-        const int cw = std::max(0, std::min(d.clip[2], t.width) - std::max(d.clip[0], 0));
-        const int ch = std::max(0, std::min(d.clip[3], t.height) - std::max(d.clip[1], 0));
-        if (cw > 0 && ch > 0 && d.count > 0) {
-          d.flags |= WR_DF_MASK_ROWS;
-          mr_slots += (uint64_t)d.count; mr_rows += (uint64_t)d.count * ch * 1;      // work items: rows x parts
-          mr_bytes += (uint64_t)d.count * ((uint64_t)((cw + 7) & ~3) * ch + (uint64_t)ch * 4 + 48 + sizeof(WrAccTabs));      // rows + row map + row-sum tables
-          L.mr_rows += (uint64_t)d.count * ch * 1;
-        }
-      }
-      if ((d.flags & (WR_DF_DEPTH_TEST | WR_DF_CLEAR_DEPTH)) && T.format == WR_FMT_RGBA8) L.any_depth = true;
-      // A wave of the setup stage runs every vertex shader its 64 prims need one after the other (divergence), and the setup
-      // stage of a small flush is one long dependent chain per wave: while the flush is small, a draw with another program
-      // starts a wave of its own (cfg4: the box-shadow and the clip-out rect of a mask target, 2 x 12 us in one wave).
-      if (prim_cursor < 4096 && (prim_cursor & 63) && !draws.empty() && draws.back().target == oi && draws.back().shader != d.shader)
-        prim_cursor = (prim_cursor + 63) & ~63;
-      d.first_prim = prim_cursor;
-      if ((d.flags & WR_DF_DEPTH_WRITE) && d.shader != WR_SH_CLEAR_OP) {
-        if (T.dw_end <= T.dw_first) T.dw_first = prim_cursor;
-        T.dw_end = prim_cursor + d.count;
-      }
-      prim_cursor += d.count;
-      // per-row v table budget for draws whose prims can take the nearest-fast texture path
-      d.gtab_base = -1;
-      if (d.flags & WR_DF_GTAB) {
-        d.gtab_base = (int)gtab_words; gtab_words += (size_t)d.count * WR_GTAB_WORDS;
-        // (the promise of THIS draw is redeemed; those of draws a partial flush leaves recorded stay counted: ADVICE r5)
-        c->gtab_pending -= std::min(c->gtab_pending, (size_t)d.count * WR_GTAB_WORDS);
-      }
-      d.vtab_base = -1; d.vtab_rows = 0;
-      if (T.format == WR_FMT_RGBA8 && !(d.flags & WR_DF_SIMPLE) &&
-          (d.shader == WR_SH_COMPOSITE || d.shader == WR_SH_COMPOSITE_FAST || d.shader == WR_SH_CS_SCALE ||
-           d.shader == WR_SH_PS_QUAD_TEXTURED || d.shader == WR_SH_BRUSH_IMAGE || d.shader == WR_SH_BRUSH_IMAGE_ALPHA)) {
-        const int rows = std::max(0, std::min(d.clip[3], t.height) - std::max(d.clip[1], 0));
-        const size_t need = (size_t)rows * d.count;
-        if (rows > 0 && vtab_cursor + need <= ((size_t)64 << 20)) {
-          d.vtab_base = (int)vtab_cursor; d.vtab_rows = rows;
-          vtab_cursor += need;
-        }
-      }
-      if (!no_qtab && T.format == WR_FMT_RGBA8 && (d.flags & WR_DF_XFORM) && !(d.flags & WR_DF_SIMPLE) && d.shader != WR_SH_CLEAR_OP) {
-        const int rows = std::max(0, std::min(d.clip[3], t.height) - std::max(d.clip[1], 0));
-        qtab_need += (size_t)rows * (size_t)d.count * 10;
-      }
-      // (the same pool takes the depth runs of a row and the occluder list of a strip that outgrow their LDS copies: a draw that is
-      // depth-tested and may consume interpolants can ask for them)
-      if (T.format == WR_FMT_RGBA8 && (d.flags & WR_DF_DEPTH_TEST) && !(d.flags & WR_DF_SIMPLE) && d.shader != WR_SH_CLEAR_OP) runs_pool = true;
-      draws.push_back(d);
-    }
-    T.end_prim = prim_cursor;
-    {
-      // a general-quad draw with the depth test on may hold perspective prims: they flatten the depth rows they touch
-      bool persp_possible = false;
-      if (T.format == WR_FMT_RGBA8)
-        for (const WrDrawDesc& d0 : w.draws) if ((d0.flags & WR_DF_XFORM) && (d0.flags & WR_DF_DEPTH_TEST) && !(d0.flags & WR_DF_SIMPLE)) { persp_possible = true; break; }
-      flat_off.push_back(persp_possible ? flat_words : SIZE_MAX);
-      if (persp_possible) flat_words += (size_t)t.height + 1;
-    }
-    int nrel = T.end_prim - T.first_prim;
-    T.words_per_bin = (nrel + 63) / 64;
-    T.word_base = word_cursor;
-    if (T.rows_mode == 2) {
-      T.words_per_bin = 0;
-      if (L.trow_n == 0) L.trow_t0 = oi;
-      L.trow_n++; n_row_targets++;
-      L.trow_items += std::max(0, T.y_end - T.y_begin) * ((t.width + 255) >> 8);
-    } else if (T.rows_mode) {
-      // no bins, no mask words: the level's span-rows launch takes targets [row_t0, row_t0 + row_n)
-      T.words_per_bin = 0;
-      if (L.row_n == 0) { L.row_t0 = oi; L.row_fmt = T.format; }
-      L.row_n++; n_row_targets++;
-      L.row_items += std::max(0, T.y_end - T.y_begin) * WR_SPAN_PIECES(t.width);
-    } else {
-      word_cursor += T.words_per_bin * T.bins_x * T.bins_y;
-      bin_cursor += T.bins_x * T.bins_y;
-      (T.format == WR_FMT_RGBA8 ? L.bins_rgba : L.bins_r8) += T.bins_x * T.bins_y;
-    }
-    uint64_t owned = (uint64_t)t.width * std::max(0, T.y_end - T.y_begin);
-    pixels += owned;
-    {
-      uint64_t tb = owned * t.bpp * (T.load_color ? 2 : 1);
-      // unique source texels sampled: bounded by what a 1:1 mapping can touch
-      uint64_t src = 0;
-      for (GLuint id : w.reads)
-        if (Texture* rt = c->textures.find(id))
-          if (rt->internal_format == GL_RGBA8 || rt->internal_format == GL_R8) src += (uint64_t)rt->stride * rt->height;
-      tb += std::min<uint64_t>(src, owned * t.bpp);
-      if (w.fwd_tex) tb += (uint64_t)std::max(0, w.fwd_clip[2] - w.fwd_clip[0]) * std::max(0, w.fwd_clip[3] - w.fwd_clip[1]) * 4;   // the write-through
-      algo_bytes += tb;
-      (T.rows_mode == 2 ? L.bytes_trows : T.rows_mode ? L.bytes_rows : (T.format == WR_FMT_RGBA8 ? L.bytes_rgba : L.bytes_r8)) += tb;
-    }
-    if (dt && nrel > 0 && w.depth_live && dt->depth_cleared && dt->depth_owner == w.tex) {
-      // The caller has not invalidated (or fully cleared) the depth these draws leave behind: it outlives the flush -- a
-      // flush in the middle of a target (host upload to a sampled texture, readback of the target being drawn, a
-      // TIME_ELAPSED query) -- so it is materialised: stored per pixel now, loaded by the continuation.  WebRender's own
-      // pattern (clear, draw, InvalidateFramebuffer, flush later) never gets here.
-      bool uses = T.load_depth != 0;
-      for (const WrDrawDesc& d0 : w.draws) if (d0.flags & (WR_DF_DEPTH_WRITE | WR_DF_CLEAR_DEPTH)) uses = true;
-      if (uses) {
-        const size_t need = (size_t)t.width * t.height * 4;
-        if (!dt->dptr || dt->dsize < need || dt->width != t.width || dt->height != t.height) {
-          // (depth attachments have the size of their colour target in every caller; anything else keeps the uniform value)
-          if (dt->width == t.width && dt->height == t.height) {
-            if (dt->dptr) pool_free(dt->dptr, dt->dsize);
-            size_t actual = 0;
-            dt->dptr = pool_alloc(need, &actual); dt->dsize = actual;
-          }
-        }
-        if (dt->dptr && dt->dsize >= need && dt->width == t.width && dt->height == t.height) {
-          T.depth = (uint32_t*)dt->dptr; T.store_depth = 1;
-          dt->depth_materialized = true;
-          L.any_depth = true;
-        }
-      }
-    }
-    if (T.load_depth) L.any_depth = true;
+}
+
+// One recorded draw of target `oi` (level P.levels.back()) joins the plan: its prim range and its shares of the flush's tables.
+// False: it was a leading full-target clear, which initialises the bins instead of loading HBM, and is not kept.
+bool plan_draw(FlushPlan& P, int oi, const Texture& t, const WrDrawDesc& d0, size_t inst_base, bool any_kept) {
+  Context* c = ctx;
+  WrTargetDesc& T = P.targets[oi];
+  Level& L = P.levels.back();
+  WrDrawDesc d = d0;
+  d.target = oi;
+  d.inst_offset += inst_base;
+  if (!any_kept && d.shader == WR_SH_CLEAR_OP && d.clip[0] <= 0 && d.clip[1] <= 0 && d.clip[2] >= t.width && d.clip[3] >= t.height) {
+    if (d.flags & WR_DF_CLEAR_COLOR) { T.load_color = 0; T.init_color = d.clear_color; }
+    if (d.flags & WR_DF_CLEAR_DEPTH) { T.init_depth = d.clear_depth; T.load_depth = 0; }
+    return false;
   }
-  const int n_prims = prim_cursor, n_bins = bin_cursor, n_words = word_cursor;
-  const int nd = (int)draws.size();
-  const bool any_work = n_bins > 0 || n_row_targets > 0;
+  if (c->mask_rows && T.format == WR_FMT_R8 && !(d.flags & WR_DF_SIMPLE) && is_clip_mask(d.shader)) {
+    const int cw = std::max(0, std::min(d.clip[2], t.width) - std::max(d.clip[0], 0));
+    const int ch = std::max(0, std::min(d.clip[3], t.height) - std::max(d.clip[1], 0));
+    if (cw > 0 && ch > 0 && d.count > 0) {
+      d.flags |= WR_DF_MASK_ROWS;
+      P.mr_slots += (uint64_t)d.count; P.mr_rows += (uint64_t)d.count * ch * 1;      // work items: rows x parts
+      P.mr_bytes += (uint64_t)d.count * ((uint64_t)((cw + 7) & ~3) * ch + (uint64_t)ch * 4 + 48 + sizeof(WrAccTabs));      // rows + row map + row-sum tables
+      L.mr_rows += (uint64_t)d.count * ch * 1;
+    }
+  }
+  if ((d.flags & (WR_DF_DEPTH_TEST | WR_DF_CLEAR_DEPTH)) && T.format == WR_FMT_RGBA8) L.any_depth = true;
+  // A wave of the setup stage runs every vertex shader its 64 prims need one after the other (divergence), and the setup
+  // stage of a small flush is one long dependent chain per wave: while the flush is small, a draw with another program
+  // starts a wave of its own (cfg4: the box-shadow and the clip-out rect of a mask target, 2 x 12 us in one wave).
+  if (P.n_prims < 4096 && (P.n_prims & 63) && !P.draws.empty() && P.draws.back().target == oi && P.draws.back().shader != d.shader)
+    P.n_prims = (P.n_prims + 63) & ~63;
+  d.first_prim = P.n_prims;
+  if ((d.flags & WR_DF_DEPTH_WRITE) && d.shader != WR_SH_CLEAR_OP) {
+    if (T.dw_end <= T.dw_first) T.dw_first = P.n_prims;
+    T.dw_end = P.n_prims + d.count;
+  }
+  P.n_prims += d.count;
+  d.gtab_base = -1;
+  if (d.flags & WR_DF_GTAB) {
+    d.gtab_base = (int)P.gtab_words; P.gtab_words += (size_t)d.count * WR_GTAB_WORDS;
+    // (the promise of THIS draw is redeemed; those of draws a partial flush leaves recorded stay counted: ADVICE r5)
+    c->gtab_pending -= std::min(c->gtab_pending, (size_t)d.count * WR_GTAB_WORDS);
+  }
+  // per-row v table budget for draws whose prims can take the nearest-fast texture path
+  d.vtab_base = -1; d.vtab_rows = 0;
+  if (T.format == WR_FMT_RGBA8 && !(d.flags & WR_DF_SIMPLE) &&
+      (d.shader == WR_SH_COMPOSITE || d.shader == WR_SH_COMPOSITE_FAST || d.shader == WR_SH_CS_SCALE ||
+       d.shader == WR_SH_PS_QUAD_TEXTURED || d.shader == WR_SH_BRUSH_IMAGE || d.shader == WR_SH_BRUSH_IMAGE_ALPHA)) {
+    const int rows = std::max(0, std::min(d.clip[3], t.height) - std::max(d.clip[1], 0));
+    const size_t need = (size_t)rows * d.count;
+    if (rows > 0 && P.vtab_words + need <= ((size_t)64 << 20)) {
+      d.vtab_base = (int)P.vtab_words; d.vtab_rows = rows;
+      P.vtab_words += need;
+    }
+  }
+  if (c->quad_rowtabs && T.format == WR_FMT_RGBA8 && (d.flags & WR_DF_XFORM) && !(d.flags & WR_DF_SIMPLE) && d.shader != WR_SH_CLEAR_OP) {
+    const int rows = std::max(0, std::min(d.clip[3], t.height) - std::max(d.clip[1], 0));
+    P.qtab_need += (size_t)rows * (size_t)d.count * 10;
+  }
+  // (the same pool takes the depth runs of a row and the occluder list of a strip that outgrow their LDS copies: a draw that is
+  // depth-tested and may consume interpolants can ask for them)
+  if (T.format == WR_FMT_RGBA8 && (d.flags & WR_DF_DEPTH_TEST) && !(d.flags & WR_DF_SIMPLE) && d.shader != WR_SH_CLEAR_OP) P.runs_pool = true;
+  P.draws.push_back(d);
+  return true;
+}
+
+// The caller has not invalidated (or fully cleared) the depth the draws of `w` leave behind: it outlives the flush -- a
+// flush in the middle of a target (host upload to a sampled texture, readback of the target being drawn, a
+// TIME_ELAPSED query) -- so it is materialised: stored per pixel now, loaded by the continuation.  WebRender's own
+// pattern (clear, draw, InvalidateFramebuffer, flush later) never gets here.
+void materialise_depth(const TargetWork& w, const Texture& t, Texture* dt, WrTargetDesc& T, Level& L) {
+  if (!(dt && T.end_prim > T.first_prim && w.depth_live && dt->depth_cleared && dt->depth_owner == w.tex)) return;
+  bool uses = T.load_depth != 0;
+  for (const WrDrawDesc& d0 : w.draws) if (d0.flags & (WR_DF_DEPTH_WRITE | WR_DF_CLEAR_DEPTH)) uses = true;
+  if (!uses) return;
+  const size_t need = (size_t)t.width * t.height * 4;
+  if (!dt->dptr || dt->dsize < need || dt->width != t.width || dt->height != t.height) {
+    // (depth attachments have the size of their colour target in every caller; anything else keeps the uniform value)
+    if (dt->width == t.width && dt->height == t.height) {
+      if (dt->dptr) pool_free(dt->dptr, dt->dsize);
+      size_t actual = 0;
+      dt->dptr = pool_alloc(need, &actual); dt->dsize = actual;
+    }
+  }
+  if (dt->dptr && dt->dsize >= need && dt->width == t.width && dt->height == t.height) {
+    T.depth = (uint32_t*)dt->dptr; T.store_depth = 1;
+    dt->depth_materialized = true;
+    L.any_depth = true;
+  }
+}
+
+// Target `oi` of the plan: its descriptor, its draws, its place in its level's launches.
+void plan_target(FlushPlan& P, int oi) {
+  Context* c = ctx;
+  TargetWork& w = c->work[P.sel[oi]];
+  Texture& t = c->textures[w.tex];
+  WrTargetDesc& T = P.targets[oi];
+  memset(&T, 0, sizeof(T));
+  if (P.levels.empty() || w.level != c->work[P.sel[oi - 1]].level) { P.levels.emplace_back(); P.levels.back().bin0 = P.n_bins; }
+  Level& L = P.levels.back();
+  P.target_level.push_back((int)P.levels.size() - 1);
+  T.color = t.dptr; T.width = t.width; T.height = t.height; T.stride = t.stride;
+  T.format = t.internal_format == GL_R8 ? WR_FMT_R8 : WR_FMT_RGBA8;
+  T.bins_x = (t.width + WR_BIN_W - 1) / WR_BIN_W; T.bins_y = (t.height + WR_BIN_H - 1) / WR_BIN_H;
+  // every target starts on a 64-prim boundary: a wave of the setup kernel then holds prims of one
+  // target and one mask word only (the slots in between are skipped as instance >= count)
+  P.n_prims = (P.n_prims + 63) & ~63;
+  T.first_bin = P.n_bins; T.first_prim = P.n_prims;
+  T.load_color = 1; T.init_color = 0; T.load_depth = 0; T.store_depth = 0;
+  Texture* dt = w.depth_tex ? c->textures.find(w.depth_tex) : nullptr;
+  T.init_depth = w.init_depth_set ? w.init_depth : (dt ? dt->depth_value : 0xFFFFFF);
+  if (dt && dt->depth_materialized && dt->dptr) { T.load_depth = 1; T.depth = (uint32_t*)dt->dptr; }
+  T.fwd_color = nullptr;
+  if (w.fwd_tex) {
+    Texture& ft = c->textures[w.fwd_tex];
+    c->stats.forwarded_targets++;
+    T.fwd_color = ft.dptr; T.fwd_stride = ft.stride; T.fwd_dx = w.fwd_dx; T.fwd_y0 = w.fwd_y0; T.fwd_ys = w.fwd_ys;
+    for (int k = 0; k < 4; k++) T.fwd_clip[k] = w.fwd_clip[k];
+  }
+  T.cells = c->cell_raster ? 1 : 0;
+  T.rows_mode = P.rows_of[P.sel[oi]];
+  T.y_begin = 0; T.y_end = t.height;
+  if (t.own_y1 > t.own_y0) {   // WrhipSetTargetRows: rows of this target owned by this process
+    T.y_begin = std::max(0, t.own_y0); T.y_end = std::min(t.height, t.own_y1);
+  } else if (c->shard_world > 1) {  // WrhipSetShard: contiguous strips of bin rows per rank
+    T.y_begin = (int)((int64_t)T.bins_y * c->shard_rank / c->shard_world) * WR_BIN_H;
+    T.y_end = std::min(t.height, (int)((int64_t)T.bins_y * (c->shard_rank + 1) / c->shard_world) * WR_BIN_H);
+  }
+  // (the target's instance bytes go from its snapshot straight into the staging ring when the arena is laid out: gathering
+  // them in one vector first was a second pass over 2.4 MB per cfg5 frame)
+  const size_t inst_base = (P.inst_bytes + 15) & ~size_t(15);
+  P.inst_bytes = inst_base + w.inst.size();
+  if (!w.inst.empty()) P.inst_segs.push_back(InstSeg{inst_base, w.inst.data(), w.inst.size()});
+  bool any_kept = false;
+  T.dw_first = 0; T.dw_end = 0;
+  for (const WrDrawDesc& d0 : w.draws) any_kept = plan_draw(P, oi, t, d0, inst_base, any_kept);
+  T.end_prim = P.n_prims;
+  {
+    // a general-quad draw with the depth test on may hold perspective prims: they flatten the depth rows they touch
+    bool persp_possible = false;
+    if (T.format == WR_FMT_RGBA8)
+      for (const WrDrawDesc& d0 : w.draws) if ((d0.flags & WR_DF_XFORM) && (d0.flags & WR_DF_DEPTH_TEST) && !(d0.flags & WR_DF_SIMPLE)) { persp_possible = true; break; }
+    P.flat_off.push_back(persp_possible ? P.flat_words : SIZE_MAX);
+    if (persp_possible) P.flat_words += (size_t)t.height + 1;
+  }
+  T.words_per_bin = (T.end_prim - T.first_prim + 63) / 64;
+  T.word_base = P.n_words;
+  if (T.rows_mode == 2) {
+    T.words_per_bin = 0;
+    if (L.trow_n == 0) L.trow_t0 = oi;
+    L.trow_n++; P.n_row_targets++;
+    L.trow_items += std::max(0, T.y_end - T.y_begin) * ((t.width + 255) >> 8);
+  } else if (T.rows_mode) {
+    // no bins, no mask words: the level's span-rows launch takes targets [row_t0, row_t0 + row_n)
+    T.words_per_bin = 0;
+    if (L.row_n == 0) { L.row_t0 = oi; L.row_fmt = T.format; }
+    L.row_n++; P.n_row_targets++;
+    L.row_items += std::max(0, T.y_end - T.y_begin) * WR_SPAN_PIECES(t.width);
+  } else {
+    P.n_words += T.words_per_bin * T.bins_x * T.bins_y;
+    P.n_bins += T.bins_x * T.bins_y;
+    (T.format == WR_FMT_RGBA8 ? L.bins_rgba : L.bins_r8) += T.bins_x * T.bins_y;
+  }
+  const uint64_t owned = (uint64_t)t.width * std::max(0, T.y_end - T.y_begin);
+  P.pixels += owned;
+  {
+    uint64_t tb = owned * t.bpp * (T.load_color ? 2 : 1);
+    // unique source texels sampled: bounded by what a 1:1 mapping can touch
+    uint64_t src = 0;
+    for (GLuint id : w.reads)
+      if (Texture* rt = c->textures.find(id))
+        if (rt->internal_format == GL_RGBA8 || rt->internal_format == GL_R8) src += (uint64_t)rt->stride * rt->height;
+    tb += std::min<uint64_t>(src, owned * t.bpp);
+    if (w.fwd_tex) tb += (uint64_t)std::max(0, w.fwd_clip[2] - w.fwd_clip[0]) * std::max(0, w.fwd_clip[3] - w.fwd_clip[1]) * 4;   // the write-through
+    P.algo_bytes += tb;
+    (T.rows_mode == 2 ? L.bytes_trows : T.rows_mode ? L.bytes_rows : (T.format == WR_FMT_RGBA8 ? L.bytes_rgba : L.bytes_r8)) += tb;
+  }
+  materialise_depth(w, t, dt, T, L);
+  if (T.load_depth) L.any_depth = true;
+}
+void plan_targets(FlushPlan& P) {
+  P.targets.resize(P.sel.size());
+  for (int oi = 0; oi < P.n_targets(); oi++) plan_target(P, oi);
+}
+
+// One buffer of a scratch set: replaced by one of `new_cap` elements (of `elem` bytes) if it holds fewer than `want`.  Its last readers
+// complete first -- sync_scratch(), once per group of buffers that share `synced`: Stats::scratch_grown_held counts those calls.
+template <class E> bool grow_scratch(E*& p, size_t& cap, size_t want, size_t new_cap, bool& synced, size_t elem = sizeof(E)) {
+  if (cap >= want) return false;
+  if (!synced) { sync_scratch(); synced = true; }
+  wrrt::dev_free(p);
+  cap = new_cap;
+  p = (E*)wrrt::dev_alloc(cap * elem);
+  return true;
+}
+// The flush's scratch set `S` grows to what the plan needs, and the target descriptors get its addresses.  Every buffer of the set is
+// sized here, before the flush picks a held-back launch to carry its setup stage and defers its upload scatter to it (flush_work).
+void size_scratch(FlushPlan& P, Context::Scratch& S) {
+  Context* c = ctx;
+  static const bool no_run_share = getenv("WRHIP_NO_RUN_SHARE") != nullptr;
+  static const bool no_flat = getenv("WRHIP_NO_FLAT") != nullptr;      // (debugging: leave flattened depth rows unmodelled)
+  const bool any_work = P.any_work();
   if (any_work) {
-    // the prim arrays of this flush's scratch set, sized here: the address of its glyph records goes into the target descriptors
-    Context::Scratch& S = c->scratch[c->flush_seq & 1];
-    if (S.prims_cap < (size_t)n_prims + 1) {
-      sync_scratch();
-      wrrt::dev_free(S.prims); wrrt::dev_free(S.recs); wrrt::dev_free(S.aux);
-      S.prims_cap = (size_t)(n_prims + 1) * 2;
-      S.prims = (WrPrim*)wrrt::dev_alloc(S.prims_cap * sizeof(WrPrim));
-      S.recs = (WrRec*)wrrt::dev_alloc(S.prims_cap * (sizeof(WrRec) + sizeof(WrGlyphRec)));      // recs[], then the glyph records (WrTargetDesc::grecs)
-      S.aux = (WrAux*)wrrt::dev_alloc(S.prims_cap * sizeof(WrAux));
-    }
-    if (S.bin_ctr_cap < (size_t)n_bins || !S.bin_ctr) {
-      sync_scratch();
-      wrrt::dev_free(S.bin_ctr);
-      S.bin_ctr_cap = (size_t)std::max(n_bins, 64) * 2;
-      S.bin_ctr = (unsigned*)wrrt::dev_alloc(S.bin_ctr_cap * sizeof(unsigned));
+    // the prim arrays share one capacity; recs[] is followed by the glyph records (WrTargetDesc::grecs)
+    bool prims_synced = false;
+    const size_t prims_want = (size_t)P.n_prims + 1;
+    size_t recs_cap = S.prims_cap, aux_cap = S.prims_cap;
+    grow_scratch(S.prims, S.prims_cap, prims_want, prims_want * 2, prims_synced);
+    grow_scratch(S.recs, recs_cap, prims_want, prims_want * 2, prims_synced, sizeof(WrRec) + sizeof(WrGlyphRec));
+    grow_scratch(S.aux, aux_cap, prims_want, prims_want * 2, prims_synced);
+    // (at least one counter, so that a set gets its array with its first flush, even one of row targets only)
+    bool ctr_synced = false;
+    if (grow_scratch(S.bin_ctr, S.bin_ctr_cap, (size_t)std::max(P.n_bins, 1), (size_t)std::max(P.n_bins, 64) * 2, ctr_synced))
       wrrt::memset8(S.bin_ctr, 0, S.bin_ctr_cap * sizeof(unsigned), c->stream);      // (the workgroups leave them at zero)
-    }
     // the flush's pool: the gradient-table copies (fixed head, <= 256 MB of promises), what the flush's WR_DF_XFORM draws could ask for in
     // row tables (<= 64 MB), and the depth runs' share (WRHIP_RUNS_POOL_WORDS, 64 MB by default)
-    const size_t qtab_want = gtab_words + std::min<size_t>(qtab_need, (size_t)16 << 20) + (runs_pool ? runs_pool_words : 0);
-    if (S.qtab_cap < qtab_want) {
-      sync_scratch();
-      wrrt::dev_free(S.qtab);
-      S.qtab_cap = qtab_want + qtab_want / 4;
-      S.qtab = (float*)wrrt::dev_alloc(S.qtab_cap * sizeof(float));
-    }
-    // ... and the vertex tables and coverage masks: the set's buffers are all sized before the flush picks a held-back launch to
-    // carry its setup stage and defers its upload scatter to it (fuse_at, below)
-    if (S.vtab_cap < vtab_cursor + 1 || S.masks_cap < (size_t)n_words + 1) {
-      sync_scratch();
-      if (S.vtab_cap < vtab_cursor + 1) {
-        wrrt::dev_free(S.vtab);
-        S.vtab_cap = (vtab_cursor + 1) * 2;
-        S.vtab = (float*)wrrt::dev_alloc(S.vtab_cap * sizeof(float));
-      }
-      if (S.masks_cap < (size_t)n_words + 1) {
-        wrrt::dev_free(S.masks);
-        S.masks_cap = (size_t)(n_words + 1) * 2;
-        S.masks = (unsigned long long*)wrrt::dev_alloc(S.masks_cap * 8);
-        wrrt::memset8(S.masks, 0, S.masks_cap * 8, c->stream);   // raster workgroups re-zero what they consume
-      }
-    }
-    for (WrTargetDesc& T : targets) {
+    const size_t qtab_want = P.gtab_words + std::min<size_t>(P.qtab_need, (size_t)16 << 20) + (P.runs_pool ? c->runs_pool_words : 0);
+    bool qtab_synced = false;
+    grow_scratch(S.qtab, S.qtab_cap, qtab_want, qtab_want + qtab_want / 4, qtab_synced);
+    // ... and the vertex tables and coverage masks, which wait together
+    bool tabs_synced = false;
+    grow_scratch(S.vtab, S.vtab_cap, P.vtab_words + 1, (P.vtab_words + 1) * 2, tabs_synced);
+    if (grow_scratch(S.masks, S.masks_cap, (size_t)P.n_words + 1, (size_t)(P.n_words + 1) * 2, tabs_synced))
+      wrrt::memset8(S.masks, 0, S.masks_cap * 8, c->stream);   // raster workgroups re-zero what they consume
+    for (WrTargetDesc& T : P.targets) {
       T.grecs = (const WrGlyphRec*)(S.recs + S.prims_cap); T.bin_ctr = S.bin_ctr + T.first_bin;
-      T.qtab = qtab_want ? S.qtab : nullptr; T.qtab_cap = (uint32_t)std::min<size_t>(S.qtab_cap, (size_t)1 << 30); T.qtab_ctl = nullptr; T.qtab_pad = (no_qtab ? 1u : 0u) | (no_run_share ? 2u : 0u);
+      T.qtab = qtab_want ? S.qtab : nullptr; T.qtab_cap = (uint32_t)std::min<size_t>(S.qtab_cap, (size_t)1 << 30); T.qtab_ctl = nullptr; T.qtab_pad = (c->quad_rowtabs ? 0u : 1u) | (no_run_share ? 2u : 0u);
     }
   }
   // Mask-row store.  When the bounds fit, no reservation of the setup stage can fail and the R8 launches take the light
   // variant (the rows kernel evaluates, the bins blend bytes); otherwise the store is capped, prims that do not fit keep their
   // in-raster evaluation and the launches the variant that has it.
-  bool mr_on = mr_slots > 0, mr_safe = false;
-  if (mr_on) {
-    Context::Scratch& S = c->scratch[c->flush_seq & 1];
+  P.mr_on = P.mr_slots > 0;
+  if (P.mr_on) {
     const uint64_t kCap = (uint64_t)1 << 30;
-    mr_safe = mr_slots <= WR_MR_MAX_SLOTS && mr_rows <= WR_MR_MAX_ROWS && mr_bytes <= kCap;
-    const size_t want_slots = (size_t)std::min<uint64_t>(mr_slots, WR_MR_MAX_SLOTS);
-    const size_t want_bytes = (size_t)std::min<uint64_t>(mr_bytes, mr_safe ? kCap : ((uint64_t)256 << 20));
-    if (S.mr_slots_cap < want_slots || S.mr_store_cap < want_bytes) {
-      sync_scratch();
-      if (S.mr_slots_cap < want_slots) {
-        wrrt::dev_free(S.mr_slots);
-        S.mr_slots_cap = std::min<size_t>(want_slots * 2, WR_MR_MAX_SLOTS);
-        S.mr_slots = (WrMaskSlot*)wrrt::dev_alloc(S.mr_slots_cap * sizeof(WrMaskSlot));
-      }
-      if (S.mr_store_cap < want_bytes) {
-        wrrt::dev_free(S.mr_store);
-        S.mr_store_cap = (want_bytes + 4095) & ~size_t(4095);
-        S.mr_store = (uint8_t*)wrrt::dev_alloc(S.mr_store_cap);
-      }
-    }
-    for (WrTargetDesc& T : targets) {
+    P.mr_safe = P.mr_slots <= WR_MR_MAX_SLOTS && P.mr_rows <= WR_MR_MAX_ROWS && P.mr_bytes <= kCap;
+    const size_t want_slots = (size_t)std::min<uint64_t>(P.mr_slots, WR_MR_MAX_SLOTS);
+    const size_t want_bytes = (size_t)std::min<uint64_t>(P.mr_bytes, P.mr_safe ? kCap : ((uint64_t)256 << 20));
+    bool synced = false;
+    grow_scratch(S.mr_slots, S.mr_slots_cap, want_slots, std::min<size_t>(want_slots * 2, WR_MR_MAX_SLOTS), synced);
+    grow_scratch(S.mr_store, S.mr_store_cap, want_bytes, (want_bytes + 4095) & ~size_t(4095), synced);
+    for (WrTargetDesc& T : P.targets) {
       if (T.format != WR_FMT_R8) continue;
-      T.mr_ctl = nullptr; T.mr_slots = S.mr_slots; T.mr_store = S.mr_store;       // (mr_ctl: 512 bytes of this flush's arena, below)
+      T.mr_ctl = nullptr; T.mr_slots = S.mr_slots; T.mr_store = S.mr_store;       // (mr_ctl: 512 bytes of this flush's arena, stage_arena)
       T.mr_cap16 = (uint32_t)std::min<uint64_t>(S.mr_store_cap >> 4, WR_MR_MAX_CAP16);
       T.mr_max_slots = (uint32_t)S.mr_slots_cap;
     }
   }
-  for (WrTargetDesc& T : targets) { T.flat_rows = nullptr; T.counters = c->dcounters; }
-  static const bool no_flat = getenv("WRHIP_NO_FLAT") != nullptr;      // (debugging: leave flattened depth rows unmodelled)
-  if (flat_words && any_work && !no_flat) {
-    Context::Scratch& S = c->scratch[c->flush_seq & 1];
-    if (S.flat_cap < flat_words) {
-      sync_scratch();
-      wrrt::dev_free(S.flat);
-      S.flat_cap = flat_words * 2;
-      S.flat = (uint32_t*)wrrt::dev_alloc(S.flat_cap * 4);
-    }
-    wrrt::memset8(S.flat, 0xFF, flat_words * 4, c->stream);          // (this set's previous user, two flushes back, has been launched)
-    for (int oi = 0; oi < n_targets; oi++) if (flat_off[oi] != SIZE_MAX) targets[oi].flat_rows = S.flat + flat_off[oi];
+  for (WrTargetDesc& T : P.targets) { T.flat_rows = nullptr; T.counters = c->dcounters; }
+  if (P.flat_words && any_work && !no_flat) {
+    bool synced = false;
+    grow_scratch(S.flat, S.flat_cap, P.flat_words, P.flat_words * 2, synced);
+    wrrt::memset8(S.flat, 0xFF, P.flat_words * 4, c->stream);          // (this set's previous user, two flushes back, has been launched)
+    for (int oi = 0; oi < P.n_targets(); oi++) if (P.flat_off[oi] != SIZE_MAX) P.targets[oi].flat_rows = S.flat + P.flat_off[oi];
   }
-  if (any_work) {
-    lap(0);      // planning: forwarding, levels, per-target descriptors
-    // ---- frame arena: [draws | targets | instance bytes] -> one H2D copy ----
-    size_t off_draws = 0;
-    size_t off_targets = (off_draws + sizeof(WrDrawDesc) * nd + 255) & ~size_t(255);
-    size_t off_inst = (off_targets + sizeof(WrTargetDesc) * n_targets + 255) & ~size_t(255);
-    // first draw of every 64-prim block (wr_vertex_prim starts its draw lookup there)
-    const int n_blocks = (n_prims + 63) / 64;
-    size_t off_blk = (off_inst + inst_bytes + 255) & ~size_t(255);
-    const size_t off_qctl = (off_blk + sizeof(WrBlock) * n_blocks + 63) & ~size_t(63);      // the row-table pool's allocation word: zero on arrival
-    // ... and the mask-row store's control block ([0] allocation word, [32..63] byte counters): part of the arena as well, so that it
-    // arrives zeroed with the arena's DMA instead of by a fill launch of its own per flush (4.7 us of stream time and a runtime call
-    // per frame of every workload with clip masks)
-    const size_t off_mrctl = off_qctl + 64;
-    size_t total = off_mrctl + 512 + 256;
-    size_t aoff = staging_alloc(total);
-    uint8_t* h = c->staging + aoff;
-    // (the last call that can close the open batch before this flush ships it: the mirror views are decided here)
-    for (GLuint id : c->view_texs) {
-      Texture* t = c->textures.find(id);
-      if (!t || !t->dptr || !c->upload_open || t->view_batch != c->upload_batch) continue;
-      const void* view = c->dupload + t->view_off;
-      for (WrDrawDesc& d : draws)
-        for (WrTexDesc& td : d.tex) if (td.ptr == t->dptr) td.ptr = view;
+}
+
+// ---- frame arena: [draws | targets | instance bytes | block table | control words] -> one H2D copy ----
+void stage_arena(FlushPlan& P, Context::Scratch& S) {
+  Context* c = ctx;
+  FlushPlan::Arena& A = P.arena;
+  const int nd = P.nd(), n_targets = P.n_targets();
+  A.off_draws = 0;
+  A.off_targets = (A.off_draws + sizeof(WrDrawDesc) * nd + 255) & ~size_t(255);
+  A.off_inst = (A.off_targets + sizeof(WrTargetDesc) * n_targets + 255) & ~size_t(255);
+  // first draw of every 64-prim block (wr_vertex_prim starts its draw lookup there)
+  const int n_blocks = (P.n_prims + 63) / 64;
+  A.off_blk = (A.off_inst + P.inst_bytes + 255) & ~size_t(255);
+  A.off_qctl = (A.off_blk + sizeof(WrBlock) * n_blocks + 63) & ~size_t(63);      // the row-table pool's allocation word: zero on arrival
+  // ... and the mask-row store's control block ([0] allocation word, [32..63] byte counters): part of the arena as well, so that it
+  // arrives zeroed with the arena's DMA instead of by a fill launch of its own per flush (4.7 us of stream time and a runtime call
+  // per frame of every workload with clip masks)
+  A.off_mrctl = A.off_qctl + 64;
+  A.total = A.off_mrctl + 512 + 256;
+  A.aoff = staging_alloc(A.total);
+  uint8_t* h = c->staging + A.aoff;
+  // (the last call that can close the open batch before this flush ships it: the mirror views are decided here)
+  for (GLuint id : c->view_texs) {
+    Texture* t = c->textures.find(id);
+    if (!t || !t->dptr || !c->upload_open || t->view_batch != c->upload_batch) continue;
+    const void* view = c->dupload + t->view_off;
+    for (WrDrawDesc& d : P.draws)
+      for (WrTexDesc& td : d.tex) if (td.ptr == t->dptr) td.ptr = view;
+  }
+  c->view_texs.clear();
+  memset(h + A.off_qctl, 0, 64 + 512);
+  if (P.mr_on) {
+    S.mr_ctl = (unsigned long long*)(c->dupload + A.aoff + A.off_mrctl); S.mr_seen = 0;
+    for (WrTargetDesc& T : P.targets) if (T.format == WR_FMT_R8 && T.mr_slots) T.mr_ctl = S.mr_ctl;
+  }
+  *(unsigned long long*)(h + A.off_qctl) = (unsigned long long)P.gtab_words;      // (WR_GTAB_WORDS is a multiple of 4: the pieces behind stay on 16 bytes)
+  for (WrTargetDesc& T : P.targets) T.qtab_ctl = T.qtab ? (unsigned long long*)(c->dupload + A.aoff + A.off_qctl) : nullptr;
+  c->last_qctl = nullptr;
+  for (const WrTargetDesc& T : P.targets) if (T.qtab) { c->last_qctl = T.qtab_ctl; c->last_qtab_cap = T.qtab_cap; c->last_qctl_v = c->ring_base + A.aoff + A.off_qctl; break; }
+  if (nd) stage_copy(h + A.off_draws, P.draws.data(), sizeof(WrDrawDesc) * nd);
+  stage_copy(h + A.off_targets, P.targets.data(), sizeof(WrTargetDesc) * n_targets);
+  uint8_t* hinst = h + A.off_inst;
+  if (P.inst_bytes >= PARALLEL_COPY_MIN && P.inst_segs.size() > 1) {
+    // many targets' worth of instances (cfg5: 72 snapshots of ~33 KB): the helpers take whole segments
+    copy_pool().run([&](int part, int parts) {
+      for (size_t i = (size_t)part; i < P.inst_segs.size(); i += (size_t)parts) stage_copy(hinst + P.inst_segs[i].base, P.inst_segs[i].src, P.inst_segs[i].size);
+    });
+  } else {
+    for (const InstSeg& sg : P.inst_segs) {
+      if (sg.size >= PARALLEL_COPY_MIN) big_memcpy(hinst + sg.base, sg.src, sg.size);
+      else stage_copy(hinst + sg.base, sg.src, sg.size);
     }
-    c->view_texs.clear();
-    memset(h + off_qctl, 0, 64 + 512);
-    if (mr_on) {
-      Context::Scratch& Sm = c->scratch[c->flush_seq & 1];
-      Sm.mr_ctl = (unsigned long long*)(c->dupload + aoff + off_mrctl); Sm.mr_seen = 0;
-      for (WrTargetDesc& T : targets) if (T.format == WR_FMT_R8 && T.mr_slots) T.mr_ctl = Sm.mr_ctl;
-    }
-    *(unsigned long long*)(h + off_qctl) = (unsigned long long)gtab_words;      // (WR_GTAB_WORDS is a multiple of 4: the pieces behind stay on 16 bytes)
-    for (WrTargetDesc& T : targets) T.qtab_ctl = T.qtab ? (unsigned long long*)(c->dupload + aoff + off_qctl) : nullptr;
-    c->last_qctl = nullptr;
-    for (const WrTargetDesc& T : targets) if (T.qtab) { c->last_qctl = T.qtab_ctl; c->last_qtab_cap = T.qtab_cap; c->last_qctl_v = c->ring_base + aoff + off_qctl; break; }
-    if (nd) stage_copy(h + off_draws, draws.data(), sizeof(WrDrawDesc) * nd);
-    stage_copy(h + off_targets, targets.data(), sizeof(WrTargetDesc) * n_targets);
-    if (inst_bytes >= PARALLEL_COPY_MIN && inst_segs.size() > 1) {
-      // many targets' worth of instances (cfg5: 72 snapshots of ~33 KB): the helpers take whole segments
-      copy_pool().run([&](int part, int parts) {
-        for (size_t i = (size_t)part; i < inst_segs.size(); i += (size_t)parts) stage_copy(h + off_inst + inst_segs[i].base, inst_segs[i].src, inst_segs[i].size);
-      });
-    } else {
-      for (const InstSeg& sg : inst_segs) {
-        if (sg.size >= PARALLEL_COPY_MIN) big_memcpy(h + off_inst + sg.base, sg.src, sg.size);
-        else stage_copy(h + off_inst + sg.base, sg.src, sg.size);
-      }
-    }
-    {
-      // (... and the draws and targets the block's wave stages in LDS: WrDescView)
-      WrBlock* blk = (WrBlock*)(h + off_blk);
-      int j = 0;
-      for (int b = 0; b < n_blocks; b++) {
-        while (j + 1 < nd && draws[j + 1].first_prim <= 64 * b) j++;
-        WrBlock B;
-        B.lo0 = j; B.nk = nd - j >= 2 ? 2 : nd - j;
-        B.t0 = B.nk > 0 ? draws[j].target : -1; B.t1 = B.nk > 1 ? draws[j + 1].target : -1;
-        blk[b] = B;
-      }
-    }
-    // the launch that will carry this flush's setup stage (if any): it also runs the batch's scatter, in its first workgroups
-    int fuse_at = -1;
-    if (n_prims > 0 && c->tail.pending && !c->setup_on_stream) {
-      // the launch that hides the setup stage best, among those pick_variant() lets carry it: the largest mask-rows launch if there
-      // is one, else the largest tile-rows launch (a wave per row piece of a few heavy prims, the long launch of such a flush -- behind
-      // the short rect pass of the same flush a setup stage would stick out), else the first
-      const bool have_mask_rows = c->scratch[c->tail.set].mr_ctl != nullptr;
-      int64_t best = 0;
-      for (size_t hi = 0; hi < c->tail.held.size(); hi++) {
-        const Context::Held& Hh = c->tail.held[hi];
-        const Variant V = pick_variant(Hh, c->sw, true, have_mask_rows);
-        const int size = V.mask_rows ? Hh.mr_rows : Hh.row_items;
-        const int64_t rank = !V.carries ? 0 : size > 0 ? ((int64_t)(V.mask_rows ? 2 : 1) << 32) + size : 1;
-        if (rank > best) { best = rank; fuse_at = (int)hi; }
-      }
-    }
-    lap(1);      // arena staged
-    flush_uploads(0, fuse_at >= 0);     // one DMA: queued texture uploads + this arena; then the scatter (its own launch, or the carrier's first workgroups)
-    uint8_t* darena = c->dupload + aoff;
-    c->stats.h2d_bytes += total;
-    algo_bytes += inst_bytes + sizeof(WrDrawDesc) * nd;
-    lap(2);      // DMA + scatter queued
-    // ---- scratch (two sets: the deferred tail of the previous flush still reads the other one; vtab / masks: sized above) ----
-    Context::Scratch& S = c->scratch[c->flush_seq & 1];
+  }
+  // (... and the draws and targets the block's wave stages in LDS: WrDescView)
+  WrBlock* blk = (WrBlock*)(h + A.off_blk);
+  int j = 0;
+  for (int b = 0; b < n_blocks; b++) {
+    while (j + 1 < nd && P.draws[j + 1].first_prim <= 64 * b) j++;
+    WrBlock B;
+    B.lo0 = j; B.nk = nd - j >= 2 ? 2 : nd - j;
+    B.t0 = B.nk > 0 ? P.draws[j].target : -1; B.t1 = B.nk > 1 ? P.draws[j + 1].target : -1;
+    blk[b] = B;
+  }
+}
+
+// The held-back launch that will carry this flush's setup stage (it also runs the batch's scatter, in its first workgroups), or -1.
+int pick_carrier(const FlushPlan& P) {
+  Context* c = ctx;
+  int fuse_at = -1;
+  if (!(P.n_prims > 0 && c->tail.pending && !c->setup_on_stream)) return fuse_at;
+  // the launch that hides the setup stage best, among those pick_variant() lets carry it: the largest mask-rows launch if there
+  // is one, else the largest tile-rows launch (a wave per row piece of a few heavy prims, the long launch of such a flush -- behind
+  // the short rect pass of the same flush a setup stage would stick out), else the first
+  const bool have_mask_rows = c->scratch[c->tail.set].mr_ctl != nullptr;
+  int64_t best = 0;
+  for (size_t hi = 0; hi < c->tail.held.size(); hi++) {
+    const Context::Held& Hh = c->tail.held[hi];
+    const Variant V = pick_variant(Hh, c->sw, true, have_mask_rows);
+    const int size = V.mask_rows ? Hh.mr_rows : Hh.row_items;
+    const int64_t rank = !V.carries ? 0 : size > 0 ? ((int64_t)(V.mask_rows ? 2 : 1) << 32) + size : 1;
+    if (rank > best) { best = rank; fuse_at = (int)hi; }
+  }
+  return fuse_at;
+}
+
+// The setup stage goes out -- on the setup stream, in front of the held-back launch `fuse_at`, or as a launch of its own -- and with
+// it whatever the previous flush held back.
+void issue_setup(const FlushPlan& P, Context::Scratch& S, int fuse_at) {
+  Context* c = ctx;
+  const FlushPlan::Arena& A = P.arena;
+  const int n_prims = P.n_prims;
 #ifdef WRHIP_HOSTSIM
-    wrrt::memset8(S.masks, 0, (size_t)n_words * 8, c->stream);
+  wrrt::memset8(S.masks, 0, (size_t)P.n_words * 8, c->stream);
 #endif
-    const WrDrawDesc* ddraws = (const WrDrawDesc*)(darena + off_draws);
-    const WrTargetDesc* dtargets = (const WrTargetDesc*)(darena + off_targets);
-    const uint8_t* dinst = darena + off_inst;
-    const int* dblk = (const int*)(darena + off_blk);
-    if (n_prims > 0) {
+  if (n_prims <= 0) {
+    drain_tail();
+    launch_pending_scatter();
+    return;
+  }
 #ifdef WRHIP_TIMING
-      static const int setup_mode = getenv("WRHIP_SETUP_MODE") ? atoi(getenv("WRHIP_SETUP_MODE")) : 0;
-      const int nd_arg = nd | (setup_mode << 24);
+  static const int setup_mode = getenv("WRHIP_SETUP_MODE") ? atoi(getenv("WRHIP_SETUP_MODE")) : 0;
+  const int nd_arg = P.nd() | (setup_mode << 24);
 #else
-      const int nd_arg = nd;
+  const int nd_arg = P.nd();
 #endif
-      const int n_setup_blocks = (n_prims + 255) / 256;
-      const uint64_t setup_bytes = inst_bytes + sizeof(WrDrawDesc) * nd + (uint64_t)n_prims * (sizeof(WrPrim) + sizeof(WrRec));
-      if (c->tail.pending && c->setup_on_stream) {
-        wrrt::event_record(&c->ev_up, c->stream);                 // (this flush's uploads and table resets are enqueued)
-        wrrt::stream_wait_event(c->setup_stream, &c->ev_up);
-        prof_begin(&c->setup_stream);
-        WR_LAUNCH(wr_setup_kernel, n_setup_blocks, 256, c->setup_stream, ddraws, nd_arg, dinst, S.prims, S.recs, S.aux, n_prims,
-                  dtargets, S.masks, S.vtab, c->dcounters, dblk);
-        prof_end(WR_KIND_SETUP, 0, 0, 0, setup_bytes, (uint64_t)n_setup_blocks, &c->setup_stream);
-        wrrt::event_record(&c->ev_setup, c->setup_stream);
-        c->stats.kernel_launches += 1;
-        drain_tail();                                            // the previous flush's raster launches, concurrently
-        wrrt::stream_wait_event(c->stream, &c->ev_setup);
-      } else {
-      if (fuse_at >= 0 && !(c->tail.pending && fuse_at < (int)c->tail.held.size())) {
-        // the carrier is gone (something drained the tail after fuse_at was chosen): the setup stage and the deferred scatter go
-        // out on their own, below -- a launch more, never a flush whose setup stage did not run
-        c->stats.carrier_lost++;
-        fuse_at = -1;
-      }
-      if (fuse_at >= 0) {
-        // the previous flush's held-back raster launches, in order; the first one the fused kernel has a
-        // variant for (normally the tile pass, the longest) carries this flush's setup stage along
-        Context::Tail& T = c->tail;
-        WrSetupArgs SA{ddraws, nd_arg, dinst, S.prims, S.recs, S.aux, n_prims, dtargets, S.masks, S.vtab, c->dcounters, dblk, nullptr, 0, 0, 0};
-        uint64_t carried = setup_bytes;
-        if (c->ps.valid) {
-          SA.up_segs = (const WrUploadSeg*)(c->dupload + c->ps.seg_off); SA.up_nseg = c->ps.nseg; SA.up_parts = c->ps.parts; SA.up_blocks = c->ps.nseg * c->ps.parts;
-          carried += c->ps.bytes;
-          c->ps.valid = false;
-        }
-        c->stats.setup_carried++;
-        launch_held(T.held, T.targets, T.n_targets, T.draws, c->scratch[T.set], fuse_at, &SA, n_setup_blocks, carried);
-        tail_launched();
-      } else {
-        launch_pending_scatter();      // (the setup stage reads the data textures it uploads)
-        prof_begin();
-        WR_LAUNCH(wr_setup_kernel, n_setup_blocks, 256, c->stream, ddraws, nd_arg, dinst, S.prims, S.recs, S.aux, n_prims,
-                  dtargets, S.masks, S.vtab, c->dcounters, dblk);
-        prof_end(WR_KIND_SETUP, 0, 0, 0, setup_bytes, (uint64_t)n_setup_blocks);
-        c->stats.kernel_launches += 1;
-        drain_tail();        // (held-back launches the fused kernel has no variant for)
-      }
-      }
-    } else {
-      drain_tail();
-    }
-    launch_pending_scatter();      // (nothing is pending here: a deferred scatter went out with its carrier or ahead of the setup stage)
-    lap(3);      // setup + held launches queued
-#ifdef WRHIP_HOSTSIM
-    if (getenv("WRHIP_DEBUG")) {
-      fprintf(stderr, "flush: targets %d draws %d prims %d bins %d words %d vtab %zu set %d carried %llu grown_held %llu\n", n_targets, nd, n_prims, n_bins,
-              n_words, vtab_cursor, (int)(c->flush_seq & 1), (unsigned long long)c->stats.setup_carried, (unsigned long long)c->stats.scratch_grown_held);
-      for (int i = 0; i < n_targets; i++)
-        fprintf(stderr, "  T%d %dx%d fmt %d load %d init %08x prims [%d,%d) wpb %d\n", i, targets[i].width, targets[i].height,
-                targets[i].format, targets[i].load_color, targets[i].init_color, targets[i].first_prim, targets[i].end_prim,
-                targets[i].words_per_bin);
-      for (int i = 0; i < nd && i < 6; i++)
-        fprintf(stderr, "  D%d sh %d tgt %d first %d n %d blend %d flags %x clip %d %d %d %d vp %g %g %g %g\n", i, draws[i].shader,
-                draws[i].target, draws[i].first_prim, draws[i].count, draws[i].blend, draws[i].flags, draws[i].clip[0],
-                draws[i].clip[1], draws[i].clip[2], draws[i].clip[3], draws[i].vp_origin[0], draws[i].vp_origin[1],
-                draws[i].vp_size[0], draws[i].vp_size[1]);
-      for (int i = 0; i < nd && i < 6; i++)
-        fprintf(stderr, "     inst off %llu stride %d attr_off %d %d %d %d %d %d bytes %d %d quad %g %g %g %g %g %g %g %g\n",
-                (unsigned long long)draws[i].inst_offset, draws[i].inst_stride, draws[i].attr_off[0], draws[i].attr_off[1],
-                draws[i].attr_off[2], draws[i].attr_off[3], draws[i].attr_off[4], draws[i].attr_off[5], draws[i].attr_bytes[0],
-                draws[i].attr_bytes[1], draws[i].quad[0], draws[i].quad[1], draws[i].quad[2], draws[i].quad[3], draws[i].quad[4],
-                draws[i].quad[5], draws[i].quad[6], draws[i].quad[7]);
-      for (int i = 0; i < nd && i < 6; i++) {
-        const float* f = (const float*)(dinst + draws[i].inst_offset);
-        fprintf(stderr, "     flush inst D%d: %g %g %g %g (inst bytes %zu)\n", i, f[0], f[1], f[2], f[3], inst_bytes);
-      }
-      for (int i = 0; i < n_prims && i < 6; i++) {
-        const WrPrim& P = S.prims[i];
-        fprintf(stderr, "  P%d kind %d rect %d %d %d %d z %u blend %d flags %x color %08x %08x\n", i, P.kind, P.x0, P.y0, P.x1, P.y1,
-                P.z, P.blend, P.flags, P.color[0], P.color[1]);
-      }
-    }
-#endif
-    // Four waves per 64x64 bin, each lane owning 4 x 4 pixels (R = 4; two waves x
-    // 32 pixels measured slower on MI355X, profiles/r01_*).  The kernel is
-    // specialised on the prim families present in the launch (FEAT) so that
-    // rect-only passes do not pay the registers of the texture paths.
-    for (int i = 0; i < nd; i++) {
-      if (targets[draws[i].target].rows_mode) continue;          // (span-rows targets are in no bin launch)
-      const bool to_r8 = targets[draws[i].target].format == WR_FMT_R8;
-      Level& L = levels[target_level[draws[i].target]];
-      int f = 0;
-      if (!(draws[i].flags & WR_DF_SIMPLE)) {
-        switch (draws[i].shader) {
-          case WR_SH_PS_CLEAR: case WR_SH_CLEAR_OP: break;
-          case WR_SH_PS_TEXT_RUN: case WR_SH_PS_TEXT_RUN_DUAL: case WR_SH_PS_TEXT_RUN_GT: case WR_SH_PS_TEXT_RUN_DUAL_GT: f = WR_FEAT_R8TEX | WR_FEAT_TEX | WR_FEAT_GENERIC; break;
-          case WR_SH_BRUSH_SOLID: case WR_SH_BRUSH_SOLID_ALPHA: f = WR_FEAT_R8TEX | WR_FEAT_GENERIC; break;   // masked / odd blend
-          case WR_SH_CS_BLUR_ALPHA: case WR_SH_CS_BLUR_COLOR: f = WR_FEAT_BLUR; break;
-          case WR_SH_CS_CLIP_RECT: case WR_SH_CS_CLIP_RECT_FAST: case WR_SH_CS_CLIP_BOX_SHADOW:
-            f = ((draws[i].flags & WR_DF_MASK_ROWS) && mr_safe) ? WR_FEAT_BLUR : WR_FEAT_CLIP; break;
-          case WR_SH_BRUSH_LINEAR_GRADIENT: case WR_SH_BRUSH_LINEAR_GRADIENT_ALPHA: case WR_SH_CS_LINEAR_GRADIENT: case WR_SH_CS_RADIAL_GRADIENT: case WR_SH_CS_CONIC_GRADIENT: f = WR_FEAT_SHADE | WR_FEAT_GENERIC; break;
-          case WR_SH_BRUSH_BLEND: case WR_SH_BRUSH_BLEND_ALPHA: f = WR_FEAT_SHADE | WR_FEAT_GENERIC; break;
-          case WR_SH_BRUSH_MIX_BLEND: case WR_SH_BRUSH_MIX_BLEND_ALPHA: f = WR_FEAT_SHADE | WR_FEAT_GENERIC; break;
-          case WR_SH_CS_SVG_FILTER: case WR_SH_CS_SVG_FILTER_NODE: f = WR_FEAT_SHADE | WR_FEAT_GENERIC; break;
-          case WR_SH_BRUSH_YUV: case WR_SH_BRUSH_YUV_ALPHA: case WR_SH_COMPOSITE_YUV: f = WR_FEAT_SHADE | WR_FEAT_GENERIC; break;
-          case WR_SH_PS_QUAD_MASK: case WR_SH_PS_QUAD_MASK_FAST: case WR_SH_PS_QUAD_RADIAL_GRADIENT: case WR_SH_PS_QUAD_CONIC_GRADIENT:
-            f = WR_FEAT_SHADE | WR_FEAT_GENERIC; break;
-          case WR_SH_CS_BORDER_SOLID: case WR_SH_CS_BORDER_SEGMENT: case WR_SH_CS_FAST_LINEAR_GRADIENT: case WR_SH_CS_LINE_DECORATION:
-            f = WR_FEAT_SHADE | WR_FEAT_GENERIC; break;
-          case WR_SH_BRUSH_IMAGE_REPEAT: case WR_SH_BRUSH_IMAGE_REPEAT_ALPHA: case WR_SH_BRUSH_IMAGE_REPEAT_DUAL: f = WR_FEAT_SHADE | WR_FEAT_GENERIC; break;
-          default: f = WR_FEAT_TEX | WR_FEAT_GENERIC; break;
-        }
-      }
-      if (draws[i].flags & WR_DF_QUADS) f |= WR_FEAT_SHADE | WR_FEAT_GENERIC;
-      (to_r8 ? L.feat_r8 : L.feat_rgba) |= f;
-      if (!to_r8 && !(draws[i].flags & WR_DF_SIMPLE) && (draws[i].shader == WR_SH_PS_TEXT_RUN || draws[i].shader == WR_SH_PS_TEXT_RUN_DUAL || draws[i].shader == WR_SH_PS_TEXT_RUN_GT || draws[i].shader == WR_SH_PS_TEXT_RUN_DUAL_GT)) L.text = true;
-    }
-    // one raster launch per dependency level and target format, in level order on the one stream: the
-    // smallest instantiated superset of each level's feature set.  They are held back (Context::Tail)
-    // unless the flush is being profiled or deferral is off.
-    std::vector<Context::Held> launches;
-    for (const Level& L : levels) {
-      if (L.bins_rgba > 0) {
-        const int f = round_feat(WR_FMT_RGBA8, L.feat_rgba);
-        launches.push_back(Context::Held{WR_FMT_RGBA8, L.any_depth ? 1 : 0, f, L.bins_rgba, L.bin0, L.bytes_rgba, 0, (L.text && c->dense_text && f == WR_FS_TEXT) ? 1 : 0});
-      }
-      if (L.bins_r8 > 0) {
-        const int f = round_feat(WR_FMT_R8, L.feat_r8);
-        launches.push_back(Context::Held{WR_FMT_R8, 0, f, L.bins_r8, L.bin0 + L.bins_rgba, L.bytes_r8, (int)std::min<uint64_t>(L.mr_rows, WR_MR_MAX_ROWS)});
-      }
-      if (L.row_n > 0) {
-        Context::Held H{L.row_fmt, 0, 0, 0, 0, L.bytes_rows};
-        H.row_t0 = L.row_t0; H.row_n = L.row_n; H.row_items = L.row_items; H.row_mode = 1;
-        launches.push_back(H);
-      }
-      if (L.trow_n > 0) {
-        Context::Held H{WR_FMT_RGBA8, 0, 0, 0, 0, L.bytes_trows};
-        H.row_t0 = L.trow_t0; H.row_n = L.trow_n; H.row_items = L.trow_items; H.row_mode = 2;
-        launches.push_back(H);
-      }
-    }
-    if (c->defer_tail && (!c->profiling || c->profiling_deferred) && !launches.empty()) {
-      Context::Tail& T = c->tail;      // (the previous tail went out with this flush's setup launch)
-      T.pending = true; T.held = launches; T.n_targets = n_targets;
-      T.targets = dtargets; T.draws = ddraws; T.set = (int)(c->flush_seq & 1);
-      for (int oi = 0; oi < n_targets; oi++) {
-        const TargetWork& w = c->work[sel[oi]];
-        T.refs.push_back(w.tex);
-        if (w.fwd_tex) T.refs.push_back(w.fwd_tex);
-        for (GLuint id : w.rreads) T.refs.push_back(id);
-      }
-      for (GLuint id : T.refs) if (Texture* t = c->textures.find(id)) t->tail_ref = true;
-    } else {
-      launch_held(launches, dtargets, n_targets, ddraws, S);
-    }
-    {
-      // (for WrhipFlushHeld: which flushes wrote the window -- as a target, or as the destination of forwarded tile stores)
-      const GLuint fbt = c->framebuffers.find(0) ? c->framebuffers[0].color_attachment : 0;
-      bool wrote = false;
-      for (int wi : sel_in) { const TargetWork& w = c->work[wi]; if (fbt && (w.tex == fbt || w.fwd_tex == fbt)) wrote = true; }
-      if (wrote) c->fb_writes_since_held++;
-      c->last_flush_wrote_fb = wrote;
-    }
-    ring_record_fence();
-    c->flush_seq++;
-    c->stats.flushes++;
-    c->stats.prims += n_prims;
-    c->stats.raster_pixels += pixels;
-    c->stats.raster_algo_bytes += algo_bytes;
+  const int n_setup_blocks = (n_prims + 255) / 256;
+  const uint64_t setup_bytes = P.inst_bytes + sizeof(WrDrawDesc) * P.nd() + (uint64_t)n_prims * (sizeof(WrPrim) + sizeof(WrRec));
+  if (fuse_at >= 0 && !(c->tail.pending && fuse_at < (int)c->tail.held.size())) {
+    // the carrier is gone (something drained the tail after fuse_at was chosen): the setup stage and the deferred scatter go
+    // out on their own, below -- a launch more, never a flush whose setup stage did not run
+    c->stats.carrier_lost++;
+    fuse_at = -1;
   }
-  lap(4);        // this flush's own launches
-  // ---- drop the flushed work, keep the rest, rebuild hazard flags ----------
+  if (c->tail.pending && c->setup_on_stream) {
+    wrrt::event_record(&c->ev_up, c->stream);                 // (this flush's uploads and table resets are enqueued)
+    wrrt::stream_wait_event(c->setup_stream, &c->ev_up);
+    prof_begin(&c->setup_stream);
+    WR_LAUNCH(wr_setup_kernel, n_setup_blocks, 256, c->setup_stream, A.ddraws(), nd_arg, A.dinst(), S.prims, S.recs, S.aux, n_prims,
+              A.dtargets(), S.masks, S.vtab, c->dcounters, A.dblk());
+    prof_end(WR_KIND_SETUP, 0, 0, 0, setup_bytes, (uint64_t)n_setup_blocks, &c->setup_stream);
+    wrrt::event_record(&c->ev_setup, c->setup_stream);
+    c->stats.kernel_launches += 1;
+    drain_tail();                                            // the previous flush's raster launches, concurrently
+    wrrt::stream_wait_event(c->stream, &c->ev_setup);
+  } else if (fuse_at >= 0) {
+    // the previous flush's held-back raster launches, in order; the one pick_carrier() chose (normally the tile pass, the
+    // longest) carries this flush's setup stage along
+    Context::Tail& T = c->tail;
+    WrSetupArgs SA{A.ddraws(), nd_arg, A.dinst(), S.prims, S.recs, S.aux, n_prims, A.dtargets(), S.masks, S.vtab, c->dcounters, A.dblk(), nullptr, 0, 0, 0};
+    uint64_t carried = setup_bytes;
+    if (c->ps.valid) {
+      SA.up_segs = (const WrUploadSeg*)(c->dupload + c->ps.seg_off); SA.up_nseg = c->ps.nseg; SA.up_parts = c->ps.parts; SA.up_blocks = c->ps.nseg * c->ps.parts;
+      carried += c->ps.bytes;
+      c->ps.valid = false;
+    }
+    c->stats.setup_carried++;
+    launch_held(T.held, T.targets, T.n_targets, T.draws, c->scratch[T.set], fuse_at, &SA, n_setup_blocks, carried);
+    tail_launched();
+  } else {
+    launch_pending_scatter();      // (the setup stage reads the data textures it uploads)
+    prof_begin();
+    WR_LAUNCH(wr_setup_kernel, n_setup_blocks, 256, c->stream, A.ddraws(), nd_arg, A.dinst(), S.prims, S.recs, S.aux, n_prims,
+              A.dtargets(), S.masks, S.vtab, c->dcounters, A.dblk());
+    prof_end(WR_KIND_SETUP, 0, 0, 0, setup_bytes, (uint64_t)n_setup_blocks);
+    c->stats.kernel_launches += 1;
+    drain_tail();        // (held-back launches the fused kernel has no variant for)
+  }
+  launch_pending_scatter();      // (nothing is pending here: a deferred scatter went out with its carrier or ahead of the setup stage)
+}
+
+#ifdef WRHIP_HOSTSIM
+// WRHIP_DEBUG=1: the plan, and the first prims the setup stage made of it
+void dump_flush(const FlushPlan& P, const Context::Scratch& S) {
+  Context* c = ctx;
+  if (!getenv("WRHIP_DEBUG")) return;
+  const std::vector<WrTargetDesc>& targets = P.targets;
+  const std::vector<WrDrawDesc>& draws = P.draws;
+  const int nd = P.nd();
+  fprintf(stderr, "flush: targets %d draws %d prims %d bins %d words %d vtab %zu set %d carried %llu grown_held %llu\n", P.n_targets(), nd, P.n_prims, P.n_bins,
+          P.n_words, P.vtab_words, (int)(c->flush_seq & 1), (unsigned long long)c->stats.setup_carried, (unsigned long long)c->stats.scratch_grown_held);
+  for (int i = 0; i < P.n_targets(); i++)
+    fprintf(stderr, "  T%d %dx%d fmt %d load %d init %08x prims [%d,%d) wpb %d\n", i, targets[i].width, targets[i].height,
+            targets[i].format, targets[i].load_color, targets[i].init_color, targets[i].first_prim, targets[i].end_prim,
+            targets[i].words_per_bin);
+  for (int i = 0; i < nd && i < 6; i++)
+    fprintf(stderr, "  D%d sh %d tgt %d first %d n %d blend %d flags %x clip %d %d %d %d vp %g %g %g %g\n", i, draws[i].shader,
+            draws[i].target, draws[i].first_prim, draws[i].count, draws[i].blend, draws[i].flags, draws[i].clip[0],
+            draws[i].clip[1], draws[i].clip[2], draws[i].clip[3], draws[i].vp_origin[0], draws[i].vp_origin[1],
+            draws[i].vp_size[0], draws[i].vp_size[1]);
+  for (int i = 0; i < nd && i < 6; i++)
+    fprintf(stderr, "     inst off %llu stride %d attr_off %d %d %d %d %d %d bytes %d %d quad %g %g %g %g %g %g %g %g\n",
+            (unsigned long long)draws[i].inst_offset, draws[i].inst_stride, draws[i].attr_off[0], draws[i].attr_off[1],
+            draws[i].attr_off[2], draws[i].attr_off[3], draws[i].attr_off[4], draws[i].attr_off[5], draws[i].attr_bytes[0],
+            draws[i].attr_bytes[1], draws[i].quad[0], draws[i].quad[1], draws[i].quad[2], draws[i].quad[3], draws[i].quad[4],
+            draws[i].quad[5], draws[i].quad[6], draws[i].quad[7]);
+  for (int i = 0; i < nd && i < 6; i++) {
+    const float* f = (const float*)(P.arena.dinst() + draws[i].inst_offset);
+    fprintf(stderr, "     flush inst D%d: %g %g %g %g (inst bytes %zu)\n", i, f[0], f[1], f[2], f[3], P.inst_bytes);
+  }
+  for (int i = 0; i < P.n_prims && i < 6; i++) {
+    const WrPrim& Pr = S.prims[i];
+    fprintf(stderr, "  P%d kind %d rect %d %d %d %d z %u blend %d flags %x color %08x %08x\n", i, Pr.kind, Pr.x0, Pr.y0, Pr.x1, Pr.y1,
+            Pr.z, Pr.blend, Pr.flags, Pr.color[0], Pr.color[1]);
+  }
+}
+#endif
+
+// One raster launch per dependency level and target format, in level order on the one stream.  Four waves per 64x64 bin, each lane
+// owning 4 x 4 pixels (R = 4; two waves x 32 pixels measured slower on MI355X, profiles/r01_*).  The kernel is specialised on the prim
+// families present in the launch (FEAT) so that rect-only passes do not pay the registers of the texture paths: each level's feature
+// set is rounded up to the smallest instantiated superset.
+std::vector<Context::Held> build_launches(FlushPlan& P) {
+  Context* c = ctx;
+  for (const WrDrawDesc& d : P.draws) {
+    const WrTargetDesc& T = P.targets[d.target];
+    if (T.rows_mode) continue;          // (span-rows targets are in no bin launch)
+    const bool to_r8 = T.format == WR_FMT_R8;
+    Level& L = P.levels[P.target_level[d.target]];
+    int f = 0;
+    if (!(d.flags & WR_DF_SIMPLE)) {
+      f = shader_feat(d.shader);
+      if (is_clip_mask(d.shader) && (d.flags & WR_DF_MASK_ROWS) && P.mr_safe) f = WR_FEAT_BLUR;      // (the rows kernel evaluates it)
+      if (!to_r8 && is_text_run(d.shader)) L.text = true;
+    }
+    if (d.flags & WR_DF_QUADS) f |= WR_FEAT_SHADE | WR_FEAT_GENERIC;
+    (to_r8 ? L.feat_r8 : L.feat_rgba) |= f;
+  }
+  std::vector<Context::Held> launches;
+  for (const Level& L : P.levels) {
+    if (L.bins_rgba > 0) {
+      const int f = round_feat(WR_FMT_RGBA8, L.feat_rgba);
+      launches.push_back(Context::Held{WR_FMT_RGBA8, L.any_depth ? 1 : 0, f, L.bins_rgba, L.bin0, L.bytes_rgba, 0, (L.text && c->dense_text && f == WR_FS_TEXT) ? 1 : 0});
+    }
+    if (L.bins_r8 > 0) {
+      const int f = round_feat(WR_FMT_R8, L.feat_r8);
+      launches.push_back(Context::Held{WR_FMT_R8, 0, f, L.bins_r8, L.bin0 + L.bins_rgba, L.bytes_r8, (int)std::min<uint64_t>(L.mr_rows, WR_MR_MAX_ROWS)});
+    }
+    if (L.row_n > 0) {
+      Context::Held H{L.row_fmt, 0, 0, 0, 0, L.bytes_rows};
+      H.row_t0 = L.row_t0; H.row_n = L.row_n; H.row_items = L.row_items; H.row_mode = 1;
+      launches.push_back(H);
+    }
+    if (L.trow_n > 0) {
+      Context::Held H{WR_FMT_RGBA8, 0, 0, 0, 0, L.bytes_trows};
+      H.row_t0 = L.trow_t0; H.row_n = L.trow_n; H.row_items = L.trow_items; H.row_mode = 2;
+      launches.push_back(H);
+    }
+  }
+  return launches;
+}
+
+// The flush's own launches are held back (Context::Tail) unless the flush is being profiled or deferral is off; then the flush is
+// on the books.
+void hold_or_launch(const FlushPlan& P, Context::Scratch& S, const std::vector<Context::Held>& launches, const std::vector<int>& sel_in) {
+  Context* c = ctx;
+  if (c->defer_tail && (!c->profiling || c->profiling_deferred) && !launches.empty()) {
+    Context::Tail& T = c->tail;      // (the previous tail went out with this flush's setup launch)
+    T.pending = true; T.held = launches; T.n_targets = P.n_targets();
+    T.targets = P.arena.dtargets(); T.draws = P.arena.ddraws(); T.set = (int)(c->flush_seq & 1);
+    for (int wi : P.sel) {
+      const TargetWork& w = c->work[wi];
+      T.refs.push_back(w.tex);
+      if (w.fwd_tex) T.refs.push_back(w.fwd_tex);
+      for (GLuint id : w.rreads) T.refs.push_back(id);
+    }
+    for (GLuint id : T.refs) if (Texture* t = c->textures.find(id)) t->tail_ref = true;
+  } else {
+    launch_held(launches, P.arena.dtargets(), P.n_targets(), P.arena.ddraws(), S);
+  }
+  {
+    // (for WrhipFlushHeld: which flushes wrote the window -- as a target, or as the destination of forwarded tile stores)
+    const GLuint fbt = c->framebuffers.find(0) ? c->framebuffers[0].color_attachment : 0;
+    bool wrote = false;
+    for (int wi : sel_in) { const TargetWork& w = c->work[wi]; if (fbt && (w.tex == fbt || w.fwd_tex == fbt)) wrote = true; }
+    if (wrote) c->fb_writes_since_held++;
+    c->last_flush_wrote_fb = wrote;
+  }
+  ring_record_fence();
+  c->flush_seq++;
+  c->stats.flushes++;
+  c->stats.prims += P.n_prims;
+  c->stats.raster_pixels += P.pixels;
+  c->stats.raster_algo_bytes += P.algo_bytes;
+}
+
+// ---- drop the flushed work, keep the rest, rebuild hazard flags ----------
+void retire_work(const FlushPlan& P) {
+  Context* c = ctx;
   std::vector<char> gone(c->work.size(), 0);
-  for (int i : sel) gone[i] = 1;
-  for (int i : forwarded_sel) gone[i] = 1;
+  for (int i : P.sel) gone[i] = 1;
+  for (int i : P.forwarded_sel) gone[i] = 1;
   std::vector<TargetWork> rest;
   for (size_t i = 0; i < c->work.size(); i++) {
     if (!gone[i]) rest.push_back(std::move(c->work[i]));
@@ -2449,6 +2485,51 @@ void flush_work(const std::vector<int>& sel_in) {
     mark_ref(c->work[i].tex, c->textures[c->work[i].tex], true, (int)i);
     for (GLuint id : c->work[i].reads) if (Texture* t = c->textures.find(id)) mark_ref(id, *t, false);
   }
+}
+
+// The recorded work of the targets `sel_in` goes to the GPU.  The phases, and what their order has to keep:
+//  - All scratch growth happens in size_scratch() -- the mask-row store and the flat tables included --, so every sync_scratch()
+//    runs before pick_carrier() and before flush_uploads(): a sync that drained the tail would take the carrier with it.
+//    issue_setup() still re-checks the carrier (Stats::carrier_lost) as the backstop.
+//  - stage_arena()'s staging_alloc() is the last call that can close the open upload batch; the mirror views of Context::view_texs
+//    are substituted directly behind it, before the draws are staged.
+//  - size_scratch()'s fills (the flat tables' 0xFF, the zeroes of new bin_ctr and masks arrays) go on the stream before anything of
+//    this flush is launched.
+//  - Planning keeps its side effects: Context::gtab_pending, Stats::forwarded_targets, the pool_alloc / pool_free of materialised depth.
+//  - last_qctl, last_qtab_cap and last_qctl_v are set by stage_arena(), so only by a flush that has work.
+//  - Of the phases only issue_setup() calls tail_launched() / drain_tail(); it ends with launch_pending_scatter().
+//  - The getenv latches of the phases (and `laps` here) are function-local statics: read once per process.
+void flush_work(const std::vector<int>& sel_in) {
+  Context* c = ctx;
+  if (!c || c->work.empty() || sel_in.empty()) return;
+  HostTimer ht(&c->stats.host_flush_ns);
+  static const bool laps = getenv("WRHIP_DEBUG_LAPS") != nullptr;
+  auto lap_t = std::chrono::steady_clock::now();
+  auto lap = [&](int i) { if (laps) { const auto n = std::chrono::steady_clock::now(); c->lap_ns[i] += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(n - lap_t).count(); lap_t = n; } };
+  if (laps) c->lap_n++;
+  FlushPlan P;
+  Context::Scratch& S = c->scratch[c->flush_seq & 1];      // (two sets: the deferred tail of the previous flush still reads the other one)
+  select_targets(P, sel_in);
+  plan_targets(P);
+  size_scratch(P, S);
+  if (P.any_work()) {
+    lap(0);      // planning: forwarding, levels, per-target descriptors
+    stage_arena(P, S);
+    const int fuse_at = pick_carrier(P);
+    lap(1);      // arena staged
+    flush_uploads(0, fuse_at >= 0);     // one DMA: queued texture uploads + this arena; then the scatter (its own launch, or the carrier's first workgroups)
+    c->stats.h2d_bytes += P.arena.total;
+    P.algo_bytes += P.inst_bytes + sizeof(WrDrawDesc) * P.nd();
+    lap(2);      // DMA + scatter queued
+    issue_setup(P, S, fuse_at);
+    lap(3);      // setup + held launches queued
+#ifdef WRHIP_HOSTSIM
+    dump_flush(P, S);
+#endif
+    hold_or_launch(P, S, build_launches(P), sel_in);
+  }
+  lap(4);        // this flush's own launches
+  retire_work(P);
   lap(5);        // bookkeeping
   if (laps && (c->lap_n % 1000) == 0) {
     fprintf(stderr, "libwrhip flush laps (us per flush, %llu flushes): plan %.2f arena %.2f uploads %.2f setup+held %.2f own launches %.2f bookkeeping %.2f\n",
@@ -3323,9 +3404,7 @@ void DrawElementsInstanced(GLenum mode, GLsizei count, GLenum type, GLintptr off
       c->work[wi].level = std::max(c->work[wi].level, c->work[t->pending_target].level + 1);
   }
   Texture& colortex = c->textures[color_id];
-  const bool grad_prog = info->kind == WR_SH_BRUSH_LINEAR_GRADIENT || info->kind == WR_SH_BRUSH_LINEAR_GRADIENT_ALPHA || info->kind == WR_SH_PS_QUAD_RADIAL_GRADIENT ||
-                         info->kind == WR_SH_PS_QUAD_CONIC_GRADIENT || info->kind == WR_SH_CS_LINEAR_GRADIENT || info->kind == WR_SH_CS_RADIAL_GRADIENT ||
-                         info->kind == WR_SH_CS_CONIC_GRADIENT;
+  const bool grad_prog = is_gradient_prog(info->kind);
   // a table copy per instance (WR_GTAB_WORDS words): promised here, where the raster stage's reads are booked, for draws of up to 256
   // gradients while the promises of the pending flush stay under 256 MB
   const bool gtab = grad_prog && c->grad_tables && instancecount <= 256 && c->gtab_pending + (size_t)instancecount * WR_GTAB_WORDS <= ((size_t)64 << 20);
@@ -3402,7 +3481,7 @@ void DrawElementsInstanced(GLenum mode, GLsizei count, GLenum type, GLintptr off
       Texture* ht = tid ? c->textures.find(tid) : nullptr;
       return !ht || !(headers ? ht->complex_ids_headers : ht->complex_ids_gpubuf);
     };
-    if (info->kind == WR_SH_BRUSH_SOLID || info->kind == WR_SH_BRUSH_SOLID_ALPHA)
+    if (is_brush_solid(info->kind))
       simple = plain_blend && !maskable && ids_clean(WR_S_PRIM_HEADERS_I, true);
     else if (info->kind == WR_SH_PS_QUAD_TEXTURED)
       simple = plain_blend && d.tex[WR_S_COLOR0].width < 2 && ids_clean(WR_S_GPU_BUFFER_I, false);
@@ -3417,8 +3496,7 @@ void DrawElementsInstanced(GLenum mode, GLsizei count, GLenum type, GLintptr off
     {
       // can a prim of this draw sit under a rotation or a projective transform?  (brushes / text: transform ids in the prim
       // headers; quads: in the GPU buffer)
-      const bool quad_prog = info->kind == WR_SH_PS_QUAD_TEXTURED || info->kind == WR_SH_PS_QUAD_MASK || info->kind == WR_SH_PS_QUAD_MASK_FAST ||
-                             info->kind == WR_SH_PS_QUAD_RADIAL_GRADIENT || info->kind == WR_SH_PS_QUAD_CONIC_GRADIENT;
+      const bool quad_prog = is_quad_prog(info->kind);
       if (!ids_clean(quad_prog ? WR_S_GPU_BUFFER_I : WR_S_PRIM_HEADERS_I, !quad_prog)) d.flags |= WR_DF_XFORM;
       if (info->kind == WR_SH_PS_SPLIT_COMPOSITE) d.flags |= WR_DF_XFORM;      // (its vertices are any convex quad, whatever the transform)
     }
@@ -3433,11 +3511,11 @@ void DrawElementsInstanced(GLenum mode, GLsizei count, GLenum type, GLintptr off
                      info->kind == WR_SH_BRUSH_YUV || info->kind == WR_SH_BRUSH_YUV_ALPHA;
     // (glyph quads under a rotation -- local raster space -- ride on the same path; the program never asks for swgl_antiAlias,
     // and a glyph instance's third word is not a brush's flags: the transform ids alone decide)
-    const bool text = info->kind == WR_SH_PS_TEXT_RUN || info->kind == WR_SH_PS_TEXT_RUN_DUAL || info->kind == WR_SH_PS_TEXT_RUN_GT || info->kind == WR_SH_PS_TEXT_RUN_DUAL_GT;
+    const bool text = is_text_run(info->kind);
     const bool texquad = (info->kind == WR_SH_PS_QUAD_TEXTURED && d.tex[WR_S_COLOR0].width >= 2) ||
                          info->kind == WR_SH_PS_QUAD_MASK || info->kind == WR_SH_PS_QUAD_MASK_FAST ||
                          info->kind == WR_SH_PS_QUAD_RADIAL_GRADIENT || info->kind == WR_SH_PS_QUAD_CONIC_GRADIENT;
-    const bool solid_masked = (info->kind == WR_SH_BRUSH_SOLID || info->kind == WR_SH_BRUSH_SOLID_ALPHA) && maskable;
+    const bool solid_masked = is_brush_solid(info->kind) && maskable;
     if (colortex.internal_format == GL_RGBA8 && (img || texquad || solid_masked || text)) {
       bool quads = !ids_clean(texquad ? WR_S_GPU_BUFFER_I : WR_S_PRIM_HEADERS_I, !texquad);
       if (!quads && !text && d.blend != WR_BLEND_NONE && d.attr_off[0] >= 0 && d.attr_bytes[0] >= 12 && inst_stride >= 12) {
