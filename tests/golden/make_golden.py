@@ -36,6 +36,9 @@ def round3_digests():
     from parity_cases import GLYPH_TRANSFORM
     for name, make in GLYPH_TRANSFORM[:3]:      # ps_text_run GLYPH_TRANSFORM (hold with the same PIL glyph bitmaps only: golden_applies)
         out[name] = digest(render_direct(LIB, make())[0])
+    from parity_cases import AA_SCAN, aa_scan_frame
+    for name, enc, n, flagged, _plain in AA_SCAN:      # one AA request at the boundaries of the recording's scan
+        out[name] = digest(render_direct(LIB, aa_scan_frame(enc, n, flagged))[0])
     for name, make in ROTATED:
         if (name.startswith("near_clipped") or name in ("perspective_filters_exact", "perspective_opacity", "perspective_gradients", "perspective_quad_gradients", "perspective_images_repeat", "perspective_quad_masks", "rotated_text", "perspective_text")) and name in ROTATED_GOLDEN:
             out[name] = digest(render_direct(LIB, make())[0])

@@ -393,6 +393,46 @@ TEXTURE_RECT = [
 ]
 
 
+# The boundaries of the recording's scan for swgl_antiAlias requests (any_aa_request in wrhip.hip: eight instances at a time from 16
+# instances on, a scalar tail, a scalar loop below 16): one picture tile, n translucent rects with fractional edges under
+# PremultipliedAlpha, of which exactly ONE -- or none -- carries the request.  A scan that misses it records the draw as
+# rectangle-only (WR_DF_SIMPLE) and the rect loses its anti-aliased edges.  Every rect starts at x.5, y.5 on the white clear colour
+# and is dark, so the oracle's image of a flagged case differs from its image of the unflagged one (the tests assert that as well).
+def aa_scan_frame(encoding, n, flagged):
+    import numpy as np
+    i = np.arange(n)
+    x0, y0 = 12.5 + 140.0 * (i % 7), 10.5 + 120.0 * (i // 7)
+    rects = np.stack([x0, y0, x0 + 100.25, y0 + 80.75], axis=1).astype(np.float32)
+    rgba = np.stack([(37 * i) % 90, (53 * i) % 90, (71 * i) % 90, np.full(n, 128)], axis=1).astype(np.uint8)
+    aa = np.zeros(n, int)
+    if flagged is not None:
+        aa[flagged] = 15
+    return scenes.build_rect_frame(1024, 512, rects, scenes.premultiply(rgba), np.zeros(n, bool), encoding, aa_edges=aa)
+
+
+# (name, encoding, rects, index of the flagged rect or None, name of the unflagged case to differ from)
+AA_SCAN = []
+for _enc in ("brush", "quad"):
+    AA_SCAN += [
+        (f"aa_scan_{_enc}_25_none", _enc, 25, None, None),
+        (f"aa_scan_{_enc}_25_first", _enc, 25, 0, f"aa_scan_{_enc}_25_none"),
+        (f"aa_scan_{_enc}_25_last_of_group", _enc, 25, 23, f"aa_scan_{_enc}_25_none"),      # last lane of the last full group of 8
+        (f"aa_scan_{_enc}_25_tail", _enc, 25, 24, f"aa_scan_{_enc}_25_none"),               # the scalar tail behind the groups
+        (f"aa_scan_{_enc}_9_none", _enc, 9, None, None),
+        (f"aa_scan_{_enc}_9_last", _enc, 9, 8, f"aa_scan_{_enc}_9_none"),                   # below 16 instances: the scalar loop only
+    ]
+_aa_scan_want = {}
+
+
+def aa_scan_oracle(lib, name):
+    """the oracle's image of an AA_SCAN case, rendered once per session"""
+    if name not in _aa_scan_want:
+        from webrender_amd.harness import render_direct
+        _, enc, n, flagged, _ = next(c for c in AA_SCAN if c[0] == name)
+        _aa_scan_want[name] = render_direct(lib, aa_scan_frame(enc, n, flagged))[0]
+    return _aa_scan_want[name]
+
+
 # cs_svg_filter / cs_svg_filter_node: every filter kind main() has a case for (and kinds it has none for), two chained colour
 # targets, 1:1 / scaled / fractionally offset inputs; linear and nearest input samplers
 SVG_FILTERS = [

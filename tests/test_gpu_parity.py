@@ -10,7 +10,7 @@ import pytest
 from conftest import ROOT, wrhip_lib, oracle_ref
 from webrender_amd import scenes
 from webrender_amd.harness import render_direct, record_scene, ScenePlayer
-from parity_cases import TEXT_REFTESTS, TILE_ROWS, WRENCH, TEXTURE_RECT, YUV, SVG_FILTERS, OCCLUDED, BLEND, ROTATED, BORDERS, BORDER_SEGMENTS, DECORATIONS, FLAT, RUN_OVERFLOW, COPIES, copies_expected, MIX_BLEND, DUAL_SOURCE, REPEAT_DUAL, SPLIT, SPLIT_GOLDEN, GLYPH_TRANSFORM
+from parity_cases import TEXT_REFTESTS, TILE_ROWS, WRENCH, TEXTURE_RECT, YUV, SVG_FILTERS, OCCLUDED, BLEND, ROTATED, BORDERS, BORDER_SEGMENTS, DECORATIONS, FLAT, RUN_OVERFLOW, COPIES, copies_expected, MIX_BLEND, DUAL_SOURCE, REPEAT_DUAL, SPLIT, SPLIT_GOLDEN, GLYPH_TRANSFORM, AA_SCAN, aa_scan_frame, aa_scan_oracle
 
 pytestmark = pytest.mark.gpu
 GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "digests.json")))
@@ -471,6 +471,21 @@ def test_hip_texture_rect_keys_match_oracle(name, make):
     else:
         assert (want != 255).any()
         assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("name,encoding,n,flagged,plain", AA_SCAN, ids=[c[0] for c in AA_SCAN])
+def test_hip_aa_scan_boundaries_match_oracle(name, encoding, n, flagged, plain):
+    """The one anti-aliasing request of an alpha batch at the boundaries of the recording's scan (parity_cases.AA_SCAN) on the
+    MI355X: 0 differing bytes against the oracle where it is built, its committed digest everywhere -- and the request does change
+    the oracle's image, so a draw wrongly recorded as rectangle-only cannot pass."""
+    got, st = render_direct(wrhip_lib(), aa_scan_frame(encoding, n, flagged))
+    assert st["gl_error"] == 0 and st["raster_launches"] >= 1
+    ref = oracle_ref()
+    if ref:
+        assert np.array_equal(got, aa_scan_oracle(ref, name))
+        assert not plain or not np.array_equal(aa_scan_oracle(ref, name), aa_scan_oracle(ref, plain))
+    assert digest(got) == GOLDEN[name]
+    assert not plain or GOLDEN[name] != GOLDEN[plain]
 
 
 @pytest.mark.parametrize("name,make", SVG_FILTERS, ids=[c[0] for c in SVG_FILTERS])

@@ -11,7 +11,7 @@ import pytest
 from conftest import ROOT
 from webrender_amd import scenes
 from webrender_amd.harness import render_direct, record_scene, ScenePlayer
-from parity_cases import TEXT_REFTESTS, TILE_ROWS, WRENCH, TEXTURE_RECT, YUV, SVG_FILTERS, OCCLUDED, BLEND, ROTATED, BORDERS, BORDER_SEGMENTS, DECORATIONS, FLAT, RUN_OVERFLOW, COPIES, copies_expected, MIX_BLEND, DUAL_SOURCE, REPEAT_DUAL, SPLIT, SPLIT_GOLDEN, GLYPH_TRANSFORM
+from parity_cases import TEXT_REFTESTS, TILE_ROWS, WRENCH, TEXTURE_RECT, YUV, SVG_FILTERS, OCCLUDED, BLEND, ROTATED, BORDERS, BORDER_SEGMENTS, DECORATIONS, FLAT, RUN_OVERFLOW, COPIES, copies_expected, MIX_BLEND, DUAL_SOURCE, REPEAT_DUAL, SPLIT, SPLIT_GOLDEN, GLYPH_TRANSFORM, AA_SCAN, aa_scan_frame, aa_scan_oracle
 
 GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "digests.json")))
 
@@ -417,6 +417,20 @@ def test_hostsim_texture_rect_keys_match_oracle(hostsim, oracle_gcc, name, make)
     else:
         assert (want != 255).any()
         assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("name,encoding,n,flagged,plain", AA_SCAN, ids=[c[0] for c in AA_SCAN])
+def test_hostsim_aa_scan_boundaries_match_oracle(hostsim, oracle_gcc, name, encoding, n, flagged, plain):
+    """The one anti-aliasing request of an alpha batch at the boundaries of the recording's scan (parity_cases.AA_SCAN): first
+    instance, last lane of the last group of eight, scalar tail, the short batch's scalar loop, no request.  0 differing bytes --
+    and the request does change the oracle's image, so a draw wrongly recorded as rectangle-only cannot pass."""
+    want = aa_scan_oracle(oracle_gcc, name)
+    got, stats = render_direct(hostsim, aa_scan_frame(encoding, n, flagged))
+    assert stats["gl_error"] == 0
+    assert np.array_equal(got, want)
+    assert digest(want) == GOLDEN[name]
+    if plain:
+        assert not np.array_equal(want, aa_scan_oracle(oracle_gcc, plain))
 
 
 def test_hostsim_texture_rect_key_is_not_the_2d_key(hostsim):

@@ -26,6 +26,7 @@
 #include "wrhip_types.h"
 #include "wrhip_rt.h"
 #include "wr_grab_codec.h"
+#include "wr_draw_class.h"
 #include "wrhip_kernels.h"
 // The list of raster kernel instantiations: launch_raster() dispatches from it, and a static_assert holds pick_variant() to it.
 #include "wrhip_inst.h"
@@ -1361,36 +1362,7 @@ constexpr int round_feat(int fmt, int feat) {
   if (fmt == WR_FMT_R8) return feat == 0 ? 0 : !(feat & WR_FEAT_CLIP) ? WR_FS_BLUR : WR_FS_CLIP;
   return feat == 0 ? 0 : !(feat & ~WR_FS_IMAGE) ? WR_FS_IMAGE : !(feat & ~WR_FS_TEXT) ? WR_FS_TEXT : WR_FS_ALL;
 }
-// Shader classes that the flush plan and DrawElementsInstanced ask about.
-constexpr bool is_text_run(int sh) { return sh == WR_SH_PS_TEXT_RUN || sh == WR_SH_PS_TEXT_RUN_DUAL || sh == WR_SH_PS_TEXT_RUN_GT || sh == WR_SH_PS_TEXT_RUN_DUAL_GT; }
-constexpr bool is_clip_mask(int sh) { return sh == WR_SH_CS_CLIP_RECT || sh == WR_SH_CS_CLIP_RECT_FAST || sh == WR_SH_CS_CLIP_BOX_SHADOW; }
-constexpr bool is_brush_solid(int sh) { return sh == WR_SH_BRUSH_SOLID || sh == WR_SH_BRUSH_SOLID_ALPHA; }
-constexpr bool is_quad_prog(int sh) {
-  return sh == WR_SH_PS_QUAD_TEXTURED || sh == WR_SH_PS_QUAD_MASK || sh == WR_SH_PS_QUAD_MASK_FAST || sh == WR_SH_PS_QUAD_RADIAL_GRADIENT || sh == WR_SH_PS_QUAD_CONIC_GRADIENT;
-}
-constexpr bool is_gradient_prog(int sh) {
-  return sh == WR_SH_BRUSH_LINEAR_GRADIENT || sh == WR_SH_BRUSH_LINEAR_GRADIENT_ALPHA || sh == WR_SH_PS_QUAD_RADIAL_GRADIENT || sh == WR_SH_PS_QUAD_CONIC_GRADIENT ||
-         sh == WR_SH_CS_LINEAR_GRADIENT || sh == WR_SH_CS_RADIAL_GRADIENT || sh == WR_SH_CS_CONIC_GRADIENT;
-}
-// The prim families (WR_FEAT_*) a draw of this program can hold unless the host has verified it plain (WR_DF_SIMPLE: none).  A clip
-// mask that the rows kernel evaluates asks for WR_FEAT_BLUR instead: build_launches() knows which do.
-constexpr int shader_feat(int sh) {
-  if (sh == WR_SH_PS_CLEAR || sh == WR_SH_CLEAR_OP) return 0;
-  if (is_text_run(sh)) return WR_FEAT_R8TEX | WR_FEAT_TEX | WR_FEAT_GENERIC;
-  if (is_brush_solid(sh)) return WR_FEAT_R8TEX | WR_FEAT_GENERIC;      // masked / odd blend
-  if (sh == WR_SH_CS_BLUR_ALPHA || sh == WR_SH_CS_BLUR_COLOR) return WR_FEAT_BLUR;
-  if (is_clip_mask(sh)) return WR_FEAT_CLIP;
-  if (is_gradient_prog(sh)) return WR_FEAT_SHADE | WR_FEAT_GENERIC;
-  switch (sh) {
-    case WR_SH_BRUSH_BLEND: case WR_SH_BRUSH_BLEND_ALPHA: case WR_SH_BRUSH_MIX_BLEND: case WR_SH_BRUSH_MIX_BLEND_ALPHA:
-    case WR_SH_CS_SVG_FILTER: case WR_SH_CS_SVG_FILTER_NODE: case WR_SH_BRUSH_YUV: case WR_SH_BRUSH_YUV_ALPHA: case WR_SH_COMPOSITE_YUV:
-    case WR_SH_PS_QUAD_MASK: case WR_SH_PS_QUAD_MASK_FAST:
-    case WR_SH_CS_BORDER_SOLID: case WR_SH_CS_BORDER_SEGMENT: case WR_SH_CS_FAST_LINEAR_GRADIENT: case WR_SH_CS_LINE_DECORATION:
-    case WR_SH_BRUSH_IMAGE_REPEAT: case WR_SH_BRUSH_IMAGE_REPEAT_ALPHA: case WR_SH_BRUSH_IMAGE_REPEAT_DUAL:
-      return WR_FEAT_SHADE | WR_FEAT_GENERIC;
-    default: return WR_FEAT_TEX | WR_FEAT_GENERIC;
-  }
-}
+// (the shader classes that the flush plan and the record steps ask about, and shader_feat(): wr_draw_class.h)
 // (named like the kernels, so that an entry of WR_INST_ALL names its family)
 enum class Family { wr_raster_kernel, wr_setup_raster_kernel, wr_raster_dense_kernel, wr_setup_raster_dense_kernel, wr_setup_raster_thin_kernel, wr_span_rows_kernel, wr_tile_rows_kernel, wr_setup_tile_rows_kernel };
 constexpr uint32_t inst_key(Family k, int fmt, bool depth, int r, int feat) { return (uint32_t)k << 20 | (uint32_t)fmt << 16 | (uint32_t)depth << 12 | (uint32_t)r << 8 | (uint32_t)feat; }
@@ -3296,127 +3268,143 @@ static bool any_aa_request(const uint8_t* ib, int n, int stride, bool quad) {
 }
 
 // ---- the hot path: record one instanced batch ------------------------------
-void DrawElementsInstanced(GLenum mode, GLsizei count, GLenum type, GLintptr offset, GLsizei instancecount) {
-  Context* c = ctx;
-  HostTimer ht(c ? &c->stats.host_record_ns : nullptr);
-  Program* prog = c->programs.find(c->current_program);
-  if (offset < 0 || count <= 0 || instancecount <= 0 || !prog) return;
-  // What cannot be drawn is refused HERE, when the draw is recorded (GL_INVALID_OPERATION is visible to the caller's very
-  // next GetError()), not discovered by the device after the frame was presented without it.
-  auto refuse = [&](const char* why) {
-    c->last_error = GL_INVALID_OPERATION;
-    if (!prog->refused_once) fprintf(stderr, "libwrhip: draw refused (program '%s'): %s\n", prog->name, why);
-    prog->refused_once = true;
-  };
-  if (!prog->info) { refuse("this shader key has no implementation"); return; }
-  Framebuffer& fb = *get_framebuffer(GL_DRAW_FRAMEBUFFER, true);
-  if (!fb.color_attachment) return;
-  GLuint color_id = fb.color_attachment;
-  {
-    Texture& colortex = c->textures[color_id];
-    if (!colortex.dptr || colortex.own_none()) return;      // (own_none: another rank's target, WrhipSetTargetRows)
-    if (colortex.internal_format != GL_RGBA8 && colortex.internal_format != GL_R8) { refuse("colour target is neither RGBA8 nor R8"); return; }
-  }
-  VertexArray& v = c->vertex_arrays[c->current_vertex_array];
+// What the record steps hand to each other, beside the WrDrawDesc they fill in place.
+struct DrawRec {
+  Program* prog = nullptr; const ShaderInfo* info = nullptr;
+  Framebuffer* fb = nullptr; GLuint color_id = 0;
+  VertexArray* vao = nullptr; int first_vertex = 0;      // (the unit quad's first index)
+  GLuint inst_buf = 0; Buffer* instb = nullptr; int inst_stride = 0; size_t need = 0;      // the one instance buffer, the bytes of this draw in it
+  int wi = -1;             // the target's index in Context::work
+  bool gtab = false;       // the draw's gradient tables are promised a copy in the flush's pool (WR_DF_GTAB)
+};
+
+// What cannot be drawn is refused HERE, when the draw is recorded (GL_INVALID_OPERATION is visible to the caller's very
+// next GetError()), not discovered by the device after the frame was presented without it.
+static void refuse_draw(Context* c, Program* prog, const char* why) {
+  c->last_error = GL_INVALID_OPERATION;
+  if (!prog->refused_once) fprintf(stderr, "libwrhip: draw refused (program '%s'): %s\n", prog->name, why);
+  prog->refused_once = true;
+}
+
+// program, target format, unit-quad mode and index pattern; false: nothing to draw into or from (dropped), or refused
+static bool validate_draw(Context* c, DrawRec& R, GLenum mode, GLsizei count, GLenum type, GLintptr offset, GLsizei instancecount) {
+  Program* prog = R.prog = c->programs.find(c->current_program);
+  if (offset < 0 || count <= 0 || instancecount <= 0 || !prog) return false;
+  if (!prog->info) { refuse_draw(c, prog, "this shader key has no implementation"); return false; }
+  R.info = prog->info;
+  R.fb = get_framebuffer(GL_DRAW_FRAMEBUFFER, true);
+  if (!R.fb->color_attachment) return false;
+  R.color_id = R.fb->color_attachment;
+  const Texture& colortex = c->textures[R.color_id];
+  if (!colortex.dptr || colortex.own_none()) return false;      // (own_none: another rank's target, WrhipSetTargetRows)
+  if (colortex.internal_format != GL_RGBA8 && colortex.internal_format != GL_R8) { refuse_draw(c, prog, "colour target is neither RGBA8 nor R8"); return false; }
+  R.vao = &c->vertex_arrays[c->current_vertex_array];
   // Only WebRender's instanced unit quad is supported: TRIANGLES, 6 x u16,
   // indices i, i+1, i+2, i+2, i+1, i+3 (rasterize.h:1646-1659; vertex.rs:1079-1080).
   if (mode != GL_TRIANGLES || type != GL_UNSIGNED_SHORT || count != 6) {
-    refuse("only WebRender's instanced unit quad (TRIANGLES, 6 x UNSIGNED_SHORT) is drawn");
-    return;
+    refuse_draw(c, prog, "only WebRender's instanced unit quad (TRIANGLES, 6 x UNSIGNED_SHORT) is drawn");
+    return false;
   }
-  Buffer& ib = c->buffers[v.element_array_buffer_binding];
-  if (!ib.buf || (size_t)offset + 12 > ib.size) return;
+  Buffer& ib = c->buffers[R.vao->element_array_buffer_binding];
+  if (!ib.buf || (size_t)offset + 12 > ib.size) return false;
   const uint16_t* idx = (const uint16_t*)(ib.buf + offset);
   if (!(idx[1] == idx[0] + 1 && idx[2] == idx[0] + 2 && idx[5] == idx[0] + 3)) {
-    refuse("index pattern is not the unit quad's");
-    return;
+    refuse_draw(c, prog, "index pattern is not the unit quad's");
+    return false;
   }
-  const ShaderInfo* info = prog->info;
-  WrDrawDesc d;
-  memset(&d, 0, sizeof(d));
-  d.shader = info->kind;
-  d.count = instancecount;
-  // per-vertex aPosition of the 4 quad lanes 0,1,3,2 (load_attrib, gl.cc:1031-1039)
-  {
-    int loc = prog->attrib_loc[0];
-    VertexAttrib& va = v.attribs[loc];
-    Buffer& vb = c->buffers[va.vertex_buffer];
-    static const int lane_vertex[4] = {0, 1, 3, 2};
-    for (int n = 0; n < 4; n++) {
-      float xy[2] = {0.f, 0.f};
-      const size_t voff = (size_t)va.stride * (idx[0] + lane_vertex[n]) + va.offset;
-      if (loc != NULL_ATTRIB && va.enabled && vb.buf && voff + va.size <= vb.size) {
-        const uint8_t* src = vb.buf + voff;
-        int comps = 2;
-        for (int k = 0; k < comps; k++) {
-          if (va.type == GL_UNSIGNED_BYTE) {
-            if ((size_t)k < va.size) xy[k] = va.normalized ? float(src[k]) * (1.0f / 255.0f) : float(src[k]);
-          } else if (va.type == GL_UNSIGNED_SHORT) {
-            if ((size_t)k * 2 < va.size) { uint16_t u; memcpy(&u, src + 2 * k, 2); xy[k] = va.normalized ? float(u) * (1.0f / 65535.0f) : float(u); }
-          } else if (va.type == GL_FLOAT) {
-            if ((size_t)k * 4 < va.size) memcpy(&xy[k], src + 4 * k, 4);
-          }
+  R.first_vertex = idx[0];
+  return true;
+}
+
+// per-vertex aPosition of the 4 quad lanes 0,1,3,2 (load_attrib, gl.cc:1031-1039)
+static void fetch_quad_corners(Context* c, const DrawRec& R, WrDrawDesc& d) {
+  int loc = R.prog->attrib_loc[0];
+  VertexAttrib& va = R.vao->attribs[loc];
+  Buffer& vb = c->buffers[va.vertex_buffer];
+  static const int lane_vertex[4] = {0, 1, 3, 2};
+  for (int n = 0; n < 4; n++) {
+    float xy[2] = {0.f, 0.f};
+    const size_t voff = (size_t)va.stride * (R.first_vertex + lane_vertex[n]) + va.offset;
+    if (loc != NULL_ATTRIB && va.enabled && vb.buf && voff + va.size <= vb.size) {
+      const uint8_t* src = vb.buf + voff;
+      int comps = 2;
+      for (int k = 0; k < comps; k++) {
+        if (va.type == GL_UNSIGNED_BYTE) {
+          if ((size_t)k < va.size) xy[k] = va.normalized ? float(src[k]) * (1.0f / 255.0f) : float(src[k]);
+        } else if (va.type == GL_UNSIGNED_SHORT) {
+          if ((size_t)k * 2 < va.size) { uint16_t u; memcpy(&u, src + 2 * k, 2); xy[k] = va.normalized ? float(u) * (1.0f / 65535.0f) : float(u); }
+        } else if (va.type == GL_FLOAT) {
+          if ((size_t)k * 4 < va.size) memcpy(&xy[k], src + 4 * k, 4);
         }
       }
-      d.quad[2 * n] = xy[0]; d.quad[2 * n + 1] = xy[1];
     }
+    d.quad[2 * n] = xy[0]; d.quad[2 * n + 1] = xy[1];
   }
-  // instance attributes: all must come from one interleaved instance buffer
-  GLuint inst_buf = 0; int inst_stride = 0;
+}
+
+// instance attributes: all must come from one interleaved instance buffer that holds the draw's bytes; false: refused
+static bool instance_layout(Context* c, DrawRec& R, WrDrawDesc& d) {
   for (int k = 0; k < WR_MAX_ATTRIBS; k++) { d.attr_off[k] = -1; d.attr_bytes[k] = 0; }
   d.attr_u16 = 0;
-  for (int k = 1; k < WR_MAX_ATTRIBS + 1 && info->attribs[k]; k++) {
-    int loc = prog->attrib_loc[k];
+  for (int k = 1; k < WR_MAX_ATTRIBS + 1 && R.info->attribs[k]; k++) {
+    int loc = R.prog->attrib_loc[k];
     if (loc == NULL_ATTRIB) continue;
-    VertexAttrib& va = v.attribs[loc];
+    VertexAttrib& va = R.vao->attribs[loc];
     if (!va.enabled || va.divisor != 1) continue;
-    if (va.type != GL_INT && va.type != GL_FLOAT && va.type != GL_UNSIGNED_SHORT) { refuse("instance attribute type is neither INT, FLOAT nor UNSIGNED_SHORT"); return; }
+    if (va.type != GL_INT && va.type != GL_FLOAT && va.type != GL_UNSIGNED_SHORT) { refuse_draw(c, R.prog, "instance attribute type is neither INT, FLOAT nor UNSIGNED_SHORT"); return false; }
     if (va.type == GL_UNSIGNED_SHORT) d.attr_u16 |= 1u << (k - 1);
-    if (!inst_buf) { inst_buf = va.vertex_buffer; inst_stride = va.stride; }
-    if (va.vertex_buffer != inst_buf || va.stride != inst_stride) { refuse("instance attributes come from more than one buffer / stride"); return; }
+    if (!R.inst_buf) { R.inst_buf = va.vertex_buffer; R.inst_stride = va.stride; }
+    if (va.vertex_buffer != R.inst_buf || va.stride != R.inst_stride) { refuse_draw(c, R.prog, "instance attributes come from more than one buffer / stride"); return false; }
     d.attr_off[k - 1] = va.offset; d.attr_bytes[k - 1] = (int)va.size;
   }
-  Buffer* instb = inst_buf ? c->buffers.find(inst_buf) : nullptr;
-  size_t need = (size_t)inst_stride * instancecount;
-  if (!instb || !instb->buf || need > instb->size) {
-    if (inst_buf) { refuse("instance buffer holds fewer bytes than instancecount x stride"); return; }
+  R.instb = R.inst_buf ? c->buffers.find(R.inst_buf) : nullptr;
+  R.need = (size_t)R.inst_stride * d.count;
+  if (!R.instb || !R.instb->buf || R.need > R.instb->size) {
+    if (R.inst_buf) { refuse_draw(c, R.prog, "instance buffer holds fewer bytes than instancecount x stride"); return false; }
   }
-  if (c->depthtest && fb.depth_attachment) {
-    Texture* dtx = c->textures.find(fb.depth_attachment);
-    if (dtx && dtx->internal_format == GL_DEPTH_COMPONENT24 && dtx->depth_cleared) claim_depth(color_id, fb.depth_attachment, false);
-  }
-  int wi = find_or_add_work(color_id);   // may flush (target sampled by pending draws)
-  // A pending target that gets sampled is not flushed on the spot: the sampling target moves one
-  // dependency level above it and the whole chain (masks -> blurs -> tiles -> composite) goes
-  // through ONE flush -- one arena copy, one upload scatter, one setup launch, one raster launch
-  // per level -- instead of a full launch sequence per pass.
-  // (sampler2DRect samplers read the unit's GL_TEXTURE_RECTANGLE binding, gl.cc:853-855)
-  auto bound_tex = [&](int s) {
-    const Context::TextureUnit& u = c->texture_units[prog->sampler_unit[s] & 15];
-    return (info->rect && (s == WR_S_COLOR0 || s == WR_S_COLOR1 || s == WR_S_COLOR2)) ? u.texture_rectangle_binding : u.texture_2d_binding;
-  };
+  return true;
+}
+
+// The depth attachment this draw tests against -- depth test on, a DEPTH24 attachment, cleared (rasterize.h:962) -- or none.  The
+// Texture object stays where it is and a flush changes none of the three, so one lookup serves claim_depth() in front of
+// find_or_add_work() and book_depth() behind it.
+static Texture* tested_depth(Context* c, const DrawRec& R) {
+  Texture* dt = (c->depthtest && R.fb->depth_attachment) ? c->textures.find(R.fb->depth_attachment) : nullptr;
+  return dt && dt->internal_format == GL_DEPTH_COMPONENT24 && dt->depth_cleared ? dt : nullptr;
+}
+static void book_depth(Context* c, const DrawRec& R, const Texture& depthtex, WrDrawDesc& d) {
+  d.flags |= WR_DF_DEPTH_TEST;
+  if (c->depthmask) d.flags |= WR_DF_DEPTH_WRITE;
+  if (c->depthfunc == GL_LESS) d.flags |= WR_DF_DEPTH_LESS;
+  TargetWork& dw = c->work[R.wi];
+  dw.depth_tex = R.fb->depth_attachment;
+  if (!dw.init_depth_set) { dw.init_depth = depthtex.depth_value; dw.init_depth_set = true; }
+  dw.depth_live = true;
+}
+
+// The program's samplers, in ONE walk: the target's level, the WrTexDesc of each slot, what the flush has to know about the reads.
+// A pending target that gets sampled is not flushed on the spot: the sampling target moves one
+// dependency level above it and the whole chain (masks -> blurs -> tiles -> composite) goes
+// through ONE flush -- one arena copy, one upload scatter, one setup launch, one raster launch
+// per level -- instead of a full launch sequence per pass.  (The level only reads pending_write / pending_target of the sampled
+// textures and the levels of OTHER targets; the bookkeeping below -- mark_ref(read), the reads lists, the view list -- writes none of
+// them, so raising the level slot by slot beside it gives what a walk of its own in front gave.)
+static void bind_samplers(Context* c, const DrawRec& R, WrDrawDesc& d) {
+  const ShaderInfo* info = R.info;
+  const unsigned rmask = raster_read_mask(info->kind, R.gtab);
   for (int s = 0; s < WR_MAX_TEX; s++) {
     if (!((info->samplers >> s) & 1)) continue;
-    GLuint tid = bound_tex(s);
+    // (sampler2DRect samplers read the unit's GL_TEXTURE_RECTANGLE binding, gl.cc:853-855)
+    const Context::TextureUnit& u = c->texture_units[R.prog->sampler_unit[s] & 15];
+    const bool rect_s = info->rect && (s == WR_S_COLOR0 || s == WR_S_COLOR1 || s == WR_S_COLOR2);
+    const GLuint tid = rect_s ? u.texture_rectangle_binding : u.texture_2d_binding;
     Texture* t = tid ? c->textures.find(tid) : nullptr;
-    if (!t || !t->dptr || tid == color_id) continue;
+    if (!t || !t->dptr || tid == R.color_id) continue;
+    const int wi = R.wi;
     if (t->pending_write && t->pending_target >= 0)
       c->work[wi].level = std::max(c->work[wi].level, c->work[t->pending_target].level + 1);
-  }
-  Texture& colortex = c->textures[color_id];
-  const bool grad_prog = is_gradient_prog(info->kind);
-  // a table copy per instance (WR_GTAB_WORDS words): promised here, where the raster stage's reads are booked, for draws of up to 256
-  // gradients while the promises of the pending flush stay under 256 MB
-  const bool gtab = grad_prog && c->grad_tables && instancecount <= 256 && c->gtab_pending + (size_t)instancecount * WR_GTAB_WORDS <= ((size_t)64 << 20);
-  if (gtab) c->gtab_pending += (size_t)instancecount * WR_GTAB_WORDS;
-  for (int s = 0; s < WR_MAX_TEX; s++) {
-    if (!((info->samplers >> s) & 1)) continue;
-    GLuint tid = bound_tex(s);
-    Texture* t = tid ? c->textures.find(tid) : nullptr;
-    if (!t || !t->dptr || tid == color_id) continue;
     WrTexDesc& td = d.tex[s];
     td.ptr = t->dptr; td.width = t->width; td.height = t->height;
-    const bool rect_s = info->rect && (s == WR_S_COLOR0 || s == WR_S_COLOR1 || s == WR_S_COLOR2);
     td.sw = rect_s ? 1.0f : float(t->width); td.sh = rect_s ? 1.0f : float(t->height);
     td.stride = t->bpp >= 4 ? t->stride / 4 : (t->bpp == 2 ? t->stride / 2 : t->stride);
     td.format = (int16_t)wr_format(t->internal_format);
@@ -3425,11 +3413,6 @@ void DrawElementsInstanced(GLenum mode, GLsizei count, GLenum type, GLintptr off
     mark_ref(tid, *t, false);
     std::vector<GLuint>& reads = c->work[wi].reads;
     if (std::find(reads.begin(), reads.end(), tid) == reads.end()) reads.push_back(tid);
-    unsigned rmask = (1u << WR_S_COLOR0) | (1u << WR_S_COLOR1) | (1u << WR_S_COLOR2) | (1u << WR_S_CLIP_MASK);
-    if (info->kind == WR_SH_BRUSH_BLEND || info->kind == WR_SH_BRUSH_BLEND_ALPHA || info->kind == WR_SH_CS_SVG_FILTER || info->kind == WR_SH_CS_SVG_FILTER_NODE) rmask |= 1u << WR_S_GPU_CACHE;      // (component-transfer tables, read by main())
-    // (gradient tables: the span shaders and main() of every gradient program read the stops where the frame builder put them --
-    // unless the setup stage copies them into the flush's pool for this draw, WR_DF_GTAB)
-    if (grad_prog && !gtab) rmask |= 1u << WR_S_GPU_BUFFER_F;
     // Fused scatter: what the SETUP stage reads (the data textures: everything outside rmask) must not depend on the batch's scatter,
     // which runs beside it in the same launch.  A texture the open batch uploads whole is read in the staging mirror (same layout,
     // alive as long as the flush's arena); one it writes in part keeps the scatter in front of the setup stage.
@@ -3447,106 +3430,105 @@ void DrawElementsInstanced(GLenum mode, GLsizei count, GLenum type, GLintptr off
       if (std::find(rr.begin(), rr.end(), tid) == rr.end()) rr.push_back(tid);
     }
   }
-  d.target = wi;
+}
+
+// The blend key.  One without an implementation sets GL_INVALID_OPERATION -- and the draw is recorded all the same.
+static void record_blend(Context* c, const DrawRec& R, WrDrawDesc& d) {
   d.blend = c->blend ? c->blend_key : WR_BLEND_NONE;
-  // (GL_ONE, GL_ONE_MINUS_SRC1_COLOR under the dual-source text program is fine: every prim of that
-  // program replaces the key with swgl_blendSubpixelText / swgl_blendDropShadow in its vertex stage)
-  const bool dual_text = d.blend == WR_BLEND_DUAL_SRC && (info->kind == WR_SH_PS_TEXT_RUN_DUAL || info->kind == WR_SH_PS_TEXT_RUN_DUAL_GT || info->kind == WR_SH_BRUSH_IMAGE_DUAL || info->kind == WR_SH_BRUSH_IMAGE_REPEAT_DUAL);      // (the image program writes the second colour itself)
-  if (!dual_text && (d.blend == WR_BLEND_UNSUPPORTED || d.blend == WR_BLEND_DUAL_SRC)) {
+  if (d.blend == WR_BLEND_UNSUPPORTED || (d.blend == WR_BLEND_DUAL_SRC && !writes_second_colour(R.info->kind))) {
     // not in swgl's key table either (gl.cc:614-645: the reference asserts) -- or GL_ONE, GL_ONE_MINUS_SRC1_COLOR outside the
-    // dual-source text program, which needs gl_SecondaryFragColor from a shader that is not implemented
+    // dual-source programs, which needs gl_SecondaryFragColor from a shader that is not implemented
     fprintf(stderr, "libwrhip: blend state without an implementation (funcs %x %x %x %x equation %x)\n", c->blendfunc_srgb, c->blendfunc_drgb,
             c->blendfunc_sa, c->blendfunc_da, c->blend_equation);
     c->last_error = GL_INVALID_OPERATION;
   }
-  d.flags = (info->rect ? WR_DF_TEX_RECT : 0) | (gtab ? WR_DF_GTAB : 0);
-  Texture* depthtex = (c->depthtest && fb.depth_attachment) ? c->textures.find(fb.depth_attachment) : nullptr;
-  if (depthtex && depthtex->internal_format == GL_DEPTH_COMPONENT24 && depthtex->depth_cleared) {
-    d.flags |= WR_DF_DEPTH_TEST;
-    if (c->depthmask) d.flags |= WR_DF_DEPTH_WRITE;
-    if (c->depthfunc == GL_LESS) d.flags |= WR_DF_DEPTH_LESS;
-    TargetWork& dw = c->work[wi];
-    dw.depth_tex = fb.depth_attachment;
-    if (!dw.init_depth_set) { dw.init_depth = depthtex->depth_value; dw.init_depth_set = true; }
-    dw.depth_live = true;
-  }
-  d.query_slot = c->samples_passed_query ? c->queries[c->samples_passed_query].slot : -1;
-  {
-    // draws that can only produce solid prims with a blend the inline raster paths know (WrFeat)
-    const bool plain_blend = d.blend == WR_BLEND_NONE || d.blend == WR_BLEND_PREMULT;
-    const bool maskable = d.blend != WR_BLEND_NONE && d.tex[WR_S_CLIP_MASK].ptr && d.tex[WR_S_CLIP_MASK].width >= 2;
-    bool simple = false;
-    auto ids_clean = [&](int slot, bool headers) {
-      GLuint tid = c->texture_units[prog->sampler_unit[slot] & 15].texture_2d_binding;
-      Texture* ht = tid ? c->textures.find(tid) : nullptr;
-      return !ht || !(headers ? ht->complex_ids_headers : ht->complex_ids_gpubuf);
-    };
-    if (is_brush_solid(info->kind))
-      simple = plain_blend && !maskable && ids_clean(WR_S_PRIM_HEADERS_I, true);
-    else if (info->kind == WR_SH_PS_QUAD_TEXTURED)
-      simple = plain_blend && d.tex[WR_S_COLOR0].width < 2 && ids_clean(WR_S_GPU_BUFFER_I, false);
-    if (simple && d.blend != WR_BLEND_NONE && d.attr_off[0] >= 0 && d.attr_bytes[0] >= 12 && inst_stride >= 12) {
-      // swgl_antiAlias only matters with blending on; the request travels in aData.z of every
-      // instance (brush: flags = z >> 16, BRUSH_FLAG_FORCE_AA = 1024, gpu_types.rs:690-703; quad:
-      // part = (z >> 8) & 0xff, edge flags = (z >> 16) & 0xff, gpu_types.rs:564-589)
-      const uint8_t* ib = (const uint8_t*)instb->buf + d.attr_off[0];
-      if (any_aa_request(ib, instancecount, inst_stride, info->kind == WR_SH_PS_QUAD_TEXTURED)) simple = false;
-    }
-    if (simple) d.flags |= WR_DF_SIMPLE;
-    {
-      // can a prim of this draw sit under a rotation or a projective transform?  (brushes / text: transform ids in the prim
-      // headers; quads: in the GPU buffer)
-      const bool quad_prog = is_quad_prog(info->kind);
-      if (!ids_clean(quad_prog ? WR_S_GPU_BUFFER_I : WR_S_PRIM_HEADERS_I, !quad_prog)) d.flags |= WR_DF_XFORM;
-      if (info->kind == WR_SH_PS_SPLIT_COMPOSITE) d.flags |= WR_DF_XFORM;      // (its vertices are any convex quad, whatever the transform)
-    }
-    // textured prims on rotated quads or with swgl_antiAlias need the WR_PK_TEX_QUAD path (WR_FEAT_SHADE launches): the
-    // transform ids in the bound header texture and the AA requests in the instances say whether this draw can hold any
-    const bool img = info->kind == WR_SH_BRUSH_IMAGE || info->kind == WR_SH_BRUSH_IMAGE_ALPHA ||
-                     info->kind == WR_SH_BRUSH_OPACITY || info->kind == WR_SH_BRUSH_OPACITY_ALPHA ||
-                     info->kind == WR_SH_BRUSH_IMAGE_REPEAT || info->kind == WR_SH_BRUSH_IMAGE_REPEAT_ALPHA || info->kind == WR_SH_BRUSH_IMAGE_REPEAT_DUAL ||
-                     info->kind == WR_SH_BRUSH_LINEAR_GRADIENT || info->kind == WR_SH_BRUSH_LINEAR_GRADIENT_ALPHA ||
-                     info->kind == WR_SH_BRUSH_BLEND || info->kind == WR_SH_BRUSH_BLEND_ALPHA ||
-                     info->kind == WR_SH_BRUSH_MIX_BLEND || info->kind == WR_SH_BRUSH_MIX_BLEND_ALPHA ||
-                     info->kind == WR_SH_BRUSH_YUV || info->kind == WR_SH_BRUSH_YUV_ALPHA;
-    // (glyph quads under a rotation -- local raster space -- ride on the same path; the program never asks for swgl_antiAlias,
-    // and a glyph instance's third word is not a brush's flags: the transform ids alone decide)
-    const bool text = is_text_run(info->kind);
-    const bool texquad = (info->kind == WR_SH_PS_QUAD_TEXTURED && d.tex[WR_S_COLOR0].width >= 2) ||
-                         info->kind == WR_SH_PS_QUAD_MASK || info->kind == WR_SH_PS_QUAD_MASK_FAST ||
-                         info->kind == WR_SH_PS_QUAD_RADIAL_GRADIENT || info->kind == WR_SH_PS_QUAD_CONIC_GRADIENT;
-    const bool solid_masked = is_brush_solid(info->kind) && maskable;
-    if (colortex.internal_format == GL_RGBA8 && (img || texquad || solid_masked || text)) {
-      bool quads = !ids_clean(texquad ? WR_S_GPU_BUFFER_I : WR_S_PRIM_HEADERS_I, !texquad);
-      if (!quads && !text && d.blend != WR_BLEND_NONE && d.attr_off[0] >= 0 && d.attr_bytes[0] >= 12 && inst_stride >= 12) {
-        const uint8_t* ib = (const uint8_t*)instb->buf + d.attr_off[0];
-        quads = any_aa_request(ib, instancecount, inst_stride, texquad);
-      }
-      if (quads) d.flags |= WR_DF_QUADS;
-    }
-    // (a split polygon is a general quad by construction: ps_split_composite.glsl:85-87)
-    if (info->kind == WR_SH_PS_SPLIT_COMPOSITE && colortex.internal_format == GL_RGBA8) d.flags |= WR_DF_QUADS;
-  }
+}
+
+// WR_DF_SIMPLE / WR_DF_XFORM / WR_DF_QUADS (wr_draw_class.h): the facts, the scan of the instance bytes where aa_scan() asks for
+// one -- in the caller's buffer, before the snapshot -- and the class.
+static int classify_draw(Context* c, const DrawRec& R, const WrDrawDesc& d) {
+  // (the unit's GL_TEXTURE_2D binding, whatever the program's sampler set; no texture: clean)
+  auto unit_tex = [&](int slot) { const GLuint tid = c->texture_units[R.prog->sampler_unit[slot] & 15].texture_2d_binding; return tid ? c->textures.find(tid) : nullptr; };
+  const Texture* headers = unit_tex(WR_S_PRIM_HEADERS_I);
+  const Texture* gpubuf = unit_tex(WR_S_GPU_BUFFER_I);
+  DrawFacts f;
+  f.kind = R.info->kind; f.blend = d.blend;
+  f.rgba8 = c->textures[R.color_id].internal_format == GL_RGBA8;
+  f.mask_wide = d.tex[WR_S_CLIP_MASK].ptr && d.tex[WR_S_CLIP_MASK].width >= 2;
+  f.color0_wide = d.tex[WR_S_COLOR0].width >= 2;
+  f.complex_headers = headers && headers->complex_ids_headers;
+  f.complex_gpubuf = gpubuf && gpubuf->complex_ids_gpubuf;
+  f.third_word = d.attr_off[0] >= 0 && d.attr_bytes[0] >= 12 && R.inst_stride >= 12;
+  const WrAaScan scan = aa_scan(f);
+  const bool aa = scan != WR_AA_SCAN_NONE && any_aa_request((const uint8_t*)R.instb->buf + d.attr_off[0], d.count, R.inst_stride, scan == WR_AA_SCAN_QUAD);
+  return draw_class_flags(f, aa);
+}
+
+// scissor, viewport, uTransform, blend colour, the occlusion query
+static void draw_state(Context* c, const DrawRec& R, WrDrawDesc& d) {
+  const Texture& colortex = c->textures[R.color_id];
   apply_scissor(colortex, d.clip);
   d.vp_origin[0] = float(c->viewport[0] - colortex.offx); d.vp_origin[1] = float(c->viewport[1] - colortex.offy);
   d.vp_size[0] = float(c->viewport[2] - c->viewport[0]); d.vp_size[1] = float(c->viewport[3] - c->viewport[1]);
-  memcpy(d.transform, prog->transform, sizeof(d.transform));
+  memcpy(d.transform, R.prog->transform, sizeof(d.transform));
   d.blend_color[0] = c->blendcolor[0]; d.blend_color[1] = c->blendcolor[1];
-  // snapshot the instance bytes (the caller may overwrite the VBO right after)
-  TargetWork& w = c->work[wi];
+  d.query_slot = c->samples_passed_query ? c->queries[c->samples_passed_query].slot : -1;
+}
+
+// snapshot the instance bytes (the caller may overwrite the VBO right after)
+static void snapshot_instances(const DrawRec& R, TargetWork& w, WrDrawDesc& d) {
+  const size_t need = R.need;
   size_t pos = (w.inst.size() + 15) & ~size_t(15);
   if (need >= PARALLEL_COPY_MIN) {
     w.inst.resize(pos + need);
-    big_memcpy(w.inst.data() + pos, instb->buf, need);
+    big_memcpy(w.inst.data() + pos, R.instb->buf, need);
   } else {
     // (one pass: resize() would zero the bytes the copy is about to overwrite -- 72 snapshots of ~33 KB per cfg5 frame)
     w.inst.resize(pos);
-    if (need) w.inst.insert(w.inst.end(), (const uint8_t*)instb->buf, (const uint8_t*)instb->buf + need);
+    if (need) w.inst.insert(w.inst.end(), (const uint8_t*)R.instb->buf, (const uint8_t*)R.instb->buf + need);
   }
-  d.inst_offset = pos; d.inst_stride = inst_stride;
+  d.inst_offset = pos; d.inst_stride = R.inst_stride;
 #ifdef WRHIP_HOSTSIM
-  if (getenv("WRHIP_DEBUG") && need >= 16) { const float* f = (const float*)(w.inst.data() + pos); fprintf(stderr, "record: sh %d buf %u need %zu first %g %g %g %g\n", d.shader, inst_buf, need, f[0], f[1], f[2], f[3]); }
+  if (getenv("WRHIP_DEBUG") && need >= 16) { const float* f = (const float*)(w.inst.data() + pos); fprintf(stderr, "record: sh %d buf %u need %zu first %g %g %g %g\n", d.shader, R.inst_buf, need, f[0], f[1], f[2], f[3]); }
 #endif
+}
+
+// One instanced batch becomes one WrDrawDesc, built in place and pushed once.  What the order of the steps has to keep:
+//  - Every refusal (validate_draw, instance_layout) returns before the first state change; the state changes are claim_depth(),
+//    find_or_add_work() and Context::gtab_pending.
+//  - claim_depth() precedes find_or_add_work(): another target's depth that this one inherits has to be flushed before this target's
+//    work exists.
+//  - find_or_add_work() may flush and may reallocate Context::work: nothing that points into Context::work is taken before it, and
+//    the steps look the colour Texture up themselves.
+//  - An unsupported blend state sets GL_INVALID_OPERATION and the draw is still recorded (record_blend).
+//  - classify_draw() reads the instance bytes in the caller's buffer, so it comes before snapshot_instances() -- and after
+//    bind_samplers() and record_blend(), whose results are among its facts.
+void DrawElementsInstanced(GLenum mode, GLsizei count, GLenum type, GLintptr offset, GLsizei instancecount) {
+  Context* c = ctx;
+  HostTimer ht(c ? &c->stats.host_record_ns : nullptr);
+  DrawRec R;
+  if (!validate_draw(c, R, mode, count, type, offset, instancecount)) return;
+  WrDrawDesc d;
+  memset(&d, 0, sizeof(d));
+  d.shader = R.info->kind;
+  d.count = instancecount;
+  fetch_quad_corners(c, R, d);
+  if (!instance_layout(c, R, d)) return;
+  Texture* depthtex = tested_depth(c, R);
+  if (depthtex) claim_depth(R.color_id, R.fb->depth_attachment, false);
+  d.target = R.wi = find_or_add_work(R.color_id);   // may flush (target sampled by pending draws)
+  // a table copy per instance (WR_GTAB_WORDS words): promised here, where the raster stage's reads are booked, for draws of up to 256
+  // gradients while the promises of the pending flush stay under 256 MB
+  R.gtab = is_gradient_prog(R.info->kind) && c->grad_tables && instancecount <= 256 && c->gtab_pending + (size_t)instancecount * WR_GTAB_WORDS <= ((size_t)64 << 20);
+  if (R.gtab) c->gtab_pending += (size_t)instancecount * WR_GTAB_WORDS;
+  bind_samplers(c, R, d);
+  record_blend(c, R, d);
+  d.flags = (R.info->rect ? WR_DF_TEX_RECT : 0) | (R.gtab ? WR_DF_GTAB : 0);
+  if (depthtex) book_depth(c, R, *depthtex, d);
+  d.flags |= classify_draw(c, R, d);
+  draw_state(c, R, d);
+  TargetWork& w = c->work[R.wi];
+  snapshot_instances(R, w, d);
   w.draws.push_back(d);
   w.prims += instancecount;
 }

@@ -59,10 +59,12 @@ def build_rect_frame(width, height, rects, colors, opaque, encoding="quad",
     premultiplied; opaque: bool [N].  encoding: "quad" (ps_quad_textured, what
     Rectangle prims use today: prepare.rs:218-256) or "brush" (brush_solid,
     the legacy path: batch.rs:2317-2332).  tile_filter(tx,ty)->bool selects
-    the tiles this process owns (multi-GPU sharding)."""
+    the tiles this process owns (multi-GPU sharding).  aa_edges: the edges (0..15)
+    to anti-alias on the translucent rects -- one value for all, or one per rect."""
     frame = Frame(width, height, clear_color)
     rects = np.asarray(rects, np.float32)
     n = len(rects)
+    aa = [int(a) for a in np.broadcast_to(np.asarray(aa_edges), (n,))]
     z_ids = np.arange(1, n + 1, dtype=np.int32)
 
     # brush path: one PrimitiveHeader + one GPU-cache colour block per prim,
@@ -90,13 +92,13 @@ def build_rect_frame(width, height, rects, colors, opaque, encoding="quad",
             if encoding == "quad":
                 qf = QF_APPLY_DEVICE_CLIP | (QF_IS_OPAQUE if opaque[i] else 0)
                 inst = frame.quad_instance(r, (-BIG, -BIG, BIG, BIG), c, int(z_ids[i]), task,
-                                           quad_flags=qf, edge_flags=0 if opaque[i] else aa_edges)
+                                           quad_flags=qf, edge_flags=0 if opaque[i] else aa[i])
             else:
                 addr = frame.gpu_cache.push([list(c)])
                 ph = frame.add_prim_header(r, (-BIG, -BIG, BIG, BIG), int(z_ids[i]), addr, 0,
                                            task, (65535, 0, 0, 0))
-                if aa_edges and not opaque[i]:      # BRUSH_FLAG_FORCE_AA + the edges to anti-alias
-                    inst = frame.brush_instance(ph, CLIP_TASK_EMPTY, brush_flags=1024, edge_flags=aa_edges)
+                if aa[i] and not opaque[i]:      # BRUSH_FLAG_FORCE_AA + the edges to anti-alias
+                    inst = frame.brush_instance(ph, CLIP_TASK_EMPTY, brush_flags=1024, edge_flags=aa[i])
                 else:
                     inst = frame.brush_instance(ph, CLIP_TASK_EMPTY)
             (op_inst if opaque[i] else al_inst).append(inst)
