@@ -252,7 +252,7 @@ void WrhipSetProfiling(int enabled);
  * (picture targets of a few large gradient / image prims, likewise), 11 = wr_setup_tile_rows_kernel (10 fused with the next flush's setup stage), 12 = a thin launch of the raster kernel (13: the same with the next flush's setup stage in front, wr_setup_raster_thin_kernel) (wr_raster_kernel<fmt, false, 1, feat>:
  * small levels, several workgroups per bin), 14 = wr_tap_kernel (WrhipTapTexture: fmt of the tapped texture, feat 1 against an expected texture;
  * algo_bytes: the rect's bytes, twice with an expected texture), 15 = wr_grab_pack_kernel (WrhipGrabTexture: fmt of the grabbed texture,
- * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta; algo_bytes: bytes read plus bytes written, as far as they are known at the launch).  algo_bytes: the launch's algorithmic bytes:
+ * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta, feat 3: wr_grab_scale_kernel, the launches of one WrhipGrabTextureScaled; algo_bytes: bytes read plus bytes written, as far as they are known at the launch).  algo_bytes: the launch's algorithmic bytes:
  * raster launches count every destination pixel they own once (twice when the target's old content is loaded) plus
  * the source texels their draws can sample; the setup stage counts instance + descriptor + record bytes.  Returns the
  * number of entries written (<= max). */
@@ -388,12 +388,32 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  *                   bytes); then zero bytes to the next multiple of 16.
  *   A tie between RUNS and RAW goes to RAW: a full RGBA8 block is RUNS up to n = 3964 and RAW from 3965, a full R8 block RUNS up
  *   to n = 3568 and RAW from 3569.  No entry is larger than a plain delta entry, so slots are sized as for a plain delta grab.
- * Not routed through grabs: Finish, GetColorBuffer, ReadPixels.  Not supported: scaling, other formats, sharded targets. */
+ *
+ * WrhipGrabTextureScaled(tex, rect, dst_w, dst_h, flags): a grab of ONE rect (x, y, w, h) of a GL_RGBA8 texture scaled down to
+ * dst_w x dst_h (1 <= dst_w <= w, 1 <= dst_h <= h), byte for byte what the reference's screenshot chain (webrender's
+ * AsyncScreenshotGrabber::scale_screenshot) gets from BlitFramebuffer(.., GL_LINEAR) calls that never halve by more than 2:
+ *   levels  L is the smallest L >= 0 with w <= 2 * dst_w * 2^L (the width alone decides); level k is dst_w << k x dst_h << k.
+ *   top     BlitFramebuffer(x, y, x + w, y + h, 0, 0, dst_w << L, dst_h << L, COLOR, GL_LINEAR) into level L: linear_blit's 1/128-texel
+ *           walk, clamped at the TEXTURE's edges (a tap at the rect's edge reads the texel beyond it where there is one); equal sizes,
+ *           or a texture narrower than 2, make it a nearest copy.  The height ratio may be anything.
+ *   lower   level k from level k + 1 by BlitFramebuffer(0, 0, dst_w << (k + 1), dst_h << (k + 1), 0, 0, dst_w << k, dst_h << k, COLOR, GL_LINEAR).
+ *   result  level 0.
+ * One kernel walks the chain tile by tile with the intermediate levels in LDS (a launch per 4 levels beyond the first 4; those hand
+ * a level on through HBM).  Ticket ring, ordering, parking behind held-back launches, slot growth, transport, `bytes` and "later
+ * writes do not change the result" are a full grab's.  `flags`: FLIP_ROWS and / or SWAP_RB, applied to the delivered rows.  The
+ * payload is dst_w * dst_h * 4 bytes; WrhipGrabResultGet delivers dst_h rows of dst_w * 4 bytes at `dst_stride` (0: tight; below
+ * dst_w * 4: -1 with GL_INVALID_VALUE) and reports flags | WRHIP_GRAB_SCALED, the rect as given, scaled_w, scaled_h and levels = L.
+ * Returns -1 and sets GL_INVALID_VALUE, launching and flushing nothing, for an unknown texture, a format other than GL_RGBA8, a rect
+ * that is empty or not inside `tex`, dst_w or dst_h below 1 or above the rect's, dst_w << L or dst_h << L above GL_MAX_TEXTURE_SIZE,
+ * any other flag, and while sharding is on; -1 with GL_OUT_OF_MEMORY as WrhipGrabTexture.
+ * Not routed through grabs: Finish, GetColorBuffer, ReadPixels.  Not supported: other formats, sharded targets; scaling other than
+ * WrhipGrabTextureScaled's. */
 #define WRHIP_GRAB_FLIP_ROWS 1u   /* full mode: deliver the rect's last row first */
 #define WRHIP_GRAB_SWAP_RB   2u   /* full mode, RGBA8 only: bytes 0 and 2 of every pixel exchanged */
 #define WRHIP_GRAB_DELTA     4u   /* only the 64x64 blocks that differ from the previous DELTA grab of this texture and rect */
 #define WRHIP_GRAB_KEY       8u   /* with DELTA: ignore the retained copy, send every block */
 #define WRHIP_GRAB_PACKED    32u  /* with DELTA: sent blocks as SOLID / RUNS / RAW entries (the packed payload above); 16 is no flag */
+#define WRHIP_GRAB_SCALED    64u  /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureScaled ticket; no flag of WrhipGrabTexture, which rejects it */
 #define WRHIP_GRAB_MAX_RECTS 16
 #define WRHIP_GRAB_HEADER    16u  /* bytes that cross with every grab ahead of its payload (the payload's byte count) */
 typedef struct WrhipGrabInfo {
@@ -404,8 +424,11 @@ typedef struct WrhipGrabInfo {
   uint32_t blocks, blocks_total;   /* DELTA: blocks sent / blocks of the rect */
   int32_t  damage[4];              /* DELTA: x, y, w, h (relative to the rect) bounding the sent blocks, each cut to the rect; 0,0,0,0 if none */
   uint64_t bytes;                  /* bytes that crossed to the host for this ticket (header + payload) */
+  int32_t  scaled_w, scaled_h;     /* WrhipGrabTextureScaled: the delivered size; 0 for other grabs */
+  uint32_t levels;                 /* WrhipGrabTextureScaled: L, the 2:1 steps below the top step */
 } WrhipGrabInfo;
 int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint32_t flags);
+int32_t WrhipGrabTextureScaled(GLuint tex, const int32_t rect[4], int32_t dst_w, int32_t dst_h, uint32_t flags);
 int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64_t dst_stride, int32_t wait);
 int32_t WrhipGrabPayloadGet(int32_t ticket, void* dst, uint64_t capacity, uint64_t* bytes, int32_t wait);
 int32_t WrhipGrabDecode(const void* payload, uint64_t bytes, uint32_t format, uint32_t flags, int32_t rect_w, int32_t rect_h, void* dst, int64_t dst_stride, int32_t damage[4], uint32_t* blocks);

@@ -10,10 +10,15 @@
              no grab, a tap per frame, a full grab per frame, a delta grab per frame (identical frames), a ReadPixels per frame;
              then cfg2 frames of different seeds in turn: no grab, a delta grab per frame, a packed delta grab per frame, with the
              bytes per frame that crossed
+  scaled     WrhipGrabTextureScaled, the 4K window -> 350 x 197 (L = 3: 2800x1576, 1400x788, 700x394, 350x197), on noise and on the
+             cfg2 frame: wr_grab_scale_kernel by hipEvents (kind 15 feat 3); then 50 grabs enqueued back to back with one Finish
+             behind them, on the host clock, against the same chain as libwrhip ran it before -- four BlitFramebuffer calls
+             (wr_blit_kernel, which has no entry in the kernel statistics: hence the host clock for both) and a full grab of
+             level 0; then cfg2 streamed as in `stream`: no grab, a full grab per frame, a scaled grab per frame, frames/s
   ab         plain bench.py against another build of the library (WRHIP_LIB_PATH), alternated, no grab issued
 
 Every section runs three alternated rounds.  Needs the GPU: there is no fallback.
-  python tools/grab_bench.py [--sections pack,transport,stream] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
+  python tools/grab_bench.py [--sections pack,transport,stream,scaled] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -27,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from webrender_amd import glapi, scenes, glconst as G      # noqa: E402
 from webrender_amd.renderer import Renderer                # noqa: E402
-from webrender_amd.harness import record_scene, ScenePlayer  # noqa: E402
+from webrender_amd.harness import record_scene, ScenePlayer, screenshot_size  # noqa: E402
 
 W, H = 3840, 2160
 ROUNDS = 3
@@ -263,6 +268,121 @@ def section_stream(lib, frames):
         say(f"  {name:22s} " + "  ".join(f"{fps:9.1f}" for fps, _, _ in v) + "   frames/s   " + (f"({v[0][1] / 1e6:7.3f} MB and {v[0][2]:6.1f} blocks per frame crossed)" if v[0][1] else ""))
 
 
+def section_scaled(lib, content):
+    dw, dh = screenshot_size((W, H), (350, 350))
+    L = 0
+    while W > 2 * dw * (1 << L):
+        L += 1
+    say(f"## scaled: {W}x{H} window of {content} -> {dw}x{dh}, L = {L}")
+    w = Window(lib, content)
+    gl, d = w.gl, w.r.device
+    levels = [d.create_texture(dw << k, dh << k, G.GL_RGBA8, render_target=True) for k in range(L + 1)]
+
+    def blit(src_fbo, sw, sh, dst):
+        gl.BindFramebuffer(G.GL_READ_FRAMEBUFFER, src_fbo)
+        gl.BindFramebuffer(G.GL_DRAW_FRAMEBUFFER, dst.fbo)
+        gl.BlitFramebuffer(0, 0, sw, sh, 0, 0, dst.width, dst.height, G.GL_COLOR_BUFFER_BIT, G.GL_LINEAR)
+
+    def chain():
+        blit(0, W, H, levels[L])
+        for k in range(L - 1, -1, -1):
+            blit(levels[k + 1].fbo, levels[k + 1].width, levels[k + 1].height, levels[k])
+        gl.BindFramebuffer(G.GL_DRAW_FRAMEBUFFER, 0)
+        gl.BindFramebuffer(G.GL_READ_FRAMEBUFFER, 0)
+        return gl.grab_texture(levels[0].id)
+
+    def fused():
+        return gl.grab_texture_scaled(w.tex, None, (dw, dh))
+    # the two agree byte for byte (and both are warm)
+    a = gl.grab_result(chain())[1]
+    b = gl.grab_result(fused())[1]
+    assert np.array_equal(a, b), "the fused pass and the blit chain differ"
+    algo = W * H * 4 + dw * dh * 4
+    N = 50
+    ev, host = [], {"chain": [], "fused": []}
+    for rnd in range(ROUNDS):
+        gl.WrhipSetProfiling(1)
+        gl.WrhipResetStats()
+        for _ in range(30):
+            t = fused()
+        gl.grab_result(t)
+        ks = [k for k in kernel_stats(gl, 15) if k.feat == 3]
+        assert len(ks) == 1 and ks[0].launches == 30 and ks[0].algo_bytes == 30 * algo, [(k.feat, k.launches, k.algo_bytes) for k in ks]
+        ev.append(ks[0].ns / 30 / 1e3)
+        gl.WrhipSetProfiling(0)
+        for name, fn in (("chain", chain), ("fused", fused)):
+            gl.Finish()
+            t0 = time.perf_counter()
+            for _ in range(N):
+                t = fn()
+            gl.Finish()
+            host[name].append((time.perf_counter() - t0) / N * 1e6)
+            gl.grab_result(t)
+    say("  wr_grab_scale_kernel, hipEvents     " + "  ".join(f"{us:8.1f}" for us in ev) + f"   us per launch   ({algo / 1e6:.2f} MB algorithmic: " + "  ".join(f"{algo / us / 1e3:6.0f}" for us in ev) + " GB/s)")
+    say(f"  {N} enqueued, one Finish, host clock, us per grab:")
+    say(f"    {L + 1} x BlitFramebuffer + full grab   " + "  ".join(f"{us:8.1f}" for us in host["chain"]))
+    say("    WrhipGrabTextureScaled            " + "  ".join(f"{us:8.1f}" for us in host["fused"]))
+    w.close()
+
+
+def section_scaled_stream(lib, frames):
+    dw, dh = screenshot_size((W, H), (350, 350))
+    say(f"## scaled stream: cfg2 {W}x{H} streamed as in `stream`, {frames} frames per region, frames/s; the scaled grab delivers {dw}x{dh}")
+    rec, _ = record_scene(lib, scenes.make_workload("cfg2", width=W, height=H))
+    p = ScenePlayer(lib, rec)
+    sym = lambda name, res, *args: C.CFUNCTYPE(res, *args)(p.symbol(name))
+    finish = sym("Finish", None)
+    window = sym("WrhipGetFramebufferTexture", C.c_uint32, C.c_uint32)(0)
+    grab = sym("WrhipGrabTexture", C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_uint32)
+    grab_scaled = sym("WrhipGrabTextureScaled", C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32)
+    grab_get = sym("WrhipGrabResultGet", C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
+    get_stats = sym("WrhipGetStats", None, C.c_void_p)
+    reset_stats = sym("WrhipResetStats", None)
+    rect = (C.c_int32 * 4)(0, 0, W, H)
+    host = np.zeros((H, W, 4), np.uint8)
+    info = glapi.WrhipGrabInfo()
+
+    def run(kind, n):
+        waiting = []
+
+        def fetch(wait):
+            while waiting:
+                rc = grab_get(waiting[0], C.byref(info), host.ctypes.data, 0, 1 if wait else 0)
+                if rc == 1:
+                    return
+                assert rc == 0, rc
+                waiting.pop(0)
+                wait = False
+        for _ in range(n):
+            p.rp.exec(rec.stream)
+            if kind != "no grab":
+                if len(waiting) == 8:
+                    fetch(True)
+                t = grab(window, C.addressof(rect), 1, 0) if kind == "full grab" else grab_scaled(window, C.addressof(rect), dw, dh, 0)
+                assert t >= 0
+                waiting.append(t)
+                fetch(False)
+        finish()
+        while waiting:
+            fetch(True)
+    kinds = ["no grab", "full grab", "scaled grab"]
+    rows, carried = {}, {}
+    for k in kinds:
+        run(k, 10)
+    for rnd in range(ROUNDS):
+        for k in kinds:
+            reset_stats()
+            t0 = time.perf_counter()
+            run(k, frames)
+            dt = time.perf_counter() - t0
+            st = glapi.WrhipStats()
+            get_stats(C.byref(st))
+            rows.setdefault(k, []).append(frames / dt)
+            carried.setdefault(k, []).append(int(st.setup_carried))
+    for k in kinds:
+        say(f"  {k:22s} " + "  ".join(f"{v:9.1f}" for v in rows[k]) + f"   frames/s   (setup_carried {carried[k][0]} of {frames} flushes)")
+
+
 def section_ab(other, steps, warmup):
     say(f"## ab: bench.py --gpus 1 --steps {steps} --warmup {warmup} (cfg2), this library against {os.path.basename(other)}, alternated, frames/s")
     rows = {"parent": [], "this": []}
@@ -313,6 +433,10 @@ def main():
                 section_transport(lib)
             elif s == "stream":
                 section_stream(lib, args.frames)
+            elif s == "scaled":
+                section_scaled(lib, "noise")
+                section_scaled(lib, "cfg2")
+                section_scaled_stream(lib, args.frames)
         if args.ab:
             section_ab(args.ab, args.steps, args.warmup)
     finally:

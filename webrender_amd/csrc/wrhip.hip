@@ -665,12 +665,18 @@ struct Context {
     uint8_t* dev = nullptr; uint8_t* host = nullptr; size_t cap = 0;
     GLenum format = 0; uint32_t flags = 0; int bpp = 0, nrects = 0; int32_t rects[WR_GRAB_MAX_RECTS][4];
     bool keyframe = false; uint32_t blocks_total = 0;
+    int scaled_w = 0, scaled_h = 0, levels = 0;      // WrhipGrabTextureScaled: the delivered size and L
   };
-  struct GrabParked { uint64_t n; WrGrabArgs args; };
+  // WrhipGrabTextureScaled as it was asked for; its launches are laid out when it is issued (grab_issue_scaled), since the levels
+  // that go through HBM live in a scratch that may have grown by then
+  struct GrabScaled { const uint8_t* tex; int32_t tex_stride, tex_w, tex_h, rect[4], dw, dh, levels, flip, swap_rb; };
+  struct GrabParked { uint64_t n; bool scaled; WrGrabArgs args; GrabScaled scale; };
   GrabSlot grab_slot[GRAB_RING];
   uint64_t grab_next = 0;
   std::vector<GrabParked> grab_parked;
   std::vector<std::pair<void*, size_t>> grab_keep_dead;      // retained copies replaced while a parked grab may still name them
+  void* grab_scale_scratch = nullptr;              // the levels a scaled grab of more than WR_SCALE_STEPS halvings passes from launch to
+  size_t grab_scale_scratch_size = 0;              // launch (pool storage, grown on demand; every user is on `stream`, one after the other)
   wr_stream_t grab_stream;
   bool grab_ready = false;
   size_t grab_pinned_max = (size_t)512 << 20;      // WRHIP_GRAB_PINNED_MAX, bytes
@@ -1312,6 +1318,7 @@ Context::~Context() {
     wrrt::stream_destroy(grab_stream);
   }
   for (auto& kd : grab_keep_dead) wrrt::dev_free(kd.first);
+  wrrt::dev_free(grab_scale_scratch);
   wrrt::event_destroy(ev_a); wrrt::event_destroy(ev_b);
   wrrt::event_destroy(ev_copy);
   for (RingFence& f : ring_fence) if (f.made) wrrt::event_destroy(f.ev);
@@ -1620,6 +1627,24 @@ void grab_init() {
   if (const char* e = getenv("WRHIP_GRAB_FULL_PUSH")) c->grab_full_kernel = strcmp(e, "kernel") == 0;
   c->grab_ready = true;
 }
+// The transport of a slot that has just been packed on the draw stream: on the grab stream behind the pack, the ticket's event
+// behind it.  by_kernel: wr_grab_push_kernel reads the byte count from the slot; otherwise a plain copy of `payload` bytes.
+static void grab_push(Context::GrabSlot& gs, uint32_t payload, bool by_kernel) {
+  Context* c = ctx;
+  WrGrabPushArgs pa;
+  pa.src = gs.dev; pa.dst = gs.host; pa.capacity = (uint32_t)gs.cap;
+#ifdef WRHIP_HOSTSIM
+  (void)payload; (void)by_kernel;
+  WR_LAUNCH(wr_grab_push_kernel, 1, 256, c->stream, pa);
+#else
+  wrrt::event_record(&gs.ev_pack, c->stream);
+  wrrt::stream_wait_event(c->grab_stream, &gs.ev_pack);
+  if (by_kernel) WR_LAUNCH(wr_grab_push_kernel, c->grab_push_wgs, 256, c->grab_stream, pa);
+  else wrrt::d2h(gs.host, gs.dev, (size_t)WR_GRAB_HEADER + payload, c->grab_stream);
+  wrrt::event_record(&gs.ev, c->grab_stream);
+#endif
+  gs.parked = false;
+}
 // One grab, now: the pack on the draw stream -- behind the transport of the slot's previous ticket --, the transport on the grab
 // stream behind the pack, the ticket's event behind the transport.  Enqueued through the submit thread; nothing here waits.
 void grab_issue(uint64_t n, const WrGrabArgs& a) {
@@ -1641,18 +1666,59 @@ void grab_issue(uint64_t n, const WrGrabArgs& a) {
   // known here and is not counted)
   prof_end(WR_KIND_GRAB, a.bpp == 4 ? WR_FMT_RGBA8 : WR_FMT_R8, 0, a.packed ? 2 : a.delta ? 1 : 0, a.delta && a.keyframe && !a.packed ? 2 * rect_bytes + a.payload : 2 * rect_bytes, (uint64_t)grid);
   c->stats.kernel_launches++;
-  WrGrabPushArgs pa;
-  pa.src = gs.dev; pa.dst = gs.host; pa.capacity = (uint32_t)gs.cap;
-#ifdef WRHIP_HOSTSIM
-  WR_LAUNCH(wr_grab_push_kernel, 1, 256, c->stream, pa);
-#else
-  wrrt::event_record(&gs.ev_pack, c->stream);
-  wrrt::stream_wait_event(c->grab_stream, &gs.ev_pack);
-  if (a.delta || c->grab_full_kernel) WR_LAUNCH(wr_grab_push_kernel, c->grab_push_wgs, 256, c->grab_stream, pa);
-  else wrrt::d2h(gs.host, gs.dev, (size_t)WR_GRAB_HEADER + a.payload, c->grab_stream);
-  wrrt::event_record(&gs.ev, c->grab_stream);
-#endif
-  gs.parked = false;
+  grab_push(gs, a.payload, a.delta || c->grab_full_kernel);
+}
+// The launches of one scaled grab (WrGrabScaleArgs), now: up to WR_SCALE_STEPS halvings each, the first from the texture, every
+// later one from the level the one before it left in the scratch, whose two halves alternate; the last one fills the slot.
+static size_t grab_scale_level_bytes(const Context::GrabScaled& s, int level) {
+  return ((size_t)(s.dw << level) * (size_t)(s.dh << level) * 4 + 15) & ~(size_t)15;
+}
+// the scratch a grab needs: the levels its first and its second launch leave (a third one writes where the first did)
+static size_t grab_scale_scratch_need(const Context::GrabScaled& s) {
+  const int o0 = s.levels - std::min(WR_SCALE_STEPS, s.levels);
+  if (o0 == 0) return 0;
+  const int o1 = o0 - 1 - std::min(WR_SCALE_STEPS, o0 - 1);
+  return grab_scale_level_bytes(s, o0) + (o1 > 0 ? grab_scale_level_bytes(s, o1) : 0);
+}
+void grab_issue_scaled(uint64_t n, const Context::GrabScaled& s) {
+  Context* c = ctx;
+  Context::GrabSlot& gs = c->grab_slot[n % Context::GRAB_RING];
+  wrrt::stream_wait_event(c->stream, &gs.ev);
+  const uint32_t payload = (uint32_t)((size_t)s.dw * s.dh * 4);
+  uint8_t* const scratch = (uint8_t*)c->grab_scale_scratch;
+  const size_t second_half = grab_scale_level_bytes(s, s.levels - std::min(WR_SCALE_STEPS, s.levels));
+  uint64_t launches = 0, workgroups = 0;
+  const uint8_t* prev = nullptr;
+  prof_begin();
+  for (int top = s.levels;;) {
+    WrGrabScaleArgs a;
+    memset(&a, 0, sizeof(a));
+    a.steps = std::min(WR_SCALE_STEPS, top);
+    a.tw = s.dw << top; a.th = s.dh << top;
+    if (!prev) {
+      a.src = s.tex; a.src_stride = s.tex_stride; a.sw = s.tex_w; a.sh = s.tex_h;
+      a.rx = s.rect[0]; a.ry = s.rect[1]; a.rw = s.rect[2]; a.rh = s.rect[3];
+      // (BlitFramebuffer: equal sizes, or a source texture narrower than 2, take scale_blit's nearest stepping)
+      a.mode = !(a.rw == a.tw && a.rh == a.th) && s.tex_w >= 2 ? 0 : 1;
+    } else {
+      a.src = prev; a.sw = 2 * a.tw; a.sh = 2 * a.th; a.src_stride = 4 * a.sw;
+      a.mode = 2;
+    }
+    a.last = top == a.steps ? 1 : 0;
+    a.dst = a.last ? gs.dev + WR_GRAB_HEADER : scratch + ((launches & 1) ? second_half : 0);
+    a.slot = gs.dev; a.flip = s.flip; a.swap_rb = s.swap_rb; a.payload = payload;
+    a.tiles_x = (a.tw + WR_SCALE_TILE - 1) / WR_SCALE_TILE;
+    const int grid = a.tiles_x * ((a.th + WR_SCALE_TILE - 1) / WR_SCALE_TILE);
+    WR_LAUNCH(wr_grab_scale_kernel, grid, 256, c->stream, a);
+    launches++; workgroups += (uint64_t)grid;
+    if (a.last) break;
+    prev = a.dst;
+    top -= a.steps + 1;
+  }
+  // (15, feat 3: wr_grab_scale_kernel, all launches of the grab as one entry; the rect read once, the payload written)
+  prof_end(WR_KIND_GRAB, WR_FMT_RGBA8, 0, 3, (uint64_t)s.rect[2] * s.rect[3] * 4 + payload, workgroups);
+  c->stats.kernel_launches += launches;
+  grab_push(gs, payload, c->grab_full_kernel);
 }
 // tail_launched(): the grabs that waited for the held-back launches follow them, in the order they were made
 void grab_issue_parked() {
@@ -1669,7 +1735,8 @@ void grab_issue_parked() {
     auto st = std::find(stale.begin(), stale.end(), (const uint8_t*)p.args.keep);
     if (gs.n != p.n) { if (p.args.delta && st == stale.end()) stale.push_back(p.args.keep); continue; }
     if (p.args.delta && st != stale.end()) { p.args.keyframe = 1; gs.keyframe = true; stale.erase(st); }
-    grab_issue(p.n, p.args);
+    if (p.scaled) grab_issue_scaled(p.n, p.scale);
+    else grab_issue(p.n, p.args);
   }
   for (const uint8_t* k : stale)
     for (Texture* t : c->textures.objects) if (t && t->grab_keep == k) t->grab_valid = false;
@@ -3972,6 +4039,32 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait) {
   *out = r;
   return 0;
 }
+// The ring slot of the next ticket, holding `payload` bytes behind the header; what was recorded so far is submitted on the way.
+// Null with GL_OUT_OF_MEMORY set -- nothing flushed -- when the ring's pinned memory would pass its bound.
+static Context::GrabSlot* grab_reserve(uint64_t payload) {
+  Context* c = ctx;
+  grab_init();
+  // the pinned memory of the ring with this grab's slot grown to hold it
+  const int si = (int)(c->grab_next % Context::GRAB_RING);
+  Context::GrabSlot& gs = c->grab_slot[si];
+  const uint64_t need = (WR_GRAB_HEADER + payload + 15) & ~(uint64_t)15;
+  uint64_t pinned = 0;
+  for (const Context::GrabSlot& o : c->grab_slot) pinned += &o == &gs ? std::max<uint64_t>(o.cap, need) : o.cap;
+  if (pinned > c->grab_pinned_max || need > 0xFFFFFFF0ull) { out_of_memory(); return nullptr; }
+  // what was recorded so far goes out the way WrhipFlushHeld sends it: this flush's raster launches stay held back
+  flush_all();
+  flush_uploads(3760);
+  if (gs.cap < need) {
+    // (the slot's previous ticket may still be crossing: a grab larger than any before it waits for that, once per slot)
+    if (gs.n != ~0ull && !gs.parked) { HostTimer ht(&c->stats.host_wait_ns); wrrt::event_sync(&gs.ev); }
+    uint8_t* nd = (uint8_t*)wrrt::try_dev_alloc((size_t)need);
+    if (!nd) { out_of_memory(); return nullptr; }
+    wrrt::dev_free(gs.dev); wrrt::pinned_free(gs.host);
+    gs.n = ~0ull; gs.parked = false;
+    gs.dev = nd; gs.host = (uint8_t*)wrrt::pinned_alloc((size_t)need); gs.cap = (size_t)need;
+  }
+  return &gs;
+}
 // A grab: see include/wrhip.h.  Arguments are checked before anything is flushed or launched.
 int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint32_t flags) {
   if (!ctx) return -1;
@@ -3992,28 +4085,11 @@ int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint3
   }
   ok = ok && c->shard_world <= 1 && t->own_y0 == t->own_y1;      // (sharded targets hold a strip of the frame each: out of scope)
   if (!ok) { c->last_error = GL_INVALID_VALUE; return -1; }
-  grab_init();
   const int bx = (rects[2] + WR_GRAB_BLOCK - 1) / WR_GRAB_BLOCK, by = (rects[3] + WR_GRAB_BLOCK - 1) / WR_GRAB_BLOCK;
   if (delta) payload = (uint64_t)bx * by * WR_GRAB_ENTRY(t->bpp);
-  // the pinned memory of the ring with this grab's slot grown to hold it
-  const int si = (int)(c->grab_next % Context::GRAB_RING);
-  Context::GrabSlot& gs = c->grab_slot[si];
-  const uint64_t need = (WR_GRAB_HEADER + payload + 15) & ~(uint64_t)15;
-  uint64_t pinned = 0;
-  for (const Context::GrabSlot& o : c->grab_slot) pinned += &o == &gs ? std::max<uint64_t>(o.cap, need) : o.cap;
-  if (pinned > c->grab_pinned_max || need > 0xFFFFFFF0ull) { out_of_memory(); return -1; }
-  // what was recorded so far goes out the way WrhipFlushHeld sends it: this flush's raster launches stay held back
-  flush_all();
-  flush_uploads(3760);
-  if (gs.cap < need) {
-    // (the slot's previous ticket may still be crossing: a grab larger than any before it waits for that, once per slot)
-    if (gs.n != ~0ull && !gs.parked) { HostTimer ht(&c->stats.host_wait_ns); wrrt::event_sync(&gs.ev); }
-    uint8_t* nd = (uint8_t*)wrrt::try_dev_alloc((size_t)need);
-    if (!nd) { out_of_memory(); return -1; }
-    wrrt::dev_free(gs.dev); wrrt::pinned_free(gs.host);
-    gs.n = ~0ull; gs.parked = false;
-    gs.dev = nd; gs.host = (uint8_t*)wrrt::pinned_alloc((size_t)need); gs.cap = (size_t)need;
-  }
+  Context::GrabSlot* const slot = grab_reserve(payload);
+  if (!slot) return -1;
+  Context::GrabSlot& gs = *slot;
   WrGrabArgs a;
   memset(&a, 0, sizeof(a));
   a.tex = (const uint8_t*)t->dptr; a.tex_stride = t->stride; a.bpp = t->bpp;
@@ -4054,12 +4130,62 @@ int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint3
   gs.format = t->internal_format; gs.flags = flags; gs.bpp = t->bpp; gs.nrects = nrects;
   memcpy(gs.rects, rects, sizeof(int32_t) * 4 * nrects);
   gs.keyframe = keyframe; gs.blocks_total = delta ? (uint32_t)(bx * by) : 0;
+  gs.scaled_w = gs.scaled_h = gs.levels = 0;
   if (c->tail.pending && t->tail_ref) {
     // the held-back launches write (or read) the texture: the grab waits for them to leave, and does not make them (see WrhipTapTexture)
     gs.parked = true;
-    c->grab_parked.push_back(Context::GrabParked{n, a});
+    c->grab_parked.push_back(Context::GrabParked{n, false, a, Context::GrabScaled()});
   } else {
     grab_issue(n, a);
+  }
+  return (int32_t)(n & 0x7FFFFFFFull);
+}
+// A scaled grab: see include/wrhip.h.  Ticket ring, ordering and parking are WrhipGrabTexture's.
+int32_t WrhipGrabTextureScaled(GLuint tex, const int32_t rect[4], int32_t dst_w, int32_t dst_h, uint32_t flags) {
+  if (!ctx) return -1;
+  Context* c = ctx;
+  Texture* t = tex ? c->textures.find(tex) : nullptr;
+  bool ok = t && t->dptr && t->internal_format == GL_RGBA8 && rect;
+  ok = ok && (flags & ~(WRHIP_GRAB_FLIP_ROWS | WRHIP_GRAB_SWAP_RB)) == 0;
+  ok = ok && rect[2] >= 1 && rect[3] >= 1 && rect[0] >= 0 && rect[1] >= 0 && rect[0] <= t->width - rect[2] && rect[1] <= t->height - rect[3];
+  ok = ok && dst_w >= 1 && dst_h >= 1 && dst_w <= rect[2] && dst_h <= rect[3];
+  // the reference's chain (screen_capture.rs:270): the smallest L with w <= 2 * dw * 2^L -- the width alone decides -- and a top
+  // level it could allocate
+  const int max_size = 1 << 15;                      // GL_MAX_TEXTURE_SIZE
+  int levels = 0;
+  while (ok && (int64_t)rect[2] > ((int64_t)2 * dst_w << levels)) levels++;
+  ok = ok && ((int64_t)dst_w << levels) <= max_size && ((int64_t)dst_h << levels) <= max_size;
+  ok = ok && c->shard_world <= 1 && t->own_y0 == t->own_y1;      // (sharded targets hold a strip of the frame each: out of scope)
+  if (!ok) { c->last_error = GL_INVALID_VALUE; return -1; }
+  Context::GrabScaled s;
+  s.tex = (const uint8_t*)t->dptr; s.tex_stride = t->stride; s.tex_w = t->width; s.tex_h = t->height;
+  memcpy(s.rect, rect, sizeof(s.rect));
+  s.dw = dst_w; s.dh = dst_h; s.levels = levels;
+  s.flip = (flags & WRHIP_GRAB_FLIP_ROWS) ? 1 : 0; s.swap_rb = (flags & WRHIP_GRAB_SWAP_RB) ? 1 : 0;
+  Context::GrabSlot* const slot = grab_reserve((uint64_t)dst_w * dst_h * 4);
+  if (!slot) return -1;
+  Context::GrabSlot& gs = *slot;
+  // (the scratch only grows: a parked grab finds at least what it asked for here when it is issued)
+  const size_t scratch = grab_scale_scratch_need(s);
+  if (scratch > c->grab_scale_scratch_size) {
+    if (c->grab_scale_scratch) pool_free(c->grab_scale_scratch, c->grab_scale_scratch_size);
+    c->grab_scale_scratch = pool_alloc(scratch, &c->grab_scale_scratch_size);
+    if (!c->grab_scale_scratch) { c->grab_scale_scratch_size = 0; out_of_memory(); return -1; }
+  }
+  const uint64_t n = c->grab_next++;
+  gs.n = n; gs.counted = false;
+  gs.format = t->internal_format; gs.flags = flags | WRHIP_GRAB_SCALED; gs.bpp = t->bpp; gs.nrects = 1;
+  memcpy(gs.rects, rect, sizeof(int32_t) * 4);
+  gs.keyframe = false; gs.blocks_total = 0;
+  gs.scaled_w = dst_w; gs.scaled_h = dst_h; gs.levels = levels;
+  if (c->tail.pending && t->tail_ref) {
+    gs.parked = true;
+    Context::GrabParked p;
+    memset(&p, 0, sizeof(p));
+    p.n = n; p.scaled = true; p.scale = s;
+    c->grab_parked.push_back(p);
+  } else {
+    grab_issue_scaled(n, s);
   }
   return (int32_t)(n & 0x7FFFFFFFull);
 }
@@ -4101,7 +4227,8 @@ int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64
   if (!gs) return -1;
   const bool delta = (gs->flags & WRHIP_GRAB_DELTA) != 0;
   const int bpp = gs->bpp;
-  const int64_t tight = (int64_t)gs->rects[0][2] * bpp;
+  const bool scaled = (gs->flags & WRHIP_GRAB_SCALED) != 0;      // (one rect, delivered as scaled_h rows of scaled_w pixels)
+  const int64_t tight = (int64_t)(scaled ? gs->scaled_w : gs->rects[0][2]) * bpp;
   if (dst && dst_stride != 0 && (gs->nrects > 1 || dst_stride < tight)) { c->last_error = GL_INVALID_VALUE; return -1; }
   uint32_t payload;
   if (grab_arrived(gs, wait, &payload)) return 1;
@@ -4111,10 +4238,11 @@ int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64
   r.format = gs->format; r.flags = gs->flags; r.nrects = gs->nrects;
   memcpy(r.rects, gs->rects, sizeof(int32_t) * 4 * gs->nrects);
   r.bytes = (uint64_t)WR_GRAB_HEADER + payload;
+  r.scaled_w = gs->scaled_w; r.scaled_h = gs->scaled_h; r.levels = (uint32_t)gs->levels;
   if (!delta) {
     for (int i = 0; i < gs->nrects; i++) {
-      const size_t row = (size_t)gs->rects[i][2] * bpp;
-      const int h = gs->rects[i][3];
+      const size_t row = (size_t)(scaled ? gs->scaled_w : gs->rects[i][2]) * bpp;
+      const int h = scaled ? gs->scaled_h : gs->rects[i][3];
       if (dst) {
         const size_t ds = gs->nrects == 1 && dst_stride ? (size_t)dst_stride : row;
         // (tight rects leave as one copy: they follow each other in `dst` as they do in the slot)

@@ -32,8 +32,29 @@ __global__ void wr_upload_kernel(const WrUploadSeg* __restrict__ segs, int n_seg
 }
 #endif
 
+// linear_blit's walk over the source (composite.h:342-418): srcUV = quantize(srcReq.origin (+ size when flipped) + srcDUV *
+// (dstBounds.origin + 0.5)), stepped by srcDUV * 128 per pixel (init_interp lanes, then one add of 4 * srcDU per 4-pixel chunk)
+// and per row.  wr_blit_walk_u(i) / wr_blit_walk_v(j): the coordinates, in 1/128 texel, of column i / row j of the dest bounds.
+struct WrBlitWalk { float u0, v0, du, dv; };
+WR_DEVICE WrBlitWalk wr_blit_walk(int srx0, int sry0, int srw, int srh, int drw, int drh, int bx0, int by0, int invert_x, int invert_y) {
+  float u0 = float(srx0), v0 = float(sry0);
+  float du = float(srw) / float(drw), dv = float(srh) / float(drh);
+  if (invert_x) { u0 += float(srw); du = -du; }
+  if (invert_y) { v0 += float(srh); dv = -dv; }
+  u0 += du * (float(bx0) + 0.5f); v0 += dv * (float(by0) + 0.5f);
+  u0 = u0 * 128.0f + (0.5f - 0.5f * 128.0f); v0 = v0 * 128.0f + (0.5f - 0.5f * 128.0f);
+  du *= 128.0f; dv *= 128.0f;
+  return WrBlitWalk{u0, v0, du, dv};
+}
+WR_DEVICE float wr_blit_walk_u(const WrBlitWalk& w, int i) {
+  float lu = w.u0;
+  for (int k = 0; k < (i & 3); k++) lu = lu + w.du;
+  return wr_accum(lu, 4.0f * w.du, i >> 2);
+}
+WR_DEVICE float wr_blit_walk_v(const WrBlitWalk& w, int j) { return wr_accum(w.v0, w.dv, j); }
+
 // BlitFramebuffer with scaling / flipping / format conversion (composite.h:62-283, 285-418); one thread per dest pixel.
-#ifndef WR_INST_ONLY      /* (not a template: defined by wrhip.hip alone, not by the instantiation units wrhip_inst.hip) */
+#ifndef WR_INST_ONLY     /* (not a template: defined by wrhip.hip alone, not by the instantiation units wrhip_inst.hip) */
 __global__ void wr_blit_kernel(WrBlitArgs a) {
   const int bw = a.bx1 - a.bx0, bh = a.by1 - a.by0;
   const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -69,19 +90,9 @@ __global__ void wr_blit_kernel(WrBlitArgs a) {
     }
     return;
   }
-  // linear_blit: srcUV = quantize(srcReq.origin (+ size when flipped) + srcDUV * (dstBounds.origin + 0.5)), stepped by
-  // srcDUV * 128 per pixel (init_interp lanes, then one add of 4 * srcDU per 4-pixel chunk) and per row
-  float u0 = float(a.srx0), v0 = float(a.sry0);
-  float du = float(a.srw) / float(a.drw), dv = float(a.srh) / float(a.drh);
-  if (a.invert_x) { u0 += float(a.srw); du = -du; }
-  if (a.invert_y) { v0 += float(a.srh); dv = -dv; }
-  u0 += du * (float(a.bx0) + 0.5f); v0 += dv * (float(a.by0) + 0.5f);
-  u0 = u0 * 128.0f + (0.5f - 0.5f * 128.0f); v0 = v0 * 128.0f + (0.5f - 0.5f * 128.0f);
-  du *= 128.0f; dv *= 128.0f;
-  float lu = u0;
-  for (int k = 0; k < (i & 3); k++) lu = lu + du;
-  lu = wr_accum(lu, 4.0f * du, i >> 2);
-  const float lv = wr_accum(v0, dv, j);
+  const WrBlitWalk bw_ = wr_blit_walk(a.srx0, a.sry0, a.srw, a.srh, a.drw, a.drh, a.bx0, a.by0, a.invert_x, a.invert_y);
+  const float lu = wr_blit_walk_u(bw_, i);
+  const float lv = wr_blit_walk_v(bw_, j);
   WrTexDesc t;
   t.ptr = a.src; t.width = a.sw; t.height = a.sh; t.stride = a.sbpp == 4 ? a.src_stride / 4 : (a.sbpp == 2 ? a.src_stride / 2 : a.src_stride);
   t.format = a.sbpp == 4 ? WR_FMT_RGBA8 : WR_FMT_R8; t.linear = 1; t.sw = float(a.sw); t.sh = float(a.sh);
@@ -480,6 +491,122 @@ __global__ void __launch_bounds__(256) wr_grab_pack_runs_kernel(WrGrabArgs a) {
   else wr_grab_pack_runs<1>(a, B, t, stage, outb, lw);
 #endif
 }
+// WrhipGrabTextureScaled (include/wrhip.h; the launch: WrGrabScaleArgs): a workgroup per 64 x 64 tile of the launch's top level.
+//   coords  (modes 0, 1) the source coordinate of each of the tile's columns and rows, once, into LDS: the blit kernel's own walk
+//           (wr_blit_walk_u / _v -- wr_accum is not cheap) in mode 0, scale_blit's integer stepping in mode 1
+//   fill    the tile's pixels: thread t has pixels t, t + 256, ... in row-major order, so a wave fills a row of 64 words -- one
+//           linear_blit tap of the texture each (wr_sample_linear_rgba8: clamped at the TEXTURE's edges, plain global loads), a
+//           copied texel, or the 2 x 2 texels of the level above under the 2:1 rule (wr_bilerp_half_rgba8)
+//   halve   `steps` times, a barrier in between: level k of the tile (pitch 64 >> k words) alternates between the buffers `a`
+//           and `b`; a thread reads the 2 x 2 texels of an output as two 8-byte words.  Pitch 64: the 32 lanes of a half-wave read
+//           one whole 256-byte bank row each time -- no conflicts; the two smaller levels (a quarter and a sixteenth of the
+//           work) have rows 2 j and 2 j + 2 of the level on the same banks: 2- and 4-way.
+//   store   what is left, (64 >> steps) pixels square, cut to the level: 16-byte stores for every 4 pixels of a row that start
+//           on a 16-byte boundary of the destination, single pixels otherwise; the last launch of a grab flips the rows and
+//           exchanges R and B here and writes the slot's header.
+// Each phase is a function of the thread's number.  The device runs them with barriers between; the host simulation, whose
+// threads run one after the other, has thread 0 run each phase for every thread number in turn.
+struct WrGrabScaleTile { uint32_t a[WR_SCALE_TILE * WR_SCALE_TILE]; uint32_t b[WR_SCALE_TILE * WR_SCALE_TILE / 4]; int qx[WR_SCALE_TILE], qy[WR_SCALE_TILE]; };
+struct WrGrabScaleGeom { int x0, y0, cw, ch; };      // the workgroup's tile of the top level: origin, size cut to the level
+WR_DEVICE WrGrabScaleGeom wr_grab_scale_geom(const WrGrabScaleArgs& a, int b) {
+  WrGrabScaleGeom g;
+  g.x0 = (b % a.tiles_x) * WR_SCALE_TILE; g.y0 = (b / a.tiles_x) * WR_SCALE_TILE;
+  g.cw = wr_imin(WR_SCALE_TILE, a.tw - g.x0); g.ch = wr_imin(WR_SCALE_TILE, a.th - g.y0);
+  return g;
+}
+WR_DEVICE void wr_grab_scale_coords(const WrGrabScaleArgs& a, const WrGrabScaleGeom& g, WrGrabScaleTile& T, int t) {
+  if (a.mode == 2 || t >= 2 * WR_SCALE_TILE) return;
+  const bool row = t >= WR_SCALE_TILE;
+  const int k = row ? t - WR_SCALE_TILE : t;
+  if (k >= (row ? g.ch : g.cw)) return;
+  if (a.mode == 1) {
+    // scale_row's stepping (wr_blit_kernel): the source column of dest column X is floor(srcWidth * X / dstWidth), rows likewise
+    if (row) T.qy[k] = a.ry + int((long long)a.rh * (g.y0 + k) / a.th);
+    else T.qx[k] = a.rx + int((long long)a.rw * (g.x0 + k) / a.tw);
+    return;
+  }
+  const WrBlitWalk w = wr_blit_walk(a.rx, a.ry, a.rw, a.rh, a.tw, a.th, 0, 0, 0, 0);
+  if (row) T.qy[k] = int(wr_blit_walk_v(w, g.y0 + k));
+  else T.qx[k] = int(wr_blit_walk_u(w, g.x0 + k));
+}
+WR_DEVICE void wr_grab_scale_fill(const WrGrabScaleArgs& a, const WrGrabScaleGeom& g, WrGrabScaleTile& T, int t) {
+  WrTexDesc d;
+  d.ptr = a.src; d.width = a.sw; d.height = a.sh; d.stride = a.src_stride / 4;
+  d.format = WR_FMT_RGBA8; d.linear = 1; d.sw = float(a.sw); d.sh = float(a.sh);
+  for (int p = t; p < WR_SCALE_TILE * WR_SCALE_TILE; p += 256) {
+    const int c = p % WR_SCALE_TILE, r = p / WR_SCALE_TILE;
+    if (c >= g.cw || r >= g.ch) continue;
+    uint32_t v;
+    if (a.mode == 0) {
+      v = wr_pack(wr_sample_linear_rgba8(d, T.qx[c], T.qy[r]));
+    } else if (a.mode == 1) {
+      v = wr_load4(a.src + (size_t)T.qy[r] * a.src_stride + (size_t)T.qx[c] * 4);
+    } else {
+      const uint8_t* s = a.src + (size_t)(2 * (g.y0 + r)) * a.src_stride + (size_t)(2 * (g.x0 + c)) * 4;
+      v = wr_pack(wr_bilerp_half_rgba8(wr_load4(s), wr_load4(s + 4), wr_load4(s + a.src_stride), wr_load4(s + a.src_stride + 4)));
+    }
+    T.a[p] = v;
+  }
+}
+// level k + 1 of the tile (pitch `pitch` / 2, cw / 2 x ch / 2 pixels) from level k
+WR_DEVICE void wr_grab_scale_halve(const uint32_t* src, uint32_t* dst, int pitch, int cw, int ch, int t) {
+  const int hp = pitch / 2;
+  for (int p = t; p < hp * hp; p += 256) {
+    const int i = p % hp, j = p / hp;
+    if (i >= cw / 2 || j >= ch / 2) continue;
+    uint32_t r0[2], r1[2];
+    __builtin_memcpy(r0, __builtin_assume_aligned(src + (2 * j) * pitch + 2 * i, 8), 8);
+    __builtin_memcpy(r1, __builtin_assume_aligned(src + (2 * j + 1) * pitch + 2 * i, 8), 8);
+    dst[p] = wr_pack(wr_bilerp_half_rgba8(r0[0], r0[1], r1[0], r1[1]));
+  }
+}
+// the tile's last level (pitch `pitch`, ow x oh pixels) to its place in the launch's output level
+WR_DEVICE void wr_grab_scale_store(const WrGrabScaleArgs& a, const WrGrabScaleGeom& g, const uint32_t* src, int pitch, int t) {
+  const int lw = a.tw >> a.steps, lh = a.th >> a.steps;            // the output level
+  const int ox = g.x0 >> a.steps, oy = g.y0 >> a.steps, ow = g.cw >> a.steps, oh = g.ch >> a.steps;
+  for (int p = t; p < ow * oh; p += 256) {
+    const int c = p % ow, r = p / ow;
+    const int dr = a.last && a.flip ? lh - 1 - (oy + r) : oy + r;
+    const size_t at = (size_t)dr * lw + (size_t)(ox + c);          // in pixels; `dst` is 16-byte aligned
+    const int c4 = c - (int)(at & 3);                              // where the 16-byte piece this pixel lies in starts in the tile's row
+    const bool whole = c4 >= 0 && c4 + 4 <= ow;
+    if (whole && c != c4) continue;                                // (stored by the piece's first pixel)
+    const uint32_t* s = src + r * pitch + c;
+    if (whole) {
+      wr_u4 v{s[0], s[1], s[2], s[3]};
+      if (a.last && a.swap_rb) { v.x = wr_grab_swap(v.x); v.y = wr_grab_swap(v.y); v.z = wr_grab_swap(v.z); v.w = wr_grab_swap(v.w); }
+      wr_grab_st16(a.dst + 4 * at, v);
+    } else {
+      wr_grab_st4(a.dst + 4 * at, a.last && a.swap_rb ? wr_grab_swap(s[0]) : s[0]);
+    }
+  }
+}
+#ifdef WRHIP_HOSTSIM
+#define WR_SCALE_PHASE(call) for (int t = 0; t < 256; t++) { call; }
+#else
+#define WR_SCALE_PHASE(call) { call; } __syncthreads();
+#endif
+__global__ void __launch_bounds__(256) wr_grab_scale_kernel(WrGrabScaleArgs a) {
+  const WrGrabScaleGeom g = wr_grab_scale_geom(a, (int)blockIdx.x);
+#ifdef WRHIP_HOSTSIM
+  if (threadIdx.x != 0) return;
+  WrGrabScaleTile T;
+#else
+  __shared__ WrGrabScaleTile T;
+  const int t = (int)threadIdx.x;
+#endif
+  WR_SCALE_PHASE(wr_grab_scale_coords(a, g, T, t))
+  WR_SCALE_PHASE(wr_grab_scale_fill(a, g, T, t))
+  uint32_t* from = T.a;
+  uint32_t* to = T.b;
+  for (int k = 0; k < a.steps; k++) {
+    WR_SCALE_PHASE(wr_grab_scale_halve(from, to, WR_SCALE_TILE >> k, g.cw >> k, g.ch >> k, t))
+    uint32_t* const was = from; from = to; to = was;
+  }
+  WR_SCALE_PHASE(wr_grab_scale_store(a, g, from, WR_SCALE_TILE >> a.steps, t);
+                 if (a.last && blockIdx.x == 0 && t == 0) wr_grab_st16(a.slot, wr_u4{a.payload, 0u, 0u, 0u}))
+}
+#undef WR_SCALE_PHASE
 // The slot's header and as many bytes as its count word says, device slot -> pinned host slot, 16 bytes per store.  A small grid on
 // the grab stream: the link, not the chip, bounds it, and the raster launches of the following frames keep the CUs.
 __global__ void __launch_bounds__(256) wr_grab_push_kernel(WrGrabPushArgs a) {

@@ -3425,19 +3425,8 @@ WR_DEVICE WrWide wr_apply_color(WrWide src, const uint32_t color[2]) {
 
 // textureLinearUnpackedRGBA8 for ONE pixel (texture.h:1028-1071): 7-bit
 // fixed-point bilinear on quantised coords i = uv*size*128 + (0.5 - 64).
-WR_DEVICE WrWide wr_sample_linear_rgba8(const WrTexDesc& t, int qx, int qy) {
-  int fx = qx, fy = qy;
-  int ix = qx >> 7, iy = qy >> 7;
-  // computeRow(sampler, i) with margin 1
-  int cx = wr_clamp_coord(ix, t.width - 1), cy = wr_clamp_coord(iy, t.height);
-  const uint32_t* buf = (const uint32_t*)t.ptr;
-  size_t row0 = (size_t)cx + (size_t)cy * t.stride;
-  size_t row1 = row0 + ((iy >= 0 && iy < t.height - 1) ? t.stride : 0);
-  // computeFracX: ((frac.x & (i.x >= 0)) | overread) & 0x7F) - overread, overread = i.x > width-2 as all-ones
-  int over = ix > t.width - 2 ? -1 : 0;
-  int fracx = ((((ix >= 0) ? fx : 0) | over) & 0x7F) - over;
-  int fracy = fy & 0x7F;
-  uint32_t a0 = buf[row0], a0n = buf[row0 + 1], a1 = buf[row1], a1n = buf[row1 + 1];
+// ... its arithmetic on the four texels (a0 a0n / a1 a1n: rows iy and iy + 1, columns ix and ix + 1): rows first, then columns
+WR_DEVICE WrWide wr_bilerp_rgba8(uint32_t a0, uint32_t a0n, uint32_t a1, uint32_t a1n, int fracx, int fracy) {
   WrWide out;
   int ch[4];
   for (int c = 0; c < 4; c++) {
@@ -3451,6 +3440,23 @@ WR_DEVICE WrWide wr_sample_linear_rgba8(const WrTexDesc& t, int qx, int qy) {
   out.bg = (uint32_t(ch[0]) & 0xFFFF) | ((uint32_t(ch[1]) & 0xFFFF) << 16);
   out.ra = (uint32_t(ch[2]) & 0xFFFF) | ((uint32_t(ch[3]) & 0xFFFF) << 16);
   return out;
+}
+// (an exact 2:1 linear blit samples every destination pixel at quantised coordinate 256 * i + 64: texel 2 * i, fraction 64 / 128)
+WR_DEVICE WrWide wr_bilerp_half_rgba8(uint32_t a0, uint32_t a0n, uint32_t a1, uint32_t a1n) { return wr_bilerp_rgba8(a0, a0n, a1, a1n, 64, 64); }
+WR_DEVICE WrWide wr_sample_linear_rgba8(const WrTexDesc& t, int qx, int qy) {
+  int fx = qx, fy = qy;
+  int ix = qx >> 7, iy = qy >> 7;
+  // computeRow(sampler, i) with margin 1
+  int cx = wr_clamp_coord(ix, t.width - 1), cy = wr_clamp_coord(iy, t.height);
+  const uint32_t* buf = (const uint32_t*)t.ptr;
+  size_t row0 = (size_t)cx + (size_t)cy * t.stride;
+  size_t row1 = row0 + ((iy >= 0 && iy < t.height - 1) ? t.stride : 0);
+  // computeFracX: ((frac.x & (i.x >= 0)) | overread) & 0x7F) - overread, overread = i.x > width-2 as all-ones
+  int over = ix > t.width - 2 ? -1 : 0;
+  int fracx = ((((ix >= 0) ? fx : 0) | over) & 0x7F) - over;
+  int fracy = fy & 0x7F;
+  uint32_t a0 = buf[row0], a0n = buf[row0 + 1], a1 = buf[row1], a1n = buf[row1 + 1];
+  return wr_bilerp_rgba8(a0, a0n, a1, a1n, fracx, fracy);
 }
 
 // textureLinearUnpackedR8 for ONE pixel (texture.h:543-574): same 7-bit

@@ -734,6 +734,28 @@ struct WrGrabArgs {
   uint32_t payload;                    // full, and a keyframe: the payload's bytes (known on the host)
   int32_t rects[WR_GRAB_MAX_RECTS][4]; // x, y, w, h
 };
+// WrhipGrabTextureScaled: one launch of wr_grab_scale_kernel.  The chain of linear blits that scales a texture rect down -- a top
+// step of any ratio to level L (dw << L x dh << L), then L exact 2:1 steps to level 0 (dw x dh) -- walked tile by tile: a workgroup
+// computes a WR_SCALE_TILE x WR_SCALE_TILE tile of the launch's top level `tw` x `th` into LDS, halves it there `steps` times and
+// stores what is left.  The first launch of a grab takes its top level from the texture (mode 0: linear_blit's taps, 1: scale_blit's
+// nearest copy); a later one takes it by the 2:1 rule from the level the launch before left in HBM (mode 2).  tw and th are
+// multiples of 1 << steps, so a tile's pyramid needs no pixel of another tile.
+#define WR_SCALE_TILE 64
+#define WR_SCALE_STEPS 3             // halvings one launch may hold
+struct WrGrabScaleArgs {
+  const uint8_t* src;                  // mode 0, 1: the texture's storage (its origin); mode 2: the level above `tw` x `th`, tight rows
+  uint8_t* dst;                        // level (tw >> steps) x (th >> steps), tight rows: scratch, or the slot's payload (`last`)
+  uint8_t* slot;                       // last: the ticket's device slot, whose header the launch writes
+  int32_t src_stride;                  // bytes
+  int32_t sw, sh;                      // size of the source texture / level
+  int32_t mode;
+  int32_t rx, ry, rw, rh;              // mode 0, 1: the grabbed rect
+  int32_t tw, th;                      // the launch's top level
+  int32_t steps;                       // 0 .. WR_SCALE_STEPS
+  int32_t tiles_x;                     // tiles across: workgroup b has tile (b % tiles_x, b / tiles_x)
+  int32_t last, flip, swap_rb;         // last: rows flipped / R and B exchanged at the store
+  uint32_t payload;                    // last: the payload's bytes
+};
 struct WrGrabPushArgs {
   const uint8_t* src; uint8_t* dst;    // device slot -> pinned host slot
   uint32_t capacity;                   // of either, bytes (a multiple of 16): the count read from the slot is held to it

@@ -140,6 +140,7 @@ EXTRA_SIGNATURES = {
     "WrhipTapTexture": (i32, [u32, i32, i32, i32, i32, u32]),
     "WrhipTapResultGet": (i32, [i32, P, i32]),
     "WrhipGrabTexture": (i32, [u32, P, i32, u32]),
+    "WrhipGrabTextureScaled": (i32, [u32, P, i32, i32, u32]),
     "WrhipGrabResultGet": (i32, [i32, P, P, C.c_int64, i32]),
     "WrhipGrabPayloadGet": (i32, [i32, P, u64, P, i32]),
     "WrhipGrabDecode": (i32, [P, u64, u32, u32, i32, i32, P, C.c_int64, P, P]),
@@ -165,12 +166,14 @@ class WrhipTapResult(C.Structure):
 
 # WrhipGrabTexture flags, and the bytes that cross ahead of every grab's payload (include/wrhip.h)
 GRAB_FLIP_ROWS, GRAB_SWAP_RB, GRAB_DELTA, GRAB_KEY, GRAB_PACKED = 1, 2, 4, 8, 32
+GRAB_SCALED = 64          # reported in a scaled grab's info["flags"] (WrhipGrabTextureScaled); no flag of WrhipGrabTexture
 GRAB_MAX_RECTS, GRAB_HEADER, GRAB_BLOCK = 16, 16, 64
 
 
 class WrhipGrabInfo(C.Structure):
     _fields_ = [("status", i32), ("format", u32), ("flags", u32), ("nrects", i32), ("rects", (i32 * 4) * GRAB_MAX_RECTS),
-                ("keyframe", u32), ("blocks", u32), ("blocks_total", u32), ("damage", i32 * 4), ("bytes", u64)]
+                ("keyframe", u32), ("blocks", u32), ("blocks_total", u32), ("damage", i32 * 4), ("bytes", u64),
+                ("scaled_w", i32), ("scaled_h", i32), ("levels", u32)]
 
 
 def _as_ptr(x):
@@ -280,9 +283,21 @@ class GL:
         arr = (i32 * max(1, len(flat)))(*flat)
         return self.WrhipGrabTexture(tex, C.addressof(arr), len(rects), flags)
 
+    def grab_texture_scaled(self, tex, rect, size, flags=0):
+        """Enqueue a scaled grab (include/wrhip.h, WrhipGrabTextureScaled) of `rect` = (x, y, w, h) of the RGBA8 texture id `tex`
+        -- None: all of it -- scaled down to `size` = (width, height) as the reference's chain of linear blits scales it.
+        `flags`: GRAB_FLIP_ROWS and / or GRAB_SWAP_RB.  Returns the ticket, or -1 (GL_INVALID_VALUE / GL_OUT_OF_MEMORY is then set)."""
+        if rect is None:
+            w, h = i32(0), i32(0)
+            if not self.WrhipGetTextureSize(tex, C.byref(w), C.byref(h)):
+                w = h = i32(0)
+            rect = (0, 0, w.value, h.value)
+        arr = (i32 * 4)(*[int(v) for v in rect])
+        return self.WrhipGrabTextureScaled(tex, C.addressof(arr), int(size[0]), int(size[1]), flags)
+
     def grab_result(self, ticket, wait=True, into=None):
         """The result of a grab: (info dict, pixels).  Full mode: one array per rect ((h, w, 4) stored B, G, R, A bytes, or (h, w)
-        for R8) -- the array itself for a single rect, a list for several.  Delta mode: the caller's image `into` of the rect (a
+        for R8) -- the array itself for a single rect, a list for several.  A scaled grab: the (scaled_h, scaled_w, 4) array.  Delta mode: the caller's image `into` of the rect (a
         C-contiguous uint8 array of the rect's shape; None: a fresh one of zeros) with the sent blocks patched in.  None if the
         result has not arrived (wait=False only); a ticket the ring no longer holds raises KeyError."""
         import numpy as np
@@ -295,7 +310,9 @@ class GL:
         rects = [tuple(r.rects[i]) for i in range(r.nrects)]
         bpp = 1 if r.format == 0x8229 else 4          # GL_R8
         shape = lambda w, h: (h, w) if bpp == 1 else (h, w, 4)
-        if r.flags & GRAB_DELTA:
+        if r.flags & GRAB_SCALED:
+            pixels = buf = np.empty((r.scaled_h, r.scaled_w, 4), np.uint8)
+        elif r.flags & GRAB_DELTA:
             out = np.zeros(shape(*rects[0][2:]), np.uint8) if into is None else into
             assert out.dtype == np.uint8 and out.flags["C_CONTIGUOUS"] and out.shape == shape(*rects[0][2:]), "grab_result: `into` is not the rect's image"
             pixels, buf = out, out
@@ -309,7 +326,8 @@ class GL:
         rc = self.WrhipGrabResultGet(ticket, C.byref(r), buf.ctypes.data, 0, 1)
         assert rc == 0, rc
         info = {"status": r.status, "format": r.format, "flags": r.flags, "rects": rects, "keyframe": r.keyframe, "blocks": r.blocks,
-                "blocks_total": r.blocks_total, "damage": tuple(r.damage), "bytes": int(r.bytes)}
+                "blocks_total": r.blocks_total, "damage": tuple(r.damage), "bytes": int(r.bytes),
+                "scaled_w": r.scaled_w, "scaled_h": r.scaled_h, "levels": r.levels}
         return info, pixels
 
     def grab_payload(self, ticket, wait=True):

@@ -170,13 +170,29 @@ def render_streamed_tapped(backend_path, frames):
     return px, stats, taps
 
 
-def render_streamed_grabbed(backend_path, frames, delta=False, rect=None, packed=False):
+def screenshot_size(window_size, buffer_size):
+    """The size the reference's screenshot grabber scales a window of `window_size` = (w, h) to so that it fits a buffer of
+    `buffer_size` (screen_capture.rs:121-124): scale = min(bw / w, bh / h), each dimension times it, rounded half away from
+    zero -- all in float32, as the Rust expression evaluates it."""
+    f = np.float32
+    w, h = f(window_size[0]), f(window_size[1])
+    scale = min(f(buffer_size[0]) / w, f(buffer_size[1]) / h)
+
+    def rnd(v):
+        # (f32::round on a value >= 0: the fraction v - trunc(v) is exact, which v + 0.5 need not be)
+        t = np.trunc(v)
+        return int(t) + (1 if v - t >= f(0.5) else 0)
+    return rnd(w * scale), rnd(h * scale)
+
+
+def render_streamed_grabbed(backend_path, frames, delta=False, rect=None, packed=False, scale_to=None):
     """render_streamed_tapped with the pixels: after each frame's render `rect` of the window (None: all of it) is grabbed
     (GL.grab_texture: packed on the device in stream order behind that frame, carried to the host on the library's second
     stream) -- still nothing between the frames that drains the held-back raster launches.  Results are fetched in order as they
     arrive, and the oldest is waited for (that ticket alone) only when the ring of 8 would otherwise lose it, so any number of
     frames goes through.  delta=True: delta grabs, patched one after the other into one host image; packed=True (with delta):
-    their blocks cross in the packed form (glapi.GRAB_PACKED).
+    their blocks cross in the packed form (glapi.GRAB_PACKED).  scale_to=(w, h) (without delta): every grab is the scaled one
+    (GL.grab_texture_scaled) and every image the (h, w, 4) result.
     Returns the final window (RGBA8), the backend's statistics, the host's image of the rect after every frame's grab (stored
     bytes, B, G, R, A) and the grabs' info dicts.  libwrhip only."""
     from . import glapi
@@ -203,7 +219,11 @@ def render_streamed_grabbed(backend_path, frames, delta=False, rect=None, packed
         r.render(f)
         if len(waiting) == 8:
             fetch(True)
-        t = gl.grab_texture(window, rect, (glapi.GRAB_DELTA if delta else 0) | (glapi.GRAB_PACKED if packed else 0))
+        if scale_to is not None:
+            assert not delta, "render_streamed_grabbed: a scaled grab is a full one"
+            t = gl.grab_texture_scaled(window, rect, scale_to)
+        else:
+            t = gl.grab_texture(window, rect, (glapi.GRAB_DELTA if delta else 0) | (glapi.GRAB_PACKED if packed else 0))
         assert t >= 0, (t, gl.GetError())
         waiting.append(t)
         fetch(False)
