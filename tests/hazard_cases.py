@@ -33,11 +33,12 @@ F32 = (G.GL_RGBA, G.GL_FLOAT)
 # ---------------------------------------------------------------------------- the script runner
 
 class Script:
-    """One context and a 512 x 512 window on one backend"""
+    """One context and a window (512 x 512 unless told otherwise) on one backend"""
 
-    def __init__(self, backend_path):
+    def __init__(self, backend_path, w=W, h=H):
         self.gl = GL(backend_path)
-        self.r = Renderer(self.gl, W, H)
+        self.w, self.h = w, h
+        self.r = Renderer(self.gl, w, h)
         self.d = self.r.device
         self.wrhip = self.gl.is_wrhip
         self.keep = {}                  # result name -> TextureRef of a target read after the Finish
@@ -62,9 +63,10 @@ class Script:
         self.gb = [r._create_gpu_buffer_texture("sGpuBufferF", frame.gpu_buffer_f, G.GL_RGBA32F, G.GL_RGBA, G.GL_FLOAT),
                    r._create_gpu_buffer_texture("sGpuBufferI", frame.gpu_buffer_i, G.GL_RGBA32I, G.GL_RGBA_INTEGER, G.GL_INT)]
 
-    def draw(self, target, keep=True):
+    def draw(self, target, keep=True, valid_rect=None):
+        """A picture tile's dirty rect goes with the target (Target.dirty_rect); valid_rect: what the compositor shows of the tile"""
         if target.kind == "picture_tile":
-            self.r.draw_picture_cache_target(target)
+            self.r.draw_picture_cache_target(target, valid_rect)
         else:
             self.r.draw_offscreen_target(target)
         if self.flushes_first_draw is None:
@@ -108,10 +110,13 @@ class Script:
         return out
 
     # -- group B
-    def stream(self, frames, probe="after_frame"):
+    def stream(self, frames, probe="after_frame", tiles=()):
         """frames: [(pre, frame)]: `pre(script)` issues the writes that come before the frame (None: none).  probe: where
         WrhipFlushHeld is called, once per frame -- "after_frame", or "end_frame": ahead of the deletion of the frame's GpuBuffer
-        textures at the end of Renderer.render, for frames whose held-back launches read those (the deletion is then the write)"""
+        textures at the end of Renderer.render, for frames whose held-back launches read those (the deletion is then the write).
+        tiles: TextureRefs of targets that live across the frames -- all are read back after the last frame ("tile/<name>"), the
+        oracle's after every frame as well ("frame<k>/<name>"); libwrhip's WrhipStats are noted after every frame ("stats<k>": a frame's
+        held-back launches are not in them yet) and after the Finish ("stats_end")"""
         gl, r = self.gl, self.r
         window = gl.WrhipGetFramebufferTexture(0) if self.wrhip else 0
         tickets, held = [], []
@@ -131,18 +136,26 @@ class Script:
                 tickets.append(gl.tap_texture(window))
                 if probe == "after_frame":
                     held.append(int(gl.WrhipFlushHeld()))
+                if tiles:
+                    self.out["stats%d" % k] = dict(gl.stats())
             else:
                 self.out["frame%d" % k] = r.read_pixels().copy()
+                for ref in tiles:
+                    self.out["frame%d/%s" % (k, ref.name)] = self.d.read_texture(self.tex(ref)).copy()
         gl.Finish()
         self.out["gl_error"] = np.array(int(gl.GetError()))
         if self.wrhip:
             assert all(t >= 0 for t in tickets), tickets
             for k, t in enumerate(tickets):
                 res = gl.tap_result(t)
-                assert (res["status"], res["width"], res["height"], res["format"]) == (0, W, H, G.GL_RGBA8), res
+                assert (res["status"], res["width"], res["height"], res["format"]) == (0, self.w, self.h, G.GL_RGBA8), res
                 self.out["tap%d" % k] = np.array(res["digest"], dtype=np.uint64)
             self.out["held"] = np.array(held)
+            if tiles:
+                self.out["stats_end"] = dict(gl.stats())
         self.out["window"] = r.read_pixels().copy()
+        for ref in tiles:
+            self.out["tile/" + ref.name] = self.d.read_texture(self.tex(ref)).copy()
         r.destroy()
         return self.out
 

@@ -1278,8 +1278,15 @@ void record_clear(GLuint tex_id, bool color, uint32_t color_value, bool depth, G
     w.depth_live = true;
     dt.depth_owner = tex_id;
   }
+  // A depth clear that follows depth-writing draws of the same target (WebRender clears before it draws, and invalidates after): the
+  // depth runs of the prims that come after it are derived from the geometry of ALL the target's depth writers of the flush
+  // (wr_build_runs over WrTargetDesc::dw_first / dw_end), which knows nothing of a clear between them.  The target is flushed with
+  // the clear applied; what follows continues from the materialised depth, pixel by pixel (wr_scan_runs).
+  bool after_writers = false;
+  if (depth) for (const WrDrawDesc& e : w.draws) if ((e.flags & WR_DF_DEPTH_WRITE) && e.shader != WR_SH_CLEAR_OP) { after_writers = true; break; }
   w.draws.push_back(d);
   w.prims += 1;
+  if (after_writers) flush_all();
 }
 
 void download_texture(Texture& t) {
@@ -3154,12 +3161,18 @@ void InvalidateFramebuffer(GLenum target, GLsizei num_attachments, const GLenum*
   if (!fb || num_attachments <= 0 || !attachments) return;
   for (GLsizei i = 0; i < num_attachments; i++) {
     if (attachments[i] == GL_DEPTH_ATTACHMENT && fb->depth_attachment) {
+      // the pending draws of the target it was attached to need not leave their depth behind
+      bool pending = false;
+      if (Texture* ot = ctx->textures[fb->depth_attachment].depth_owner ? ctx->textures.find(ctx->textures[fb->depth_attachment].depth_owner) : nullptr)
+        if (ot->pending_write && ot->pending_target >= 0 && ctx->work[ot->pending_target].depth_tex == fb->depth_attachment) {
+          ctx->work[ot->pending_target].depth_live = false;
+          pending = true;
+        }
+      // ... but where they continue a target whose depth a flush in its middle has materialised, they load it when THEY are flushed:
+      // they run now, while it is still there (plan_target takes Texture::depth_materialized as it is at the flush)
+      if (pending && ctx->textures[fb->depth_attachment].depth_materialized) flush_all();
       Texture& t = ctx->textures[fb->depth_attachment];
       t.depth_cleared = false; t.depth_materialized = false;
-      // the pending draws of the target it was attached to need not leave their depth behind
-      if (Texture* ot = t.depth_owner ? ctx->textures.find(t.depth_owner) : nullptr)
-        if (ot->pending_write && ot->pending_target >= 0 && ctx->work[ot->pending_target].depth_tex == fb->depth_attachment)
-          ctx->work[ot->pending_target].depth_live = false;
     }
   }
 }

@@ -110,12 +110,14 @@ class Target:
     """A render target and its ordered draw steps."""
 
     def __init__(self, texture, kind="picture_tile", clear_color=None, clear_depth=False,
-                 clear_rect=None):
+                 clear_rect=None, dirty_rect=None):
         self.texture = texture
         self.kind = kind            # picture_tile | color | alpha | texture_cache
         self.clear_color = clear_color
         self.clear_depth = clear_depth
         self.clear_rect = clear_rect
+        self.dirty_rect = dirty_rect    # picture_tile: (x0, y0, x1, y1) in tile pixels -- the part of the tile this frame redraws, the
+                                        # rest keeps last frame's pixels (PictureCacheTarget::dirty_rect); None: all of it
         self.opaque = []            # Steps, already in draw (front-to-back) order
         self.alpha = []             # Steps, back-to-front
         self.steps = []             # generic ordered steps (non-tile targets)

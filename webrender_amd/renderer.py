@@ -146,20 +146,33 @@ class Renderer:
         """Renderer::draw_picture_cache_target + draw_alpha_batch_container (renderer/mod.rs:2669-2968).  `valid_rect`: the
         tile's valid rect in tile pixels (what the compositor shows of it: a tile at the edge of the window is only valid
         inside the window) -- the picture task's scissor rect is dirty rect & valid rect (picture.rs:5213-5217), so the
-        batches are drawn scissored to it (mod.rs:2813-2820); the clear stays unscissored while dirty == valid (mod.rs:2701-2707)."""
+        batches are drawn scissored to it (mod.rs:2813-2820); the clear stays unscissored while dirty == valid (mod.rs:2701-2707).
+        A target with a `dirty_rect` is a partial update: where it differs from the valid rect the colour + depth clear is
+        scissored to it (mod.rs:2700-2751, the clear_target arm) and the batches to dirty & valid; what lies outside keeps last
+        frame's pixels.  A dirty rect that misses the valid rect draws nothing."""
         d = self.device
         tex = self.resolve(target.texture)
+        whole = (0, 0, tex.width, tex.height)
+        valid = tuple(int(v) for v in valid_rect) if valid_rect is not None else whole
+        clear_rect, task = target.clear_rect, valid
+        if target.dirty_rect is not None:
+            dirty = tuple(int(v) for v in target.dirty_rect)
+            task = (max(dirty[0], valid[0]), max(dirty[1], valid[1]), min(dirty[2], valid[2]), min(dirty[3], valid[3]))
+            if task[2] <= task[0] or task[3] <= task[1]:
+                return
+            if dirty != valid:
+                clear_rect = (dirty[0], dirty[1], dirty[2] - dirty[0], dirty[3] - dirty[1])
         d.bind_draw_target(tex.fbo_with_depth or tex.fbo, tex.width, tex.height)
         projection = ortho(0.0, tex.width, 0.0, tex.height)
         d.enable_depth_write()
         d.set_blend(False)
-        d.clear_target(target.clear_color, 1.0, target.clear_rect)
+        d.clear_target(target.clear_color, 1.0, clear_rect)
         d.disable_depth_write()
         # draw_alpha_batch_container
-        uses_scissor = valid_rect is not None and tuple(valid_rect) != (0, 0, tex.width, tex.height)
+        uses_scissor = task != whole
         if uses_scissor:
             self.gl.Enable(G.GL_SCISSOR_TEST)
-            self._scissor = (valid_rect[0], valid_rect[1], valid_rect[2] - valid_rect[0], valid_rect[3] - valid_rect[1])
+            self._scissor = (task[0], task[1], task[2] - task[0], task[3] - task[1])
             self.gl.SetScissor(*self._scissor)
         if target.opaque:
             d.set_blend(False)
