@@ -252,7 +252,7 @@ void WrhipSetProfiling(int enabled);
  * (picture targets of a few large gradient / image prims, likewise), 11 = wr_setup_tile_rows_kernel (10 fused with the next flush's setup stage), 12 = a thin launch of the raster kernel (13: the same with the next flush's setup stage in front, wr_setup_raster_thin_kernel) (wr_raster_kernel<fmt, false, 1, feat>:
  * small levels, several workgroups per bin), 14 = wr_tap_kernel (WrhipTapTexture: fmt of the tapped texture, feat 1 against an expected texture;
  * algo_bytes: the rect's bytes, twice with an expected texture), 15 = wr_grab_pack_kernel (WrhipGrabTexture: fmt of the grabbed texture,
- * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta, feat 3: wr_grab_scale_kernel, the launches of one WrhipGrabTextureScaled; algo_bytes: bytes read plus bytes written, as far as they are known at the launch).  algo_bytes: the launch's algorithmic bytes:
+ * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta, feat 3: wr_grab_scale_kernel, the launches of one WrhipGrabTextureScaled, feat 4: wr_grab_tensor_kernel or the launches of a scaled WrhipGrabTextureTensor; algo_bytes: bytes read plus bytes written, as far as they are known at the launch).  algo_bytes: the launch's algorithmic bytes:
  * raster launches count every destination pixel they own once (twice when the target's old content is loaded) plus
  * the source texels their draws can sample; the setup stage counts instance + descriptor + record bytes.  Returns the
  * number of entries written (<= max). */
@@ -406,14 +406,64 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  * Returns -1 and sets GL_INVALID_VALUE, launching and flushing nothing, for an unknown texture, a format other than GL_RGBA8, a rect
  * that is empty or not inside `tex`, dst_w or dst_h below 1 or above the rect's, dst_w << L or dst_h << L above GL_MAX_TEXTURE_SIZE,
  * any other flag, and while sharding is on; -1 with GL_OUT_OF_MEMORY as WrhipGrabTexture.
+ *
+ * WrhipGrabTextureTensor(tex, rect, desc): a grab of ONE rect whose pixels never leave the device: they are converted into a tensor
+ * of U8, F16, BF16 or F32 elements, planes (CHW) or interleaved (HWC), in the caller's device memory `desc->dst`, and only the
+ * ticket's 16-byte header crosses to the host.  The contract -- any restatement must give the same bits:
+ *   pixels    out_w x out_h equal to the rect's size: the rect's stored bytes (GL_RGBA8 or GL_R8).  Smaller (GL_RGBA8 only): the bytes
+ *             WrhipGrabTextureScaled(tex, rect, out_w, out_h, 0) delivers -- the same level rule, top step and 2:1 steps.
+ *   channels  the stored bytes of an RGBA8 pixel are B, G, R, A.  Output channel c takes R, G, B, A in that order, or B, G, R, A with
+ *             WRHIP_TENSOR_BGR; channels == 3 drops A.  An R8 texture has the one channel (BGR changes nothing).  With FLIP_ROWS
+ *             output row r holds pixel row out_h - 1 - r.
+ *   value     U8: the byte v.  Otherwise x = (float)v * scale[c] + bias[c], a float32 multiply and a float32 add, each rounded
+ *             once, never fused.  F32 stores x; F16 and BF16 store x rounded to nearest, ties to even: F16 with subnormals (2^-25
+ *             and below give zero) and 65520 and above as infinity; a NaN stays a quiet NaN.  (webrender_amd/csrc/wr_tensor_round.h
+ *             is the two roundings as integer arithmetic; a program can include it on its own.)
+ *   address   element (c, y, x) lies at element index c * plane_stride + y * row_stride + x from `dst` (CHW), or at y * row_stride
+ *             + x * channels + c (HWC, plane_stride ignored).  A stride of 0 is the tight one: out_w (CHW) or out_w * channels (HWC)
+ *             for a row, out_h * row_stride for a plane.  Nothing but these elements is written: not the padding between rows or
+ *             planes, not a byte ahead of `dst` or behind the last element.  `dst` is aligned to the element's size.
+ *   ordering  WrhipGrabTexture's: the grab sees exactly what was issued before the call, recorded work is submitted as by
+ *             WrhipFlushHeld, nothing is waited for, and a grab of a texture the held-back launches write is parked behind them;
+ *             later writes to the texture do not change the result.
+ *   ticket    rides the grab ring with an empty payload: its arrival is the completion signal.  WrhipGrabResultGet ignores `dst`
+ *             and reports flags | WRHIP_GRAB_TENSOR, the rect, `bytes` = 16, and scaled_w, scaled_h, levels = L of a scaled grab
+ *             (all 0 of an unscaled one).  The write does NOT depend on the ticket surviving: a parked tensor grab whose ticket
+ *             the ring has overwritten (8 newer grabs) is issued all the same, and only its notification is lost -- other parked
+ *             grabs in that position are dropped.
+ *   consuming on the device  once a grab has been issued, work enqueued on WrhipGetStream() follows it.  A parked grab is issued by
+ *             whatever sends the held-back launches: the next flush, a WrhipFlushHeld() that finds nothing recorded, a waiting
+ *             WrhipGrabResultGet, WrhipDeviceFree.  The caller keeps `dst` alive until then.
+ * The unscaled grab is one launch (wr_grab_tensor_kernel: 16-byte stores where `dst` and the strides in bytes are multiples of 16,
+ * single elements otherwise); a scaled one is the scaled grab's launches, 1 + L / 4, the last of which converts as it stores.
+ * Returns -1 and sets GL_INVALID_VALUE, launching and flushing nothing, for: an unknown texture or format; channels other than 3 or
+ * 4 (RGBA8) or 1 (R8); a rect that is empty or not inside `tex`; out_w or out_h below 1 or above the rect's; scaling an R8 texture;
+ * out_w << L or out_h << L above GL_MAX_TEXTURE_SIZE; an unknown dtype, layout or flag; a NULL desc or dst; a stride below its
+ * minimum (CHW: row >= out_w, plane >= (out_h - 1) * row + out_w; HWC: row >= out_w * channels) or above 2^40; an extent in bytes
+ * above dst_bytes; a dst not aligned to its element; and while sharding is on.  -1 with GL_OUT_OF_MEMORY as WrhipGrabTexture.
+ *
+ * WrhipDeviceAlloc(bytes): device memory of this context's runtime, 16-byte aligned (host memory in the host simulation); NULL with
+ * GL_OUT_OF_MEMORY when there is none.  bytes == 0 gives a valid allocation of no usable bytes: not NULL, an address of its own,
+ * freed like any other.  WrhipDeviceFree(p): first sends what parked grabs wait behind, the grabs with it, then waits for the draw
+ * stream, then frees; NULL is ignored.  WrhipDeviceRead(dst_host, src_dev, bytes): a copy on the draw stream behind everything
+ * issued so far, waited for; held-back launches stay held -- a parked grab has not written yet: fetch its ticket first.  0, or -1
+ * for a NULL pointer.  WrhipStats::d2h_bytes grows by `bytes`.
  * Not routed through grabs: Finish, GetColorBuffer, ReadPixels.  Not supported: other formats, sharded targets; scaling other than
- * WrhipGrabTextureScaled's. */
+ * WrhipGrabTextureScaled's; delta or packed tensor grabs; gamma or colour-space conversion (values are the stored premultiplied bytes). */
 #define WRHIP_GRAB_FLIP_ROWS 1u   /* full mode: deliver the rect's last row first */
 #define WRHIP_GRAB_SWAP_RB   2u   /* full mode, RGBA8 only: bytes 0 and 2 of every pixel exchanged */
 #define WRHIP_GRAB_DELTA     4u   /* only the 64x64 blocks that differ from the previous DELTA grab of this texture and rect */
 #define WRHIP_GRAB_KEY       8u   /* with DELTA: ignore the retained copy, send every block */
 #define WRHIP_GRAB_PACKED    32u  /* with DELTA: sent blocks as SOLID / RUNS / RAW entries (the packed payload above); 16 is no flag */
 #define WRHIP_GRAB_SCALED    64u  /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureScaled ticket; no flag of WrhipGrabTexture, which rejects it */
+#define WRHIP_GRAB_TENSOR    128u /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureTensor ticket; no flag of the other grab calls, which reject it */
+#define WRHIP_TENSOR_U8   0u      /* WrhipTensorDesc::dtype */
+#define WRHIP_TENSOR_F16  1u
+#define WRHIP_TENSOR_BF16 2u
+#define WRHIP_TENSOR_F32  3u
+#define WRHIP_TENSOR_CHW  0u      /* WrhipTensorDesc::layout: planes */
+#define WRHIP_TENSOR_HWC  1u      /* interleaved */
+#define WRHIP_TENSOR_BGR  256u    /* WrhipTensorDesc::flags: keep the stored channel order B, G, R(, A); default is R, G, B(, A) */
 #define WRHIP_GRAB_MAX_RECTS 16
 #define WRHIP_GRAB_HEADER    16u  /* bytes that cross with every grab ahead of its payload (the payload's byte count) */
 typedef struct WrhipGrabInfo {
@@ -429,6 +479,19 @@ typedef struct WrhipGrabInfo {
 } WrhipGrabInfo;
 int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint32_t flags);
 int32_t WrhipGrabTextureScaled(GLuint tex, const int32_t rect[4], int32_t dst_w, int32_t dst_h, uint32_t flags);
+typedef struct WrhipTensorDesc {
+  void*    dst;                    /* device memory of this process: WrhipDeviceAlloc'd, or any pointer valid for the context's HIP runtime */
+  uint64_t dst_bytes;              /* bytes the library may write from dst on; the extent of the elements must fit */
+  int32_t  out_w, out_h;           /* the rect's size: no scaling; smaller: WrhipGrabTextureScaled's chain to out_w x out_h */
+  uint32_t dtype, layout, channels;      /* channels: 3 or 4 for GL_RGBA8, 1 for GL_R8 */
+  int64_t  row_stride, plane_stride;     /* in ELEMENTS; 0: tight */
+  float    scale[4], bias[4];      /* per OUTPUT channel; ignored for U8 */
+  uint32_t flags;                  /* WRHIP_GRAB_FLIP_ROWS and / or WRHIP_TENSOR_BGR */
+} WrhipTensorDesc;
+int32_t WrhipGrabTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTensorDesc* desc);
+void* WrhipDeviceAlloc(uint64_t bytes);
+void WrhipDeviceFree(void* p);
+int32_t WrhipDeviceRead(void* dst_host, const void* src_dev, uint64_t bytes);
 int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64_t dst_stride, int32_t wait);
 int32_t WrhipGrabPayloadGet(int32_t ticket, void* dst, uint64_t capacity, uint64_t* bytes, int32_t wait);
 int32_t WrhipGrabDecode(const void* payload, uint64_t bytes, uint32_t format, uint32_t flags, int32_t rect_w, int32_t rect_h, void* dst, int64_t dst_stride, int32_t damage[4], uint32_t* blocks);

@@ -15,10 +15,16 @@
              behind them, on the host clock, against the same chain as libwrhip ran it before -- four BlitFramebuffer calls
              (wr_blit_kernel, which has no entry in the kernel statistics: hence the host clock for both) and a full grab of
              level 0; then cfg2 streamed as in `stream`: no grab, a full grab per frame, a scaled grab per frame, frames/s
+  tensor     WrhipGrabTextureTensor: wr_grab_tensor_kernel on the 4K window by hipEvents (kind 15 feat 4; F32 CHW 3 is 33.2 MB read +
+             99.5 MB written), on noise and on the cfg2 frame; then the 4K cfg2 window -> 3 x 288 x 512 F16 (L = 2, one launch) and
+             -> 3 x 224 x 224 F16 (L = 4, two launches), 50 enqueued and one Finish on the host clock, against the path a caller has
+             without tensor grabs (BlitFramebuffer chain, WrhipGetTextureDevicePtr, torch gather / permute / cast / scale / bias /
+             cast on the draw stream); then cfg2 streamed: no grab, that path per frame, a tensor grab per frame.  With --ab the
+             parent-path lines are taken again in a child process that loads the other library
   ab         plain bench.py against another build of the library (WRHIP_LIB_PATH), alternated, no grab issued
 
 Every section runs three alternated rounds.  Needs the GPU: there is no fallback.
-  python tools/grab_bench.py [--sections pack,transport,stream,scaled] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
+  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -383,6 +389,219 @@ def section_scaled_stream(lib, frames):
         say(f"  {k:22s} " + "  ".join(f"{v:9.1f}" for v in rows[k]) + f"   frames/s   (setup_carried {carried[k][0]} of {frames} flushes)")
 
 
+# ---- tensor grabs (WrhipGrabTextureTensor) -----------------------------------------------------------------
+_MEAN, _STD = np.array([0.485, 0.456, 0.406], np.float32), np.array([0.229, 0.224, 0.225], np.float32)
+T_SCALE, T_BIAS = np.float32(1.0) / (np.float32(255.0) * _STD), -_MEAN / _STD
+T_SIZES = ((512, 288), (224, 224))              # (w, h): L = 2, one launch; L = 4, two launches
+
+
+def _levels(dw):
+    L = 0
+    while W > 2 * dw * (1 << L):
+        L += 1
+    return L
+
+
+class ParentPath:
+    """What a caller has without tensor grabs: the BlitFramebuffer chain to level 0 (L + 1 wr_blit_kernel launches through HBM),
+    WrhipFlush + WrhipGetTextureDevicePtr (the held-back launches are sent), then torch on the draw stream: channel gather,
+    permute, cast, scale, bias, cast into a batch slot.  Needs nothing a library without tensor grabs lacks."""
+
+    def __init__(self, gl, size, slots, names=0):
+        """names: the first of the texture and framebuffer names to use instead of generated ones (a context a recorded trace is
+        replayed in: the trace names objects by the numbers the generator gave when it was recorded, so nothing else may draw from it)"""
+        self.names = names
+        import torch
+        from webrender_amd.dist import DeviceArray
+        self.gl, self.torch, self.DeviceArray = gl, torch, DeviceArray
+        self.dw, self.dh = size
+        self.L = _levels(self.dw)
+        self.levels = [self._texture(self.dw << k, self.dh << k) for k in range(self.L + 1)]
+        self.stream = torch.cuda.ExternalStream(int(gl.WrhipGetStream()))
+        self.batch = torch.empty((slots, 3, self.dh, self.dw), dtype=torch.float16, device="cuda")
+        self.scale = torch.from_numpy(T_SCALE).cuda()[:, None, None]
+        self.bias = torch.from_numpy(T_BIAS).cuda()[:, None, None]
+        self.order = torch.tensor([2, 1, 0], device="cuda")
+        torch.cuda.synchronize()
+
+    def _texture(self, w, h):
+        gl = self.gl
+        if self.names:
+            tid = fbo = self.names
+            self.names += 1
+        else:
+            tid, fbo = gl.gen("GenTextures"), gl.gen("GenFramebuffers")
+        gl.ActiveTexture(G.GL_TEXTURE0)
+        gl.BindTexture(G.GL_TEXTURE_2D, tid)
+        gl.TexStorage2D(G.GL_TEXTURE_2D, 1, G.GL_RGBA8, w, h)
+        gl.BindFramebuffer(G.GL_DRAW_FRAMEBUFFER, fbo)
+        gl.FramebufferTexture2D(G.GL_DRAW_FRAMEBUFFER, G.GL_COLOR_ATTACHMENT0, G.GL_TEXTURE_2D, tid, 0)
+        gl.BindFramebuffer(G.GL_DRAW_FRAMEBUFFER, 0)
+        return (tid, fbo, w, h)
+
+    def __call__(self, k):
+        gl, torch = self.gl, self.torch
+        src = (0, 0, W, H)
+        for lv in range(self.L, -1, -1):
+            tid, fbo, w, h = self.levels[lv]
+            gl.BindFramebuffer(G.GL_READ_FRAMEBUFFER, src[1])
+            gl.BindFramebuffer(G.GL_DRAW_FRAMEBUFFER, fbo)
+            gl.BlitFramebuffer(0, 0, src[2], src[3], 0, 0, w, h, G.GL_COLOR_BUFFER_BIT, G.GL_LINEAR)
+            src = self.levels[lv]
+        gl.BindFramebuffer(G.GL_DRAW_FRAMEBUFFER, 0)
+        gl.BindFramebuffer(G.GL_READ_FRAMEBUFFER, 0)
+        gl.WrhipFlush()
+        stride = C.c_int32(0)
+        ptr = gl.WrhipGetTextureDevicePtr(self.levels[0][0], None, None, C.byref(stride))
+        raw = torch.as_tensor(self.DeviceArray(ptr, self.dh * stride.value), device="cuda")
+        with torch.cuda.stream(self.stream):
+            px = raw.view(self.dh, stride.value)[:, :self.dw * 4].reshape(self.dh, self.dw, 4)
+            x = px.index_select(2, self.order).permute(2, 0, 1).float()
+            self.batch[k % self.batch.shape[0]].copy_((x * self.scale + self.bias).half())
+
+    def slot_bits(self, k):
+        self.stream.synchronize()
+        return self.batch[k % self.batch.shape[0]].cpu().numpy().view(np.uint16)
+
+
+def section_tensor_kernel(lib, content):
+    say(f"## tensor, unscaled: wr_grab_tensor_kernel, {W}x{H} RGBA8 window of {content}, hipEvents (WrhipSetProfiling(1)), us per launch")
+    w = Window(lib, content)
+    gl = w.gl
+    cases = (("F32 CHW 3", glapi.TENSOR_F32, glapi.TENSOR_CHW, 3), ("F16 CHW 3", glapi.TENSOR_F16, glapi.TENSOR_CHW, 3),
+             ("BF16 CHW 3", glapi.TENSOR_BF16, glapi.TENSOR_CHW, 3), ("F16 HWC 3", glapi.TENSOR_F16, glapi.TENSOR_HWC, 3),
+             ("U8  CHW 3", glapi.TENSOR_U8, glapi.TENSOR_CHW, 3), ("F32 HWC 4", glapi.TENSOR_F32, glapi.TENSOR_HWC, 4))
+    buf = gl.device_alloc(W * H * 16)
+    assert buf, gl.GetError()
+    info = glapi.WrhipGrabInfo()
+
+    def grab(dtype, layout, ch):
+        t = gl.grab_texture_tensor(w.tex, None, buf, W * H * 16, dtype=dtype, layout=layout, channels=ch, scale=T_SCALE, bias=T_BIAS)
+        assert t >= 0, gl.GetError()
+        assert gl.WrhipGrabResultGet(t, C.byref(info), None, 0, 1) == 0
+    for _, dtype, layout, ch in cases:
+        for _ in range(4):
+            grab(dtype, layout, ch)
+    gl.WrhipSetProfiling(1)
+    rows, n = {}, 30
+    for rnd in range(ROUNDS):
+        for name, dtype, layout, ch in cases:
+            gl.WrhipResetStats()
+            for _ in range(n):
+                grab(dtype, layout, ch)
+            ks = [k for k in kernel_stats(gl, 15) if k.feat == 4]
+            assert len(ks) == 1 and ks[0].launches == n, [(k.feat, k.launches) for k in ks]
+            rows.setdefault(name, []).append((ks[0].ns / n / 1e3, ks[0].algo_bytes // n, ks[0].workgroups // n))
+    gl.WrhipSetProfiling(0)
+    for name, v in rows.items():
+        say(f"  {name:12s} " + "  ".join(f"{us:8.1f}" for us, _, _ in v) + f"   us   ({v[0][1] / 1e6:6.1f} MB read + written: " +
+            "  ".join(f"{b / us / 1e3:6.0f}" for us, b, _ in v) + f" GB/s; {v[0][2]} workgroups)")
+    say("  (beside: the full-mode pack, 14.2 us for 33.2 MB read + 33.2 MB written, 4.7 TB/s: DESIGN.md section 6.2)")
+    gl.device_free(buf)
+    w.close()
+
+
+def section_tensor_scaled(lib, with_tensor=True):
+    """50 enqueued, one Finish, host clock per grab: the parent path, and (with_tensor) the tensor grab"""
+    say(f"## tensor, scaled: {W}x{H} window of cfg2 -> 3 x h x w F16, 50 enqueued, one Finish, host clock, us per grab" + ("" if with_tensor else "   [THE PARENT'S LIBRARY]"))
+    w = Window(lib, "cfg2")
+    gl = w.gl
+    N = 50
+    for size in T_SIZES:
+        L = _levels(size[0])
+        pp = ParentPath(gl, size, N)
+        slot = size[0] * size[1] * 3 * 2
+        slot16 = (slot + 15) & ~15
+        buf = gl.device_alloc(slot16 * N) if with_tensor else 0
+
+        def tensor(k):
+            t = gl.grab_texture_tensor(w.tex, None, buf + (k % N) * slot16, slot, size=size, dtype=glapi.TENSOR_F16, channels=3, scale=T_SCALE, bias=T_BIAS)
+            assert t >= 0, gl.GetError()
+        kinds = [("parent path", pp)] + ([("tensor grab", tensor)] if with_tensor else [])
+        for _, fn in kinds:
+            for k in range(4):
+                fn(k)
+        gl.Finish()
+        if with_tensor:
+            mine = gl.device_read(buf, slot).view(np.uint16).reshape(3, size[1], size[0])
+            say(f"  {size[0]}x{size[1]} (L = {L}, {1 + L // 4} launch(es)): elements in which the parent path's tensor differs from the tensor grab's: {int((pp.slot_bits(0) != mine).sum())} of {mine.size}")
+        host = {}
+        for rnd in range(ROUNDS):
+            for name, fn in kinds:
+                gl.Finish()
+                pp.torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for k in range(N):
+                    fn(k)
+                gl.Finish()
+                pp.stream.synchronize()
+                host.setdefault(name, []).append((time.perf_counter() - t0) / N * 1e6)
+        for name, v in host.items():
+            say(f"    {size[0]}x{size[1]}  {name:12s} " + "  ".join(f"{us:8.1f}" for us in v))
+        if with_tensor:
+            say(f"    {size[0]}x{size[1]}  ratio parent / tensor, by round: " + "  ".join(f"{a / b:6.2f}" for a, b in zip(host["parent path"], host["tensor grab"])))
+            gl.device_free(buf)
+    w.close()
+
+
+def section_tensor_stream(lib, frames, with_tensor=True):
+    size = T_SIZES[1]
+    say(f"## tensor stream: cfg2 {W}x{H} streamed as in `stream`, {frames} frames per region, frames/s; every frame to 3 x {size[1]} x {size[0]} F16 in a batch slot" + ("" if with_tensor else "   [THE PARENT'S LIBRARY]"))
+    rec, _ = record_scene(lib, scenes.make_workload("cfg2", width=W, height=H))
+    p = ScenePlayer(lib, rec)
+    gl = glapi.GL(lib)                          # (the same loaded library and current context as the player's)
+    window = gl.WrhipGetFramebufferTexture(0)
+    N = 64
+    pp = ParentPath(gl, size, N, names=6000)
+    slot = size[0] * size[1] * 3 * 2
+    slot16 = (slot + 15) & ~15
+    buf = gl.device_alloc(slot16 * N) if with_tensor else 0
+    info = glapi.WrhipGrabInfo()
+
+    def run(kind, n):
+        t = -1
+        for k in range(n):
+            p.rp.exec(rec.stream)
+            if kind == "tensor grab":
+                t = gl.grab_texture_tensor(window, (0, 0, W, H), buf + (k % N) * slot16, slot, size=size, dtype=glapi.TENSOR_F16, channels=3, scale=T_SCALE, bias=T_BIAS)
+                assert t >= 0
+            elif kind == "parent path":
+                pp(k)
+        if t >= 0:
+            assert gl.WrhipGrabResultGet(t, C.byref(info), None, 0, 1) == 0          # (the last ticket: one stream, in order)
+        gl.Finish()
+        pp.stream.synchronize()
+    kinds = ["no grab", "parent path"] + (["tensor grab"] if with_tensor else [])
+    rows, carried = {}, {}
+    for k in kinds:
+        run(k, 10)
+    for rnd in range(ROUNDS):
+        for k in kinds:
+            gl.WrhipResetStats()
+            t0 = time.perf_counter()
+            run(k, frames)
+            dt = time.perf_counter() - t0
+            rows.setdefault(k, []).append(frames / dt)
+            carried.setdefault(k, []).append(gl.stats()["setup_carried"])
+    for k in kinds:
+        say(f"  {k:14s} " + "  ".join(f"{v:9.1f}" for v in rows[k]) + f"   frames/s   (setup_carried {carried[k][0]} of {frames} flushes)")
+    if with_tensor:
+        gl.device_free(buf)
+
+
+def section_tensor_parent(other, frames):
+    """The parent-path lines again, in a fresh process that loads the parent's library"""
+    env = dict(os.environ, WRHIP_LIB_PATH=os.path.abspath(other))
+    out = subprocess.run([sys.executable, os.path.abspath(__file__), "--sections", "tensor_parent", "--frames", str(frames), "--rounds", str(ROUNDS), "--size", f"{W}x{H}"],
+                         env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    if out.returncode != 0:
+        say(f"  the parent's library: exited with {out.returncode}: {out.stderr[-400:]}")
+        return
+    for l in out.stdout.splitlines():
+        if not l.startswith("# "):
+            say(l)
+
+
 def section_ab(other, steps, warmup):
     say(f"## ab: bench.py --gpus 1 --steps {steps} --warmup {warmup} (cfg2), this library against {os.path.basename(other)}, alternated, frames/s")
     rows = {"parent": [], "this": []}
@@ -421,6 +640,9 @@ def main():
     if args.size:
         W, H = (int(v) for v in args.size.split("x"))
     lib = glapi.wrhip_path()
+    if "tensor" in args.sections:
+        import torch                            # (torch brings its own HIP runtime: it has to initialise the device before libwrhip does)
+        torch.cuda.init()
     w = Window(lib)
     say(f"# grab_bench: {w.gl.WrhipDeviceName().decode() if w.gl.WrhipDeviceName() else 'no device'}; {ROUNDS} alternated rounds per line")
     w.close()
@@ -437,6 +659,16 @@ def main():
                 section_scaled(lib, "noise")
                 section_scaled(lib, "cfg2")
                 section_scaled_stream(lib, args.frames)
+            elif s == "tensor":
+                section_tensor_kernel(lib, "noise")
+                section_tensor_kernel(lib, "cfg2")
+                section_tensor_scaled(lib)
+                section_tensor_stream(lib, args.frames)
+                if args.ab:
+                    section_tensor_parent(args.ab, args.frames)
+            elif s == "tensor_parent":          # (run by `tensor` with WRHIP_LIB_PATH set: the parent path alone, on that library)
+                section_tensor_scaled(lib, with_tensor=False)
+                section_tensor_stream(lib, args.frames, with_tensor=False)
         if args.ab:
             section_ab(args.ab, args.steps, args.warmup)
     finally:

@@ -670,7 +670,11 @@ struct Context {
   // WrhipGrabTextureScaled as it was asked for; its launches are laid out when it is issued (grab_issue_scaled), since the levels
   // that go through HBM live in a scratch that may have grown by then
   struct GrabScaled { const uint8_t* tex; int32_t tex_stride, tex_w, tex_h, rect[4], dw, dh, levels, flip, swap_rb; };
-  struct GrabParked { uint64_t n; bool scaled; WrGrabArgs args; GrabScaled scale; };
+  // WrhipGrabTextureTensor: the unscaled launch as it goes out (`args`; its slot is filled in when it is issued), or -- `scaled` --
+  // the chain of a scaled grab (`scale`) whose last launch stores the elements `out` describes
+  struct GrabTensor { bool scaled; WrGrabTensorArgs args; GrabScaled scale; WrTensorOut out; uint64_t out_bytes; };
+  enum GrabKind { GRAB_PLAIN = 0, GRAB_SCALED = 1, GRAB_TENSOR = 2 };
+  struct GrabParked { uint64_t n; GrabKind kind; WrGrabArgs args; GrabScaled scale; GrabTensor tensor; };
   GrabSlot grab_slot[GRAB_RING];
   uint64_t grab_next = 0;
   std::vector<GrabParked> grab_parked;
@@ -1687,16 +1691,15 @@ static size_t grab_scale_scratch_need(const Context::GrabScaled& s) {
   const int o1 = o0 - 1 - std::min(WR_SCALE_STEPS, o0 - 1);
   return grab_scale_level_bytes(s, o0) + (o1 > 0 ? grab_scale_level_bytes(s, o1) : 0);
 }
-void grab_issue_scaled(uint64_t n, const Context::GrabScaled& s) {
+// -> launches; *workgroups: their sum.  `tensor`: the last launch is wr_grab_scale_tensor_kernel and stores its elements (slot: the
+// ticket's, or null when the ticket is gone); otherwise it fills the payload of `slot`.
+static uint64_t grab_scale_launches(const Context::GrabScaled& s, uint8_t* slot, uint32_t payload, const WrTensorOut* tensor, uint64_t* workgroups) {
   Context* c = ctx;
-  Context::GrabSlot& gs = c->grab_slot[n % Context::GRAB_RING];
-  wrrt::stream_wait_event(c->stream, &gs.ev);
-  const uint32_t payload = (uint32_t)((size_t)s.dw * s.dh * 4);
   uint8_t* const scratch = (uint8_t*)c->grab_scale_scratch;
   const size_t second_half = grab_scale_level_bytes(s, s.levels - std::min(WR_SCALE_STEPS, s.levels));
-  uint64_t launches = 0, workgroups = 0;
+  uint64_t launches = 0;
   const uint8_t* prev = nullptr;
-  prof_begin();
+  *workgroups = 0;
   for (int top = s.levels;;) {
     WrGrabScaleArgs a;
     memset(&a, 0, sizeof(a));
@@ -1712,20 +1715,62 @@ void grab_issue_scaled(uint64_t n, const Context::GrabScaled& s) {
       a.mode = 2;
     }
     a.last = top == a.steps ? 1 : 0;
-    a.dst = a.last ? gs.dev + WR_GRAB_HEADER : scratch + ((launches & 1) ? second_half : 0);
-    a.slot = gs.dev; a.flip = s.flip; a.swap_rb = s.swap_rb; a.payload = payload;
     a.tiles_x = (a.tw + WR_SCALE_TILE - 1) / WR_SCALE_TILE;
     const int grid = a.tiles_x * ((a.th + WR_SCALE_TILE - 1) / WR_SCALE_TILE);
-    WR_LAUNCH(wr_grab_scale_kernel, grid, 256, c->stream, a);
-    launches++; workgroups += (uint64_t)grid;
+    if (a.last && tensor) {
+      WrGrabScaleTensorArgs ta;
+      a.slot = slot;
+      ta.s = a; ta.o = *tensor;
+      WR_LAUNCH(wr_grab_scale_tensor_kernel, grid, 256, c->stream, ta);
+    } else {
+      a.dst = a.last ? slot + WR_GRAB_HEADER : scratch + ((launches & 1) ? second_half : 0);
+      a.slot = slot; a.flip = s.flip; a.swap_rb = s.swap_rb; a.payload = payload;
+      WR_LAUNCH(wr_grab_scale_kernel, grid, 256, c->stream, a);
+    }
+    launches++; *workgroups += (uint64_t)grid;
     if (a.last) break;
     prev = a.dst;
     top -= a.steps + 1;
   }
+  return launches;
+}
+void grab_issue_scaled(uint64_t n, const Context::GrabScaled& s) {
+  Context* c = ctx;
+  Context::GrabSlot& gs = c->grab_slot[n % Context::GRAB_RING];
+  wrrt::stream_wait_event(c->stream, &gs.ev);
+  const uint32_t payload = (uint32_t)((size_t)s.dw * s.dh * 4);
+  uint64_t workgroups = 0;
+  prof_begin();
+  const uint64_t launches = grab_scale_launches(s, gs.dev, payload, nullptr, &workgroups);
   // (15, feat 3: wr_grab_scale_kernel, all launches of the grab as one entry; the rect read once, the payload written)
   prof_end(WR_KIND_GRAB, WR_FMT_RGBA8, 0, 3, (uint64_t)s.rect[2] * s.rect[3] * 4 + payload, workgroups);
   c->stats.kernel_launches += launches;
   grab_push(gs, payload, c->grab_full_kernel);
+}
+// One tensor grab, now: the slot's previous ticket first, as for every grab, then the launches -- the last (or only) one writes the
+// header of an empty payload -- and the transport of those 16 bytes, whose arrival tells the host that the tensor is written.
+// notify == false: the ticket has been overwritten while the grab was parked; the tensor is written all the same, nobody is told.
+void grab_issue_tensor(uint64_t n, const Context::GrabTensor& g, bool notify) {
+  Context* c = ctx;
+  Context::GrabSlot& gs = c->grab_slot[n % Context::GRAB_RING];
+  if (notify) wrrt::stream_wait_event(c->stream, &gs.ev);
+  uint8_t* const slot = notify ? gs.dev : nullptr;
+  uint64_t launches = 1, workgroups = 0, rect_bytes;
+  prof_begin();
+  if (g.scaled) {
+    launches = grab_scale_launches(g.scale, slot, 0, &g.out, &workgroups);
+    rect_bytes = (uint64_t)g.scale.rect[2] * g.scale.rect[3] * 4;
+  } else {
+    WrGrabTensorArgs a = g.args;
+    a.slot = slot;
+    workgroups = (uint64_t)((a.o.oh + a.rows_per_wg - 1) / a.rows_per_wg);
+    WR_LAUNCH(wr_grab_tensor_kernel, (int)workgroups, 256, c->stream, a);
+    rect_bytes = (uint64_t)a.o.ow * a.o.oh * a.bpp;
+  }
+  // (15, feat 4: wr_grab_tensor_kernel, or the launches of a scaled tensor grab as one entry; the rect read once, the elements written)
+  prof_end(WR_KIND_GRAB, g.args.bpp == 4 ? WR_FMT_RGBA8 : WR_FMT_R8, 0, 4, rect_bytes + g.out_bytes, workgroups);
+  c->stats.kernel_launches += launches;
+  if (notify) grab_push(gs, 0, false);
 }
 // tail_launched(): the grabs that waited for the held-back launches follow them, in the order they were made
 void grab_issue_parked() {
@@ -1740,9 +1785,11 @@ void grab_issue_parked() {
   for (Context::GrabParked& p : parked) {
     Context::GrabSlot& gs = c->grab_slot[p.n % Context::GRAB_RING];
     auto st = std::find(stale.begin(), stale.end(), (const uint8_t*)p.args.keep);
+    // (a tensor grab writes the caller's memory, not the slot: it goes out with or without its ticket)
+    if (p.kind == Context::GRAB_TENSOR) { grab_issue_tensor(p.n, p.tensor, gs.n == p.n); continue; }
     if (gs.n != p.n) { if (p.args.delta && st == stale.end()) stale.push_back(p.args.keep); continue; }
     if (p.args.delta && st != stale.end()) { p.args.keyframe = 1; gs.keyframe = true; stale.erase(st); }
-    if (p.scaled) grab_issue_scaled(p.n, p.scale);
+    if (p.kind == Context::GRAB_SCALED) grab_issue_scaled(p.n, p.scale);
     else grab_issue(p.n, p.args);
   }
   for (const uint8_t* k : stale)
@@ -4147,7 +4194,7 @@ int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint3
   if (c->tail.pending && t->tail_ref) {
     // the held-back launches write (or read) the texture: the grab waits for them to leave, and does not make them (see WrhipTapTexture)
     gs.parked = true;
-    c->grab_parked.push_back(Context::GrabParked{n, false, a, Context::GrabScaled()});
+    c->grab_parked.push_back(Context::GrabParked{n, Context::GRAB_PLAIN, a, Context::GrabScaled(), Context::GrabTensor()});
   } else {
     grab_issue(n, a);
   }
@@ -4195,12 +4242,126 @@ int32_t WrhipGrabTextureScaled(GLuint tex, const int32_t rect[4], int32_t dst_w,
     gs.parked = true;
     Context::GrabParked p;
     memset(&p, 0, sizeof(p));
-    p.n = n; p.scaled = true; p.scale = s;
+    p.n = n; p.kind = Context::GRAB_SCALED; p.scale = s;
     c->grab_parked.push_back(p);
   } else {
     grab_issue_scaled(n, s);
   }
   return (int32_t)(n & 0x7FFFFFFFull);
+}
+// A tensor grab: see include/wrhip.h.  Ticket ring, ordering and parking are WrhipGrabTexture's; the payload is empty.
+int32_t WrhipGrabTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTensorDesc* desc) {
+  if (!ctx) return -1;
+  Context* c = ctx;
+  Texture* t = tex ? c->textures.find(tex) : nullptr;
+  bool ok = t && t->dptr && (t->internal_format == GL_RGBA8 || t->internal_format == GL_R8) && rect && desc && desc->dst;
+  ok = ok && (t->internal_format == GL_RGBA8 ? desc->channels == 3 || desc->channels == 4 : desc->channels == 1);
+  ok = ok && desc->dtype <= WRHIP_TENSOR_F32 && desc->layout <= WRHIP_TENSOR_HWC && (desc->flags & ~(WRHIP_GRAB_FLIP_ROWS | WRHIP_TENSOR_BGR)) == 0;
+  ok = ok && rect[2] >= 1 && rect[3] >= 1 && rect[0] >= 0 && rect[1] >= 0 && rect[0] <= t->width - rect[2] && rect[1] <= t->height - rect[3];
+  ok = ok && desc->out_w >= 1 && desc->out_h >= 1 && desc->out_w <= rect[2] && desc->out_h <= rect[3];
+  const bool scaled = ok && !(desc->out_w == rect[2] && desc->out_h == rect[3]);
+  ok = ok && (!scaled || t->internal_format == GL_RGBA8);
+  // (a scaled one: WrhipGrabTextureScaled's level rule and its bound on the top level)
+  const int max_size = 1 << 15;                      // GL_MAX_TEXTURE_SIZE
+  int levels = 0;
+  while (ok && scaled && (int64_t)rect[2] > ((int64_t)2 * desc->out_w << levels)) levels++;
+  ok = ok && ((int64_t)desc->out_w << levels) <= max_size && ((int64_t)desc->out_h << levels) <= max_size;
+  // the elements: strides (0: tight) no smaller than what they step over, the extent inside dst_bytes, dst aligned to an element
+  const int64_t elem = ok ? (desc->dtype == WRHIP_TENSOR_U8 ? 1 : desc->dtype == WRHIP_TENSOR_F32 ? 4 : 2) : 1;
+  const int64_t stride_max = (int64_t)1 << 40;       // (keeps every product below in 64 bits)
+  int64_t row = 0, plane = 0, extent = 0;
+  if (ok) {
+    const int64_t ow = desc->out_w, oh = desc->out_h, ch = desc->channels;
+    const bool hwc = desc->layout == WRHIP_TENSOR_HWC;
+    const int64_t row_min = hwc ? ow * ch : ow;
+    row = desc->row_stride ? desc->row_stride : row_min;
+    plane = hwc ? 0 : desc->plane_stride ? desc->plane_stride : oh * row;
+    ok = row >= row_min && row <= stride_max && (hwc || (plane >= (oh - 1) * row + ow && plane <= stride_max));
+    extent = hwc ? (oh - 1) * row + ow * ch : (ch - 1) * plane + (oh - 1) * row + ow;
+    ok = ok && (uint64_t)(extent * elem) <= desc->dst_bytes && ((uintptr_t)desc->dst & (uintptr_t)(elem - 1)) == 0;
+  }
+  ok = ok && c->shard_world <= 1 && t->own_y0 == t->own_y1;      // (sharded targets hold a strip of the frame each: out of scope)
+  if (!ok) { c->last_error = GL_INVALID_VALUE; return -1; }
+  Context::GrabTensor g;
+  memset(&g, 0, sizeof(g));
+  WrTensorOut& o = g.out;
+  o.dst = (uint8_t*)desc->dst; o.row_stride = row; o.plane_stride = plane;
+  o.ow = desc->out_w; o.oh = desc->out_h;
+  o.dtype = (int32_t)desc->dtype; o.hwc = desc->layout == WRHIP_TENSOR_HWC ? 1 : 0; o.channels = (int32_t)desc->channels;
+  o.flip = (desc->flags & WRHIP_GRAB_FLIP_ROWS) ? 1 : 0;
+  o.vec = ((uintptr_t)o.dst & 15) == 0 && (row * elem) % 16 == 0 && (o.hwc || (plane * elem) % 16 == 0) ? 1 : 0;
+  for (int k = 0; k < 4; k++) {
+    // (stored bytes: B, G, R, A; an R8 texture has the one)
+    o.shift[k] = t->bpp == 1 ? 0 : (desc->flags & WRHIP_TENSOR_BGR) || k == 3 ? 8 * k : 8 * (2 - k);
+    o.scale[k] = desc->scale[k]; o.bias[k] = desc->bias[k];
+  }
+  g.scaled = scaled;
+  g.out_bytes = (uint64_t)o.ow * o.oh * o.channels * (uint64_t)elem;
+  g.args.bpp = t->bpp;
+  if (scaled) {
+    Context::GrabScaled& s = g.scale;
+    s.tex = (const uint8_t*)t->dptr; s.tex_stride = t->stride; s.tex_w = t->width; s.tex_h = t->height;
+    memcpy(s.rect, rect, sizeof(s.rect));
+    s.dw = o.ow; s.dh = o.oh; s.levels = levels;
+  } else {
+    WrGrabTensorArgs& a = g.args;
+    a.tex = (const uint8_t*)t->dptr; a.tex_stride = t->stride; a.rx = rect[0]; a.ry = rect[1];
+    a.o = o;
+    // (a workgroup per 1024 items -- groups of 16 bytes of a plane, or single pixels -- or per row, if a row has more)
+    const int per16 = 16 / (int)elem;
+    const int per_row = o.vec ? o.ow / per16 + o.ow % per16 : o.ow;
+    a.rows_per_wg = std::max(1, std::min(o.oh, 1024 / per_row));
+  }
+  Context::GrabSlot* const slot = grab_reserve(0);
+  if (!slot) return -1;
+  Context::GrabSlot& gs = *slot;
+  // (the scratch only grows: a parked grab finds at least what it asked for here when it is issued)
+  const size_t scratch = scaled ? grab_scale_scratch_need(g.scale) : 0;
+  if (scratch > c->grab_scale_scratch_size) {
+    if (c->grab_scale_scratch) pool_free(c->grab_scale_scratch, c->grab_scale_scratch_size);
+    c->grab_scale_scratch = pool_alloc(scratch, &c->grab_scale_scratch_size);
+    if (!c->grab_scale_scratch) { c->grab_scale_scratch_size = 0; out_of_memory(); return -1; }
+  }
+  const uint64_t n = c->grab_next++;
+  gs.n = n; gs.counted = false;
+  gs.format = t->internal_format; gs.flags = desc->flags | WRHIP_GRAB_TENSOR; gs.bpp = t->bpp; gs.nrects = 1;
+  memcpy(gs.rects, rect, sizeof(int32_t) * 4);
+  gs.keyframe = false; gs.blocks_total = 0;
+  gs.scaled_w = scaled ? o.ow : 0; gs.scaled_h = scaled ? o.oh : 0; gs.levels = levels;
+  if (c->tail.pending && t->tail_ref) {
+    gs.parked = true;
+    Context::GrabParked p;
+    memset(&p, 0, sizeof(p));
+    p.n = n; p.kind = Context::GRAB_TENSOR; p.tensor = g;
+    c->grab_parked.push_back(p);
+  } else {
+    grab_issue_tensor(n, g, true);
+  }
+  return (int32_t)(n & 0x7FFFFFFFull);
+}
+// Device memory for tensor grabs: see include/wrhip.h
+void* WrhipDeviceAlloc(uint64_t bytes) {
+  if (!ctx) return nullptr;
+  void* p = wrrt::try_dev_alloc((size_t)bytes);
+  if (!p) out_of_memory();
+  return p;
+}
+void WrhipDeviceFree(void* p) {
+  if (!ctx || !p) return;
+  Context* c = ctx;
+  // a parked grab may write it: what it is parked behind goes out, the grab with it; then everything on the stream completes
+  if (!c->grab_parked.empty()) drain_tail();
+  { HostTimer ht(&c->stats.host_wait_ns); wrrt::stream_sync(c->stream); }
+  wrrt::dev_free(p);
+}
+int32_t WrhipDeviceRead(void* dst_host, const void* src_dev, uint64_t bytes) {
+  if (!ctx || (bytes && (!dst_host || !src_dev))) return -1;
+  Context* c = ctx;
+  if (!bytes) return 0;
+  wrrt::d2h(dst_host, src_dev, (size_t)bytes, c->stream);
+  { HostTimer ht(&c->stats.host_wait_ns); wrrt::stream_sync(c->stream); }
+  c->stats.d2h_bytes += bytes;
+  return 0;
 }
 // The ticket's bytes in its pinned slot: 0 with *payload their count behind the header, 1 if they have not arrived (wait == 0 only)
 static int32_t grab_arrived(Context::GrabSlot* gs, int32_t wait, uint32_t* payload) {
@@ -4241,6 +4402,8 @@ int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64
   const bool delta = (gs->flags & WRHIP_GRAB_DELTA) != 0;
   const int bpp = gs->bpp;
   const bool scaled = (gs->flags & WRHIP_GRAB_SCALED) != 0;      // (one rect, delivered as scaled_h rows of scaled_w pixels)
+  const bool tensor = (gs->flags & WRHIP_GRAB_TENSOR) != 0;      // (nothing to deliver: the elements are in the caller's device memory)
+  if (tensor) dst = nullptr;
   const int64_t tight = (int64_t)(scaled ? gs->scaled_w : gs->rects[0][2]) * bpp;
   if (dst && dst_stride != 0 && (gs->nrects > 1 || dst_stride < tight)) { c->last_error = GL_INVALID_VALUE; return -1; }
   uint32_t payload;

@@ -606,6 +606,162 @@ __global__ void __launch_bounds__(256) wr_grab_scale_kernel(WrGrabScaleArgs a) {
   WR_SCALE_PHASE(wr_grab_scale_store(a, g, from, WR_SCALE_TILE >> a.steps, t);
                  if (a.last && blockIdx.x == 0 && t == 0) wr_grab_st16(a.slot, wr_u4{a.payload, 0u, 0u, 0u}))
 }
+
+// WrhipGrabTextureTensor (include/wrhip.h; WrTensorOut): the pixels of a grab stored as tensor elements in the caller's memory.
+// The pack kernel writes the bytes it reads; this writes 1 x (U8, 3 channels) to 4 x (F32, 4 channels) of them, so the work is cut
+// along the DESTINATION: a thread owns a group of G = 16 / element size consecutive pixels of one output row (4 for F32, 8 for F16
+// and BF16, 16 for U8) and stores 16 bytes per plane (CHW) or `channels` x 16 contiguous bytes (HWC).  That holds where dst and the
+// byte strides are multiples of 16 (WrTensorOut::vec): groups count from the row's start, the row's last w % G pixels leave as
+// single elements, a thread per pixel.  Any other geometry takes single elements throughout.  The formats and channel counts are
+// template parameters, so that a group's pixels and words stay in registers under constant indices; the kernels branch on them once.
+#include "wr_tensor_round.h"
+constexpr int wr_tensor_elem(int dt) { return dt == WR_TENSOR_U8 ? 1 : dt == WR_TENSOR_F32 ? 4 : 2; }
+// the bits of output channel c of the pixel whose stored word is px
+template <int DT> WR_DEVICE uint32_t wr_tensor_bits(const WrTensorOut& o, uint32_t px, int c) {
+  const uint32_t v = (px >> o.shift[c]) & 0xFFu;
+  if (DT == WR_TENSOR_U8) return v;
+  const float x = (float)v * o.scale[c] + o.bias[c];      // (two roundings: the build does not contract them)
+  uint32_t u;
+  __builtin_memcpy(&u, &x, 4);
+  if (DT == WR_TENSOR_F32) return u;
+#ifdef WRHIP_HOSTSIM
+  return DT == WR_TENSOR_F16 ? wr_f32_to_f16_bits(u) : wr_f32_to_bf16_bits(u);
+#else
+  // (the device's own converts round as wr_tensor_round.h does -- nearest even, f16 subnormals kept, overflow to infinity; the tests
+  // compare them with numpy bit for bit.  As integer arithmetic the f16 rounding made the F16 grab of a 4K window VALU-bound)
+  uint16_t h;
+  if (DT == WR_TENSOR_F16) { const _Float16 f = (_Float16)x; __builtin_memcpy(&h, &f, 2); }
+  else { const __bf16 f = (__bf16)x; __builtin_memcpy(&h, &f, 2); }
+  return h;
+#endif
+}
+// one pixel, element by element
+template <int DT> WR_DEVICE void wr_tensor_put_pixel(const WrTensorOut& o, int y, int x, uint32_t px) {
+  constexpr int E = wr_tensor_elem(DT);
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    if (c < o.channels) {
+      const long long e = o.hwc ? (long long)y * o.row_stride + (long long)x * o.channels + c : c * o.plane_stride + (long long)y * o.row_stride + x;
+      const uint32_t b = wr_tensor_bits<DT>(o, px, c);
+      uint8_t* p = o.dst + e * E;
+      if (E == 1) *p = (uint8_t)b;
+      else if (E == 2) *(uint16_t*)p = (uint16_t)b;
+      else *(uint32_t*)p = b;
+    }
+  }
+}
+// the group of G pixels px[0 .. G) that starts at x0, a multiple of G, of output row y (WrTensorOut::vec)
+template <int DT, int CH> WR_DEVICE void wr_tensor_put_group(const WrTensorOut& o, int y, int x0, const uint32_t* px) {
+  constexpr int E = wr_tensor_elem(DT), G = 16 / E;
+#pragma unroll
+  for (int k = 0; k < CH; k++) {
+    // HWC: the k-th 16 bytes of the group's G * CH elements, pixel after pixel; CHW: plane k
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < G; i++) {
+      const int j = k * G + i;
+      const uint32_t b = o.hwc ? wr_tensor_bits<DT>(o, px[j / CH], j % CH) : wr_tensor_bits<DT>(o, px[i], k);
+      w[i * E / 4] |= b << (8 * (i * E % 4));
+    }
+    const long long e = o.hwc ? (long long)y * o.row_stride + (long long)x0 * CH + k * G : k * o.plane_stride + (long long)y * o.row_stride + x0;
+    wr_grab_st16(o.dst + e * E, wr_u4{w[0], w[1], w[2], w[3]});
+  }
+}
+template <int DT> WR_DEVICE void wr_tensor_put_group_ch(const WrTensorOut& o, int y, int x0, const uint32_t* px) {
+  if (o.channels == 4) wr_tensor_put_group<DT, 4>(o, y, x0, px);
+  else if (o.channels == 3) wr_tensor_put_group<DT, 3>(o, y, x0, px);
+  else wr_tensor_put_group<DT, 1>(o, y, x0, px);
+}
+// output rows [r0, r1) of the unscaled grab, thread t of nt: a row's whole groups, then its single pixels, the rows laid end to end.
+// Source pixels are 4-byte loads -- coalesced across the wave whatever the rect's x is --, 16-byte ones where the group's are aligned.
+template <int DT> WR_DEVICE void wr_grab_tensor_rows(const WrGrabTensorArgs& a, int r0, int r1, int t, int nt) {
+  constexpr int G = 16 / wr_tensor_elem(DT);
+  const WrTensorOut& o = a.o;
+  const int w = o.ow, ng = o.vec ? w / G : 0, per_row = ng + (w - ng * G);
+  const int items = (r1 - r0) * per_row;
+  for (int it = t; it < items; it += nt) {
+    const int y = r0 + it / per_row, i = it % per_row;
+    const uint8_t* ps = a.tex + (size_t)(a.ry + (o.flip ? o.oh - 1 - y : y)) * a.tex_stride + (size_t)a.rx * a.bpp;
+    if (i < ng) {
+      uint32_t px[G];
+      const uint8_t* p = ps + (size_t)i * G * a.bpp;
+      if (a.bpp != 4) {
+#pragma unroll
+        for (int k = 0; k < G; k++) px[k] = p[k];
+      } else if (((uintptr_t)p & 15) == 0) {
+#pragma unroll
+        for (int q = 0; q < G / 4; q++) { const wr_u4 v = wr_load16(p + 16 * q); px[4 * q] = v.x; px[4 * q + 1] = v.y; px[4 * q + 2] = v.z; px[4 * q + 3] = v.w; }
+      } else {
+#pragma unroll
+        for (int k = 0; k < G; k++) px[k] = wr_load4(p + 4 * k);
+      }
+      wr_tensor_put_group_ch<DT>(o, y, i * G, px);
+    } else {
+      const int x = ng * G + (i - ng);
+      wr_tensor_put_pixel<DT>(o, y, x, a.bpp == 4 ? wr_load4(ps + (size_t)x * 4) : (uint32_t)ps[x]);
+    }
+  }
+}
+__global__ void __launch_bounds__(256) wr_grab_tensor_kernel(WrGrabTensorArgs a) {
+  const int t = (int)threadIdx.x;
+  // (the ticket's header: an empty payload)
+  if (a.slot && blockIdx.x == 0 && t == 0) wr_grab_st16(a.slot, wr_u4{0u, 0u, 0u, 0u});
+  const int r0 = (int)blockIdx.x * a.rows_per_wg, r1 = wr_imin(a.o.oh, r0 + a.rows_per_wg);
+  if (a.o.dtype == WR_TENSOR_F32) wr_grab_tensor_rows<WR_TENSOR_F32>(a, r0, r1, t, (int)blockDim.x);
+  else if (a.o.dtype == WR_TENSOR_F16) wr_grab_tensor_rows<WR_TENSOR_F16>(a, r0, r1, t, (int)blockDim.x);
+  else if (a.o.dtype == WR_TENSOR_BF16) wr_grab_tensor_rows<WR_TENSOR_BF16>(a, r0, r1, t, (int)blockDim.x);
+  else wr_grab_tensor_rows<WR_TENSOR_U8>(a, r0, r1, t, (int)blockDim.x);
+}
+// The scaled grab's last launch with a converting store: the tile's last level (wr_grab_scale_store's geometry) leaves as elements --
+// a thread per group of the OUTPUT row's grid that lies whole inside the tile's row, single pixels otherwise (a tile's row is
+// (64 >> steps) pixels at most: 8 after three halvings, shorter than U8's group).
+template <int DT> WR_DEVICE void wr_grab_scale_store_tensor(const WrGrabScaleArgs& a, const WrTensorOut& o, const WrGrabScaleGeom& g, const uint32_t* src, int pitch, int t) {
+  constexpr int G = 16 / wr_tensor_elem(DT);
+  const int ox = g.x0 >> a.steps, oy = g.y0 >> a.steps, ow = g.cw >> a.steps, oh = g.ch >> a.steps;
+  for (int p = t; p < ow * oh; p += 256) {
+    const int c = p % ow, r = p / ow;
+    const int y = o.flip ? o.oh - 1 - (oy + r) : oy + r, x = ox + c;
+    const int c0 = c - x % G;                                      // where the group this pixel lies in starts in the tile's row
+    const bool whole = o.vec && c0 >= 0 && c0 + G <= ow;
+    if (whole && c != c0) continue;                                // (stored by the group's first pixel)
+    const uint32_t* s = src + r * pitch + c;
+    if (whole) {
+      uint32_t px[G];
+#pragma unroll
+      for (int k = 0; k < G; k++) px[k] = s[k];
+      wr_tensor_put_group_ch<DT>(o, y, x, px);
+    } else {
+      wr_tensor_put_pixel<DT>(o, y, x, s[0]);
+    }
+  }
+}
+WR_DEVICE void wr_grab_scale_store_tensor_any(const WrGrabScaleArgs& a, const WrTensorOut& o, const WrGrabScaleGeom& g, const uint32_t* src, int pitch, int t) {
+  if (o.dtype == WR_TENSOR_F32) wr_grab_scale_store_tensor<WR_TENSOR_F32>(a, o, g, src, pitch, t);
+  else if (o.dtype == WR_TENSOR_F16) wr_grab_scale_store_tensor<WR_TENSOR_F16>(a, o, g, src, pitch, t);
+  else if (o.dtype == WR_TENSOR_BF16) wr_grab_scale_store_tensor<WR_TENSOR_BF16>(a, o, g, src, pitch, t);
+  else wr_grab_scale_store_tensor<WR_TENSOR_U8>(a, o, g, src, pitch, t);
+}
+__global__ void __launch_bounds__(256) wr_grab_scale_tensor_kernel(WrGrabScaleTensorArgs b) {
+  const WrGrabScaleArgs& a = b.s;
+  const WrGrabScaleGeom g = wr_grab_scale_geom(a, (int)blockIdx.x);
+#ifdef WRHIP_HOSTSIM
+  if (threadIdx.x != 0) return;
+  WrGrabScaleTile T;
+#else
+  __shared__ WrGrabScaleTile T;
+  const int t = (int)threadIdx.x;
+#endif
+  WR_SCALE_PHASE(wr_grab_scale_coords(a, g, T, t))
+  WR_SCALE_PHASE(wr_grab_scale_fill(a, g, T, t))
+  uint32_t* from = T.a;
+  uint32_t* to = T.b;
+  for (int k = 0; k < a.steps; k++) {
+    WR_SCALE_PHASE(wr_grab_scale_halve(from, to, WR_SCALE_TILE >> k, g.cw >> k, g.ch >> k, t))
+    uint32_t* const was = from; from = to; to = was;
+  }
+  WR_SCALE_PHASE(wr_grab_scale_store_tensor_any(a, b.o, g, from, WR_SCALE_TILE >> a.steps, t);
+                 if (a.slot && blockIdx.x == 0 && t == 0) wr_grab_st16(a.slot, wr_u4{0u, 0u, 0u, 0u}))
+}
 #undef WR_SCALE_PHASE
 // The slot's header and as many bytes as its count word says, device slot -> pinned host slot, 16 bytes per store.  A small grid on
 // the grab stream: the link, not the chip, bounds it, and the raster launches of the following frames keep the CUs.

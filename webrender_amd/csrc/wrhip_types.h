@@ -756,6 +756,40 @@ struct WrGrabScaleArgs {
   int32_t last, flip, swap_rb;         // last: rows flipped / R and B exchanged at the store
   uint32_t payload;                    // last: the payload's bytes
 };
+// WrhipGrabTextureTensor: where and how the pixels of a grab leave as tensor elements (the contract: include/wrhip.h).  Element
+// (c, y, x) of the `ow` x `oh` output lies at element index c * plane_stride + y * row_stride + x (CHW) or y * row_stride +
+// x * channels + c (HWC) from `dst`; its value is byte shift[c] / 8 of the pixel's stored word -- as it is (U8), or times scale[c]
+// plus bias[c], rounded to the element's format.  `vec`: dst and the byte strides are multiples of 16, so the groups of 16 / element
+// size pixels counted from a row's start take 16-byte stores.
+#define WR_TENSOR_U8 0
+#define WR_TENSOR_F16 1
+#define WR_TENSOR_BF16 2
+#define WR_TENSOR_F32 3
+struct WrTensorOut {
+  uint8_t* dst;
+  long long row_stride, plane_stride;  // elements; never 0 here
+  int32_t ow, oh;
+  int32_t dtype, hwc, channels;
+  int32_t flip;                        // output row r holds pixel row oh - 1 - r
+  int32_t vec;
+  int32_t shift[4];
+  float scale[4], bias[4];
+};
+// one launch of wr_grab_tensor_kernel: the unscaled grab.  Workgroup b converts output rows [b * rows_per_wg, ...)
+struct WrGrabTensorArgs {
+  const uint8_t* tex;                  // the texture's storage (its origin)
+  uint8_t* slot;                       // the ticket's device slot, whose header the launch writes; null: the ticket is gone, no header
+  int32_t tex_stride, bpp;             // bytes; 4: RGBA8, 1: R8
+  int32_t rx, ry;                      // the rect's origin (its size is the output's)
+  int32_t rows_per_wg;
+  WrTensorOut o;
+};
+// the last launch of a scaled tensor grab, wr_grab_scale_tensor_kernel: wr_grab_scale_kernel's launch (dst, flip, swap_rb and
+// payload unused; slot as above) whose store phase converts
+struct WrGrabScaleTensorArgs {
+  WrGrabScaleArgs s;
+  WrTensorOut o;
+};
 struct WrGrabPushArgs {
   const uint8_t* src; uint8_t* dst;    // device slot -> pinned host slot
   uint32_t capacity;                   // of either, bytes (a multiple of 16): the count read from the slot is held to it

@@ -144,6 +144,10 @@ EXTRA_SIGNATURES = {
     "WrhipGrabResultGet": (i32, [i32, P, P, C.c_int64, i32]),
     "WrhipGrabPayloadGet": (i32, [i32, P, u64, P, i32]),
     "WrhipGrabDecode": (i32, [P, u64, u32, u32, i32, i32, P, C.c_int64, P, P]),
+    "WrhipGrabTextureTensor": (i32, [u32, P, P]),
+    "WrhipDeviceAlloc": (P, [u64]),
+    "WrhipDeviceFree": (None, [P]),
+    "WrhipDeviceRead": (i32, [P, P, u64]),
 }
 
 
@@ -167,13 +171,24 @@ class WrhipTapResult(C.Structure):
 # WrhipGrabTexture flags, and the bytes that cross ahead of every grab's payload (include/wrhip.h)
 GRAB_FLIP_ROWS, GRAB_SWAP_RB, GRAB_DELTA, GRAB_KEY, GRAB_PACKED = 1, 2, 4, 8, 32
 GRAB_SCALED = 64          # reported in a scaled grab's info["flags"] (WrhipGrabTextureScaled); no flag of WrhipGrabTexture
+GRAB_TENSOR = 128         # reported in a tensor grab's info["flags"] (WrhipGrabTextureTensor); no flag of the other grab calls
 GRAB_MAX_RECTS, GRAB_HEADER, GRAB_BLOCK = 16, 16, 64
+# WrhipGrabTextureTensor: element types, layouts, and the flag that keeps the stored channel order
+TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 0, 1, 2, 3
+TENSOR_CHW, TENSOR_HWC = 0, 1
+TENSOR_BGR = 256
+TENSOR_ELEM_BYTES = {TENSOR_U8: 1, TENSOR_F16: 2, TENSOR_BF16: 2, TENSOR_F32: 4}
 
 
 class WrhipGrabInfo(C.Structure):
     _fields_ = [("status", i32), ("format", u32), ("flags", u32), ("nrects", i32), ("rects", (i32 * 4) * GRAB_MAX_RECTS),
                 ("keyframe", u32), ("blocks", u32), ("blocks_total", u32), ("damage", i32 * 4), ("bytes", u64),
                 ("scaled_w", i32), ("scaled_h", i32), ("levels", u32)]
+
+
+class WrhipTensorDesc(C.Structure):
+    _fields_ = [("dst", P), ("dst_bytes", u64), ("out_w", i32), ("out_h", i32), ("dtype", u32), ("layout", u32), ("channels", u32),
+                ("row_stride", C.c_int64), ("plane_stride", C.c_int64), ("scale", C.c_float * 4), ("bias", C.c_float * 4), ("flags", u32)]
 
 
 def _as_ptr(x):
@@ -295,9 +310,50 @@ class GL:
         arr = (i32 * 4)(*[int(v) for v in rect])
         return self.WrhipGrabTextureScaled(tex, C.addressof(arr), int(size[0]), int(size[1]), flags)
 
+    def grab_texture_tensor(self, tex, rect, dst, dst_bytes, size=None, dtype=TENSOR_F32, layout=TENSOR_CHW, channels=3, strides=(0, 0),
+                            scale=(1.0, 1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0, 0.0), flags=0):
+        """Enqueue a tensor grab (include/wrhip.h, WrhipGrabTextureTensor) of `rect` = (x, y, w, h) of texture id `tex` -- None: all
+        of it -- into the device memory `dst` (an address: device_alloc's, or any the context's runtime can write), of which
+        `dst_bytes` may be written.  size = (width, height): scaled down as grab_texture_scaled scales; None: the rect's size.
+        strides = (row, plane) in elements, 0: tight; scale, bias: per output channel (up to four values; float32).
+        `flags`: GRAB_FLIP_ROWS and / or TENSOR_BGR.  Returns the ticket, or -1 (GL_INVALID_VALUE / GL_OUT_OF_MEMORY is then set)."""
+        if rect is None:
+            w, h = i32(0), i32(0)
+            if not self.WrhipGetTextureSize(tex, C.byref(w), C.byref(h)):
+                w = h = i32(0)
+            rect = (0, 0, w.value, h.value)
+        arr = (i32 * 4)(*[int(v) for v in rect])
+        size = (rect[2], rect[3]) if size is None else size
+        d = WrhipTensorDesc()
+        d.dst, d.dst_bytes = int(dst) or None, int(dst_bytes)
+        d.out_w, d.out_h = int(size[0]), int(size[1])
+        d.dtype, d.layout, d.channels = int(dtype), int(layout), int(channels)
+        d.row_stride, d.plane_stride = int(strides[0]), int(strides[1])
+        for k in range(4):
+            d.scale[k] = float(scale[k]) if k < len(scale) else 1.0
+            d.bias[k] = float(bias[k]) if k < len(bias) else 0.0
+        d.flags = int(flags)
+        return self.WrhipGrabTextureTensor(tex, C.addressof(arr), C.addressof(d))
+
+    def device_alloc(self, nbytes):
+        """Device memory for tensor grabs (WrhipDeviceAlloc): its address, 16-byte aligned; 0 with GL_OUT_OF_MEMORY set"""
+        return self.WrhipDeviceAlloc(int(nbytes)) or 0
+
+    def device_free(self, ptr):
+        """WrhipDeviceFree: parked grabs are sent and the draw stream is waited for first"""
+        self.WrhipDeviceFree(int(ptr) or None)
+
+    def device_read(self, ptr, nbytes):
+        """`nbytes` of device memory as a uint8 array (WrhipDeviceRead: a copy on the draw stream behind everything issued so far)"""
+        import numpy as np
+        out = np.empty(int(nbytes), np.uint8)
+        rc = self.WrhipDeviceRead(out.ctypes.data, int(ptr), int(nbytes))
+        assert rc == 0, rc
+        return out
+
     def grab_result(self, ticket, wait=True, into=None):
         """The result of a grab: (info dict, pixels).  Full mode: one array per rect ((h, w, 4) stored B, G, R, A bytes, or (h, w)
-        for R8) -- the array itself for a single rect, a list for several.  A scaled grab: the (scaled_h, scaled_w, 4) array.  Delta mode: the caller's image `into` of the rect (a
+        for R8) -- the array itself for a single rect, a list for several.  A scaled grab: the (scaled_h, scaled_w, 4) array.  A tensor grab: None.  Delta mode: the caller's image `into` of the rect (a
         C-contiguous uint8 array of the rect's shape; None: a fresh one of zeros) with the sent blocks patched in.  None if the
         result has not arrived (wait=False only); a ticket the ring no longer holds raises KeyError."""
         import numpy as np
@@ -310,7 +366,9 @@ class GL:
         rects = [tuple(r.rects[i]) for i in range(r.nrects)]
         bpp = 1 if r.format == 0x8229 else 4          # GL_R8
         shape = lambda w, h: (h, w) if bpp == 1 else (h, w, 4)
-        if r.flags & GRAB_SCALED:
+        if r.flags & GRAB_TENSOR:
+            pixels = buf = None          # (the elements are in the caller's device memory)
+        elif r.flags & GRAB_SCALED:
             pixels = buf = np.empty((r.scaled_h, r.scaled_w, 4), np.uint8)
         elif r.flags & GRAB_DELTA:
             out = np.zeros(shape(*rects[0][2:]), np.uint8) if into is None else into
@@ -323,8 +381,9 @@ class GL:
                 parts.append(buf[at:at + w * h * bpp].reshape(shape(w, h)))
                 at += w * h * bpp
             pixels = parts[0] if len(parts) == 1 else parts
-        rc = self.WrhipGrabResultGet(ticket, C.byref(r), buf.ctypes.data, 0, 1)
-        assert rc == 0, rc
+        if buf is not None:
+            rc = self.WrhipGrabResultGet(ticket, C.byref(r), buf.ctypes.data, 0, 1)
+            assert rc == 0, rc
         info = {"status": r.status, "format": r.format, "flags": r.flags, "rects": rects, "keyframe": r.keyframe, "blocks": r.blocks,
                 "blocks_total": r.blocks_total, "damage": tuple(r.damage), "bytes": int(r.bytes),
                 "scaled_w": r.scaled_w, "scaled_h": r.scaled_h, "levels": r.levels}

@@ -236,3 +236,59 @@ def render_streamed_grabbed(backend_path, frames, delta=False, rect=None, packed
     stats["gl_error"] = int(err)
     r.destroy()
     return px, stats, images, infos
+
+
+def render_streamed_tensors(backend_path, frames, size, dtype, layout, channels, scale, bias):
+    """render_streamed with every frame kept ON THE DEVICE as a tensor: one [N, ...] batch is allocated there (GL.device_alloc) and,
+    after frame k's render, the window is tensor-grabbed (GL.grab_texture_tensor: scaled to `size` = (w, h) as grab_texture_scaled
+    scales, converted to `dtype` elements in `layout` with `channels` channels, times `scale` plus `bias`) into slot k -- nothing
+    between the frames drains the held-back raster launches, no Finish, and nothing but 16 bytes per frame crosses to the host.
+    Only the LAST ticket is waited for: the grabs run on one stream, in order, so every slot is written by then.  Tickets that
+    happen to have arrived are fetched on the way; one the ring of 8 overwrote first leaves None in the infos -- its slot is
+    written all the same.  Returns the batch read back ([N, C, h, w] or [N, h, w, C]; uint8, float16, float32, or the uint16
+    patterns of bfloat16), the backend's statistics and the grabs' info dicts.  libwrhip only."""
+    from . import glapi
+    gl = GL(backend_path)
+    assert gl.is_wrhip, "render_streamed_tensors: grabs are a libwrhip addition"
+    w, h = frames[0].width, frames[0].height
+    r = Renderer(gl, w, h)
+    window = gl.WrhipGetFramebufferTexture(0)
+    elem = glapi.TENSOR_ELEM_BYTES[dtype]
+    shape = (channels, size[1], size[0]) if layout == glapi.TENSOR_CHW else (size[1], size[0], channels)
+    slot = size[0] * size[1] * channels * elem
+    slot16 = (slot + 15) & ~15                      # slots start on 16 bytes: every grab takes the wide stores
+    batch = gl.device_alloc(slot16 * len(frames))
+    assert batch, gl.GetError()
+    tickets, infos = [], [None] * len(frames)
+
+    def fetch(k, wait):
+        try:
+            res = gl.grab_result(tickets[k], wait=wait)
+        except KeyError:
+            return True                             # overwritten in the ring: nothing to learn any more
+        if res is not None:
+            infos[k] = res[0]
+        return res is not None
+    oldest = 0
+    for k, f in enumerate(frames):
+        assert (f.width, f.height) == (w, h), "render_streamed_tensors: one window size"
+        r.render(f)
+        t = gl.grab_texture_tensor(window, (0, 0, w, h), batch + k * slot16, slot, size=size, dtype=dtype, layout=layout,
+                                   channels=channels, scale=scale, bias=bias)
+        assert t >= 0, (t, gl.GetError())
+        tickets.append(t)
+        while oldest < k and fetch(oldest, False):
+            oldest += 1
+    fetch(len(frames) - 1, True)
+    for k in range(oldest, len(frames) - 1):
+        fetch(k, False)
+    err = gl.GetError()
+    raw = gl.device_read(batch, slot16 * len(frames)).reshape(len(frames), slot16)[:, :slot]
+    np_dtype = {glapi.TENSOR_U8: np.uint8, glapi.TENSOR_F16: np.float16, glapi.TENSOR_BF16: np.uint16, glapi.TENSOR_F32: np.float32}[dtype]
+    out = np.ascontiguousarray(raw).view(np_dtype).reshape((len(frames),) + shape)
+    stats = gl.stats()
+    stats["gl_error"] = int(err)
+    gl.device_free(batch)
+    r.finish()
+    r.destroy()
+    return out, stats, infos
