@@ -252,7 +252,8 @@ void WrhipSetProfiling(int enabled);
  * (picture targets of a few large gradient / image prims, likewise), 11 = wr_setup_tile_rows_kernel (10 fused with the next flush's setup stage), 12 = a thin launch of the raster kernel (13: the same with the next flush's setup stage in front, wr_setup_raster_thin_kernel) (wr_raster_kernel<fmt, false, 1, feat>:
  * small levels, several workgroups per bin), 14 = wr_tap_kernel (WrhipTapTexture: fmt of the tapped texture, feat 1 against an expected texture;
  * algo_bytes: the rect's bytes, twice with an expected texture), 15 = wr_grab_pack_kernel (WrhipGrabTexture: fmt of the grabbed texture,
- * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta, feat 3: wr_grab_scale_kernel, the launches of one WrhipGrabTextureScaled, feat 4: wr_grab_tensor_kernel or the launches of a scaled WrhipGrabTextureTensor; algo_bytes: bytes read plus bytes written, as far as they are known at the launch).  algo_bytes: the launch's algorithmic bytes:
+ * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta, feat 3: wr_grab_scale_kernel, the launches of one WrhipGrabTextureScaled, feat 4: wr_grab_tensor_kernel or the launches of a scaled WrhipGrabTextureTensor; algo_bytes: bytes read plus bytes written, as far as they are known at the launch), 16 = wr_put_tensor_kernel (WrhipPutTextureTensor: fmt of the texture written;
+ * algo_bytes: the elements read plus the rect's bytes written).  algo_bytes: the launch's algorithmic bytes:
  * raster launches count every destination pixel they own once (twice when the target's old content is loaded) plus
  * the source texels their draws can sample; the setup stage counts instance + descriptor + record bytes.  Returns the
  * number of entries written (<= max). */
@@ -447,9 +448,48 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  * freed like any other.  WrhipDeviceFree(p): first sends what parked grabs wait behind, the grabs with it, then waits for the draw
  * stream, then frees; NULL is ignored.  WrhipDeviceRead(dst_host, src_dev, bytes): a copy on the draw stream behind everything
  * issued so far, waited for; held-back launches stay held -- a parked grab has not written yet: fetch its ticket first.  0, or -1
- * for a NULL pointer.  WrhipStats::d2h_bytes grows by `bytes`.
+ * for a NULL pointer.  WrhipStats::d2h_bytes grows by `bytes`.  WrhipDeviceWrite(dst_dev, src_host, bytes): its sibling, host to
+ * device on the draw stream behind everything issued so far, waited for; held-back launches stay held.  0, or -1 for a NULL pointer.
+ * WrhipStats::h2d_bytes grows by `bytes`.
+ *
+ * WrhipPutTextureTensor(tex, rect, desc): the way IN, the inverse of a tensor grab: a CHW or HWC tensor of U8, F16, BF16 or F32
+ * elements in the caller's device memory `desc->src` is converted on the device into the stored bytes of `rect` of a GL_RGBA8, GL_R8
+ * or GL_RG8 texture -- one launch on the draw stream, no pixel crosses to the host.  The contract -- any restatement must give the
+ * same bytes:
+ *   geometry  the tensor is rect.w x rect.h: no scaling.  With FLIP_ROWS tensor row r goes to rect row h - 1 - r.
+ *   address   the tensor grab's: element (c, y, x) lies at element index c * plane_stride + y * row_stride + x from `src` (CHW), or
+ *             at y * row_stride + x * channels + c (HWC, plane_stride ignored).  A stride of 0 is the tight one: w (CHW) or
+ *             w * channels (HWC) for a row, h * row_stride for a plane.  Nothing but these elements is read -- not the padding
+ *             between rows or planes -- and their extent lies inside src_bytes.  `src` is aligned to the element's size.
+ *   channels  the stored bytes of an RGBA8 pixel are B, G, R, A.  Input channel c supplies R, G, B, A in that order, or B, G, R, A
+ *             with WRHIP_TENSOR_BGR; with channels == 3, A is `desc->alpha`.  An R8 texture takes its one channel; an RG8 texture
+ *             takes channel 0 as byte 0 and channel 1 as byte 1 (BGR changes nothing for either).  Values are stored as given: no
+ *             premultiplication, no colour conversion.
+ *   value     U8: the stored byte is the element; scale and bias are ignored.  Otherwise x is the element widened to float32
+ *             exactly (F16 subnormals, infinities and NaNs included; BF16 is a 16-bit shift) and y = x * scale[c] + bias[c] with c
+ *             the INPUT channel, a float32 multiply and a float32 add, each rounded once, never fused.  The byte is 0 if y is a NaN
+ *             or y < 0, 255 if y >= 255, otherwise y rounded to nearest, ties to even (0.5 -> 0, 1.5 -> 2, 2.5 -> 2) -- the
+ *             rounding of swgl's round_pixel on x86.  (webrender_amd/csrc/wr_tensor_round.h holds the two conversions, float16 bits
+ *             -> float32 bits and float32 bits -> byte, as integer arithmetic.)
+ *   written   exactly the rect's bytes in the texture; no other byte of it is touched.
+ *   ordering  a texture write at its place in the call order, like TexSubImage2D or CopyImageSubData: draws recorded before it that
+ *             sample or target `tex` see the old bytes (recorded work is flushed), held-back launches that reference `tex` leave
+ *             first, queued uploads go out ahead of it; everything recorded, uploaded, tapped or grabbed afterwards sees the new
+ *             bytes; a tap or grab issued before it is unchanged.  On a texture that nothing pending touches the put flushes
+ *             nothing and leaves held-back launches held.  The read of `src` is enqueued on WrhipGetStream() before the call
+ *             returns and is never parked: work the caller enqueued on that stream earlier precedes it, later work follows it; a
+ *             caller producing `src` on another stream orders it itself.  One case is handled here: if [src, src + src_bytes)
+ *             overlaps the destination of a PARKED tensor grab, what that grab is parked behind is sent first, the grab with it, so
+ *             that it has written before the put reads.  Retained copies of delta grabs stay valid (they compare content).
+ *   cost      one launch: WrhipStats::kernel_launches grows by 1, h2d_bytes and d2h_bytes by 0.
+ * Returns 0; -1 and sets GL_INVALID_VALUE, launching, flushing and changing nothing, for: an unknown texture or one without storage;
+ * a format other than GL_RGBA8, GL_R8, GL_RG8; a texture whose storage is a caller's host buffer (SetTextureBuffer) or that is locked;
+ * channels other than 3 or 4 (RGBA8), 1 (R8), 2 (RG8); a rect that is empty or not inside `tex`; an unknown dtype, layout or flag;
+ * a NULL desc or src; a src not aligned to its element; a stride below the tensor grab's minimum or above 2^40; an extent in bytes
+ * above src_bytes; an alpha above 255; and while sharding is on.
  * Not routed through grabs: Finish, GetColorBuffer, ReadPixels.  Not supported: other formats, sharded targets; scaling other than
- * WrhipGrabTextureScaled's; delta or packed tensor grabs; gamma or colour-space conversion (values are the stored premultiplied bytes). */
+ * WrhipGrabTextureScaled's; delta or packed tensor grabs; gamma or colour-space conversion (values are the stored premultiplied bytes);
+ * puts that scale or filter, into other formats, into sharded targets or host-backed textures. */
 #define WRHIP_GRAB_FLIP_ROWS 1u   /* full mode: deliver the rect's last row first */
 #define WRHIP_GRAB_SWAP_RB   2u   /* full mode, RGBA8 only: bytes 0 and 2 of every pixel exchanged */
 #define WRHIP_GRAB_DELTA     4u   /* only the 64x64 blocks that differ from the previous DELTA grab of this texture and rect */
@@ -492,6 +532,17 @@ int32_t WrhipGrabTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTen
 void* WrhipDeviceAlloc(uint64_t bytes);
 void WrhipDeviceFree(void* p);
 int32_t WrhipDeviceRead(void* dst_host, const void* src_dev, uint64_t bytes);
+int32_t WrhipDeviceWrite(void* dst_dev, const void* src_host, uint64_t bytes);
+typedef struct WrhipTensorSrc {
+  const void* src;                 /* device memory of this process: WrhipDeviceAlloc'd, or any pointer valid for the context's HIP runtime */
+  uint64_t src_bytes;              /* bytes the library may read from src on; the extent of the elements must fit */
+  uint32_t dtype, layout, channels;      /* WRHIP_TENSOR_*; channels: 3 or 4 for GL_RGBA8, 1 for GL_R8, 2 for GL_RG8 */
+  int64_t  row_stride, plane_stride;     /* in ELEMENTS; 0: tight */
+  float    scale[4], bias[4];      /* per INPUT channel; ignored for U8 */
+  uint32_t alpha;                  /* the stored A byte (0..255) when channels == 3 */
+  uint32_t flags;                  /* WRHIP_GRAB_FLIP_ROWS and / or WRHIP_TENSOR_BGR */
+} WrhipTensorSrc;
+int32_t WrhipPutTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTensorSrc* desc);
 int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64_t dst_stride, int32_t wait);
 int32_t WrhipGrabPayloadGet(int32_t ticket, void* dst, uint64_t capacity, uint64_t* bytes, int32_t wait);
 int32_t WrhipGrabDecode(const void* payload, uint64_t bytes, uint32_t format, uint32_t flags, int32_t rect_w, int32_t rect_h, void* dst, int64_t dst_stride, int32_t damage[4], uint32_t* blocks);

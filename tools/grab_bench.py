@@ -21,10 +21,15 @@
              without tensor grabs (BlitFramebuffer chain, WrhipGetTextureDevicePtr, torch gather / permute / cast / scale / bias /
              cast on the draw stream); then cfg2 streamed: no grab, that path per frame, a tensor grab per frame.  With --ab the
              parent-path lines are taken again in a child process that loads the other library
+  put        WrhipPutTextureTensor: wr_put_tensor_kernel into the 4K RGBA8 window by hipEvents (kind 16): F16 CHW 3, U8 HWC 4 and F32
+             CHW 3 (the tensor grab's headline case the other way); then the same content over the only route there is without it --
+             WrhipDeviceRead, the conversion in numpy, TexSubImage2D -- each followed by a tap of the texture as the consumer, host
+             clock per frame; then image_grid at 2048 x 2048 streamed by native replay with its window fed back into its atlas every
+             frame: a tensor grab and a put, against a tensor grab, WrhipDeviceRead, numpy and TexSubImage2D, frames/s
   ab         plain bench.py against another build of the library (WRHIP_LIB_PATH), alternated, no grab issued
 
 Every section runs three alternated rounds.  Needs the GPU: there is no fallback.
-  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
+  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor,put] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -602,6 +607,127 @@ def section_tensor_parent(other, frames):
             say(l)
 
 
+def _put_bytes(el, dtype, hwc, scale):
+    """The put's conversion on the host, as the route without it has to do it: elements -> stored B, G, R, A bytes"""
+    x = el if hwc else el.transpose(1, 2, 0)
+    if dtype != glapi.TENSOR_U8:
+        y = x.astype(np.float32) * np.float32(scale)
+        x = np.where(y >= 255, 255, np.rint(np.clip(y, 0, 255))).astype(np.uint8)
+    out = np.empty(x.shape[:2] + (4,), np.uint8)
+    out[..., 0], out[..., 1], out[..., 2] = x[..., 2], x[..., 1], x[..., 0]
+    out[..., 3] = x[..., 3] if x.shape[2] == 4 else 255
+    return out
+
+
+def section_put(lib):
+    say(f"## put: wr_put_tensor_kernel into the {W}x{H} RGBA8 window, hipEvents (WrhipSetProfiling(1)), us per launch")
+    w = Window(lib, "noise")
+    gl = w.gl
+    rng = np.random.default_rng(2)
+    unit = rng.random((3, H, W), dtype=np.float32)
+    data = {"F16 CHW 3": (unit.astype(np.float16), glapi.TENSOR_F16, glapi.TENSOR_CHW, 3, 255.0),
+            "U8  HWC 4": (rng.integers(0, 256, (H, W, 4), dtype=np.uint8), glapi.TENSOR_U8, glapi.TENSOR_HWC, 4, 1.0),
+            "F32 CHW 3": (unit, glapi.TENSOR_F32, glapi.TENSOR_CHW, 3, 255.0)}
+    bufs = {}
+    for name, (el, *_) in data.items():
+        bufs[name] = gl.device_alloc(el.nbytes)
+        assert bufs[name], gl.GetError()
+        gl.device_write(bufs[name], el)
+
+    def put(name):
+        el, dtype, layout, ch, scale = data[name]
+        assert gl.put_texture_tensor(w.tex, None, bufs[name], el.nbytes, dtype=dtype, layout=layout, channels=ch, scale=[scale] * 4) == 0, gl.GetError()
+    for name in data:
+        for _ in range(4):
+            put(name)
+    # (what the kernel wrote, against the host's conversion: the figures below are of a kernel that is right)
+    for name in data:
+        put(name)
+        got = np.empty((H, W, 4), np.uint8)
+        gl.BindFramebuffer(G.GL_READ_FRAMEBUFFER, 0)
+        gl.ReadPixels(0, 0, W, H, G.GL_BGRA, G.GL_UNSIGNED_BYTE, got)
+        el, dtype, layout, ch, scale = data[name]
+        say(f"  {name}: bytes that differ from the numpy conversion: {int((got != _put_bytes(el, dtype, layout == glapi.TENSOR_HWC, scale)).sum())}")
+    gl.WrhipSetProfiling(1)
+    rows, n = {}, 30
+    for rnd in range(ROUNDS):
+        for name in data:
+            gl.WrhipResetStats()
+            for _ in range(n):
+                put(name)
+            ks = kernel_stats(gl, 16)
+            assert len(ks) == 1 and ks[0].launches == n, [(k.feat, k.launches) for k in ks]
+            rows.setdefault(name, []).append((ks[0].ns / n / 1e3, ks[0].algo_bytes // n, ks[0].workgroups // n))
+    gl.WrhipSetProfiling(0)
+    for name, v in rows.items():
+        say(f"  {name:12s} " + "  ".join(f"{us:8.1f}" for us, _, _ in v) + f"   us   ({v[0][1] / 1e6:6.1f} MB read + written: " +
+            "  ".join(f"{b / us / 1e3:6.0f}" for us, b, _ in v) + f" GB/s; {v[0][2]} workgroups)")
+    say(f"## put against the route without it: the same {W}x{H} content, WrhipDeviceRead + numpy + TexSubImage2D; a tap of the texture consumes it; host clock, ms per frame")
+    N = 5
+    host = {}
+    for rnd in range(ROUNDS):
+        for name in ("F16 CHW 3", "U8  HWC 4"):
+            el, dtype, layout, ch, scale = data[name]
+            for kind in ("put", "host route"):
+                gl.Finish()
+                t0 = time.perf_counter()
+                for _ in range(N):
+                    if kind == "put":
+                        put(name)
+                    else:
+                        raw = gl.device_read(bufs[name], el.nbytes).view(el.dtype).reshape(el.shape)
+                        w.upload(0, 0, _put_bytes(raw, dtype, layout == glapi.TENSOR_HWC, scale))
+                    t = gl.tap_texture(w.tex)
+                gl.tap_result(t)
+                host.setdefault((name, kind), []).append((time.perf_counter() - t0) / N * 1e3)
+    for (name, kind), v in host.items():
+        say(f"  {name:10s} {kind:11s} " + "  ".join(f"{ms:9.3f}" for ms in v) + "   ms")
+    for b in bufs.values():
+        gl.device_free(b)
+    w.close()
+
+
+def section_put_stream(lib, frames):
+    S = 2048
+    say(f"## put stream: image_grid {S}x{S} streamed by native replay, the window fed back into the {S}x{S} atlas every frame, {frames} frames per region, frames/s")
+    rec, _ = record_scene(lib, scenes.image_grid(width=S, height=S, atlas=S))
+    p = ScenePlayer(lib, rec)
+    gl = glapi.GL(lib)
+    window, atlas = gl.WrhipGetFramebufferTexture(0), rec.texture_ids["image_atlas"]
+    nbytes = 3 * S * S * 2
+    buf = gl.device_alloc(nbytes)
+    inv = [1.0 / 255.0] * 4
+
+    def run(kind, n):
+        for k in range(n):
+            p.rp.exec(rec.stream)
+            if kind == "no feed":
+                continue
+            t = gl.grab_texture_tensor(window, (0, 0, S, S), buf, nbytes, dtype=glapi.TENSOR_F16, channels=3, scale=inv)
+            assert t >= 0
+            if kind == "put":
+                assert gl.put_texture_tensor(atlas, (0, 0, S, S), buf, nbytes, dtype=glapi.TENSOR_F16, channels=3, scale=[255.0] * 4) == 0
+            else:
+                raw = gl.device_read(buf, nbytes).view(np.float16).reshape(3, S, S)
+                gl.ActiveTexture(G.GL_TEXTURE0)
+                gl.BindTexture(G.GL_TEXTURE_2D, atlas)
+                gl.TexSubImage2D(G.GL_TEXTURE_2D, 0, 0, 0, S, S, G.GL_BGRA, G.GL_UNSIGNED_BYTE, _put_bytes(raw, glapi.TENSOR_F16, False, 255.0))
+        gl.Finish()
+    kinds = ["no feed", "put", "host route"]
+    rows = {}
+    for k in kinds:
+        run(k, 3)
+    for rnd in range(ROUNDS):
+        for k in kinds:
+            n = frames if k != "host route" else max(5, frames // 20)
+            t0 = time.perf_counter()
+            run(k, n)
+            rows.setdefault(k, []).append(n / (time.perf_counter() - t0))
+    for k in kinds:
+        say(f"  {k:12s} " + "  ".join(f"{v:9.1f}" for v in rows[k]) + "   frames/s")
+    gl.device_free(buf)
+
+
 def section_ab(other, steps, warmup):
     say(f"## ab: bench.py --gpus 1 --steps {steps} --warmup {warmup} (cfg2), this library against {os.path.basename(other)}, alternated, frames/s")
     rows = {"parent": [], "this": []}
@@ -666,6 +792,10 @@ def main():
                 section_tensor_stream(lib, args.frames)
                 if args.ab:
                     section_tensor_parent(args.ab, args.frames)
+            elif s == "put":
+                section_tensor_kernel(lib, "noise")      # (the rate beside: the same bytes the other way)
+                section_put(lib)
+                section_put_stream(lib, args.frames)
             elif s == "tensor_parent":          # (run by `tensor` with WRHIP_LIB_PATH set: the parent path alone, on that library)
                 section_tensor_scaled(lib, with_tensor=False)
                 section_tensor_stream(lib, args.frames, with_tensor=False)

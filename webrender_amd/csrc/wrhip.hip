@@ -464,9 +464,9 @@ const size_t MAX_TEXTURE_UNITS = 16;
 
 // WrhipKernelStat::kind (include/wrhip.h documents the values; bench.py and tools/grab_bench.py read them)
 enum WrKind { WR_KIND_SCATTER = 0, WR_KIND_SETUP = 1, WR_KIND_RASTER = 2, WR_KIND_MASK_ROWS = 3, WR_KIND_CHAIN = 4, WR_KIND_DENSE = 5, WR_KIND_SETUP_RASTER = 6, WR_KIND_SETUP_DENSE = 7,
-              WR_KIND_SETUP_ROWS = 8, WR_KIND_SPAN_ROWS = 9, WR_KIND_TILE_ROWS = 10, WR_KIND_SETUP_TILE_ROWS = 11, WR_KIND_THIN = 12, WR_KIND_SETUP_THIN = 13, WR_KIND_TAP = 14, WR_KIND_GRAB = 15 };
+              WR_KIND_SETUP_ROWS = 8, WR_KIND_SPAN_ROWS = 9, WR_KIND_TILE_ROWS = 10, WR_KIND_SETUP_TILE_ROWS = 11, WR_KIND_THIN = 12, WR_KIND_SETUP_THIN = 13, WR_KIND_TAP = 14, WR_KIND_GRAB = 15, WR_KIND_PUT = 16 };
 // (WrhipStats::raster_ns: the launches that write target pixels -- not the stages ahead of them, nor taps and grabs)
-constexpr bool kind_is_raster(WrKind k) { return !(k == WR_KIND_SCATTER || k == WR_KIND_SETUP || k == WR_KIND_MASK_ROWS || k == WR_KIND_SETUP_ROWS || k == WR_KIND_TAP || k == WR_KIND_GRAB); }
+constexpr bool kind_is_raster(WrKind k) { return !(k == WR_KIND_SCATTER || k == WR_KIND_SETUP || k == WR_KIND_MASK_ROWS || k == WR_KIND_SETUP_ROWS || k == WR_KIND_TAP || k == WR_KIND_GRAB || k == WR_KIND_PUT); }
 // The switches pick_variant() looks at, read once per context (Context()).
 struct Switches {
   bool thin_r8 = true;       // WRHIP_NO_THIN=1: small launches keep the 4-wave workgroup shape
@@ -672,7 +672,7 @@ struct Context {
   struct GrabScaled { const uint8_t* tex; int32_t tex_stride, tex_w, tex_h, rect[4], dw, dh, levels, flip, swap_rb; };
   // WrhipGrabTextureTensor: the unscaled launch as it goes out (`args`; its slot is filled in when it is issued), or -- `scaled` --
   // the chain of a scaled grab (`scale`) whose last launch stores the elements `out` describes
-  struct GrabTensor { bool scaled; WrGrabTensorArgs args; GrabScaled scale; WrTensorOut out; uint64_t out_bytes; };
+  struct GrabTensor { bool scaled; WrGrabTensorArgs args; GrabScaled scale; WrTensorOut out; uint64_t out_bytes, dst_extent; };      // (dst_extent: the bytes from out.dst on that hold its elements)
   enum GrabKind { GRAB_PLAIN = 0, GRAB_SCALED = 1, GRAB_TENSOR = 2 };
   struct GrabParked { uint64_t n; GrabKind kind; WrGrabArgs args; GrabScaled scale; GrabTensor tensor; };
   GrabSlot grab_slot[GRAB_RING];
@@ -4297,6 +4297,7 @@ int32_t WrhipGrabTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTen
   }
   g.scaled = scaled;
   g.out_bytes = (uint64_t)o.ow * o.oh * o.channels * (uint64_t)elem;
+  g.dst_extent = (uint64_t)(extent * elem);
   g.args.bpp = t->bpp;
   if (scaled) {
     Context::GrabScaled& s = g.scale;
@@ -4339,6 +4340,71 @@ int32_t WrhipGrabTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTen
   }
   return (int32_t)(n & 0x7FFFFFFFull);
 }
+// A tensor put: see include/wrhip.h.  A texture write at its place in the call order -- TexSubImage2D's ordering, one launch on the
+// draw stream instead of staged rows.  Arguments are checked before anything is flushed or launched.
+int32_t WrhipPutTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTensorSrc* desc) {
+  if (!ctx) return -1;
+  Context* c = ctx;
+  Texture* t = tex ? c->textures.find(tex) : nullptr;
+  bool ok = t && t->dptr && (t->internal_format == GL_RGBA8 || t->internal_format == GL_R8 || t->internal_format == GL_RG8) && rect && desc && desc->src;
+  ok = ok && !t->ext_buf && !t->locked;              // (storage that is a caller's host buffer, or mirrored in one: out of scope)
+  ok = ok && (t->internal_format == GL_RGBA8 ? desc->channels == 3 || desc->channels == 4 : desc->channels == (uint32_t)t->bpp);
+  ok = ok && desc->dtype <= WRHIP_TENSOR_F32 && desc->layout <= WRHIP_TENSOR_HWC && (desc->flags & ~(WRHIP_GRAB_FLIP_ROWS | WRHIP_TENSOR_BGR)) == 0;
+  ok = ok && desc->alpha <= 255u;
+  ok = ok && rect[2] >= 1 && rect[3] >= 1 && rect[0] >= 0 && rect[1] >= 0 && rect[0] <= t->width - rect[2] && rect[1] <= t->height - rect[3];
+  // the elements: the tensor grab's rules -- strides (0: tight) no smaller than what they step over, the extent inside src_bytes
+  const int64_t elem = ok ? (desc->dtype == WRHIP_TENSOR_U8 ? 1 : desc->dtype == WRHIP_TENSOR_F32 ? 4 : 2) : 1;
+  const int64_t stride_max = (int64_t)1 << 40;       // (keeps every product below in 64 bits)
+  int64_t row = 0, plane = 0, extent = 0;
+  if (ok) {
+    const int64_t w = rect[2], h = rect[3], ch = desc->channels;
+    const bool hwc = desc->layout == WRHIP_TENSOR_HWC;
+    const int64_t row_min = hwc ? w * ch : w;
+    row = desc->row_stride ? desc->row_stride : row_min;
+    plane = hwc ? 0 : desc->plane_stride ? desc->plane_stride : h * row;
+    ok = row >= row_min && row <= stride_max && (hwc || (plane >= (h - 1) * row + w && plane <= stride_max));
+    extent = hwc ? (h - 1) * row + w * ch : (ch - 1) * plane + (h - 1) * row + w;
+    ok = ok && (uint64_t)(extent * elem) <= desc->src_bytes && ((uintptr_t)desc->src & (uintptr_t)(elem - 1)) == 0;
+  }
+  ok = ok && c->shard_world <= 1 && t->own_y0 == t->own_y1;      // (sharded targets hold a strip of the frame each: out of scope)
+  if (!ok) { c->last_error = GL_INVALID_VALUE; return -1; }
+  // A parked tensor grab that writes what this put reads -- the closed loop -- has to have written: what it is parked behind goes out,
+  // the grab with it
+  const uint8_t* const s0 = (const uint8_t*)desc->src;
+  const uint8_t* const s1 = s0 + desc->src_bytes;
+  for (const Context::GrabParked& p : c->grab_parked) {
+    const uint8_t* const d0 = p.tensor.out.dst;
+    if (p.kind == Context::GRAB_TENSOR && d0 < s1 && s0 < d0 + p.tensor.dst_extent) { drain_tail(); break; }
+  }
+  // the write: draws recorded so far that sample or target the texture are flushed, held-back launches that reference it leave,
+  // queued uploads go out ahead of it
+  sync_texture_for_write(*t);
+  flush_uploads(4300);
+  t->view_batch = 0;
+  WrPutTensorArgs a;
+  memset(&a, 0, sizeof(a));
+  a.tex = (uint8_t*)t->dptr; a.tex_stride = t->stride; a.bpp = t->bpp;
+  a.rx = rect[0]; a.ry = rect[1]; a.w = rect[2]; a.h = rect[3];
+  WrTensorIn& in = a.in;
+  in.src = s0; in.row_stride = row; in.plane_stride = plane;
+  in.dtype = (int32_t)desc->dtype; in.hwc = desc->layout == WRHIP_TENSOR_HWC ? 1 : 0; in.channels = (int32_t)desc->channels;
+  in.flip = (desc->flags & WRHIP_GRAB_FLIP_ROWS) ? 1 : 0;
+  in.bgr = (desc->flags & WRHIP_TENSOR_BGR) ? 1 : 0;
+  in.vec = ((uintptr_t)s0 & 15) == 0 && (row * elem) % 16 == 0 && (in.hwc || (plane * elem) % 16 == 0) ? 1 : 0;
+  in.alpha = desc->alpha;
+  for (int k = 0; k < 4; k++) { in.scale[k] = desc->scale[k]; in.bias[k] = desc->bias[k]; }
+  // (a row touches (w * bpp + 15) / 16 pieces of 16 bytes, and one more when it starts inside one; a workgroup per 1024 items or
+  // per row, if a row has more: the tensor grab's deal)
+  a.slots = (a.w * a.bpp + 31 - a.bpp) / 16;
+  a.rows_per_wg = std::max(1, std::min(a.h, 1024 / a.slots));
+  const int grid = (a.h + a.rows_per_wg - 1) / a.rows_per_wg;
+  prof_begin();
+  WR_LAUNCH(wr_put_tensor_kernel, grid, 256, c->stream, a);
+  // (16: wr_put_tensor_kernel; the elements read, the rect's bytes written)
+  prof_end(WR_KIND_PUT, wr_format(t->internal_format), 0, 0, (uint64_t)a.w * a.h * ((uint64_t)in.channels * (uint64_t)elem + (uint64_t)a.bpp), (uint64_t)grid);
+  c->stats.kernel_launches++;
+  return 0;
+}
 // Device memory for tensor grabs: see include/wrhip.h
 void* WrhipDeviceAlloc(uint64_t bytes) {
   if (!ctx) return nullptr;
@@ -4361,6 +4427,15 @@ int32_t WrhipDeviceRead(void* dst_host, const void* src_dev, uint64_t bytes) {
   wrrt::d2h(dst_host, src_dev, (size_t)bytes, c->stream);
   { HostTimer ht(&c->stats.host_wait_ns); wrrt::stream_sync(c->stream); }
   c->stats.d2h_bytes += bytes;
+  return 0;
+}
+int32_t WrhipDeviceWrite(void* dst_dev, const void* src_host, uint64_t bytes) {
+  if (!ctx || (bytes && (!dst_dev || !src_host))) return -1;
+  Context* c = ctx;
+  if (!bytes) return 0;
+  wrrt::h2d(dst_dev, src_host, (size_t)bytes, c->stream);
+  { HostTimer ht(&c->stats.host_wait_ns); wrrt::stream_sync(c->stream); }
+  c->stats.h2d_bytes += bytes;
   return 0;
 }
 // The ticket's bytes in its pinned slot: 0 with *payload their count behind the header, 1 if they have not arrived (wait == 0 only)

@@ -712,6 +712,145 @@ __global__ void __launch_bounds__(256) wr_grab_tensor_kernel(WrGrabTensorArgs a)
   else if (a.o.dtype == WR_TENSOR_BF16) wr_grab_tensor_rows<WR_TENSOR_BF16>(a, r0, r1, t, (int)blockDim.x);
   else wr_grab_tensor_rows<WR_TENSOR_U8>(a, r0, r1, t, (int)blockDim.x);
 }
+
+// WrhipPutTextureTensor (include/wrhip.h; WrTensorIn): wr_grab_tensor_kernel the other way -- tensor elements in the caller's memory
+// become the stored bytes of a texture rect.  The work is again cut along the DESTINATION, which now is the texture: an item is one
+// 16-byte piece of the texture's storage in one row -- P = 4 RGBA8 pixels, 8 RG8, 16 R8.  A piece that lies whole inside the rect's
+// row leaves as one 16-byte store; the pieces a row starts and ends in leave pixel by pixel.  A texture row need not be a multiple
+// of 16 bytes (333 RGBA8 pixels: the phase moves by a pixel every row), so where the pieces lie is taken from each row's ADDRESS.
+// The elements behind a whole piece are P consecutive ones of each plane (CHW) or P * channels consecutive ones (HWC): such a run is
+// fetched with the widest loads that divide it -- 16 bytes, or 8 or 4 where it is shorter (4 RGBA8 pixels are 8 bytes of an F16
+// plane) -- if WrTensorIn::vec holds and the run's own address is aligned to them, with single-element loads otherwise.  Formats and
+// channel counts are template parameters, so that a piece's elements and bytes stay in registers under constant indices.
+WR_DEVICE void wr_put_load8(const void* p, uint32_t* w) {
+#ifdef WRHIP_HOSTSIM
+  __builtin_memcpy(w, p, 8);
+#else
+  typedef uint32_t wr_gu2 __attribute__((ext_vector_type(2)));
+  const wr_gu2 v = *(const __attribute__((address_space(1))) wr_gu2*)p;
+  w[0] = v.x; w[1] = v.y;
+#endif
+}
+// the loads a run of `bytes` is cut into (every run is a multiple of 4 bytes: P * E is 4 at least)
+constexpr int wr_put_chunk(int bytes) { return bytes % 16 == 0 ? 16 : bytes % 8 == 0 ? 8 : 4; }
+// the bits of the one element of E bytes at p
+template <int E> WR_DEVICE uint32_t wr_put_load_elem(const uint8_t* p) {
+  if (E == 1) return *p;
+  if (E == 2) { uint16_t h; __builtin_memcpy(&h, p, 2); return h; }
+  uint32_t u; __builtin_memcpy(&u, p, 4); return u;
+}
+// the bits of N consecutive elements from p on -> el[0 .. N); N * E is a multiple of 4
+template <int DT, int N> WR_DEVICE void wr_put_load_run(const uint8_t* p, bool vec, uint32_t* el) {
+  constexpr int E = wr_tensor_elem(DT), BYTES = N * E, A = wr_put_chunk(BYTES);
+  if (vec && ((uintptr_t)p & (uintptr_t)(A - 1)) == 0) {
+    uint32_t w[BYTES / 4];
+#pragma unroll
+    for (int k = 0; k < BYTES / A; k++) {
+      if (A == 16) { const wr_u4 v = wr_load16(p + 16 * k); w[4 * k] = v.x; w[4 * k + 1] = v.y; w[4 * k + 2] = v.z; w[4 * k + 3] = v.w; }
+      else if (A == 8) wr_put_load8(p + 8 * k, w + 2 * k);
+      else w[k] = wr_load4(p + 4 * k);
+    }
+#pragma unroll
+    for (int j = 0; j < N; j++) el[j] = E == 4 ? w[j] : E == 2 ? (w[j / 2] >> (16 * (j % 2))) & 0xFFFFu : (w[j / 4] >> (8 * (j % 4))) & 0xFFu;
+  } else {
+#pragma unroll
+    for (int j = 0; j < N; j++) el[j] = wr_put_load_elem<E>(p + E * j);
+  }
+}
+// the stored byte of the element of input channel c whose bits are b
+template <int DT> WR_DEVICE uint32_t wr_put_byte(const WrTensorIn& in, uint32_t b, int c) {
+  if (DT == WR_TENSOR_U8) return b;
+#ifdef WRHIP_HOSTSIM
+  const float x = wr_bits_f(DT == WR_TENSOR_F32 ? b : DT == WR_TENSOR_F16 ? wr_f16_bits_to_f32_bits((uint16_t)b) : b << 16);
+  const float y = x * in.scale[c] + in.bias[c];           // (two roundings: the build does not contract them)
+  return wr_f32_bits_to_byte(wr_float_bits(y));
+#else
+  // (the device's own converts: v_cvt_f32_f16 is exact, subnormals included; round-to-nearest-even is the conversion's mode.  The
+  // tests compare them with numpy on every f16 and bf16 pattern)
+  float x;
+  if (DT == WR_TENSOR_F16) { const uint16_t h = (uint16_t)b; _Float16 f; __builtin_memcpy(&f, &h, 2); x = (float)f; }
+  else x = wr_bits_f(DT == WR_TENSOR_F32 ? b : b << 16);
+  const float y = x * in.scale[c] + in.bias[c];
+  return y >= 255.0f ? 255u : y >= 0.0f ? (uint32_t)__builtin_rintf(y) : 0u;      // (a NaN fails both comparisons)
+#endif
+}
+// a pixel's stored word from the bytes v[c] of its input channels
+template <int CH, int BPP> WR_DEVICE uint32_t wr_put_pack(const WrTensorIn& in, const uint32_t* v) {
+  if (BPP == 1) return v[0];
+  if (BPP == 2) return v[0] | (v[1] << 8);
+  return (in.bgr ? v[0] : v[2]) | (v[1] << 8) | ((in.bgr ? v[2] : v[0]) << 16) | ((CH == 4 ? v[3] : in.alpha) << 24);
+}
+// one pixel, element by element: x of tensor row ty -> the BPP bytes at d
+template <int DT, int CH, int BPP> WR_DEVICE void wr_put_pixel(const WrTensorIn& in, int ty, int x, uint8_t* d) {
+  constexpr int E = wr_tensor_elem(DT);
+  uint32_t v[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int c = 0; c < CH; c++) {
+    const long long e = in.hwc ? (long long)ty * in.row_stride + (long long)x * CH + c : c * in.plane_stride + (long long)ty * in.row_stride + x;
+    v[c] = wr_put_byte<DT>(in, wr_put_load_elem<E>(in.src + e * E), c);
+  }
+  const uint32_t px = wr_put_pack<CH, BPP>(in, v);
+  if (BPP == 1) *d = (uint8_t)px;
+  else if (BPP == 2) { const uint16_t h = (uint16_t)px; __builtin_memcpy(d, &h, 2); }
+  else wr_grab_st4(d, px);
+}
+// a whole piece: the P pixels from x0 on of tensor row ty -> the 16 aligned bytes at d
+template <int DT, int CH, int BPP> WR_DEVICE void wr_put_piece(const WrTensorIn& in, int ty, int x0, uint8_t* d) {
+  constexpr int E = wr_tensor_elem(DT), P = 16 / BPP;
+  uint32_t v[P][4];
+  if (in.hwc) {
+    uint32_t el[P * CH];
+    wr_put_load_run<DT, P * CH>(in.src + ((long long)ty * in.row_stride + (long long)x0 * CH) * E, in.vec != 0, el);
+#pragma unroll
+    for (int i = 0; i < P; i++)
+#pragma unroll
+      for (int c = 0; c < CH; c++) v[i][c] = wr_put_byte<DT>(in, el[i * CH + c], c);
+  } else {
+#pragma unroll
+    for (int c = 0; c < CH; c++) {
+      uint32_t el[P];
+      wr_put_load_run<DT, P>(in.src + (c * in.plane_stride + (long long)ty * in.row_stride + x0) * E, in.vec != 0, el);
+#pragma unroll
+      for (int i = 0; i < P; i++) v[i][c] = wr_put_byte<DT>(in, el[i], c);
+    }
+  }
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+  for (int i = 0; i < P; i++) w[i * BPP / 4] |= wr_put_pack<CH, BPP>(in, v[i]) << (8 * (i * BPP % 4));
+  wr_grab_st16(d, wr_u4{w[0], w[1], w[2], w[3]});
+}
+// rect rows [r0, r1), thread t of nt: the rows' items laid end to end, a.slots of them per row -- the last of a row may lie behind it
+template <int DT, int CH, int BPP> WR_DEVICE void wr_put_tensor_rows(const WrPutTensorArgs& a, int r0, int r1, int t, int nt) {
+  constexpr int P = 16 / BPP;
+  const int items = (r1 - r0) * a.slots;
+  for (int it = t; it < items; it += nt) {
+    const int y = r0 + it / a.slots, s = it % a.slots;
+    uint8_t* const row = a.tex + (size_t)(a.ry + y) * a.tex_stride + (size_t)a.rx * BPP;      // the first byte of the rect's row
+    const int x0 = s * P - (int)((uintptr_t)row & 15) / BPP;      // the piece's first pixel, counted from the rect's left edge
+    if (x0 >= a.w) continue;
+    const int ty = a.in.flip ? a.h - 1 - y : y;
+    if (x0 >= 0 && x0 + P <= a.w) {
+      wr_put_piece<DT, CH, BPP>(a.in, ty, x0, row + (ptrdiff_t)x0 * BPP);
+    } else {
+      const int xa = wr_imax(x0, 0), xb = wr_imin(x0 + P, a.w);
+      for (int x = xa; x < xb; x++) wr_put_pixel<DT, CH, BPP>(a.in, ty, x, row + (size_t)x * BPP);
+    }
+  }
+}
+template <int DT> WR_DEVICE void wr_put_tensor_rows_fmt(const WrPutTensorArgs& a, int r0, int r1, int t, int nt) {
+  if (a.bpp == 4 && a.in.channels == 4) wr_put_tensor_rows<DT, 4, 4>(a, r0, r1, t, nt);
+  else if (a.bpp == 4) wr_put_tensor_rows<DT, 3, 4>(a, r0, r1, t, nt);
+  else if (a.bpp == 2) wr_put_tensor_rows<DT, 2, 2>(a, r0, r1, t, nt);
+  else wr_put_tensor_rows<DT, 1, 1>(a, r0, r1, t, nt);
+}
+__global__ void __launch_bounds__(256) wr_put_tensor_kernel(WrPutTensorArgs a) {
+  const int t = (int)threadIdx.x;
+  const int r0 = (int)blockIdx.x * a.rows_per_wg, r1 = wr_imin(a.h, r0 + a.rows_per_wg);
+  if (a.in.dtype == WR_TENSOR_F32) wr_put_tensor_rows_fmt<WR_TENSOR_F32>(a, r0, r1, t, (int)blockDim.x);
+  else if (a.in.dtype == WR_TENSOR_F16) wr_put_tensor_rows_fmt<WR_TENSOR_F16>(a, r0, r1, t, (int)blockDim.x);
+  else if (a.in.dtype == WR_TENSOR_BF16) wr_put_tensor_rows_fmt<WR_TENSOR_BF16>(a, r0, r1, t, (int)blockDim.x);
+  else wr_put_tensor_rows_fmt<WR_TENSOR_U8>(a, r0, r1, t, (int)blockDim.x);
+}
 // The scaled grab's last launch with a converting store: the tile's last level (wr_grab_scale_store's geometry) leaves as elements --
 // a thread per group of the OUTPUT row's grid that lies whole inside the tile's row, single pixels otherwise (a tile's row is
 // (64 >> steps) pixels at most: 8 after three halvings, shorter than U8's group).

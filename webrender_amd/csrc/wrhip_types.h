@@ -790,6 +790,30 @@ struct WrGrabScaleTensorArgs {
   WrGrabScaleArgs s;
   WrTensorOut o;
 };
+// WrhipPutTextureTensor: where and how tensor elements become the stored bytes of a texture rect (the contract: include/wrhip.h) --
+// WrTensorOut read the other way.  Element (c, y, x) of the `w` x `h` tensor lies at element index c * plane_stride + y * row_stride
+// + x (CHW) or y * row_stride + x * channels + c (HWC) from `src`; its byte is the element itself (U8), or the element widened to
+// float32, times scale[c] plus bias[c], clamped to [0, 255] and rounded to nearest even.  `vec`: src and the byte strides are
+// multiples of 16, so the elements behind a 16-byte piece of a texture row can be fetched with wide loads wherever their own address
+// allows it.  bgr: an RGBA8 pixel's stored bytes B, G, R take channels 0, 1, 2 (default: 2, 1, 0); alpha: the A byte of 3 channels.
+struct WrTensorIn {
+  const uint8_t* src;
+  long long row_stride, plane_stride;  // elements; never 0 here
+  int32_t dtype, hwc, channels;
+  int32_t flip;                        // tensor row r goes to rect row h - 1 - r
+  int32_t vec, bgr;
+  uint32_t alpha;
+  float scale[4], bias[4];
+};
+// one launch of wr_put_tensor_kernel.  Workgroup b converts rect rows [b * rows_per_wg, ...); a row is `slots` items at most: the
+// 16-byte pieces of the texture's storage its pixels touch
+struct WrPutTensorArgs {
+  uint8_t* tex;                        // the texture's storage (its origin)
+  int32_t tex_stride, bpp;             // bytes; 4: RGBA8, 2: RG8, 1: R8
+  int32_t rx, ry, w, h;                // the rect
+  int32_t rows_per_wg, slots;
+  WrTensorIn in;
+};
 struct WrGrabPushArgs {
   const uint8_t* src; uint8_t* dst;    // device slot -> pinned host slot
   uint32_t capacity;                   // of either, bytes (a multiple of 16): the count read from the slot is held to it

@@ -148,6 +148,8 @@ EXTRA_SIGNATURES = {
     "WrhipDeviceAlloc": (P, [u64]),
     "WrhipDeviceFree": (None, [P]),
     "WrhipDeviceRead": (i32, [P, P, u64]),
+    "WrhipDeviceWrite": (i32, [P, P, u64]),
+    "WrhipPutTextureTensor": (i32, [u32, P, P]),
 }
 
 
@@ -189,6 +191,12 @@ class WrhipGrabInfo(C.Structure):
 class WrhipTensorDesc(C.Structure):
     _fields_ = [("dst", P), ("dst_bytes", u64), ("out_w", i32), ("out_h", i32), ("dtype", u32), ("layout", u32), ("channels", u32),
                 ("row_stride", C.c_int64), ("plane_stride", C.c_int64), ("scale", C.c_float * 4), ("bias", C.c_float * 4), ("flags", u32)]
+
+
+class WrhipTensorSrc(C.Structure):
+    _fields_ = [("src", P), ("src_bytes", u64), ("dtype", u32), ("layout", u32), ("channels", u32),
+                ("row_stride", C.c_int64), ("plane_stride", C.c_int64), ("scale", C.c_float * 4), ("bias", C.c_float * 4),
+                ("alpha", u32), ("flags", u32)]
 
 
 def _as_ptr(x):
@@ -350,6 +358,37 @@ class GL:
         rc = self.WrhipDeviceRead(out.ctypes.data, int(ptr), int(nbytes))
         assert rc == 0, rc
         return out
+
+    def device_write(self, ptr, data):
+        """The bytes of `data` (bytes, or a C-contiguous numpy array) into device memory at `ptr` (WrhipDeviceWrite: a copy on the draw
+        stream behind everything issued so far, waited for)"""
+        import numpy as np
+        buf = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray)) else data)
+        rc = self.WrhipDeviceWrite(int(ptr), buf.ctypes.data, int(buf.nbytes))
+        assert rc == 0, rc
+
+    def put_texture_tensor(self, tex, rect, src, src_bytes, dtype=TENSOR_F32, layout=TENSOR_CHW, channels=3, strides=(0, 0),
+                           scale=(1.0, 1.0, 1.0, 1.0), bias=(0.0, 0.0, 0.0, 0.0), alpha=255, flags=0):
+        """A tensor put (include/wrhip.h, WrhipPutTextureTensor): the tensor of rect.w x rect.h pixels in the device memory `src` (an
+        address: device_alloc's, or any the context's runtime can read), of which `src_bytes` may be read, becomes the stored bytes
+        of `rect` = (x, y, w, h) of texture id `tex` -- None: all of it.  strides = (row, plane) in elements, 0: tight; scale, bias:
+        per input channel (up to four values; float32); alpha: the A byte of a 3-channel tensor.  `flags`: GRAB_FLIP_ROWS and / or
+        TENSOR_BGR.  Returns 0, or -1 (GL_INVALID_VALUE is then set)."""
+        if rect is None:
+            w, h = i32(0), i32(0)
+            if not self.WrhipGetTextureSize(tex, C.byref(w), C.byref(h)):
+                w = h = i32(0)
+            rect = (0, 0, w.value, h.value)
+        arr = (i32 * 4)(*[int(v) for v in rect])
+        d = WrhipTensorSrc()
+        d.src, d.src_bytes = int(src) or None, int(src_bytes)
+        d.dtype, d.layout, d.channels = int(dtype), int(layout), int(channels)
+        d.row_stride, d.plane_stride = int(strides[0]), int(strides[1])
+        for k in range(4):
+            d.scale[k] = float(scale[k]) if k < len(scale) else 1.0
+            d.bias[k] = float(bias[k]) if k < len(bias) else 0.0
+        d.alpha, d.flags = int(alpha), int(flags)
+        return self.WrhipPutTextureTensor(tex, C.addressof(arr), C.addressof(d))
 
     def grab_result(self, ticket, wait=True, into=None):
         """The result of a grab: (info dict, pixels).  Full mode: one array per rect ((h, w, 4) stored B, G, R, A bytes, or (h, w)

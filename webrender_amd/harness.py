@@ -292,3 +292,87 @@ def render_streamed_tensors(backend_path, frames, size, dtype, layout, channels,
     r.finish()
     r.destroy()
     return out, stats, infos
+
+
+def _fed_bytes(window_bgra):
+    """What render_streamed_fed feeds back, restated in numpy for a backend without tensor calls: the window's stored bytes (B, G, R,
+    A) as a tensor grab's F16 elements of R, G, B with scale 1 / 255 (a float32 multiply, then the rounding to float16), and those as
+    a tensor put's bytes with scale 255 (the float16 widened, a float32 multiply, clamped, rounded to nearest even), alpha 255"""
+    x = window_bgra[:, :, :3].astype(np.float32) * (np.float32(1.0) / np.float32(255.0))
+    y = x.astype(np.float16).astype(np.float32) * np.float32(255.0)
+    out = np.empty_like(window_bgra)
+    out[:, :, :3] = np.where(y >= 255, 255, np.rint(np.clip(y, 0, 255))).astype(np.uint8)
+    out[:, :, 3] = 255
+    return out
+
+
+def render_streamed_fed(backend_path, frames, feed_name, feed=True, initial=None):
+    """A closed loop: frame k + 1 draws images textured from frame k's window.  `frames` (one window size) sample a window-sized
+    RGBA8 texture they call `feed_name`; two such textures are used alternately -- frame k samples number k % 2 and its window is
+    fed into the other one --, both holding `initial` (stored bytes B, G, R, A; None: zeros) at the start.
+    libwrhip: after frame k's render the window is tensor-grabbed into device memory (F16, CHW, R, G, B, scale 1 / 255), that tensor
+    is put into the other texture (GL.put_texture_tensor, scale 255, alpha 255), and the frame is presented by a plain grab -- no
+    Finish, no ReadPixels and no TexSubImage2D of the fed texture anywhere in the loop: the pixels never leave the device except as
+    the presented frame.  Any other backend: ReadPixels, the same two conversions in numpy, TexSubImage2D.
+    feed=False: the loop without the feedback (both textures keep `initial`), the measure of what the frames themselves cost.
+    Returns the presented frames (stored bytes, B, G, R, A) and the backend's statistics (libwrhip; None otherwise)."""
+    from . import glapi
+    from .device import Texture
+    gl = GL(backend_path)
+    w, h = frames[0].width, frames[0].height
+    r = Renderer(gl, w, h)
+    d = r.device
+    first = np.zeros((h, w, 4), np.uint8) if initial is None else np.ascontiguousarray(initial, np.uint8)
+    assert first.shape == (h, w, 4), first.shape
+    ref = None
+    for f in frames:
+        assert (f.width, f.height) == (w, h), "render_streamed_fed: one window size"
+        for t in f.static_textures:
+            if t.name == feed_name:
+                ref = t
+    assert ref is not None and (ref.w, ref.h, ref.fmt) == (w, h, G.GL_RGBA8), "render_streamed_fed: a window-sized RGBA8 texture called feed_name"
+    fed = [d.create_texture(w, h, G.GL_RGBA8, ref.filter) for _ in range(2)]
+    for t in fed:
+        d.upload_texture(t, 0, 0, w, h, G.GL_BGRA, G.GL_UNSIGNED_BYTE, first)
+    images, waiting = [], []
+    if gl.is_wrhip:
+        window = gl.WrhipGetFramebufferTexture(0)
+        nbytes = 3 * w * h * 2
+        buf = gl.device_alloc(nbytes) if feed else 0
+        assert buf or not feed, gl.GetError()
+        inv = [float(np.float32(1.0) / np.float32(255.0))] * 4
+    for k, f in enumerate(frames):
+        r.textures[feed_name] = fed[k % 2]
+        r.render(f)
+        if not gl.is_wrhip:
+            px = d.read_texture(Texture(0, w, h, G.GL_RGBA8, fbo=0)).copy()
+            images.append(px)
+            if feed:
+                d.upload_texture(fed[(k + 1) % 2], 0, 0, w, h, G.GL_BGRA, G.GL_UNSIGNED_BYTE, _fed_bytes(px))
+            continue
+        if feed:
+            t = gl.grab_texture_tensor(window, (0, 0, w, h), buf, nbytes, dtype=glapi.TENSOR_F16, layout=glapi.TENSOR_CHW, channels=3, scale=inv)
+            assert t >= 0, (t, gl.GetError())
+            rc = gl.put_texture_tensor(fed[(k + 1) % 2].id, (0, 0, w, h), buf, nbytes, dtype=glapi.TENSOR_F16, layout=glapi.TENSOR_CHW,
+                                       channels=3, scale=[255.0] * 4, alpha=255)
+            assert rc == 0, (rc, gl.GetError())
+        if len(waiting) == 8:
+            images.append(gl.grab_result(waiting.pop(0))[1])
+        t = gl.grab_texture(window, [(0, 0, w, h)], 0)
+        assert t >= 0, (t, gl.GetError())
+        waiting.append(t)
+    stats = None
+    if gl.is_wrhip:
+        stats = gl.stats()                  # (the loop's: before the results are fetched and the last launches drained)
+        images += [gl.grab_result(t)[1] for t in waiting]
+        if feed:
+            gl.device_free(buf)
+    r.finish()
+    err = gl.GetError()
+    if stats is not None:
+        stats["gl_error"] = int(err)
+    del r.textures[feed_name]
+    for t in fed:
+        d.delete_texture(t)
+    r.destroy()
+    return images, stats
