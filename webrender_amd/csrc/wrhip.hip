@@ -3100,6 +3100,20 @@ void SetTextureBuffer(GLuint texid, GLenum internal_format, GLsizei width, GLsiz
   set_tex_storage(ctx->textures[texid], internal_format, width, height, buf, stride);
 }
 
+// A clear of a 2-byte texture.  No draw has an RG8 target, so there is no recorded work of the texture's own to order the clear in
+// (record_clear's targets are RGBA8 / R8): it is written at once, like a blit's destination -- behind every recorded or held-back draw
+// that still reads the texture and every queued upload into it.
+static void clear_rg8(Texture& t, uint16_t value, const int rect[4]) {
+  if (!t.has_storage() || t.own_none()) return;
+  const int x0 = std::max(rect[0], 0), y0 = std::max(rect[1], 0), x1 = std::min(rect[2], t.width), y1 = std::min(rect[3], t.height);
+  if (x1 <= x0 || y1 <= y0) return;
+  sync_texture_for_write(t);
+  flush_uploads(3160);
+  const long long n = (long long)(x1 - x0) * (y1 - y0);
+  WR_LAUNCH(wr_clear_rg8_kernel, (int)((n + 255) / 256), 256, ctx->stream, (uint8_t*)t.dptr, (int)t.stride, x0, y0, x1 - x0, y1 - y0, value);
+  ctx->stats.kernel_launches++;
+}
+
 void ClearTexSubImage(GLenum texture, GLint level, GLint xoffset, GLint yoffset, GLint zoffset, GLsizei width,
                       GLsizei height, GLsizei depth, GLenum format, GLenum type, const void* data) {
   if (level != 0) return;
@@ -3155,7 +3169,8 @@ void ClearTexSubImage(GLenum texture, GLint level, GLint xoffset, GLint yoffset,
       record_clear(texture, true, (color & 0xFF00FF00) | ((color << 16) & 0xFF0000) | ((color >> 16) & 0xFF), false, 0, 0, rect);
       break;
     case GL_R8: record_clear(texture, true, color & 0xFF, false, 0, 0, rect); break;
-    default: break;  // RG8 targets are not drawn to by WebRender
+    case GL_RG8: clear_rg8(t, uint16_t(color & 0xFFFF), rect); break;      // request_clear<uint16_t> (gl.cc:2481-2483): R in the low byte
+    default: break;
   }
 }
 void ClearTexImage(GLenum texture, GLint level, GLenum format, GLenum type, const void* data) {
@@ -3345,7 +3360,7 @@ void BlitFramebuffer(GLint srcX0, GLint srcY0, GLint srcX1, GLint srcY1, GLint d
   const int srcW = sr[2] - sr[0], srcH = sr[3] - sr[1], dstW = dr[2] - dr[0], dstH = dr[3] - dr[1];
   if (srcW <= 0 || srcH <= 0 || dstW <= 0 || dstH <= 0) return;
   const bool linear = !(srcW == dstW && srcH == dstH) && s.width >= 2 && filter == GL_LINEAR && s.internal_format == d.internal_format &&
-                      (s.internal_format == GL_RGBA8 || s.internal_format == GL_R8);
+                      renderable(s.internal_format);
   blit_textures(srcfb->color_attachment, s, dstfb->color_attachment, d, sr, dr, false, invertY, linear, false, nullptr, true);
 }
 

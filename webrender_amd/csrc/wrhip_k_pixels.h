@@ -95,7 +95,7 @@ __global__ void wr_blit_kernel(WrBlitArgs a) {
   const float lv = wr_blit_walk_v(bw_, j);
   WrTexDesc t;
   t.ptr = a.src; t.width = a.sw; t.height = a.sh; t.stride = a.sbpp == 4 ? a.src_stride / 4 : (a.sbpp == 2 ? a.src_stride / 2 : a.src_stride);
-  t.format = a.sbpp == 4 ? WR_FMT_RGBA8 : WR_FMT_R8; t.linear = 1; t.sw = float(a.sw); t.sh = float(a.sh);
+  t.format = a.sbpp == 4 ? WR_FMT_RGBA8 : (a.sbpp == 2 ? WR_FMT_RG8 : WR_FMT_R8); t.linear = 1; t.sw = float(a.sw); t.sh = float(a.sh);
   if (a.sbpp == 4) {
     const WrWide w = wr_sample_linear_rgba8(t, int(lu), int(lv));
     uint32_t o = wr_pack(w);
@@ -105,9 +105,22 @@ __global__ void wr_blit_kernel(WrBlitArgs a) {
       o = wr_blend_rgba8(WR_BLEND_PREMULT, dv_, w, nullptr);
     }
     __builtin_memcpy(dp, &o, 4);
+  } else if (a.sbpp == 2) {                                  // linear_row_blit(uint16_t*): textureLinearPackedRG8 -- the NV12 chroma plane's filter
+    int v[4];
+    wr_bilinear<2>(t, int(lu), int(lv), v);
+    const uint16_t o = uint16_t(wr_pack1(uint32_t(v[0]) & 0xFFFF) | (wr_pack1(uint32_t(v[1]) & 0xFFFF) << 8));
+    __builtin_memcpy(dp, &o, 2);
   } else {
     dp[0] = (uint8_t)wr_pack1(uint32_t(wr_sample_linear_r8(t, int(lu), int(lv))) & 0xFFFF);
   }
+}
+// ClearTexSubImage of an RG8 texture (clear_buffer<uint16_t>, gl.cc:2161-2188): `value` into the w x h texels from (x0, y0) on, which the
+// host has cut to the texture; one thread per texel.
+__global__ void wr_clear_rg8_kernel(uint8_t* dst, int stride, int x0, int y0, int w, int h, uint16_t value) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long long)w * h) return;
+  const int i = int(idx % w), j = int(idx / w);
+  __builtin_memcpy(dst + (size_t)(y0 + j) * stride + (size_t)(x0 + i) * 2, &value, 2);
 }
 #endif
 
