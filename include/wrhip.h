@@ -252,7 +252,7 @@ void WrhipSetProfiling(int enabled);
  * (picture targets of a few large gradient / image prims, likewise), 11 = wr_setup_tile_rows_kernel (10 fused with the next flush's setup stage), 12 = a thin launch of the raster kernel (13: the same with the next flush's setup stage in front, wr_setup_raster_thin_kernel) (wr_raster_kernel<fmt, false, 1, feat>:
  * small levels, several workgroups per bin), 14 = wr_tap_kernel (WrhipTapTexture: fmt of the tapped texture, feat 1 against an expected texture;
  * algo_bytes: the rect's bytes, twice with an expected texture), 15 = wr_grab_pack_kernel (WrhipGrabTexture: fmt of the grabbed texture,
- * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta, feat 3: wr_grab_scale_kernel, the launches of one WrhipGrabTextureScaled, feat 4: wr_grab_tensor_kernel or the launches of a scaled WrhipGrabTextureTensor; algo_bytes: bytes read plus bytes written, as far as they are known at the launch), 16 = wr_put_tensor_kernel (WrhipPutTextureTensor: fmt of the texture written;
+ * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta, feat 3: wr_grab_scale_kernel, the launches of one WrhipGrabTextureScaled, feat 4: wr_grab_tensor_kernel or the launches of a scaled WrhipGrabTextureTensor, feat 5: wr_grab_yuv_kernel, a WrhipGrabTextureYuv (the rect read once plus the planes written); algo_bytes: bytes read plus bytes written, as far as they are known at the launch), 16 = wr_put_tensor_kernel (WrhipPutTextureTensor: fmt of the texture written;
  * algo_bytes: the elements read plus the rect's bytes written).  algo_bytes: the launch's algorithmic bytes:
  * raster launches count every destination pixel they own once (twice when the target's old content is loaded) plus
  * the source texels their draws can sample; the setup stage counts instance + descriptor + record bytes.  Returns the
@@ -487,9 +487,57 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  * channels other than 3 or 4 (RGBA8), 1 (R8), 2 (RG8); a rect that is empty or not inside `tex`; an unknown dtype, layout or flag;
  * a NULL desc or src; a src not aligned to its element; a stride below the tensor grab's minimum or above 2^40; an extent in bytes
  * above src_bytes; an alpha above 255; and while sharding is on.
+ *
+ * WrhipGrabTextureYuv(tex, rect, desc): a grab of ONE rect of a GL_RGBA8 texture as 8-bit Y'CbCr planes for a video encoder -- the
+ * inverse of the video that CompositeYUV and brush_yuv_image draw.  One launch (wr_grab_yuv_kernel) converts the rect; the planes
+ * cross to the host as the ticket's payload (desc->dst == NULL: 1.5 bytes per pixel in 4:2:0 against a full grab's 4), or are
+ * written into the caller's device memory.  The contract -- any restatement must give the same bytes:
+ *   pixels    the rect's stored bytes B, G, R, A; A is ignored.  Stored colours are premultiplied, so what is converted is the page
+ *             over BLACK; nothing is un-premultiplied.  No scaling.  With FLIP_ROWS image row r is rect row h - 1 - r; the flip
+ *             comes first, chroma blocks are formed on the flipped image.
+ *   planes    Y is w x h.  WRHIP_YUV_I420: a Cb and a Cr plane of cw x ch samples, cw = (w + 1) / 2, ch = (h + 1) / 2.
+ *             WRHIP_YUV_NV12: one plane of ch rows of cw (Cb, Cr) byte pairs.  WRHIP_YUV_I444: a Cb and a Cr plane of w x h.
+ *   luma      Y = (Yr * R + Yg * G + Yb * B + (y0 << 16) + 0x8000) >> 16 with y0 = 16 in the narrow ranges and 0 in the full ones;
+ *             it cannot leave 0 .. 255.
+ *   chroma    I444, per pixel: C = clamp((Cr_ * R + Cg * G + Cb_ * B + (128 << 16) + 0x8000) >> 16, 0, 255).  4:2:0, sample (i, j):
+ *             S is the channel-wise sum of the four pixels at image positions (min(2i + dx, w - 1), min(2j + dy, h - 1)), dx, dy in
+ *             {0, 1} -- clamped to the RECT, not the texture -- and C = clamp((c . S + (128 << 18) + (1 << 17)) >> 18, 0, 255).
+ *             32-bit integer arithmetic, arithmetic right shifts; no intermediate reaches 2^27.  The clamp is live: pure blue or
+ *             pure red gives 256 in a full range.
+ *   rows      desc->color_space is a YuvRangedColorSpace, 0 .. 5; the rows, R, G, B, in 16.16 fixed point:
+ *               0 Rec601Narrow   Y 16829 33039 6416   Cb  -9714 -19070 28784   Cr 28784 -24103 -4681
+ *               1 Rec601Full     Y 19595 38470 7471   Cb -11058 -21710 32768   Cr 32768 -27439 -5329
+ *               2 Rec709Narrow   Y 11966 40254 4064   Cb  -6596 -22188 28784   Cr 28784 -26145 -2639
+ *               3 Rec709Full     Y 13933 46871 4732   Cb  -7509 -25259 32768   Cr 32768 -29763 -3005
+ *               4 Rec2020Narrow  Y 14786 38160 3338   Cb  -8038 -20746 28784   Cr 28784 -26469 -2315
+ *               5 Rec2020Full    Y 17216 44434 3886   Cb  -9151 -23617 32768   Cr 32768 -30133 -2635
+ *             From Kr, Kb = (0.299, 0.114), (0.2126, 0.0722), (0.2627, 0.0593): the real row, times 219 / 255 (Y) or 224 / 255
+ *             (chroma) in a narrow range, times 65536, each entry rounded to nearest; then the GREEN entry is adjusted so that a Y
+ *             row sums to 56284 (narrow) or 65536 (full) and a chroma row to 0.  So a grey g gives Y = y0 + round(g * 219 / 255)
+ *             (or g) and chroma exactly 128, a flat 2 x 2 block gives I444's chroma, and no sample is further than 1 from the
+ *             real formula rounded half up.
+ *   host sink (dst == NULL; the strides and dst_bytes must be 0)  the payload is the planes, each tight, one after another: Y, Cb,
+ *             Cr -- NV12: Y, then the plane of pairs.  It rides the grab ring as a full grab's does: slot growth,
+ *             WRHIP_GRAB_PINNED_MAX, transport on the grab stream.  WrhipGrabResultGet copies the payload to `dst` (dst_stride must
+ *             be 0: -1 with GL_INVALID_VALUE otherwise) and reports flags | WRHIP_GRAB_YUV, format GL_RGBA8, the rect, `bytes` =
+ *             header + payload.  WrhipGrabPayloadGet works as for any grab.
+ *   device sink (dst != NULL)  Y row r lies at dst + r * y_stride; the chroma planes follow at dst + h * y_stride, rows c_stride
+ *             apart, the second plane of I420 and I444 a further rows * c_stride on.  Strides are in BYTES; 0 is the tight one (w;
+ *             cw, 2 * cw for NV12, or w).  Nothing but the planes' samples is written: not the padding of a row, not a byte ahead
+ *             of `dst` or behind the last sample.  The ticket carries an empty payload and its arrival is the completion signal
+ *             (`bytes` = 16, WrhipGrabResultGet ignores `dst`); the write does NOT depend on the ticket surviving, as for a tensor
+ *             grab, and "consuming on the device" is the tensor grab's.  A parked YUV grab's destination takes part in
+ *             WrhipPutTextureTensor's overlap rule as a parked tensor grab's does.
+ *   ordering  WrhipGrabTexture's, parking and "later writes do not change the result" included.
+ *   cost      one launch: WrhipStats::kernel_launches grows by 1, flushes by 0.
+ * Returns -1 and sets GL_INVALID_VALUE, launching and flushing nothing, for: an unknown texture or a format other than GL_RGBA8; a
+ * rect that is empty or not inside `tex`; an unknown format, colour space (GbrIdentity and above) or flag; a NULL desc; a host sink
+ * with a non-zero stride or dst_bytes; a device sink with a stride below its row's bytes or above 2^40, or an extent above
+ * dst_bytes; and while sharding is on.  -1 with GL_OUT_OF_MEMORY as WrhipGrabTexture.
  * Not routed through grabs: Finish, GetColorBuffer, ReadPixels.  Not supported: other formats, sharded targets; scaling other than
- * WrhipGrabTextureScaled's; delta or packed tensor grabs; gamma or colour-space conversion (values are the stored premultiplied bytes);
- * puts that scale or filter, into other formats, into sharded targets or host-backed textures. */
+ * WrhipGrabTextureScaled's; delta or packed tensor grabs; gamma or colour-space conversion of tensors (values are the stored
+ * premultiplied bytes); puts that scale or filter, into other formats, into sharded targets or host-backed textures; YUV grabs of 10-
+ * or 16-bit samples (P010), 4:2:2 or YUY2, scaled or delta YUV grabs, R8 sources, un-premultiplying, GbrIdentity. */
 #define WRHIP_GRAB_FLIP_ROWS 1u   /* full mode: deliver the rect's last row first */
 #define WRHIP_GRAB_SWAP_RB   2u   /* full mode, RGBA8 only: bytes 0 and 2 of every pixel exchanged */
 #define WRHIP_GRAB_DELTA     4u   /* only the 64x64 blocks that differ from the previous DELTA grab of this texture and rect */
@@ -497,6 +545,10 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
 #define WRHIP_GRAB_PACKED    32u  /* with DELTA: sent blocks as SOLID / RUNS / RAW entries (the packed payload above); 16 is no flag */
 #define WRHIP_GRAB_SCALED    64u  /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureScaled ticket; no flag of WrhipGrabTexture, which rejects it */
 #define WRHIP_GRAB_TENSOR    128u /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureTensor ticket; no flag of the other grab calls, which reject it */
+#define WRHIP_GRAB_YUV       512u /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureYuv ticket; rejected by the other grab calls */
+#define WRHIP_YUV_I420 0u         /* WrhipYuvDesc::format: Y plane, Cb plane, Cr plane; chroma 4:2:0 */
+#define WRHIP_YUV_NV12 1u         /* Y plane, one plane of interleaved Cb,Cr pairs; chroma 4:2:0 */
+#define WRHIP_YUV_I444 2u         /* Y, Cb, Cr planes, all w x h */
 #define WRHIP_TENSOR_U8   0u      /* WrhipTensorDesc::dtype */
 #define WRHIP_TENSOR_F16  1u
 #define WRHIP_TENSOR_BF16 2u
@@ -543,6 +595,15 @@ typedef struct WrhipTensorSrc {
   uint32_t flags;                  /* WRHIP_GRAB_FLIP_ROWS and / or WRHIP_TENSOR_BGR */
 } WrhipTensorSrc;
 int32_t WrhipPutTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTensorSrc* desc);
+typedef struct WrhipYuvDesc {
+  uint32_t format;                 /* WRHIP_YUV_* */
+  uint32_t color_space;            /* YuvRangedColorSpace 0..5: Rec601Narrow, Rec601Full, Rec709Narrow, Rec709Full, Rec2020Narrow, Rec2020Full */
+  uint32_t flags;                  /* 0 or WRHIP_GRAB_FLIP_ROWS */
+  void*    dst;                    /* NULL: planes go to the host through the ticket ring; else device memory */
+  uint64_t dst_bytes;              /* device sink: bytes the library may write from dst on */
+  int64_t  y_stride, c_stride;     /* device sink, BYTES per row of the Y plane / of a chroma plane; 0: tight */
+} WrhipYuvDesc;
+int32_t WrhipGrabTextureYuv(GLuint tex, const int32_t rect[4], const WrhipYuvDesc* desc);
 int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64_t dst_stride, int32_t wait);
 int32_t WrhipGrabPayloadGet(int32_t ticket, void* dst, uint64_t capacity, uint64_t* bytes, int32_t wait);
 int32_t WrhipGrabDecode(const void* payload, uint64_t bytes, uint32_t format, uint32_t flags, int32_t rect_w, int32_t rect_h, void* dst, int64_t dst_stride, int32_t damage[4], uint32_t* blocks);

@@ -26,10 +26,12 @@
              WrhipDeviceRead, the conversion in numpy, TexSubImage2D -- each followed by a tap of the texture as the consumer, host
              clock per frame; then image_grid at 2048 x 2048 streamed by native replay with its window fed back into its atlas every
              frame: a tensor grab and a put, against a tensor grab, WrhipDeviceRead, numpy and TexSubImage2D, frames/s
+  yuv        WrhipGrabTextureYuv: wr_grab_yuv_kernel per launch for I420, NV12 and I444, host and device sink, beside the full-mode
+             pack of the same job; the cfg2 stream with an I420 host grab per frame against a full grab plus numpy on the host
   ab         plain bench.py against another build of the library (WRHIP_LIB_PATH), alternated, no grab issued
 
 Every section runs three alternated rounds.  Needs the GPU: there is no fallback.
-  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor,put] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
+  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor,put,yuv] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -728,6 +730,113 @@ def section_put_stream(lib, frames):
     gl.device_free(buf)
 
 
+# ---- YUV grabs (WrhipGrabTextureYuv) ------------------------------------------------------------------------
+YUV_NAMES = {glapi.YUV_I420: "I420", glapi.YUV_NV12: "NV12", glapi.YUV_I444: "I444"}
+YUV_ROWS = np.array([[11966, 40254, 4064], [-6596, -22188, 28784], [28784, -26145, -2639]], np.int32)      # Rec709Narrow: Y, Cb, Cr over R, G, B
+
+
+def yuv_numpy_i420(px):
+    """The contract's I420 planes of Rec709Narrow restated in numpy on the host -- what a caller does today behind a full grab"""
+    rgb = px[..., [2, 1, 0]].astype(np.int32)
+    y = ((rgb @ YUV_ROWS[0] + (16 << 16) + 0x8000) >> 16).astype(np.uint8)
+    h, w = y.shape
+    ys, xs = np.minimum(np.arange(0, 2 * ((h + 1) // 2)), h - 1), np.minimum(np.arange(0, 2 * ((w + 1) // 2)), w - 1)
+    v = rgb[ys][:, xs]
+    s = v[0::2, 0::2] + v[0::2, 1::2] + v[1::2, 0::2] + v[1::2, 1::2]
+    c = [np.clip((s @ YUV_ROWS[k] + (128 << 18) + (1 << 17)) >> 18, 0, 255).astype(np.uint8) for k in (1, 2)]
+    return np.concatenate([y.reshape(-1), c[0].reshape(-1), c[1].reshape(-1)])
+
+
+def section_yuv_kernel(lib, content):
+    say(f"## yuv: wr_grab_yuv_kernel, {W}x{H} RGBA8 window of {content}, Rec709Narrow, hipEvents (WrhipSetProfiling(1)), us per launch")
+    w = Window(lib, content)
+    gl = w.gl
+    buf = gl.device_alloc(W * H * 3)
+    assert buf, gl.GetError()
+    info = glapi.WrhipGrabInfo()
+
+    def grab(fmt, device):
+        if fmt is None:
+            return w.grab(0)
+        t = gl.grab_texture_yuv(w.tex, None, fmt, glapi.YUV_REC709_NARROW, dst=buf if device else None, dst_bytes=W * H * 3 if device else 0)
+        assert t >= 0, gl.GetError()
+        assert gl.WrhipGrabResultGet(t, C.byref(info), None, 0, 1) == 0
+    cases = [("full-mode pack", None, False)] + [(f"{YUV_NAMES[f]} {'device' if d else 'host  '}", f, d) for f in YUV_NAMES for d in (True, False)]
+    for _, fmt, dev in cases:
+        for _ in range(4):
+            grab(fmt, dev)
+    if content == "noise":
+        flat = gl.grab_result(gl.grab_texture_yuv(w.tex, None, glapi.YUV_I420, glapi.YUV_REC709_NARROW))[1]
+        px = gl.grab_result(gl.grab_texture(w.tex, None, 0))[1]
+        say(f"  bytes in which the I420 grab differs from numpy on the full grab's pixels: {int((flat != yuv_numpy_i420(px)).sum())} of {flat.size}")
+    gl.WrhipSetProfiling(1)
+    rows, n = {}, 30
+    for rnd in range(ROUNDS):
+        for name, fmt, dev in cases:
+            gl.WrhipResetStats()
+            for _ in range(n):
+                grab(fmt, dev)
+            ks = [k for k in kernel_stats(gl, 15) if k.feat == (0 if fmt is None else 5)]
+            assert len(ks) == 1 and ks[0].launches == n, [(k.feat, k.launches) for k in ks]
+            rows.setdefault(name, []).append((ks[0].ns / n / 1e3, ks[0].algo_bytes // n, ks[0].workgroups // n))
+    gl.WrhipSetProfiling(0)
+    for name, v in rows.items():
+        say(f"  {name:14s} " + "  ".join(f"{us:8.1f}" for us, _, _ in v) + f"   us   ({v[0][1] / 1e6:6.1f} MB read + written: " +
+            "  ".join(f"{b / us / 1e3:6.0f}" for us, b, _ in v) + f" GB/s; {v[0][2]} workgroups)")
+    gl.device_free(buf)
+    w.close()
+
+
+def section_yuv_stream(lib, frames):
+    say(f"## yuv stream: cfg2 {W}x{H} streamed as in `stream`, {frames} frames per region, frames/s; tickets fetched one frame late")
+    rec, _ = record_scene(lib, scenes.make_workload("cfg2", width=W, height=H))
+    p = ScenePlayer(lib, rec)
+    gl = glapi.GL(lib)                          # (the same loaded library and current context as the player's)
+    window = gl.WrhipGetFramebufferTexture(0)
+    payload = W * H + 2 * ((W + 1) // 2) * ((H + 1) // 2)
+    host = np.empty(W * H * 4, np.uint8)
+    info = glapi.WrhipGrabInfo()
+
+    def run(kind, n):
+        prev = -1
+
+        def fetch(t):
+            assert gl.WrhipGrabResultGet(t, C.byref(info), host.ctypes.data, 0, 1) == 0
+            if kind == "full grab + numpy":
+                yuv_numpy_i420(host.reshape(H, W, 4))
+        for k in range(n):
+            p.rp.exec(rec.stream)
+            t = -1
+            if kind == "I420 host grab":
+                t = gl.grab_texture_yuv(window, (0, 0, W, H), glapi.YUV_I420, glapi.YUV_REC709_NARROW)
+            elif kind == "full grab + numpy":
+                t = gl.grab_texture(window, (0, 0, W, H), 0)
+            if prev >= 0:
+                fetch(prev)
+            prev = t
+        if prev >= 0:
+            fetch(prev)
+        gl.Finish()
+    kinds = ["no grab", "I420 host grab", "full grab + numpy"]
+    rows, carried, crossed = {}, {}, {}
+    for k in kinds:
+        run(k, 4)
+    for rnd in range(ROUNDS):
+        for k in kinds:
+            n = frames if k != "full grab + numpy" else max(4, frames // 10)      # (the host conversion: tens of ms per frame)
+            gl.WrhipResetStats()
+            t0 = time.perf_counter()
+            run(k, n)
+            dt = time.perf_counter() - t0
+            st = gl.stats()
+            rows.setdefault(k, []).append(n / dt)
+            carried[k] = (st["setup_carried"], n)
+            crossed[k] = st["d2h_bytes"] / n
+    for k in kinds:
+        say(f"  {k:18s} " + "  ".join(f"{v:9.1f}" for v in rows[k]) + f"   frames/s   (setup_carried {carried[k][0]} of {carried[k][1]} flushes; {crossed[k] / 1e6:.2f} MB per frame crossed)")
+    say(f"  (an I420 payload is {payload / 1e6:.2f} MB, a full grab's {W * H * 4 / 1e6:.2f} MB)")
+
+
 def section_ab(other, steps, warmup):
     say(f"## ab: bench.py --gpus 1 --steps {steps} --warmup {warmup} (cfg2), this library against {os.path.basename(other)}, alternated, frames/s")
     rows = {"parent": [], "this": []}
@@ -796,6 +905,10 @@ def main():
                 section_tensor_kernel(lib, "noise")      # (the rate beside: the same bytes the other way)
                 section_put(lib)
                 section_put_stream(lib, args.frames)
+            elif s == "yuv":
+                section_yuv_kernel(lib, "noise")
+                section_yuv_kernel(lib, "cfg2")
+                section_yuv_stream(lib, args.frames)
             elif s == "tensor_parent":          # (run by `tensor` with WRHIP_LIB_PATH set: the parent path alone, on that library)
                 section_tensor_scaled(lib, with_tensor=False)
                 section_tensor_stream(lib, args.frames, with_tensor=False)

@@ -673,8 +673,11 @@ struct Context {
   // WrhipGrabTextureTensor: the unscaled launch as it goes out (`args`; its slot is filled in when it is issued), or -- `scaled` --
   // the chain of a scaled grab (`scale`) whose last launch stores the elements `out` describes
   struct GrabTensor { bool scaled; WrGrabTensorArgs args; GrabScaled scale; WrTensorOut out; uint64_t out_bytes, dst_extent; };      // (dst_extent: the bytes from out.dst on that hold its elements)
-  enum GrabKind { GRAB_PLAIN = 0, GRAB_SCALED = 1, GRAB_TENSOR = 2 };
-  struct GrabParked { uint64_t n; GrabKind kind; WrGrabArgs args; GrabScaled scale; GrabTensor tensor; };
+  // WrhipGrabTextureYuv: the launch as it goes out.  device: the planes go to the caller's memory (`dst_extent` bytes from args.y on)
+  // and the ticket carries an empty payload; otherwise they are the ticket's payload, and args.y, cb, cr are offsets from its start
+  struct GrabYuv { bool device; WrGrabYuvArgs args; uint64_t out_bytes, dst_extent; };
+  enum GrabKind { GRAB_PLAIN = 0, GRAB_SCALED = 1, GRAB_TENSOR = 2, GRAB_YUV = 3 };
+  struct GrabParked { uint64_t n; GrabKind kind; WrGrabArgs args; GrabScaled scale; GrabTensor tensor; GrabYuv yuv; };
   GrabSlot grab_slot[GRAB_RING];
   uint64_t grab_next = 0;
   std::vector<GrabParked> grab_parked;
@@ -1772,6 +1775,28 @@ void grab_issue_tensor(uint64_t n, const Context::GrabTensor& g, bool notify) {
   c->stats.kernel_launches += launches;
   if (notify) grab_push(gs, 0, false);
 }
+// One YUV grab, now: the slot's previous ticket first, then the one launch, which writes the header -- of the planes' bytes behind
+// it in the slot (host sink), or of an empty payload (device sink) -- and the transport.  notify == false (device sink only): the
+// ticket has been overwritten while the grab was parked; the planes are written all the same, nobody is told.
+void grab_issue_yuv(uint64_t n, const Context::GrabYuv& g, bool notify) {
+  Context* c = ctx;
+  Context::GrabSlot& gs = c->grab_slot[n % Context::GRAB_RING];
+  if (notify) wrrt::stream_wait_event(c->stream, &gs.ev);
+  WrGrabYuvArgs a = g.args;
+  a.slot = notify ? gs.dev : nullptr;
+  if (!g.device) {
+    uint8_t* const base = gs.dev + WR_GRAB_HEADER;
+    a.y = base + (uintptr_t)g.args.y; a.cb = base + (uintptr_t)g.args.cb; a.cr = base + (uintptr_t)g.args.cr;
+  }
+  const int units = a.format == WR_YUV_I444 ? a.h : (a.h + 1) / 2;
+  const uint64_t workgroups = (uint64_t)((units + a.units_per_wg - 1) / a.units_per_wg);
+  prof_begin();
+  WR_LAUNCH(wr_grab_yuv_kernel, (int)workgroups, 256, c->stream, a);
+  // (15, feat 5: wr_grab_yuv_kernel; the rect read once, the planes written)
+  prof_end(WR_KIND_GRAB, WR_FMT_RGBA8, 0, 5, (uint64_t)a.w * a.h * 4 + g.out_bytes, workgroups);
+  c->stats.kernel_launches++;
+  if (notify) grab_push(gs, a.payload, c->grab_full_kernel);
+}
 // tail_launched(): the grabs that waited for the held-back launches follow them, in the order they were made
 void grab_issue_parked() {
   Context* c = ctx;
@@ -1787,9 +1812,11 @@ void grab_issue_parked() {
     auto st = std::find(stale.begin(), stale.end(), (const uint8_t*)p.args.keep);
     // (a tensor grab writes the caller's memory, not the slot: it goes out with or without its ticket)
     if (p.kind == Context::GRAB_TENSOR) { grab_issue_tensor(p.n, p.tensor, gs.n == p.n); continue; }
+    if (p.kind == Context::GRAB_YUV && p.yuv.device) { grab_issue_yuv(p.n, p.yuv, gs.n == p.n); continue; }
     if (gs.n != p.n) { if (p.args.delta && st == stale.end()) stale.push_back(p.args.keep); continue; }
     if (p.args.delta && st != stale.end()) { p.args.keyframe = 1; gs.keyframe = true; stale.erase(st); }
     if (p.kind == Context::GRAB_SCALED) grab_issue_scaled(p.n, p.scale);
+    else if (p.kind == Context::GRAB_YUV) grab_issue_yuv(p.n, p.yuv, true);
     else grab_issue(p.n, p.args);
   }
   for (const uint8_t* k : stale)
@@ -4355,6 +4382,83 @@ int32_t WrhipGrabTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTen
   }
   return (int32_t)(n & 0x7FFFFFFFull);
 }
+// A YUV grab: see include/wrhip.h.  Ticket ring, ordering and parking are WrhipGrabTexture's; the planes are the payload, or go to
+// the caller's device memory under an empty one.
+// (the rows of YuvRangedColorSpace 0 .. 5 in 16.16, R, G, B: Y, Cb, Cr; the header states how they are derived)
+static const int32_t wr_yuv_rows[6][9] = {
+  {16829, 33039, 6416, -9714, -19070, 28784, 28784, -24103, -4681},      // Rec601Narrow
+  {19595, 38470, 7471, -11058, -21710, 32768, 32768, -27439, -5329},     // Rec601Full
+  {11966, 40254, 4064, -6596, -22188, 28784, 28784, -26145, -2639},      // Rec709Narrow
+  {13933, 46871, 4732, -7509, -25259, 32768, 32768, -29763, -3005},      // Rec709Full
+  {14786, 38160, 3338, -8038, -20746, 28784, 28784, -26469, -2315},      // Rec2020Narrow
+  {17216, 44434, 3886, -9151, -23617, 32768, 32768, -30133, -2635},      // Rec2020Full
+};
+int32_t WrhipGrabTextureYuv(GLuint tex, const int32_t rect[4], const WrhipYuvDesc* desc) {
+  if (!ctx) return -1;
+  Context* c = ctx;
+  Texture* t = tex ? c->textures.find(tex) : nullptr;
+  bool ok = t && t->dptr && t->internal_format == GL_RGBA8 && rect && desc;
+  ok = ok && desc->format <= WRHIP_YUV_I444 && desc->color_space <= 5u && (desc->flags & ~WRHIP_GRAB_FLIP_ROWS) == 0;
+  ok = ok && rect[2] >= 1 && rect[3] >= 1 && rect[0] >= 0 && rect[1] >= 0 && rect[0] <= t->width - rect[2] && rect[1] <= t->height - rect[3];
+  // the planes: Y of w x h, chroma of cw x ch samples in rows of c_row bytes; strides (0: tight) no smaller than a row
+  const int64_t stride_max = (int64_t)1 << 40;       // (keeps every product below in 64 bits)
+  int64_t w = 0, h = 0, ch = 0, c_row = 0, ys = 0, cs = 0, extent = 0;
+  if (ok) {
+    w = rect[2]; h = rect[3];
+    const bool i444 = desc->format == WRHIP_YUV_I444, nv12 = desc->format == WRHIP_YUV_NV12;
+    ch = i444 ? h : (h + 1) / 2;
+    c_row = i444 ? w : nv12 ? 2 * ((w + 1) / 2) : (w + 1) / 2;
+    ys = desc->y_stride ? desc->y_stride : w;
+    cs = desc->c_stride ? desc->c_stride : c_row;
+    if (!desc->dst) ok = desc->y_stride == 0 && desc->c_stride == 0 && desc->dst_bytes == 0;
+    else ok = ys >= w && ys <= stride_max && cs >= c_row && cs <= stride_max;
+    // (the last chroma plane's last row ends the extent: one plane of pairs, or two planes)
+    extent = h * ys + ((nv12 ? 1 : 2) * ch - 1) * cs + c_row;
+    ok = ok && (!desc->dst || (uint64_t)extent <= desc->dst_bytes);
+  }
+  ok = ok && c->shard_world <= 1 && t->own_y0 == t->own_y1;      // (sharded targets hold a strip of the frame each: out of scope)
+  if (!ok) { c->last_error = GL_INVALID_VALUE; return -1; }
+  Context::GrabYuv g;
+  memset(&g, 0, sizeof(g));
+  g.device = desc->dst != nullptr;
+  g.out_bytes = (uint64_t)(w * h + (desc->format == WRHIP_YUV_NV12 ? 1 : 2) * ch * c_row);
+  g.dst_extent = (uint64_t)extent;
+  WrGrabYuvArgs& a = g.args;
+  a.tex = (const uint8_t*)t->dptr; a.tex_stride = t->stride;
+  a.rx = rect[0]; a.ry = rect[1]; a.w = rect[2]; a.h = rect[3];
+  a.format = (int32_t)desc->format; a.flip = (desc->flags & WRHIP_GRAB_FLIP_ROWS) ? 1 : 0;
+  // (host sink: offsets from the payload's start, made addresses when the grab is issued -- the slot may grow until then)
+  a.y = (uint8_t*)desc->dst; a.cb = a.y + h * ys; a.cr = a.cb + ch * cs;
+  a.y_stride = ys; a.c_stride = cs;
+  a.payload = g.device ? 0u : (uint32_t)g.out_bytes;
+  const int32_t* k = wr_yuv_rows[desc->color_space];
+  for (int i = 0; i < 3; i++) { a.cy[i] = k[i]; a.ccb[i] = k[3 + i]; a.ccr[i] = k[6 + i]; }
+  a.y0 = (desc->color_space & 1u) ? 0 : 16;
+  // (an item is eight pixels of a row pair, or of a row of I444; a row has a piece more than its bytes fill when it starts inside
+  // one.  A workgroup per 512 items, or per unit, if a unit has more)
+  const int units = desc->format == WRHIP_YUV_I444 ? a.h : (a.h + 1) / 2;
+  a.slots = (a.w + 7) / 8 + 1;
+  a.units_per_wg = std::max(1, std::min(units, 512 / a.slots));
+  Context::GrabSlot* const slot = grab_reserve(g.device ? 0 : g.out_bytes);
+  if (!slot) return -1;
+  Context::GrabSlot& gs = *slot;
+  const uint64_t n = c->grab_next++;
+  gs.n = n; gs.counted = false;
+  gs.format = t->internal_format; gs.flags = desc->flags | WRHIP_GRAB_YUV; gs.bpp = t->bpp; gs.nrects = 1;
+  memcpy(gs.rects, rect, sizeof(int32_t) * 4);
+  gs.keyframe = false; gs.blocks_total = 0;
+  gs.scaled_w = gs.scaled_h = gs.levels = 0;
+  if (c->tail.pending && t->tail_ref) {
+    gs.parked = true;
+    Context::GrabParked p;
+    memset(&p, 0, sizeof(p));
+    p.n = n; p.kind = Context::GRAB_YUV; p.yuv = g;
+    c->grab_parked.push_back(p);
+  } else {
+    grab_issue_yuv(n, g, true);
+  }
+  return (int32_t)(n & 0x7FFFFFFFull);
+}
 // A tensor put: see include/wrhip.h.  A texture write at its place in the call order -- TexSubImage2D's ordering, one launch on the
 // draw stream instead of staged rows.  Arguments are checked before anything is flushed or launched.
 int32_t WrhipPutTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTensorSrc* desc) {
@@ -4390,6 +4494,8 @@ int32_t WrhipPutTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTens
   for (const Context::GrabParked& p : c->grab_parked) {
     const uint8_t* const d0 = p.tensor.out.dst;
     if (p.kind == Context::GRAB_TENSOR && d0 < s1 && s0 < d0 + p.tensor.dst_extent) { drain_tail(); break; }
+    const uint8_t* const y0 = p.yuv.args.y;
+    if (p.kind == Context::GRAB_YUV && p.yuv.device && y0 < s1 && s0 < y0 + p.yuv.dst_extent) { drain_tail(); break; }
   }
   // the write: draws recorded so far that sample or target the texture are flushed, held-back launches that reference it leave,
   // queued uploads go out ahead of it
@@ -4494,6 +4600,8 @@ int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64
   const bool scaled = (gs->flags & WRHIP_GRAB_SCALED) != 0;      // (one rect, delivered as scaled_h rows of scaled_w pixels)
   const bool tensor = (gs->flags & WRHIP_GRAB_TENSOR) != 0;      // (nothing to deliver: the elements are in the caller's device memory)
   if (tensor) dst = nullptr;
+  const bool yuv = (gs->flags & WRHIP_GRAB_YUV) != 0;            // (the payload is the planes: delivered as it crossed, tight)
+  if (yuv && dst && dst_stride != 0) { c->last_error = GL_INVALID_VALUE; return -1; }
   const int64_t tight = (int64_t)(scaled ? gs->scaled_w : gs->rects[0][2]) * bpp;
   if (dst && dst_stride != 0 && (gs->nrects > 1 || dst_stride < tight)) { c->last_error = GL_INVALID_VALUE; return -1; }
   uint32_t payload;
@@ -4505,7 +4613,9 @@ int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64
   memcpy(r.rects, gs->rects, sizeof(int32_t) * 4 * gs->nrects);
   r.bytes = (uint64_t)WR_GRAB_HEADER + payload;
   r.scaled_w = gs->scaled_w; r.scaled_h = gs->scaled_h; r.levels = (uint32_t)gs->levels;
-  if (!delta) {
+  if (yuv) {
+    if (dst) big_memcpy(dst, src, payload);
+  } else if (!delta) {
     for (int i = 0; i < gs->nrects; i++) {
       const size_t row = (size_t)(scaled ? gs->scaled_w : gs->rects[i][2]) * bpp;
       const int h = scaled ? gs->scaled_h : gs->rects[i][3];

@@ -915,6 +915,150 @@ __global__ void __launch_bounds__(256) wr_grab_scale_tensor_kernel(WrGrabScaleTe
                  if (a.slot && blockIdx.x == 0 && t == 0) wr_grab_st16(a.slot, wr_u4{0u, 0u, 0u, 0u}))
 }
 #undef WR_SCALE_PHASE
+// WrhipGrabTextureYuv (include/wrhip.h; WrGrabYuvArgs): the rect's stored B, G, R bytes as 8-bit Y, Cb and Cr planes for a video
+// encoder -- the inverse of the video wr_composite_yuv_kernel draws.  A streaming converter bound by its read, 4 bytes per pixel
+// against 1.5 or 3 written, so the work is cut along the SOURCE rows: a unit is two image rows (4:2:0: a chroma sample never needs
+// another unit's pixels) or one (I444), an item is eight pixels of it -- two 16-byte loads per row where the address allows -- which
+// are 8 bytes of a Y row, 4 of an I420 chroma row, 8 of an NV12 or I444 one.  Which eight pixels is decided per destination row from
+// that row's ADDRESS, so that a piece lying whole inside its row leaves as one aligned 8- or 4-byte store and only the row's head and
+// tail leave as bytes: odd widths and tight strides move the phase from row to row and from plane to plane.  Where the phases agree
+// -- every stride a multiple of 8 -- the rows of a unit are loaded once; a row whose phase differs fetches its own window (WrYuvRow).
+// The format is a template parameter; the colour space is nine coefficients and y0 in the arguments; the sink is base pointers.
+WR_DEVICE void wr_yuv_st8(void* p, uint32_t lo, uint32_t hi) {
+#ifdef WRHIP_HOSTSIM
+  const uint32_t v[2] = {lo, hi};
+  __builtin_memcpy(p, v, 8);
+#else
+  typedef uint32_t wr_gu2 __attribute__((ext_vector_type(2)));
+  *(__attribute__((address_space(1))) wr_gu2*)p = wr_gu2{lo, hi};
+#endif
+}
+// eight pixels of one source row: columns x0 .. x0 + 7, each held to the rect's [0, w) -- the clamp of a 4:2:0 block at the right edge
+struct WrYuvRow { const uint8_t* row; int x0; uint32_t px[8]; };
+WR_DEVICE void wr_yuv_fetch(WrYuvRow& R, int x0, int w) {
+  if (R.x0 == x0) return;
+  R.x0 = x0;
+  if (x0 >= 0 && x0 + 8 <= w) {
+    const uint8_t* p = R.row + (size_t)x0 * 4;
+    if (((uintptr_t)p & 15) == 0) {
+      const wr_u4 u = wr_load16(p), v = wr_load16(p + 16);
+      R.px[0] = u.x; R.px[1] = u.y; R.px[2] = u.z; R.px[3] = u.w; R.px[4] = v.x; R.px[5] = v.y; R.px[6] = v.z; R.px[7] = v.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; k++) R.px[k] = wr_load4(p + 4 * k);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 8; k++) R.px[k] = wr_load4(R.row + (size_t)wr_iclamp(x0 + k, 0, w - 1) * 4);
+  }
+}
+WR_DEVICE uint32_t wr_yuv_luma(const WrGrabYuvArgs& a, uint32_t px) {
+  const int r = (int)((px >> 16) & 0xFFu), g = (int)((px >> 8) & 0xFFu), b = (int)(px & 0xFFu);
+  return (uint32_t)((a.cy[0] * r + a.cy[1] * g + a.cy[2] * b + (a.y0 << 16) + 0x8000) >> 16);
+}
+// a chroma sample of the row `c` from channel sums over 1 << (SH - 16) pixels (SH 16: one pixel, 18: a 2 x 2 block)
+// (the clamp comes BEFORE the shift -- the same value.  Shift, clamp and the OR of an NV12 pair are what the compiler turns into
+// gfx950's v_ashr_pk_u8_i32, whose result it then ORs into a 32-bit word as if its upper half were zero: it is not)
+template <int SH> WR_DEVICE uint32_t wr_yuv_chroma(const int32_t* c, int r, int g, int b) {
+  return (uint32_t)wr_iclamp(c[0] * r + c[1] * g + c[2] * b + (128 << SH) + (1 << (SH - 1)), 0, (256 << SH) - 1) >> SH;
+}
+// the block sums of 4:2:0 sample k of a window: columns 2k, 2k + 1 of both rows
+WR_DEVICE uint32_t wr_yuv_chroma420(const int32_t* c, const WrYuvRow& A, const WrYuvRow& B, int k) {
+  const uint32_t p0 = A.px[2 * k], p1 = A.px[2 * k + 1], p2 = B.px[2 * k], p3 = B.px[2 * k + 1];
+  // (R and B of the four pixels add up side by side in one word: 4 * 255 stays inside 16 bits)
+  const uint32_t rb = (p0 & 0xFF00FFu) + (p1 & 0xFF00FFu) + (p2 & 0xFF00FFu) + (p3 & 0xFF00FFu);
+  const uint32_t g = ((p0 >> 8) & 0xFFu) + ((p1 >> 8) & 0xFFu) + ((p2 >> 8) & 0xFFu) + ((p3 >> 8) & 0xFFu);
+  return wr_yuv_chroma<18>(c, (int)(rb >> 16), (int)g, (int)(rb & 0xFFFFu));
+}
+// samples v[0 .. N) of a destination row of n samples of BYTES bytes at d, from sample i0 on: one aligned store of the N * BYTES (8
+// or 4) bytes where all of them lie inside the row, bytes otherwise.  v[k] holds the sample's BYTES bytes.
+template <int N, int BYTES> WR_DEVICE void wr_yuv_put(uint8_t* d, int i0, int n, const uint32_t* v) {
+  uint8_t* const p = d + (ptrdiff_t)i0 * BYTES;
+  if (i0 >= 0 && i0 + N <= n && ((uintptr_t)p & (uintptr_t)(N * BYTES - 1)) == 0) {
+    uint32_t w[2] = {0u, 0u};
+#pragma unroll
+    for (int k = 0; k < N; k++) w[k * BYTES / 4] |= v[k] << (8 * (k * BYTES % 4));
+    if (N * BYTES == 8) wr_yuv_st8(p, w[0], w[1]);
+    else wr_grab_st4(p, w[0]);
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    if (i0 + k >= 0 && i0 + k < n) {
+      p[k * BYTES] = (uint8_t)v[k];
+      if (BYTES == 2) p[k * BYTES + 1] = (uint8_t)(v[k] >> 8);
+    }
+  }
+}
+// the first sample of piece s of a row at d: pieces of N samples of BYTES bytes count from the aligned address at or below d
+template <int N, int BYTES> WR_DEVICE int wr_yuv_first(const uint8_t* d, int s) {
+  return s * N - (int)((uintptr_t)d & (uintptr_t)(N * BYTES - 1)) / BYTES;
+}
+// piece s of the Y row at d, or of an I444 chroma row (`c`: its coefficients; null: luma), from the source row R
+WR_DEVICE void wr_yuv_row_piece(const WrGrabYuvArgs& a, WrYuvRow& R, uint8_t* d, int s, const int32_t* c) {
+  const int i0 = wr_yuv_first<8, 1>(d, s);
+  if (i0 >= a.w || i0 + 8 <= 0) return;
+  wr_yuv_fetch(R, i0, a.w);
+  uint32_t v[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const uint32_t px = R.px[k];
+    v[k] = c ? wr_yuv_chroma<16>(c, (int)((px >> 16) & 0xFFu), (int)((px >> 8) & 0xFFu), (int)(px & 0xFFu)) : wr_yuv_luma(a, px);
+  }
+  wr_yuv_put<8, 1>(d, i0, a.w, v);
+}
+// row units [u0, u1), thread t of nt: the units' items laid end to end, a.slots of them per unit
+template <int FMT> WR_DEVICE void wr_grab_yuv_units(const WrGrabYuvArgs& a, int u0, int u1, int t, int nt) {
+  const int items = (u1 - u0) * a.slots, cw = (a.w + 1) >> 1;
+  for (int it = t; it < items; it += nt) {
+    const int u = u0 + it / a.slots, s = it % a.slots;
+    const int ra = FMT == WR_YUV_I444 ? u : 2 * u, rb = wr_imin(ra + 1, a.h - 1);
+    WrYuvRow A, B;
+    A.row = a.tex + (size_t)(a.ry + (a.flip ? a.h - 1 - ra : ra)) * a.tex_stride + (size_t)a.rx * 4;
+    B.row = a.tex + (size_t)(a.ry + (a.flip ? a.h - 1 - rb : rb)) * a.tex_stride + (size_t)a.rx * 4;
+    A.x0 = B.x0 = -0x40000000;      // (nothing fetched yet)
+    wr_yuv_row_piece(a, A, a.y + ra * a.y_stride, s, nullptr);
+    if (FMT == WR_YUV_I444) {
+      wr_yuv_row_piece(a, A, a.cb + ra * a.c_stride, s, a.ccb);
+      wr_yuv_row_piece(a, A, a.cr + ra * a.c_stride, s, a.ccr);
+      continue;
+    }
+    if (ra + 1 < a.h) wr_yuv_row_piece(a, B, a.y + (ra + 1) * a.y_stride, s, nullptr);
+    if (FMT == WR_YUV_NV12) {
+      // (pairs: a row that starts at an odd address has no aligned piece of whole pairs -- it leaves as bytes)
+      uint8_t* const d = a.cb + u * a.c_stride;
+      const int i0 = wr_yuv_first<4, 2>(d, s);
+      if (i0 >= cw || i0 + 4 <= 0) continue;
+      wr_yuv_fetch(A, 2 * i0, a.w); wr_yuv_fetch(B, 2 * i0, a.w);
+      uint32_t v[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) v[k] = wr_yuv_chroma420(a.ccb, A, B, k) | (wr_yuv_chroma420(a.ccr, A, B, k) << 8);
+      wr_yuv_put<4, 2>(d, i0, cw, v);
+    } else {
+#pragma unroll
+      for (int plane = 0; plane < 2; plane++) {
+        uint8_t* const d = (plane ? a.cr : a.cb) + u * a.c_stride;
+        const int i0 = wr_yuv_first<4, 1>(d, s);
+        if (i0 >= cw || i0 + 4 <= 0) continue;
+        wr_yuv_fetch(A, 2 * i0, a.w); wr_yuv_fetch(B, 2 * i0, a.w);
+        uint32_t v[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] = wr_yuv_chroma420(plane ? a.ccr : a.ccb, A, B, k);
+        wr_yuv_put<4, 1>(d, i0, cw, v);
+      }
+    }
+  }
+}
+__global__ void __launch_bounds__(256) wr_grab_yuv_kernel(WrGrabYuvArgs a) {
+  const int t = (int)threadIdx.x;
+  // (the ticket's header: the planes' bytes behind it, or an empty payload)
+  if (a.slot && blockIdx.x == 0 && t == 0) wr_grab_st16(a.slot, wr_u4{a.payload, 0u, 0u, 0u});
+  const int units = a.format == WR_YUV_I444 ? a.h : (a.h + 1) >> 1;
+  const int u0 = (int)blockIdx.x * a.units_per_wg, u1 = wr_imin(units, u0 + a.units_per_wg);
+  if (a.format == WR_YUV_I420) wr_grab_yuv_units<WR_YUV_I420>(a, u0, u1, t, (int)blockDim.x);
+  else if (a.format == WR_YUV_NV12) wr_grab_yuv_units<WR_YUV_NV12>(a, u0, u1, t, (int)blockDim.x);
+  else wr_grab_yuv_units<WR_YUV_I444>(a, u0, u1, t, (int)blockDim.x);
+}
 // The slot's header and as many bytes as its count word says, device slot -> pinned host slot, 16 bytes per store.  A small grid on
 // the grab stream: the link, not the chip, bounds it, and the raster launches of the following frames keep the CUs.
 __global__ void __launch_bounds__(256) wr_grab_push_kernel(WrGrabPushArgs a) {

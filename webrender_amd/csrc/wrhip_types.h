@@ -814,6 +814,26 @@ struct WrPutTensorArgs {
   int32_t rows_per_wg, slots;
   WrTensorIn in;
 };
+// WrhipGrabTextureYuv: one launch of wr_grab_yuv_kernel (the contract: include/wrhip.h).  The rect's stored B, G, R bytes become
+// 8-bit Y, Cb and Cr samples in 16.16 fixed point; 4:2:0 chroma is taken from the sum of a 2 x 2 block whose positions are clamped
+// to the rect.  The planes lie in the caller's device memory or behind the header of the ticket's device slot: either way the launch
+// sees base pointers and byte strides.  Workgroup b converts row units [b * units_per_wg, ...): a unit is two image rows (4:2:0) or
+// one (I444), and `slots` items of eight pixels at most -- the 8-byte pieces of a destination row its samples touch.
+#define WR_YUV_I420 0
+#define WR_YUV_NV12 1
+#define WR_YUV_I444 2
+struct WrGrabYuvArgs {
+  const uint8_t* tex;                  // the texture's storage (its origin)
+  uint8_t* slot;                       // the ticket's device slot, whose header the launch writes; null: the ticket is gone, no header
+  uint8_t* y; uint8_t* cb; uint8_t* cr;      // the planes' first samples; NV12: cb is the plane of pairs, cr unused
+  long long y_stride, c_stride;        // bytes per row; never 0 here
+  int32_t tex_stride;                  // bytes
+  int32_t rx, ry, w, h;                // the rect
+  int32_t format, flip;                // WR_YUV_*; image row r is rect row h - 1 - r
+  int32_t units_per_wg, slots;
+  uint32_t payload;                    // the header's word: the planes' bytes behind it (host sink), 0 (device sink)
+  int32_t cy[3], ccb[3], ccr[3], y0;   // the rows of the colour space, R, G, B, in 16.16; y0: 16 or 0
+};
 struct WrGrabPushArgs {
   const uint8_t* src; uint8_t* dst;    // device slot -> pinned host slot
   uint32_t capacity;                   // of either, bytes (a multiple of 16): the count read from the slot is held to it

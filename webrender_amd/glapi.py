@@ -150,6 +150,7 @@ EXTRA_SIGNATURES = {
     "WrhipDeviceRead": (i32, [P, P, u64]),
     "WrhipDeviceWrite": (i32, [P, P, u64]),
     "WrhipPutTextureTensor": (i32, [u32, P, P]),
+    "WrhipGrabTextureYuv": (i32, [u32, P, P]),
 }
 
 
@@ -174,7 +175,11 @@ class WrhipTapResult(C.Structure):
 GRAB_FLIP_ROWS, GRAB_SWAP_RB, GRAB_DELTA, GRAB_KEY, GRAB_PACKED = 1, 2, 4, 8, 32
 GRAB_SCALED = 64          # reported in a scaled grab's info["flags"] (WrhipGrabTextureScaled); no flag of WrhipGrabTexture
 GRAB_TENSOR = 128         # reported in a tensor grab's info["flags"] (WrhipGrabTextureTensor); no flag of the other grab calls
+GRAB_YUV = 512            # reported in a YUV grab's info["flags"] (WrhipGrabTextureYuv); no flag of the other grab calls
 GRAB_MAX_RECTS, GRAB_HEADER, GRAB_BLOCK = 16, 16, 64
+# WrhipGrabTextureYuv: plane layouts, and the YuvRangedColorSpace values it converts to
+YUV_I420, YUV_NV12, YUV_I444 = 0, 1, 2
+YUV_REC601_NARROW, YUV_REC601_FULL, YUV_REC709_NARROW, YUV_REC709_FULL, YUV_REC2020_NARROW, YUV_REC2020_FULL = range(6)
 # WrhipGrabTextureTensor: element types, layouts, and the flag that keeps the stored channel order
 TENSOR_U8, TENSOR_F16, TENSOR_BF16, TENSOR_F32 = 0, 1, 2, 3
 TENSOR_CHW, TENSOR_HWC = 0, 1
@@ -197,6 +202,34 @@ class WrhipTensorSrc(C.Structure):
     _fields_ = [("src", P), ("src_bytes", u64), ("dtype", u32), ("layout", u32), ("channels", u32),
                 ("row_stride", C.c_int64), ("plane_stride", C.c_int64), ("scale", C.c_float * 4), ("bias", C.c_float * 4),
                 ("alpha", u32), ("flags", u32)]
+
+
+class WrhipYuvDesc(C.Structure):
+    _fields_ = [("format", u32), ("color_space", u32), ("flags", u32), ("dst", P), ("dst_bytes", u64),
+                ("y_stride", C.c_int64), ("c_stride", C.c_int64)]
+
+
+def yuv_plane_shapes(w, h, format):
+    """The planes of a w x h YUV grab as (rows, bytes per tight row): Y, then Cb and Cr, or NV12's one plane of (Cb, Cr) pairs"""
+    cw, ch = (w + 1) // 2, (h + 1) // 2
+    if format == YUV_I444:
+        return [(h, w), (h, w), (h, w)]
+    if format == YUV_NV12:
+        return [(h, w), (ch, 2 * cw)]
+    return [(h, w), (ch, cw), (ch, cw)]
+
+
+def yuv_split(flat, w, h, format):
+    """The flat uint8 array a YUV ticket delivers (grab_result) as its planes: [Y (h, w), Cb, Cr] of (ch, cw) or (h, w) samples, or
+    [Y, CbCr (ch, cw, 2)] for NV12 -- views, not copies"""
+    out, at = [], 0
+    for rows, row in yuv_plane_shapes(w, h, format):
+        out.append(flat[at:at + rows * row].reshape(rows, row))
+        at += rows * row
+    assert at == len(flat), (at, len(flat))
+    if format == YUV_NV12:
+        out[1] = out[1].reshape(out[1].shape[0], -1, 2)
+    return out
 
 
 def _as_ptr(x):
@@ -343,6 +376,24 @@ class GL:
         d.flags = int(flags)
         return self.WrhipGrabTextureTensor(tex, C.addressof(arr), C.addressof(d))
 
+    def grab_texture_yuv(self, tex, rect, format, color_space, flags=0, dst=None, dst_bytes=0, strides=(0, 0)):
+        """Enqueue a YUV grab (include/wrhip.h, WrhipGrabTextureYuv) of `rect` = (x, y, w, h) of the RGBA8 texture id `tex` -- None:
+        all of it -- as 8-bit planes in `format` (YUV_I420, YUV_NV12, YUV_I444) of the ranged colour space `color_space` (0 .. 5).
+        dst None: the planes cross to the host, grab_result delivers them; otherwise a device address of which `dst_bytes` may be
+        written, strides = (Y, chroma) in bytes, 0: tight.  `flags`: 0 or GRAB_FLIP_ROWS.  Returns the ticket, or -1
+        (GL_INVALID_VALUE / GL_OUT_OF_MEMORY is then set)."""
+        if rect is None:
+            w, h = i32(0), i32(0)
+            if not self.WrhipGetTextureSize(tex, C.byref(w), C.byref(h)):
+                w = h = i32(0)
+            rect = (0, 0, w.value, h.value)
+        arr = (i32 * 4)(*[int(v) for v in rect])
+        d = WrhipYuvDesc()
+        d.format, d.color_space, d.flags = int(format), int(color_space), int(flags)
+        d.dst, d.dst_bytes = (int(dst) or None) if dst is not None else None, int(dst_bytes)
+        d.y_stride, d.c_stride = int(strides[0]), int(strides[1])
+        return self.WrhipGrabTextureYuv(tex, C.addressof(arr), C.addressof(d))
+
     def device_alloc(self, nbytes):
         """Device memory for tensor grabs (WrhipDeviceAlloc): its address, 16-byte aligned; 0 with GL_OUT_OF_MEMORY set"""
         return self.WrhipDeviceAlloc(int(nbytes)) or 0
@@ -392,7 +443,7 @@ class GL:
 
     def grab_result(self, ticket, wait=True, into=None):
         """The result of a grab: (info dict, pixels).  Full mode: one array per rect ((h, w, 4) stored B, G, R, A bytes, or (h, w)
-        for R8) -- the array itself for a single rect, a list for several.  A scaled grab: the (scaled_h, scaled_w, 4) array.  A tensor grab: None.  Delta mode: the caller's image `into` of the rect (a
+        for R8) -- the array itself for a single rect, a list for several.  A scaled grab: the (scaled_h, scaled_w, 4) array.  A tensor grab: None.  A YUV grab: the planes as one flat uint8 array (yuv_split cuts it; empty for a device sink).  Delta mode: the caller's image `into` of the rect (a
         C-contiguous uint8 array of the rect's shape; None: a fresh one of zeros) with the sent blocks patched in.  None if the
         result has not arrived (wait=False only); a ticket the ring no longer holds raises KeyError."""
         import numpy as np
@@ -407,6 +458,9 @@ class GL:
         shape = lambda w, h: (h, w) if bpp == 1 else (h, w, 4)
         if r.flags & GRAB_TENSOR:
             pixels = buf = None          # (the elements are in the caller's device memory)
+        elif r.flags & GRAB_YUV:
+            # (the planes, tight, one after another -- yuv_split cuts them apart; a device sink's ticket carries none)
+            pixels = buf = np.empty(int(r.bytes) - GRAB_HEADER, np.uint8)
         elif r.flags & GRAB_SCALED:
             pixels = buf = np.empty((r.scaled_h, r.scaled_w, 4), np.uint8)
         elif r.flags & GRAB_DELTA:

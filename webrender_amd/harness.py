@@ -294,6 +294,52 @@ def render_streamed_tensors(backend_path, frames, size, dtype, layout, channels,
     return out, stats, infos
 
 
+def render_streamed_yuv(backend_path, frames, format, color_space, device=False, flags=0):
+    """render_streamed_grabbed for a video encoder: after each frame's render the whole window is YUV-grabbed (GL.grab_texture_yuv:
+    one launch in stream order behind that frame, 8-bit planes in `format` of the ranged colour space `color_space`) -- nothing
+    between the frames drains the held-back raster launches, no Finish.  Frame k's ticket is fetched after frame k + 1 has been
+    rendered and grabbed, so the host never waits for the frame it has just submitted; the last one is waited for at the end.
+    device=False: the planes cross to the host as the tickets' payloads.  device=True: each frame's planes go, tight, into a buffer
+    of its own in device memory (GL.device_alloc) -- where an encoder on the card would take them -- 16 bytes per frame cross, and
+    the buffers are read back at the end.  Returns the per-frame planes (glapi.yuv_split's lists), the backend's statistics
+    (`setup_carried` included) and the grabs' info dicts.  libwrhip only."""
+    from . import glapi
+    gl = GL(backend_path)
+    assert gl.is_wrhip, "render_streamed_yuv: grabs are a libwrhip addition"
+    w, h = frames[0].width, frames[0].height
+    r = Renderer(gl, w, h)
+    window = gl.WrhipGetFramebufferTexture(0)
+    nbytes = sum(rows * row for rows, row in glapi.yuv_plane_shapes(w, h, format))
+    bufs = [gl.device_alloc(nbytes) for _ in frames] if device else []
+    assert all(bufs), gl.GetError()
+    tickets, flats, infos = [], [], []
+
+    def fetch(k):
+        info, flat = gl.grab_result(tickets[k])
+        infos.append(info)
+        flats.append(flat)
+    for k, f in enumerate(frames):
+        assert (f.width, f.height) == (w, h), "render_streamed_yuv: one window size"
+        r.render(f)
+        t = gl.grab_texture_yuv(window, (0, 0, w, h), format, color_space, flags, dst=bufs[k] if device else None,
+                                dst_bytes=nbytes if device else 0)
+        assert t >= 0, (t, gl.GetError())
+        tickets.append(t)
+        if k >= 1:
+            fetch(k - 1)
+    fetch(len(frames) - 1)
+    err = gl.GetError()
+    stats = gl.stats()
+    stats["gl_error"] = int(err)
+    if device:
+        flats = [gl.device_read(b, nbytes) for b in bufs]
+        for b in bufs:
+            gl.device_free(b)
+    r.finish()
+    r.destroy()
+    return [glapi.yuv_split(fl, w, h, format) for fl in flats], stats, infos
+
+
 def _fed_bytes(window_bgra):
     """What render_streamed_fed feeds back, restated in numpy for a backend without tensor calls: the window's stored bytes (B, G, R,
     A) as a tensor grab's F16 elements of R, G, B with scale 1 / 255 (a float32 multiply, then the rounding to float16), and those as
