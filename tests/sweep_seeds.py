@@ -69,6 +69,32 @@ FAMILIES = {
 }
 
 
+# The transform classes of tests/transform_classes.py on seeded scenes, so that seeds nobody pinned also vary what gets mirrored, scaled,
+# flattened and drawn at another device pixel scale: xf_<family>_<class>.  The rotated builders take the four classes that rewrite
+# affine transforms and picture tasks, their projective variants are mirrored on screen.  All exact (none is in test_gpu_sweep.ONE_LSB).
+def _xf(make, cls):
+    def build(s):
+        from transform_classes import retransform
+        frame = make(s)
+        retransform(frame, cls)
+        return frame
+    return build
+
+
+_XF_TEXT = dict(width=1024, height=512, lines=20, glyphs_per_line=60, run_len=12)
+_XF = {
+    "rects": lambda s, **kw: scenes.rotated_rects(n=40, seed=s, opaque_frac=0.3, encoding="quad" if s % 2 else "brush", **kw),
+    "images": lambda s, **kw: scenes.rotated_images(n=40, seed=s, repeat=bool(s % 2), **kw),
+    "gradients": lambda s, **kw: scenes.gradient_grid(n=40, seed=s, rotate=True, **kw),
+    "quad_masks": lambda s, **kw: scenes.quad_masks(n=40, seed=s, rotate=True, **kw),
+    "text": lambda s, **kw: scenes.cfg3_text(rotate=not kw, seed=s, **_XF_TEXT, **kw),
+}
+for _fam, _mk in _XF.items():
+    for _cls in ("affine", "degenerate", "dps1.5", "dps0.77"):
+        FAMILIES[f"xf_{_fam}_{_cls}"] = _xf(_mk, _cls)
+    FAMILIES[f"xf_{_fam}_screen_mirror"] = _xf(lambda s, mk=_mk: mk(s, perspective=True), "screen_mirror")
+
+
 def main():
     first = int(sys.argv[1]) if len(sys.argv) > 1 else 1000
     n = int(sys.argv[2]) if len(sys.argv) > 2 else 4
