@@ -252,7 +252,7 @@ void WrhipSetProfiling(int enabled);
  * (picture targets of a few large gradient / image prims, likewise), 11 = wr_setup_tile_rows_kernel (10 fused with the next flush's setup stage), 12 = a thin launch of the raster kernel (13: the same with the next flush's setup stage in front, wr_setup_raster_thin_kernel) (wr_raster_kernel<fmt, false, 1, feat>:
  * small levels, several workgroups per bin), 14 = wr_tap_kernel (WrhipTapTexture: fmt of the tapped texture, feat 1 against an expected texture;
  * algo_bytes: the rect's bytes, twice with an expected texture), 15 = wr_grab_pack_kernel (WrhipGrabTexture: fmt of the grabbed texture,
- * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta, feat 3: wr_grab_scale_kernel, the launches of one WrhipGrabTextureScaled, feat 4: wr_grab_tensor_kernel or the launches of a scaled WrhipGrabTextureTensor, feat 5: wr_grab_yuv_kernel, a WrhipGrabTextureYuv (the rect read once plus the planes written); algo_bytes: bytes read plus bytes written, as far as they are known at the launch), 16 = wr_put_tensor_kernel (WrhipPutTextureTensor: fmt of the texture written;
+ * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta, feat 3: wr_grab_scale_kernel, the launches of one WrhipGrabTextureScaled, feat 4: wr_grab_tensor_kernel or the launches of a scaled WrhipGrabTextureTensor, feat 5: wr_grab_yuv_kernel, a WrhipGrabTextureYuv (the rect read once plus the planes written), feat 6: wr_grab_yuv_delta_kernel, a WrhipGrabTextureYuvDelta (the rect plus the retained planes; what its sent blocks write is not known at the launch, as for feat 1); algo_bytes: bytes read plus bytes written, as far as they are known at the launch), 16 = wr_put_tensor_kernel (WrhipPutTextureTensor: fmt of the texture written;
  * algo_bytes: the elements read plus the rect's bytes written).  algo_bytes: the launch's algorithmic bytes:
  * raster launches count every destination pixel they own once (twice when the target's old content is loaded) plus
  * the source texels their draws can sample; the setup stage counts instance + descriptor + record bytes.  Returns the
@@ -534,10 +534,58 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  * rect that is empty or not inside `tex`; an unknown format, colour space (GbrIdentity and above) or flag; a NULL desc; a host sink
  * with a non-zero stride or dst_bytes; a device sink with a stride below its row's bytes or above 2^40, or an extent above
  * dst_bytes; and while sharding is on.  -1 with GL_OUT_OF_MEMORY as WrhipGrabTexture.
+ *
+ * WrhipGrabTextureYuvDelta(tex, rect, desc, flags): WrhipGrabTextureYuv for a page that is mostly still: only the 64 x 64 blocks
+ * whose SAMPLES changed since the previous such grab cross the link (or are written to the caller's planes), with a damage rect
+ * for the encoder's skip decisions.  `desc` is WrhipGrabTextureYuv's -- formats, the six colour spaces, FLIP_ROWS, host or device
+ * sink --; `flags` is 0 or WRHIP_GRAB_KEY.  One launch (wr_grab_yuv_delta_kernel).  The contract -- any restatement must give the
+ * same bytes:
+ *   samples   exactly those WrhipGrabTextureYuv produces for the same rect and desc: table, luma, chroma, the clamp, 4:2:0 blocks
+ *             clamped to the RECT, the flip ahead of the chroma blocks.
+ *   blocks    64 x 64 luma samples of the IMAGE (after the flip), aligned to the image's origin, edge blocks cut to the image.  A cut
+ *             block of bw x bh has (bw + 1) / 2 x (bh + 1) / 2 chroma samples in 4:2:0 ((bw + 1) / 2 pairs a row for NV12) and
+ *             bw x bh in I444.  64 is even: a 2 x 2 chroma block never straddles two blocks, a pixel changes samples of its own
+ *             block only.
+ *   retained  the library keeps one retained copy of the image's PLANES per texture (pool memory, about 1.5 or 3 bytes per pixel),
+ *             apart from the plain delta grab's retained pixels: plain or packed delta grabs and delta YUV grabs of one texture never
+ *             invalidate each other.  It is valid until the texture gets new storage or is deleted, a delta YUV grab names another
+ *             rect, format, colour space, flip, sink (`dst`) or stride, or KEY is passed.
+ *   sent      a block is sent when any sample of its planes differs from the retained planes, and every block when there is no
+ *             valid retained copy (a keyframe); the same grab brings the retained copy up to date.  A change of alpha alone never
+ *             sends a block, nor does a colour change that rounds to the same samples.
+ *   host sink (dst == NULL)  the payload is a sequence of entries of one size: a 16-byte record -- four little-endian 32-bit words
+ *             x, y, w, h of the luma block, relative to the image -- and the block's planes at fixed pitches: Y, 64 rows at 64;
+ *             then I420: Cb, then Cr, 32 rows at 32 each (an entry: 16 + 6144 bytes); NV12: 32 rows of pairs at 64 (16 + 6144);
+ *             I444: Cb, then Cr, 64 rows at 64 each (16 + 12288).  Bytes beyond the cut block are unspecified; no decoder reads
+ *             them.  On a keyframe entry i is block i (row-major); otherwise the order of the entries is free.
+ *             WrhipGrabResultGet(ticket, info, dst, 0, wait): `dst` is the caller's own tight planes in WrhipGrabTextureYuv's
+ *             payload layout (Y, Cb, Cr; NV12: Y, pairs); the sent blocks are patched in and nothing else is touched; a non-zero
+ *             dst_stride: -1 with GL_INVALID_VALUE.  info: flags = WRHIP_GRAB_YUV | WRHIP_GRAB_DELTA | desc->flags (| KEY if given),
+ *             format GL_RGBA8, keyframe, blocks, blocks_total and damage as a plain delta grab's, `bytes` = 16 + blocks * entry
+ *             size.  WrhipGrabPayloadGet works as for any grab.
+ *   device sink (dst != NULL)  the sent blocks' samples are written straight into the caller's planes, WrhipGrabTextureYuv's layout
+ *             and stride rules; nothing but the samples of sent blocks is written.  The payload is the records alone, 16 bytes per
+ *             sent block -- the host still learns blocks and damage --, `bytes` = 16 + 16 * blocks, and WrhipGrabResultGet ignores
+ *             `dst`.  The write does NOT depend on the ticket surviving: a parked grab whose ticket was overwritten still patches the
+ *             planes and the retained copy; only the records are lost.  The destination takes part in WrhipPutTextureTensor's
+ *             overlap rule as a parked YUV grab's does.
+ *   ordering, parking, ring, slot growth, WRHIP_GRAB_PINNED_MAX  WrhipGrabTexture's; slots are sized for all blocks of the rect.  A
+ *             parked HOST-sink grab that lost its ticket is dropped, and the next delta YUV grab of that texture is a keyframe.
+ *   cost      one launch: WrhipStats::kernel_launches grows by 1, flushes by 0.
+ * Returns -1 and sets GL_INVALID_VALUE, launching and flushing nothing and leaving the retained copy as it was, for everything
+ * WrhipGrabTextureYuv rejects and for any `flags` bit other than KEY; -1 with GL_OUT_OF_MEMORY as WrhipGrabTexture.
+ *
+ * WrhipGrabDecodeYuv(payload, bytes, format, rect_w, rect_h, y, y_stride, c0, c1, c_stride, damage, blocks): the pure host function
+ * -- no context, no GPU -- behind the host sink's decode (webrender_amd/csrc/wr_grab_codec.h, which a program can include on its
+ * own).  It patches a host-sink payload (`payload`: its header) into planes given by pointers and BYTE strides (0: tight); NV12: c0
+ * is the plane of pairs and c1 NULL; y, c0 and c1 all NULL: only checked.  0 with the entries' bounding box and number (either may
+ * be NULL); -1, having written nothing, for a malformed payload -- a length that is not header + k entries or more than `bytes`
+ * holds, an x or y that is no multiple of 64 or outside the image, a w or h that is not the cut block's, more entries than the
+ * image has blocks -- or for planes given in part or with a stride below a row.
  * Not routed through grabs: Finish, GetColorBuffer, ReadPixels.  Not supported: other formats, sharded targets; scaling other than
  * WrhipGrabTextureScaled's; delta or packed tensor grabs; gamma or colour-space conversion of tensors (values are the stored
  * premultiplied bytes); puts that scale or filter, into other formats, into sharded targets or host-backed textures; YUV grabs of 10-
- * or 16-bit samples (P010), 4:2:2 or YUY2, scaled or delta YUV grabs, R8 sources, un-premultiplying, GbrIdentity. */
+ * or 16-bit samples (P010), 4:2:2 or YUY2, scaled YUV grabs, scaled or packed delta YUV grabs, several rects in one, R8 sources, un-premultiplying, GbrIdentity. */
 #define WRHIP_GRAB_FLIP_ROWS 1u   /* full mode: deliver the rect's last row first */
 #define WRHIP_GRAB_SWAP_RB   2u   /* full mode, RGBA8 only: bytes 0 and 2 of every pixel exchanged */
 #define WRHIP_GRAB_DELTA     4u   /* only the 64x64 blocks that differ from the previous DELTA grab of this texture and rect */
@@ -545,7 +593,7 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
 #define WRHIP_GRAB_PACKED    32u  /* with DELTA: sent blocks as SOLID / RUNS / RAW entries (the packed payload above); 16 is no flag */
 #define WRHIP_GRAB_SCALED    64u  /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureScaled ticket; no flag of WrhipGrabTexture, which rejects it */
 #define WRHIP_GRAB_TENSOR    128u /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureTensor ticket; no flag of the other grab calls, which reject it */
-#define WRHIP_GRAB_YUV       512u /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureYuv ticket; rejected by the other grab calls */
+#define WRHIP_GRAB_YUV       512u /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureYuv or (with DELTA) WrhipGrabTextureYuvDelta ticket; rejected by the other grab calls */
 #define WRHIP_YUV_I420 0u         /* WrhipYuvDesc::format: Y plane, Cb plane, Cr plane; chroma 4:2:0 */
 #define WRHIP_YUV_NV12 1u         /* Y plane, one plane of interleaved Cb,Cr pairs; chroma 4:2:0 */
 #define WRHIP_YUV_I444 2u         /* Y, Cb, Cr planes, all w x h */
@@ -604,6 +652,8 @@ typedef struct WrhipYuvDesc {
   int64_t  y_stride, c_stride;     /* device sink, BYTES per row of the Y plane / of a chroma plane; 0: tight */
 } WrhipYuvDesc;
 int32_t WrhipGrabTextureYuv(GLuint tex, const int32_t rect[4], const WrhipYuvDesc* desc);
+int32_t WrhipGrabTextureYuvDelta(GLuint tex, const int32_t rect[4], const WrhipYuvDesc* desc, uint32_t flags);
+int32_t WrhipGrabDecodeYuv(const void* payload, uint64_t bytes, uint32_t format, int32_t rect_w, int32_t rect_h, void* y, int64_t y_stride, void* c0, void* c1, int64_t c_stride, int32_t damage[4], uint32_t* blocks);
 int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64_t dst_stride, int32_t wait);
 int32_t WrhipGrabPayloadGet(int32_t ticket, void* dst, uint64_t capacity, uint64_t* bytes, int32_t wait);
 int32_t WrhipGrabDecode(const void* payload, uint64_t bytes, uint32_t format, uint32_t flags, int32_t rect_w, int32_t rect_h, void* dst, int64_t dst_stride, int32_t damage[4], uint32_t* blocks);

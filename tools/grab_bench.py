@@ -31,7 +31,7 @@
   ab         plain bench.py against another build of the library (WRHIP_LIB_PATH), alternated, no grab issued
 
 Every section runs three alternated rounds.  Needs the GPU: there is no fallback.
-  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor,put,yuv] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
+  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor,put,yuv,yuv_delta] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -837,6 +837,124 @@ def section_yuv_stream(lib, frames):
     say(f"  (an I420 payload is {payload / 1e6:.2f} MB, a full grab's {W * H * 4 / 1e6:.2f} MB)")
 
 
+# yuv_delta: what changes between two grabs -- nothing, everything (GRAB_KEY), or a square of noise that moves by a block a frame
+YUVD_CONTENTS = [("static", 0), ("keyframe", -1), ("moving 256x256", 256), ("moving 1024x1024", 1024)]
+
+
+def _yuvd_patches(side):
+    rng = np.random.default_rng(side)
+    return [rng.integers(0, 256, (side, side, 4), dtype=np.uint8) for _ in range(2)]
+
+
+def _yuvd_move(upload, patches, side, k):
+    """Frame k's change: the square, one of two noises alternately, a block further along a diagonal that wraps"""
+    upload((64 * k) % (W - side), (64 * k) % (H - side), patches[k & 1])
+
+
+def section_yuv_delta_kernel(lib):
+    say(f"## yuv_delta: wr_grab_yuv_delta_kernel beside wr_grab_yuv_kernel, {W}x{H} RGBA8 window of cfg2, Rec709Narrow, host sink, hipEvents, us per launch")
+    w = Window(lib, "cfg2")
+    gl = w.gl
+    info = glapi.WrhipGrabInfo()
+    n = 30
+
+    def full(fmt):
+        t = gl.grab_texture_yuv(w.tex, None, fmt, glapi.YUV_REC709_NARROW)
+        assert t >= 0 and gl.WrhipGrabResultGet(t, C.byref(info), None, 0, 1) == 0
+
+    def delta(fmt, key):
+        t = gl.grab_texture_yuv_delta(w.tex, None, fmt, glapi.YUV_REC709_NARROW, key=key)
+        assert t >= 0 and gl.WrhipGrabResultGet(t, C.byref(info), None, 0, 1) == 0
+        return info.blocks, int(info.bytes)
+    rows, sent = {}, {}
+    gl.WrhipSetProfiling(1)
+    for fmt in (glapi.YUV_I420, glapi.YUV_NV12):
+        for _ in range(4):
+            full(fmt)
+            delta(fmt, True)
+        for rnd in range(ROUNDS):
+            for name, side in [("full grab", None)] + YUVD_CONTENTS:
+                patches = _yuvd_patches(side) if side and side > 0 else None
+                delta(fmt, True)
+                gl.WrhipResetStats()
+                blocks = nbytes = 0
+                for k in range(n):
+                    if patches:
+                        _yuvd_move(w.upload, patches, side, k)
+                    if side is None:
+                        full(fmt)
+                    else:
+                        b, by = delta(fmt, side == -1)
+                        blocks += b
+                        nbytes += by
+                ks = [k for k in kernel_stats(gl, 15) if k.feat == (5 if side is None else 6)]
+                assert len(ks) == 1 and ks[0].launches == n, [(k.feat, k.launches) for k in ks]
+                rows.setdefault((fmt, name), []).append(ks[0].ns / n / 1e3)
+                sent[(fmt, name)] = (blocks / n, nbytes / n, ks[0].algo_bytes // n)
+    gl.WrhipSetProfiling(0)
+    for (fmt, name), v in rows.items():
+        b, by, algo = sent[(fmt, name)]
+        say(f"  {YUV_NAMES[fmt]} {name:18s} " + "  ".join(f"{us:8.1f}" for us in v) + f"   us   ({algo / 1e6:6.1f} MB counted at the launch" +
+            (f"; {b:7.1f} blocks, {by / 1e6:6.3f} MB crossed per grab)" if name != "full grab" else ")"))
+    for fmt in (glapi.YUV_I420, glapi.YUV_NV12):
+        s, f = rows[(fmt, "static")], rows[(fmt, "full grab")]
+        say(f"  {YUV_NAMES[fmt]} static / full grab: " + "  ".join(f"{a / b if b else float('nan'):6.2f}" for a, b in zip(s, f)))
+    w.close()
+
+
+def section_yuv_delta_stream(lib, frames):
+    say(f"## yuv_delta stream: cfg2 {W}x{H} streamed as in `stream`, {frames} frames per line, frames/s; I420 host sink, tickets fetched one frame late."
+        "  The moving square is a TexSubImage2D into the window behind the frame: a write that sends the held-back launches, so each content has its own `no grab`.")
+    rec, _ = record_scene(lib, scenes.make_workload("cfg2", width=W, height=H))
+    p = ScenePlayer(lib, rec)
+    gl = glapi.GL(lib)                          # (the same loaded library and current context as the player's)
+    window = gl.WrhipGetFramebufferTexture(0)
+    payload = W * H + 2 * ((W + 1) // 2) * ((H + 1) // 2)
+    host = np.zeros(payload, np.uint8)
+    info = glapi.WrhipGrabInfo()
+
+    def upload(x, y, px):
+        gl.ActiveTexture(G.GL_TEXTURE0)
+        gl.BindTexture(G.GL_TEXTURE_2D, window)
+        gl.TexSubImage2D(G.GL_TEXTURE_2D, 0, x, y, px.shape[1], px.shape[0], G.GL_BGRA, G.GL_UNSIGNED_BYTE, np.ascontiguousarray(px))
+
+    def run(kind, side, n):
+        patches = _yuvd_patches(side) if side > 0 else None
+        prev = -1
+        for k in range(n):
+            p.rp.exec(rec.stream)
+            if patches:
+                _yuvd_move(upload, patches, side, k)
+            t = -1
+            if kind == "full I420 grab":
+                t = gl.grab_texture_yuv(window, (0, 0, W, H), glapi.YUV_I420, glapi.YUV_REC709_NARROW)
+            elif kind == "delta I420 grab":
+                t = gl.grab_texture_yuv_delta(window, (0, 0, W, H), glapi.YUV_I420, glapi.YUV_REC709_NARROW, key=side == -1)
+            if prev >= 0:
+                assert gl.WrhipGrabResultGet(prev, C.byref(info), host.ctypes.data, 0, 1) == 0
+            prev = t
+        if prev >= 0:
+            assert gl.WrhipGrabResultGet(prev, C.byref(info), host.ctypes.data, 0, 1) == 0
+        gl.Finish()
+    kinds = ["no grab", "full I420 grab", "delta I420 grab"]
+    cases = [(name, side, k) for name, side in YUVD_CONTENTS for k in kinds if not (name == "keyframe" and k != "delta I420 grab")]
+    rows, extra = {}, {}
+    for name, side, k in cases:
+        run(k, side, 4)
+    for rnd in range(ROUNDS):
+        for name, side, k in cases:
+            gl.WrhipResetStats()
+            t0 = time.perf_counter()
+            run(k, side, frames)
+            dt = time.perf_counter() - t0
+            st = gl.stats()
+            rows.setdefault((name, k), []).append(frames / dt)
+            extra[(name, k)] = (st["setup_carried"], st["d2h_bytes"] / frames)
+    for (name, k), v in rows.items():
+        say(f"  {name:18s} {k:16s} " + "  ".join(f"{x:9.1f}" for x in v) + f"   frames/s   (setup_carried {extra[(name, k)][0]} of {frames} flushes; {extra[(name, k)][1] / 1e6:.6f} MB per frame crossed)")
+    say(f"  (a full I420 payload is {payload / 1e6:.2f} MB; a static delta grab crosses 16 bytes)")
+
+
 def section_ab(other, steps, warmup):
     say(f"## ab: bench.py --gpus 1 --steps {steps} --warmup {warmup} (cfg2), this library against {os.path.basename(other)}, alternated, frames/s")
     rows = {"parent": [], "this": []}
@@ -909,7 +1027,10 @@ def main():
                 section_yuv_kernel(lib, "noise")
                 section_yuv_kernel(lib, "cfg2")
                 section_yuv_stream(lib, args.frames)
-            elif s == "tensor_parent":          # (run by `tensor` with WRHIP_LIB_PATH set: the parent path alone, on that library)
+            elif s == "yuv_delta":
+                section_yuv_delta_kernel(lib)
+                section_yuv_delta_stream(lib, args.frames)
+            elif s == "tensor_parent":         # (run by `tensor` with WRHIP_LIB_PATH set: the parent path alone, on that library)
                 section_tensor_scaled(lib, with_tensor=False)
                 section_tensor_stream(lib, args.frames, with_tensor=False)
         if args.ab:

@@ -139,6 +139,84 @@ static inline int wr_gc_decode(const void* payload, uint64_t bytes, int bpp, boo
   return 0;
 }
 
+// The payload of a delta YUV grab (include/wrhip.h, WrhipGrabTextureYuvDelta; format 0: I420, 1: NV12, 2: I444): entries of one
+// size, a record x, y, w, h -- a block of 64 x 64 luma samples of the image, aligned to its origin, cut to it -- and the block's
+// planes at fixed pitches: Y, 64 rows of 64; then I420: Cb, Cr, 32 rows of 32 each; NV12: 32 rows of 32 pairs; I444: Cb, Cr, 64
+// rows of 64 each.  A cut block of w x h has (w + 1) / 2 x (h + 1) / 2 chroma samples in 4:2:0; no byte beyond them is read.
+static inline size_t wr_gc_yuv_entry_size(uint32_t format) {
+  const size_t luma = (size_t)WR_GC_BLOCK * WR_GC_BLOCK;
+  return 16 + (format == 2 ? 3 * luma : luma + luma / 2);
+}
+// the record at `p` against an image of rw x rh: false unless it names one of the image's blocks, cut as the image cuts it
+static inline bool wr_gc_yuv_record(const uint8_t* p, int rw, int rh, WrGrabEntry* E) {
+  const uint32_t x = wr_gc_load32(p), y = wr_gc_load32(p + 4), w = wr_gc_load32(p + 8), h = wr_gc_load32(p + 12);
+  if (x % WR_GC_BLOCK || y % WR_GC_BLOCK || x >= (uint32_t)rw || y >= (uint32_t)rh) return false;
+  const uint32_t bw = (uint32_t)rw - x < WR_GC_BLOCK ? (uint32_t)rw - x : WR_GC_BLOCK, bh = (uint32_t)rh - y < WR_GC_BLOCK ? (uint32_t)rh - y : WR_GC_BLOCK;
+  if (w != bw || h != bh) return false;
+  E->x = (int32_t)x; E->y = (int32_t)y; E->w = (int32_t)w; E->h = (int32_t)h; E->mode = WR_GC_RAW; E->aux = 0; E->size = 16;
+  return true;
+}
+// a checked entry's samples into the caller's planes: Y rows of `ys` bytes, chroma rows of `cs` (NV12: c0 is the plane of pairs)
+static inline void wr_gc_yuv_patch(const uint8_t* p, const WrGrabEntry& E, uint32_t format, uint8_t* y, size_t ys, uint8_t* c0, uint8_t* c1, size_t cs) {
+  const size_t B = WR_GC_BLOCK;
+  const uint8_t* body = p + 16;
+  for (int r = 0; r < E.h; r++) memcpy(y + (size_t)(E.y + r) * ys + (size_t)E.x, body + (size_t)r * B, (size_t)E.w);
+  body += B * B;
+  if (format == 2) {
+    for (int r = 0; r < E.h; r++) {
+      memcpy(c0 + (size_t)(E.y + r) * cs + (size_t)E.x, body + (size_t)r * B, (size_t)E.w);
+      memcpy(c1 + (size_t)(E.y + r) * cs + (size_t)E.x, body + B * B + (size_t)r * B, (size_t)E.w);
+    }
+    return;
+  }
+  const int cw = (E.w + 1) / 2, ch = (E.h + 1) / 2;
+  for (int r = 0; r < ch; r++) {
+    if (format == 1) {
+      memcpy(c0 + (size_t)(E.y / 2 + r) * cs + (size_t)E.x, body + (size_t)r * B, (size_t)2 * cw);
+    } else {
+      memcpy(c0 + (size_t)(E.y / 2 + r) * cs + (size_t)(E.x / 2), body + (size_t)r * (B / 2), (size_t)cw);
+      memcpy(c1 + (size_t)(E.y / 2 + r) * cs + (size_t)(E.x / 2), body + B * B / 4 + (size_t)r * (B / 2), (size_t)cw);
+    }
+  }
+}
+// A whole payload patched into the caller's planes (byte strides, 0: tight; NV12: c0 the pairs, c1 NULL; y, c0 and c1 all NULL:
+// only checked): 0, with the bounding box of the entries' blocks and their number, or -1 for a malformed one -- a count that is
+// not k entries or more than the caller holds, a record that is not a block of the image, more entries than blocks -- or for
+// planes given in part or with a stride below a row; nothing is written then.
+static inline int wr_gc_decode_yuv(const void* payload, uint64_t bytes, uint32_t format, int rw, int rh, void* y, int64_t y_stride,
+                                   void* c0, void* c1, int64_t c_stride, int32_t damage[4], uint32_t* blocks) {
+  if (!payload || bytes < WR_GC_HEADER || format > 2 || rw < 1 || rh < 1) return -1;
+  const int64_t c_row = format == 2 ? rw : format == 1 ? 2 * (((int64_t)rw + 1) / 2) : ((int64_t)rw + 1) / 2;
+  const bool patch = y || c0 || c1;
+  if (patch && (!y || !c0 || (format == 1 ? c1 != nullptr : c1 == nullptr))) return -1;
+  if (patch && ((y_stride != 0 && y_stride < rw) || (c_stride != 0 && c_stride < c_row))) return -1;
+  const uint8_t* p = (const uint8_t*)payload;
+  const uint64_t count = wr_gc_load32(p), entry = wr_gc_yuv_entry_size(format);
+  const uint64_t total = (uint64_t)((rw + WR_GC_BLOCK - 1) / WR_GC_BLOCK) * (uint64_t)((rh + WR_GC_BLOCK - 1) / WR_GC_BLOCK);
+  if (count > bytes - WR_GC_HEADER || count % entry != 0 || count / entry > total) return -1;
+  p += WR_GC_HEADER;
+  int x0 = rw, y0 = rh, x1 = 0, y1 = 0;
+  WrGrabEntry E;
+  for (uint64_t at = 0; at < count; at += entry) {
+    if (!wr_gc_yuv_record(p + at, rw, rh, &E)) return -1;
+    x0 = E.x < x0 ? E.x : x0; y0 = E.y < y0 ? E.y : y0;
+    x1 = E.x + E.w > x1 ? E.x + E.w : x1; y1 = E.y + E.h > y1 ? E.y + E.h : y1;
+  }
+  if (patch) {
+    const size_t ys = y_stride ? (size_t)y_stride : (size_t)rw, cs = c_stride ? (size_t)c_stride : (size_t)c_row;
+    for (uint64_t at = 0; at < count; at += entry) {
+      wr_gc_yuv_record(p + at, rw, rh, &E);
+      wr_gc_yuv_patch(p + at, E, format, (uint8_t*)y, ys, (uint8_t*)c0, (uint8_t*)c1, cs);
+    }
+  }
+  if (damage) {
+    damage[0] = damage[1] = damage[2] = damage[3] = 0;
+    if (x1 > x0 && y1 > y0) { damage[0] = x0; damage[1] = y0; damage[2] = x1 - x0; damage[3] = y1 - y0; }
+  }
+  if (blocks) *blocks = (uint32_t)(count / entry);
+  return 0;
+}
+
 // The packed entry of one cut block (w x h pixels at `px`, rows of `stride` bytes) at (x, y) of the rect, written to `out` (room
 // for wr_gc_raw_size(bpp) bytes): -> its size.  Serial; the device's kernel (wr_grab_pack_runs_kernel) writes the same bytes.
 static inline size_t wr_gc_encode_block(const uint8_t* px, size_t stride, int x, int y, int w, int h, int bpp, uint8_t* out) {

@@ -250,6 +250,16 @@ struct Texture {
   size_t grab_keep_size = 0;
   int grab_rect[4] = {0, 0, 0, 0};
   bool grab_valid = false;
+  // WrhipGrabTextureYuvDelta: the retained PLANES (pool storage, every 64 x 64 block whole: WrGrabYuvDeltaArgs) and what they are the
+  // planes of -- rect, format, colour space, flip, sink and strides; a grab that names anything else, or finds them not valid, is a
+  // keyframe.  Apart from the plain delta grabs' copy above: neither invalidates the other.
+  void* yuv_keep = nullptr;
+  size_t yuv_keep_size = 0;
+  int yuv_rect[4] = {0, 0, 0, 0};
+  uint32_t yuv_format = 0, yuv_space = 0, yuv_flip = 0;
+  const void* yuv_dst = nullptr;
+  int64_t yuv_strides[2] = {0, 0};
+  bool yuv_valid = false;
   // RGBA32I data textures: does any transform id in them carry TRANSFORM_NON_AXIS_ALIGNED (bit 23,
   // transform.glsl:22-29)?  Read as sPrimitiveHeadersI (2 texels per prim, id in .z of the first) and as
   // sGpuBufferI (ps_quad header, id in .x); maintained on upload.  A draw is only declared
@@ -666,6 +676,7 @@ struct Context {
     GLenum format = 0; uint32_t flags = 0; int bpp = 0, nrects = 0; int32_t rects[WR_GRAB_MAX_RECTS][4];
     bool keyframe = false; uint32_t blocks_total = 0;
     int scaled_w = 0, scaled_h = 0, levels = 0;      // WrhipGrabTextureScaled: the delivered size and L
+    uint32_t yuv_format = 0; bool yuv_device = false;      // WrhipGrabTextureYuvDelta: what its entries hold
   };
   // WrhipGrabTextureScaled as it was asked for; its launches are laid out when it is issued (grab_issue_scaled), since the levels
   // that go through HBM live in a scratch that may have grown by then
@@ -676,8 +687,10 @@ struct Context {
   // WrhipGrabTextureYuv: the launch as it goes out.  device: the planes go to the caller's memory (`dst_extent` bytes from args.y on)
   // and the ticket carries an empty payload; otherwise they are the ticket's payload, and args.y, cb, cr are offsets from its start
   struct GrabYuv { bool device; WrGrabYuvArgs args; uint64_t out_bytes, dst_extent; };
-  enum GrabKind { GRAB_PLAIN = 0, GRAB_SCALED = 1, GRAB_TENSOR = 2, GRAB_YUV = 3 };
-  struct GrabParked { uint64_t n; GrabKind kind; WrGrabArgs args; GrabScaled scale; GrabTensor tensor; GrabYuv yuv; };
+  // WrhipGrabTextureYuvDelta: the launch as it goes out (the slot is filled in when it is issued).  dst_extent as GrabYuv's (device sink)
+  struct GrabYuvDelta { WrGrabYuvDeltaArgs args; uint64_t keep_bytes, dst_extent; };
+  enum GrabKind { GRAB_PLAIN = 0, GRAB_SCALED = 1, GRAB_TENSOR = 2, GRAB_YUV = 3, GRAB_YUV_DELTA = 4 };
+  struct GrabParked { uint64_t n; GrabKind kind; WrGrabArgs args; GrabScaled scale; GrabTensor tensor; GrabYuv yuv; GrabYuvDelta yuvd; };
   GrabSlot grab_slot[GRAB_RING];
   uint64_t grab_next = 0;
   std::vector<GrabParked> grab_parked;
@@ -1318,7 +1331,7 @@ Context::~Context() {
   flush_all();
   flush_uploads(1206);
   sync_stream();
-  for (Texture* t : textures.objects) if (t) { if (t->dptr) wrrt::dev_free(t->dptr); t->dptr = nullptr; free(t->hmirror); t->hmirror = nullptr; if (t->grab_keep) wrrt::dev_free(t->grab_keep); t->grab_keep = nullptr; }
+  for (Texture* t : textures.objects) if (t) { if (t->dptr) wrrt::dev_free(t->dptr); t->dptr = nullptr; free(t->hmirror); t->hmirror = nullptr; if (t->grab_keep) wrrt::dev_free(t->grab_keep); t->grab_keep = nullptr; if (t->yuv_keep) wrrt::dev_free(t->yuv_keep); t->yuv_keep = nullptr; }
   for (auto& kv : pool) wrrt::dev_free(kv.second);
   pool.clear();
   wrrt::dev_free(dupload); wrrt::dev_free(dcounters);
@@ -1797,6 +1810,26 @@ void grab_issue_yuv(uint64_t n, const Context::GrabYuv& g, bool notify) {
   c->stats.kernel_launches++;
   if (notify) grab_push(gs, a.payload, c->grab_full_kernel);
 }
+// One delta YUV grab, now: the slot's previous ticket first, the count word the sent blocks add to zeroed (a keyframe's is known
+// and written by the launch), the one launch, the transport of as many bytes as the count says.  notify == false (device sink
+// only): the ticket has been overwritten while the grab was parked; planes and retained copy are patched all the same, the records
+// have nowhere to go.
+void grab_issue_yuv_delta(uint64_t n, const Context::GrabYuvDelta& g, bool notify) {
+  Context* c = ctx;
+  Context::GrabSlot& gs = c->grab_slot[n % Context::GRAB_RING];
+  if (notify) wrrt::stream_wait_event(c->stream, &gs.ev);
+  WrGrabYuvDeltaArgs a = g.args;
+  a.g.slot = notify ? gs.dev : nullptr;
+  if (a.g.slot && !a.keyframe) wrrt::memset8(a.g.slot, 0, WR_GRAB_HEADER, c->stream);
+  const uint64_t workgroups = (uint64_t)a.bx * a.by;
+  prof_begin();
+  WR_LAUNCH(wr_grab_yuv_delta_kernel, (int)workgroups, 256, c->stream, a);
+  // (15, feat 6: wr_grab_yuv_delta_kernel; the rect and -- unless a keyframe, which writes them -- the retained planes read; what
+  // the sent blocks write is not known here and is not counted, as for feat 1)
+  prof_end(WR_KIND_GRAB, WR_FMT_RGBA8, 0, 6, (uint64_t)a.g.w * a.g.h * 4 + g.keep_bytes, workgroups);
+  c->stats.kernel_launches++;
+  if (notify) grab_push(gs, a.g.payload, true);
+}
 // tail_launched(): the grabs that waited for the held-back launches follow them, in the order they were made
 void grab_issue_parked() {
   Context* c = ctx;
@@ -1809,29 +1842,48 @@ void grab_issue_parked() {
   std::vector<const uint8_t*> stale;
   for (Context::GrabParked& p : parked) {
     Context::GrabSlot& gs = c->grab_slot[p.n % Context::GRAB_RING];
+    // (a delta YUV grab keeps its retained planes in the same list: p.args of such a one is zeroed but for delta and keep)
     auto st = std::find(stale.begin(), stale.end(), (const uint8_t*)p.args.keep);
     // (a tensor grab writes the caller's memory, not the slot: it goes out with or without its ticket)
     if (p.kind == Context::GRAB_TENSOR) { grab_issue_tensor(p.n, p.tensor, gs.n == p.n); continue; }
     if (p.kind == Context::GRAB_YUV && p.yuv.device) { grab_issue_yuv(p.n, p.yuv, gs.n == p.n); continue; }
+    if (p.kind == Context::GRAB_YUV_DELTA && p.yuvd.args.device) {
+      // (it brings planes and retained copy up to date with or without its ticket.  Behind a HOST-sink one that was dropped it is
+      // a keyframe already -- it named another sink --, and the planes are whole again)
+      if (st != stale.end() && p.yuvd.args.keyframe) stale.erase(st);
+      grab_issue_yuv_delta(p.n, p.yuvd, gs.n == p.n);
+      continue;
+    }
     if (gs.n != p.n) { if (p.args.delta && st == stale.end()) stale.push_back(p.args.keep); continue; }
     if (p.args.delta && st != stale.end()) { p.args.keyframe = 1; gs.keyframe = true; stale.erase(st); }
+    if (p.kind == Context::GRAB_YUV_DELTA) {
+      if (p.args.keyframe) { p.yuvd.args.keyframe = 1; p.yuvd.args.g.payload = (uint32_t)WR_YUVD_ENTRY(p.yuvd.args.g.format) * (uint32_t)(p.yuvd.args.bx * p.yuvd.args.by); }
+      grab_issue_yuv_delta(p.n, p.yuvd, true);
+      continue;
+    }
     if (p.kind == Context::GRAB_SCALED) grab_issue_scaled(p.n, p.scale);
     else if (p.kind == Context::GRAB_YUV) grab_issue_yuv(p.n, p.yuv, true);
     else grab_issue(p.n, p.args);
   }
   for (const uint8_t* k : stale)
-    for (Texture* t : c->textures.objects) if (t && t->grab_keep == k) t->grab_valid = false;
+    for (Texture* t : c->textures.objects) if (t) { if (t->grab_keep == k) t->grab_valid = false; if (t->yuv_keep == k) t->yuv_valid = false; }
   for (auto& kd : c->grab_keep_dead) pool_free(kd.first, kd.second);
   c->grab_keep_dead.clear();
 }
 // The retained copy of `t` is no longer valid (new storage, deletion); release: its memory goes back to the pool -- which hands it
 // out again in stream order -- unless a parked grab was given it and has not been enqueued yet.
+static void grab_release(void*& keep, size_t& size) {
+  if (!keep) return;
+  if (ctx->grab_parked.empty()) pool_free(keep, size);
+  else ctx->grab_keep_dead.push_back(std::make_pair(keep, size));
+  keep = nullptr; size = 0;
+}
+// (both retained copies: the plain delta grabs' and the delta YUV grabs')
 void grab_forget(Texture& t, bool release) {
-  t.grab_valid = false;
-  if (!release || !t.grab_keep) return;
-  if (ctx->grab_parked.empty()) pool_free(t.grab_keep, t.grab_keep_size);
-  else ctx->grab_keep_dead.push_back(std::make_pair(t.grab_keep, t.grab_keep_size));
-  t.grab_keep = nullptr; t.grab_keep_size = 0;
+  t.grab_valid = t.yuv_valid = false;
+  if (!release) return;
+  grab_release(t.grab_keep, t.grab_keep_size);
+  grab_release(t.yuv_keep, t.yuv_keep_size);
 }
 Context::GrabSlot* grab_find(int32_t ticket) {
   Context* c = ctx;
@@ -4208,7 +4260,8 @@ int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint3
     const size_t keep_need = (size_t)keep_stride * h;
     keyframe = !(t->grab_keep && t->grab_valid && memcmp(t->grab_rect, rects, sizeof(t->grab_rect)) == 0) || (flags & WRHIP_GRAB_KEY);
     if (!t->grab_keep || t->grab_keep_size < keep_need) {
-      grab_forget(*t, true);
+      t->grab_valid = false;
+      grab_release(t->grab_keep, t->grab_keep_size);      // (its own copy alone: the delta YUV grabs' planes stay)
       size_t actual = 0;
       t->grab_keep = pool_alloc(keep_need, &actual);
       t->grab_keep_size = actual;
@@ -4393,10 +4446,10 @@ static const int32_t wr_yuv_rows[6][9] = {
   {14786, 38160, 3338, -8038, -20746, 28784, 28784, -26469, -2315},      // Rec2020Narrow
   {17216, 44434, 3886, -9151, -23617, 32768, 32768, -30133, -2635},      // Rec2020Full
 };
-int32_t WrhipGrabTextureYuv(GLuint tex, const int32_t rect[4], const WrhipYuvDesc* desc) {
-  if (!ctx) return -1;
+// What WrhipGrabTextureYuv and WrhipGrabTextureYuvDelta share: the checks of texture, rect and desc -- false: GL_INVALID_VALUE is set
+// and nothing else has happened -- and the launch's arguments, the planes as the sink lays them out.
+static bool grab_yuv_prepare(Texture* t, const int32_t rect[4], const WrhipYuvDesc* desc, Context::GrabYuv& g) {
   Context* c = ctx;
-  Texture* t = tex ? c->textures.find(tex) : nullptr;
   bool ok = t && t->dptr && t->internal_format == GL_RGBA8 && rect && desc;
   ok = ok && desc->format <= WRHIP_YUV_I444 && desc->color_space <= 5u && (desc->flags & ~WRHIP_GRAB_FLIP_ROWS) == 0;
   ok = ok && rect[2] >= 1 && rect[3] >= 1 && rect[0] >= 0 && rect[1] >= 0 && rect[0] <= t->width - rect[2] && rect[1] <= t->height - rect[3];
@@ -4417,8 +4470,7 @@ int32_t WrhipGrabTextureYuv(GLuint tex, const int32_t rect[4], const WrhipYuvDes
     ok = ok && (!desc->dst || (uint64_t)extent <= desc->dst_bytes);
   }
   ok = ok && c->shard_world <= 1 && t->own_y0 == t->own_y1;      // (sharded targets hold a strip of the frame each: out of scope)
-  if (!ok) { c->last_error = GL_INVALID_VALUE; return -1; }
-  Context::GrabYuv g;
+  if (!ok) { c->last_error = GL_INVALID_VALUE; return false; }
   memset(&g, 0, sizeof(g));
   g.device = desc->dst != nullptr;
   g.out_bytes = (uint64_t)(w * h + (desc->format == WRHIP_YUV_NV12 ? 1 : 2) * ch * c_row);
@@ -4439,6 +4491,14 @@ int32_t WrhipGrabTextureYuv(GLuint tex, const int32_t rect[4], const WrhipYuvDes
   const int units = desc->format == WRHIP_YUV_I444 ? a.h : (a.h + 1) / 2;
   a.slots = (a.w + 7) / 8 + 1;
   a.units_per_wg = std::max(1, std::min(units, 512 / a.slots));
+  return true;
+}
+int32_t WrhipGrabTextureYuv(GLuint tex, const int32_t rect[4], const WrhipYuvDesc* desc) {
+  if (!ctx) return -1;
+  Context* c = ctx;
+  Texture* t = tex ? c->textures.find(tex) : nullptr;
+  Context::GrabYuv g;
+  if (!grab_yuv_prepare(t, rect, desc, g)) return -1;
   Context::GrabSlot* const slot = grab_reserve(g.device ? 0 : g.out_bytes);
   if (!slot) return -1;
   Context::GrabSlot& gs = *slot;
@@ -4458,6 +4518,76 @@ int32_t WrhipGrabTextureYuv(GLuint tex, const int32_t rect[4], const WrhipYuvDes
     grab_issue_yuv(n, g, true);
   }
   return (int32_t)(n & 0x7FFFFFFFull);
+}
+// A delta YUV grab: see include/wrhip.h.  The YUV grab's checks and arguments, the plain delta grab's ring slot for every block of
+// the rect, and retained planes of the texture's own.
+int32_t WrhipGrabTextureYuvDelta(GLuint tex, const int32_t rect[4], const WrhipYuvDesc* desc, uint32_t flags) {
+  if (!ctx) return -1;
+  Context* c = ctx;
+  Texture* t = tex ? c->textures.find(tex) : nullptr;
+  if (flags & ~WRHIP_GRAB_KEY) { c->last_error = GL_INVALID_VALUE; return -1; }
+  Context::GrabYuv y;
+  if (!grab_yuv_prepare(t, rect, desc, y)) return -1;
+  Context::GrabYuvDelta g;
+  memset(&g, 0, sizeof(g));
+  WrGrabYuvDeltaArgs& a = g.args;
+  a.g = y.args;
+  a.device = y.device ? 1 : 0;
+  g.dst_extent = y.dst_extent;
+  const int bx = (rect[2] + WR_GRAB_BLOCK - 1) / WR_GRAB_BLOCK, by = (rect[3] + WR_GRAB_BLOCK - 1) / WR_GRAB_BLOCK;
+  const uint64_t entry = y.device ? 16u : (uint64_t)WR_YUVD_ENTRY(a.g.format);
+  Context::GrabSlot* const slot = grab_reserve((uint64_t)bx * by * entry);
+  if (!slot) return -1;
+  Context::GrabSlot& gs = *slot;
+  // the retained planes: every block whole
+  const bool i444 = desc->format == WRHIP_YUV_I444, i420 = desc->format == WRHIP_YUV_I420;
+  a.bx = bx; a.by = by;
+  a.keep_ys = bx * WR_GRAB_BLOCK; a.keep_cs = i420 ? a.keep_ys / 2 : a.keep_ys;
+  const size_t y_bytes = (size_t)a.keep_ys * by * WR_GRAB_BLOCK, c_bytes = (size_t)a.keep_cs * by * (i444 ? WR_GRAB_BLOCK : WR_GRAB_BLOCK / 2);
+  const size_t keep_need = y_bytes + (i420 || i444 ? 2 : 1) * c_bytes;
+  const int64_t strides[2] = {desc->y_stride, desc->c_stride};
+  bool keyframe = !(t->yuv_keep && t->yuv_valid && memcmp(t->yuv_rect, rect, sizeof(t->yuv_rect)) == 0 && t->yuv_format == desc->format &&
+                    t->yuv_space == desc->color_space && t->yuv_flip == (desc->flags & WRHIP_GRAB_FLIP_ROWS) && t->yuv_dst == desc->dst &&
+                    memcmp(t->yuv_strides, strides, sizeof(strides)) == 0) || (flags & WRHIP_GRAB_KEY);
+  if (!t->yuv_keep || t->yuv_keep_size < keep_need) {
+    t->yuv_valid = false;
+    grab_release(t->yuv_keep, t->yuv_keep_size);
+    size_t actual = 0;
+    t->yuv_keep = pool_alloc(keep_need, &actual);
+    t->yuv_keep_size = actual;
+    if (!t->yuv_keep) { out_of_memory(); return -1; }
+    keyframe = true;
+  }
+  memcpy(t->yuv_rect, rect, sizeof(t->yuv_rect));
+  t->yuv_format = desc->format; t->yuv_space = desc->color_space; t->yuv_flip = desc->flags & WRHIP_GRAB_FLIP_ROWS;
+  t->yuv_dst = desc->dst; memcpy(t->yuv_strides, strides, sizeof(strides));
+  t->yuv_valid = true;
+  a.keep_y = (uint8_t*)t->yuv_keep; a.keep_cb = a.keep_y + y_bytes; a.keep_cr = a.keep_cb + c_bytes;
+  a.keyframe = keyframe ? 1 : 0;
+  a.g.payload = keyframe ? (uint32_t)((uint64_t)bx * by * entry) : 0u;
+  g.keep_bytes = keep_need;
+  const uint64_t n = c->grab_next++;
+  gs.n = n; gs.counted = false;
+  gs.format = t->internal_format; gs.flags = desc->flags | flags | WRHIP_GRAB_YUV | WRHIP_GRAB_DELTA; gs.bpp = t->bpp; gs.nrects = 1;
+  memcpy(gs.rects, rect, sizeof(int32_t) * 4);
+  gs.keyframe = keyframe; gs.blocks_total = (uint32_t)(bx * by);
+  gs.scaled_w = gs.scaled_h = gs.levels = 0;
+  gs.yuv_format = desc->format; gs.yuv_device = y.device;
+  if (c->tail.pending && t->tail_ref) {
+    gs.parked = true;
+    Context::GrabParked p;
+    memset(&p, 0, sizeof(p));
+    // (args: what grab_issue_parked's rule for delta grabs that lost their ticket looks at -- the retained copy's address)
+    p.n = n; p.kind = Context::GRAB_YUV_DELTA; p.yuvd = g; p.args.delta = 1; p.args.keep = a.keep_y;
+    c->grab_parked.push_back(p);
+  } else {
+    grab_issue_yuv_delta(n, g, true);
+  }
+  return (int32_t)(n & 0x7FFFFFFFull);
+}
+int32_t WrhipGrabDecodeYuv(const void* payload, uint64_t bytes, uint32_t format, int32_t rect_w, int32_t rect_h, void* y, int64_t y_stride,
+                           void* c0, void* c1, int64_t c_stride, int32_t damage[4], uint32_t* blocks) {
+  return wr_gc_decode_yuv(payload, bytes, format, rect_w, rect_h, y, y_stride, c0, c1, c_stride, damage, blocks);
 }
 // A tensor put: see include/wrhip.h.  A texture write at its place in the call order -- TexSubImage2D's ordering, one launch on the
 // draw stream instead of staged rows.  Arguments are checked before anything is flushed or launched.
@@ -4496,6 +4626,8 @@ int32_t WrhipPutTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTens
     if (p.kind == Context::GRAB_TENSOR && d0 < s1 && s0 < d0 + p.tensor.dst_extent) { drain_tail(); break; }
     const uint8_t* const y0 = p.yuv.args.y;
     if (p.kind == Context::GRAB_YUV && p.yuv.device && y0 < s1 && s0 < y0 + p.yuv.dst_extent) { drain_tail(); break; }
+    const uint8_t* const yd = p.yuvd.args.g.y;
+    if (p.kind == Context::GRAB_YUV_DELTA && p.yuvd.args.device && yd < s1 && s0 < yd + p.yuvd.dst_extent) { drain_tail(); break; }
   }
   // the write: draws recorded so far that sample or target the texture are flushed, held-back launches that reference it leave,
   // queued uploads go out ahead of it
@@ -4613,7 +4745,28 @@ int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64
   memcpy(r.rects, gs->rects, sizeof(int32_t) * 4 * gs->nrects);
   r.bytes = (uint64_t)WR_GRAB_HEADER + payload;
   r.scaled_w = gs->scaled_w; r.scaled_h = gs->scaled_h; r.levels = (uint32_t)gs->levels;
-  if (yuv) {
+  if (yuv && delta) {
+    // the entries one after the other, each record checked (wr_grab_codec.h) before its block is patched into the caller's tight
+    // planes; one that is no block of the image is passed over: status 1.  A device sink's entries are the records alone
+    const uint32_t fmt = gs->yuv_format;
+    const size_t entry = gs->yuv_device ? 16 : wr_gc_yuv_entry_size(fmt);
+    const int rw = gs->rects[0][2], rh = gs->rects[0][3];
+    const size_t c_row = fmt == WRHIP_YUV_I444 ? (size_t)rw : fmt == WRHIP_YUV_NV12 ? 2 * (((size_t)rw + 1) / 2) : ((size_t)rw + 1) / 2;
+    const size_t c_rows = fmt == WRHIP_YUV_I444 ? (size_t)rh : ((size_t)rh + 1) / 2;
+    uint8_t* const py = gs->yuv_device ? nullptr : (uint8_t*)dst;
+    uint8_t* const pc0 = py ? py + (size_t)rw * rh : nullptr;
+    uint8_t* const pc1 = py && fmt != WRHIP_YUV_NV12 ? pc0 + c_rows * c_row : nullptr;
+    r.keyframe = gs->keyframe ? 1 : 0;
+    r.blocks = (uint32_t)(payload / entry); r.blocks_total = gs->blocks_total;
+    int x0 = rw, y0 = rh, x1 = 0, y1 = 0;
+    WrGrabEntry E;
+    for (size_t at = 0; at + entry <= payload; at += entry) {
+      if (!wr_gc_yuv_record(src + at, rw, rh, &E)) { r.status = 1; continue; }
+      x0 = std::min(x0, E.x); y0 = std::min(y0, E.y); x1 = std::max(x1, E.x + E.w); y1 = std::max(y1, E.y + E.h);
+      if (py) wr_gc_yuv_patch(src + at, E, fmt, py, (size_t)rw, pc0, pc1, c_row);
+    }
+    if (x1 > x0 && y1 > y0) { r.damage[0] = x0; r.damage[1] = y0; r.damage[2] = x1 - x0; r.damage[3] = y1 - y0; }
+  } else if (yuv) {
     if (dst) big_memcpy(dst, src, payload);
   } else if (!delta) {
     for (int i = 0; i < gs->nrects; i++) {

@@ -1059,6 +1059,224 @@ __global__ void __launch_bounds__(256) wr_grab_yuv_kernel(WrGrabYuvArgs a) {
   else if (a.format == WR_YUV_NV12) wr_grab_yuv_units<WR_YUV_NV12>(a, u0, u1, t, (int)blockDim.x);
   else wr_grab_yuv_units<WR_YUV_I444>(a, u0, u1, t, (int)blockDim.x);
 }
+// WrhipGrabTextureYuvDelta (include/wrhip.h; WrGrabYuvDeltaArgs): the YUV grab's samples, block by block, and only the blocks whose
+// samples differ from the retained planes.  A workgroup per 64 x 64 block of the image (after the flip), as wr_grab_pack_kernel has
+// it; the YUV grab's item -- eight pixels of a row pair, or of one row of I444 -- tiles the block: 32 row pairs of 8 items are one
+// item per thread in 4:2:0, 64 rows of 8 are two per thread in I444.  A thread fetches its pixels (wr_yuv_fetch: clamped to the
+// rect, so an edge block's 2 x 2 sums are the full grab's), converts them in registers into six words -- 4:2:0: Y of the upper row,
+// Y of the lower row, then Cb | Cr words (I420) or two words of pairs (NV12); I444: Y, Cb, Cr of its row -- with the bytes beyond the
+// image zero, and compares them with the retained planes' 8 + 8 + 4 + 4 bytes (I444: 8 + 8 + 8).  The vote, the entry and the
+// keyframe are the pack kernel's: a ballot per wave, one LDS word, one returning atomic per SENT block on the slot's byte count,
+// entry i = block i on a keyframe.  What is sent goes to its entry (host sink) or through wr_yuv_put into the caller's planes
+// (device sink, the entry then being the record alone), and to the retained planes.  Entry and retained rows are multiples of 8
+// bytes: those stores are whole aligned words.
+WR_DEVICE void wr_yuv_ld8(const void* p, uint32_t& lo, uint32_t& hi) {
+#ifdef WRHIP_HOSTSIM
+  uint32_t v[2];
+  __builtin_memcpy(v, p, 8);
+  lo = v[0]; hi = v[1];
+#else
+  typedef uint32_t wr_gu2 __attribute__((ext_vector_type(2)));
+  const wr_gu2 v = *(const __attribute__((address_space(1))) wr_gu2*)p;
+  lo = v.x; hi = v.y;
+#endif
+}
+// a block's samples in one of the library's own homes, seen from the block's origin: the retained planes, or an entry's body
+struct WrYuvdHome { uint8_t* y; uint8_t* c0; uint8_t* c1; int ys, cs; };
+template <int FMT> WR_DEVICE WrYuvdHome wr_yuvd_keep(const WrGrabYuvDeltaArgs& d, int x0, int y0) {
+  WrYuvdHome K;
+  K.ys = d.keep_ys; K.cs = d.keep_cs;
+  K.y = d.keep_y + (size_t)y0 * K.ys + x0;
+  const size_t c = FMT == WR_YUV_I444 ? (size_t)y0 * K.cs + x0 : (size_t)(y0 >> 1) * K.cs + (FMT == WR_YUV_NV12 ? x0 : x0 >> 1);
+  K.c0 = d.keep_cb + c; K.c1 = d.keep_cr + c;
+  return K;
+}
+template <int FMT> WR_DEVICE WrYuvdHome wr_yuvd_body(uint8_t* e) {
+  constexpr int B = WR_GRAB_BLOCK;
+  WrYuvdHome E;
+  E.ys = B; E.cs = FMT == WR_YUV_I420 ? B / 2 : B;
+  E.y = e; E.c0 = e + B * B; E.c1 = E.c0 + (FMT == WR_YUV_I444 ? B * B : B * B / 4);
+  return E;
+}
+// item j of the block at (x0, y0): -> false if none of it lies inside the image; w: its six words
+template <int FMT> WR_DEVICE bool wr_yuvd_convert(const WrGrabYuvArgs& a, int x0, int y0, int j, uint32_t (&w)[6]) {
+  const int cx = x0 + 8 * (j & 7), ra = y0 + (FMT == WR_YUV_I444 ? j >> 3 : 2 * (j >> 3));
+  if (cx >= a.w || ra >= a.h) return false;
+  const int n = wr_imin(8, a.w - cx);
+  WrYuvRow A;
+  A.row = a.tex + (size_t)(a.ry + (a.flip ? a.h - 1 - ra : ra)) * a.tex_stride + (size_t)a.rx * 4;
+  A.x0 = -0x40000000;      // (nothing fetched yet)
+  wr_yuv_fetch(A, cx, a.w);
+#pragma unroll
+  for (int k = 0; k < 6; k++) w[k] = 0u;
+  if (FMT == WR_YUV_I444) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      if (k >= n) continue;
+      const uint32_t px = A.px[k];
+      const int r = (int)((px >> 16) & 0xFFu), g = (int)((px >> 8) & 0xFFu), b = (int)(px & 0xFFu);
+      w[k >> 2] |= wr_yuv_luma(a, px) << (8 * (k & 3));
+      w[2 + (k >> 2)] |= wr_yuv_chroma<16>(a.ccb, r, g, b) << (8 * (k & 3));
+      w[4 + (k >> 2)] |= wr_yuv_chroma<16>(a.ccr, r, g, b) << (8 * (k & 3));
+    }
+    return true;
+  }
+  const int rb = wr_imin(ra + 1, a.h - 1);
+  WrYuvRow B;
+  B.row = a.tex + (size_t)(a.ry + (a.flip ? a.h - 1 - rb : rb)) * a.tex_stride + (size_t)a.rx * 4;
+  B.x0 = -0x40000000;
+  wr_yuv_fetch(B, cx, a.w);
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    if (k >= n) continue;
+    w[k >> 2] |= wr_yuv_luma(a, A.px[k]) << (8 * (k & 3));
+    if (ra + 1 < a.h) w[2 + (k >> 2)] |= wr_yuv_luma(a, B.px[k]) << (8 * (k & 3));
+  }
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    if (2 * k >= n) continue;
+    const uint32_t cb = wr_yuv_chroma420(a.ccb, A, B, k), cr = wr_yuv_chroma420(a.ccr, A, B, k);
+    if (FMT == WR_YUV_NV12) w[4 + (k >> 1)] |= (cb | (cr << 8)) << (16 * (k & 1));
+    else { w[4] |= cb << (8 * k); w[5] |= cr << (8 * k); }
+  }
+  return true;
+}
+// where item j's words lie in a home: Y (two rows in 4:2:0), chroma
+template <int FMT> WR_DEVICE bool wr_yuvd_differs(const WrYuvdHome& K, int j, const uint32_t (&w)[6]) {
+  const int i = j & 7, r = j >> 3;
+  uint32_t e[6];
+  if (FMT == WR_YUV_I444) {
+    wr_yuv_ld8(K.y + (size_t)r * K.ys + 8 * i, e[0], e[1]);
+    wr_yuv_ld8(K.c0 + (size_t)r * K.cs + 8 * i, e[2], e[3]);
+    wr_yuv_ld8(K.c1 + (size_t)r * K.cs + 8 * i, e[4], e[5]);
+  } else {
+    wr_yuv_ld8(K.y + (size_t)(2 * r) * K.ys + 8 * i, e[0], e[1]);
+    wr_yuv_ld8(K.y + (size_t)(2 * r + 1) * K.ys + 8 * i, e[2], e[3]);
+    if (FMT == WR_YUV_NV12) wr_yuv_ld8(K.c0 + (size_t)r * K.cs + 8 * i, e[4], e[5]);
+    else { e[4] = wr_load4(K.c0 + (size_t)r * K.cs + 4 * i); e[5] = wr_load4(K.c1 + (size_t)r * K.cs + 4 * i); }
+  }
+  return ((w[0] ^ e[0]) | (w[1] ^ e[1]) | (w[2] ^ e[2]) | (w[3] ^ e[3]) | (w[4] ^ e[4]) | (w[5] ^ e[5])) != 0u;
+}
+template <int FMT> WR_DEVICE void wr_yuvd_store(const WrYuvdHome& H, int j, const uint32_t (&w)[6]) {
+  const int i = j & 7, r = j >> 3;
+  if (FMT == WR_YUV_I444) {
+    wr_yuv_st8(H.y + (size_t)r * H.ys + 8 * i, w[0], w[1]);
+    wr_yuv_st8(H.c0 + (size_t)r * H.cs + 8 * i, w[2], w[3]);
+    wr_yuv_st8(H.c1 + (size_t)r * H.cs + 8 * i, w[4], w[5]);
+  } else {
+    wr_yuv_st8(H.y + (size_t)(2 * r) * H.ys + 8 * i, w[0], w[1]);
+    wr_yuv_st8(H.y + (size_t)(2 * r + 1) * H.ys + 8 * i, w[2], w[3]);
+    if (FMT == WR_YUV_NV12) wr_yuv_st8(H.c0 + (size_t)r * H.cs + 8 * i, w[4], w[5]);
+    else { wr_grab_st4(H.c0 + (size_t)r * H.cs + 4 * i, w[4]); wr_grab_st4(H.c1 + (size_t)r * H.cs + 4 * i, w[5]); }
+  }
+}
+// the eight bytes of two words as samples for wr_yuv_put: eight of a byte, or four pairs
+template <int BYTES> WR_DEVICE void wr_yuvd_samples(uint32_t lo, uint32_t hi, uint32_t (&v)[8]) {
+#pragma unroll
+  for (int k = 0; k < 8 / BYTES; k++) v[k] = ((k < 4 / BYTES ? lo : hi) >> (8 * BYTES * (k % (4 / BYTES)))) & (BYTES == 2 ? 0xFFFFu : 0xFFu);
+}
+// item j into the caller's planes (device sink): the YUV grab's addresses, its rows cut by wr_yuv_put
+template <int FMT> WR_DEVICE void wr_yuvd_put(const WrGrabYuvArgs& a, int x0, int y0, int j, const uint32_t (&w)[6]) {
+  const int cx = x0 + 8 * (j & 7), ra = y0 + (FMT == WR_YUV_I444 ? j >> 3 : 2 * (j >> 3)), cw = (a.w + 1) >> 1;
+  uint32_t v[8];
+  wr_yuvd_samples<1>(w[0], w[1], v);
+  wr_yuv_put<8, 1>(a.y + ra * a.y_stride, cx, a.w, v);
+  if (FMT == WR_YUV_I444) {
+    wr_yuvd_samples<1>(w[2], w[3], v);
+    wr_yuv_put<8, 1>(a.cb + ra * a.c_stride, cx, a.w, v);
+    wr_yuvd_samples<1>(w[4], w[5], v);
+    wr_yuv_put<8, 1>(a.cr + ra * a.c_stride, cx, a.w, v);
+    return;
+  }
+  if (ra + 1 < a.h) {
+    wr_yuvd_samples<1>(w[2], w[3], v);
+    wr_yuv_put<8, 1>(a.y + (ra + 1) * a.y_stride, cx, a.w, v);
+  }
+  if (FMT == WR_YUV_NV12) {
+    wr_yuvd_samples<2>(w[4], w[5], v);
+    wr_yuv_put<4, 2>(a.cb + (ra >> 1) * a.c_stride, cx >> 1, cw, v);
+  } else {
+    wr_yuvd_samples<1>(w[4], w[5], v);
+    wr_yuv_put<4, 1>(a.cb + (ra >> 1) * a.c_stride, cx >> 1, cw, v);
+    wr_yuv_put<4, 1>(a.cr + (ra >> 1) * a.c_stride, cx >> 1, cw, v + 4);
+  }
+}
+// lw: the vote's two LDS words (wr_grab_pack_kernel's); unused by the host simulation
+template <int FMT> WR_DEVICE void wr_grab_yuv_delta_block(const WrGrabYuvDeltaArgs& d, unsigned* lw) {
+  constexpr int ITEMS = FMT == WR_YUV_I444 ? 2 : 1;      // per thread
+  const WrGrabYuvArgs& a = d.g;
+  const int t = (int)threadIdx.x, b = (int)blockIdx.x;
+  const int x0 = (b % d.bx) * WR_GRAB_BLOCK, y0 = (b / d.bx) * WR_GRAB_BLOCK;
+  const unsigned entry_bytes = d.device ? 16u : (unsigned)WR_YUVD_ENTRY(FMT);
+  const wr_u4 record = {(uint32_t)x0, (uint32_t)y0, (uint32_t)wr_imin(WR_GRAB_BLOCK, a.w - x0), (uint32_t)wr_imin(WR_GRAB_BLOCK, a.h - y0)};
+  const WrYuvdHome K = wr_yuvd_keep<FMT>(d, x0, y0);
+  uint8_t* e = nullptr;                // the block's entry, once it has one
+#ifdef WRHIP_HOSTSIM
+  // (threads run one after the other: the first walks the block twice)
+  (void)lw;
+  if (t != 0) return;
+  bool diff = d.keyframe != 0;
+  uint32_t w[6];
+  for (int j = 0; j < 256 * ITEMS && !diff; j++)
+    if (wr_yuvd_convert<FMT>(a, x0, y0, j, w)) diff = wr_yuvd_differs<FMT>(K, j, w);
+  if (!diff) return;
+  if (a.slot) {
+    const unsigned index = d.keyframe ? (unsigned)b : atomicAdd((unsigned*)a.slot, entry_bytes) / entry_bytes;
+    e = a.slot + WR_GRAB_HEADER + (size_t)index * entry_bytes;
+    wr_grab_st16(e, record);
+  }
+  const WrYuvdHome E = wr_yuvd_body<FMT>(e ? e + 16 : nullptr);
+  for (int j = 0; j < 256 * ITEMS; j++) {
+    if (!wr_yuvd_convert<FMT>(a, x0, y0, j, w)) continue;
+    if (d.device) wr_yuvd_put<FMT>(a, x0, y0, j, w);
+    else if (e) wr_yuvd_store<FMT>(E, j, w);
+    wr_yuvd_store<FMT>(K, j, w);
+  }
+#else
+  uint32_t w[ITEMS][6];
+  bool on[ITEMS], diff = false;
+#pragma unroll
+  for (int k = 0; k < ITEMS; k++) {
+    on[k] = wr_yuvd_convert<FMT>(a, x0, y0, k * 256 + t, w[k]);
+    if (on[k] && !d.keyframe) diff = diff || wr_yuvd_differs<FMT>(K, k * 256 + t, w[k]);
+  }
+  unsigned index = (unsigned)b;
+  if (!d.keyframe) {
+    if (t == 0) lw[0] = 0u;
+    __syncthreads();
+    if (__ballot(diff) != 0ull && (t & 63) == 0) lw[0] = 1u;
+    __syncthreads();
+    if (lw[0] == 0u) return;
+    if (t == 0) lw[1] = a.slot ? atomicAdd((unsigned*)a.slot, entry_bytes) / entry_bytes : 0u;
+    __syncthreads();
+    index = lw[1];
+  }
+  if (a.slot) {
+    e = a.slot + WR_GRAB_HEADER + (size_t)index * entry_bytes;
+    if (t == 0) wr_grab_st16(e, record);
+  }
+  const WrYuvdHome E = wr_yuvd_body<FMT>(e ? e + 16 : nullptr);
+#pragma unroll
+  for (int k = 0; k < ITEMS; k++) {
+    if (!on[k]) continue;
+    if (d.device) wr_yuvd_put<FMT>(a, x0, y0, k * 256 + t, w[k]);
+    else if (e) wr_yuvd_store<FMT>(E, k * 256 + t, w[k]);
+    wr_yuvd_store<FMT>(K, k * 256 + t, w[k]);
+  }
+#endif
+}
+__global__ void __launch_bounds__(256) wr_grab_yuv_delta_kernel(WrGrabYuvDeltaArgs d) {
+  // (what the host knows of the slot's byte count is written here: a keyframe's)
+  if (d.keyframe && d.g.slot && blockIdx.x == 0 && threadIdx.x == 0) wr_grab_st16(d.g.slot, wr_u4{d.g.payload, 0u, 0u, 0u});
+#ifdef WRHIP_HOSTSIM
+  unsigned* const lw = nullptr;
+#else
+  __shared__ unsigned lw[2];           // [0]: a lane saw a difference; [1]: the entry the block takes
+#endif
+  if (d.g.format == WR_YUV_I420) wr_grab_yuv_delta_block<WR_YUV_I420>(d, lw);
+  else if (d.g.format == WR_YUV_NV12) wr_grab_yuv_delta_block<WR_YUV_NV12>(d, lw);
+  else wr_grab_yuv_delta_block<WR_YUV_I444>(d, lw);
+}
 // The slot's header and as many bytes as its count word says, device slot -> pinned host slot, 16 bytes per store.  A small grid on
 // the grab stream: the link, not the chip, bounds it, and the raster launches of the following frames keep the CUs.
 __global__ void __launch_bounds__(256) wr_grab_push_kernel(WrGrabPushArgs a) {

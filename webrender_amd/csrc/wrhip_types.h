@@ -834,6 +834,22 @@ struct WrGrabYuvArgs {
   uint32_t payload;                    // the header's word: the planes' bytes behind it (host sink), 0 (device sink)
   int32_t cy[3], ccb[3], ccr[3], y0;   // the rows of the colour space, R, G, B, in 16.16; y0: 16 or 0
 };
+// WrhipGrabTextureYuvDelta: one launch of wr_grab_yuv_delta_kernel (the contract: include/wrhip.h).  `g` is the YUV grab's launch --
+// rect, flip, colour space; its planes are the caller's (device sink) or unused (host sink) --, the image is cut into bx x by
+// blocks of 64 x 64 luma samples, and workgroup b converts block b, compares its samples with the retained planes and, if one
+// differs (or on a keyframe), sends it.  The retained planes are the library's own: every block whole, so Y rows of bx * 64 bytes,
+// I420 chroma rows of bx * 32, NV12 and I444 chroma rows of bx * 64 -- a thread's 8 or 4 bytes are aligned there whatever the
+// rect is; bytes beyond the image are zero.  An entry in the slot: a 16-byte record x, y, w, h, then Y at a pitch of 64, then
+// chroma (I420: Cb, Cr at 32; NV12: pairs at 64; I444: Cb, Cr at 64).  Device sink: the slot takes the records alone.
+#define WR_YUVD_ENTRY(format) (16 + ((format) == WR_YUV_I444 ? 3 : 1) * WR_GRAB_BLOCK * WR_GRAB_BLOCK + ((format) == WR_YUV_I444 ? 0 : WR_GRAB_BLOCK * WR_GRAB_BLOCK / 2))
+struct WrGrabYuvDeltaArgs {
+  WrGrabYuvArgs g;                     // slot: null when the ticket is gone (device sink: no record is written); payload: a keyframe's
+  uint8_t* keep_y; uint8_t* keep_cb; uint8_t* keep_cr;      // the retained planes; NV12: keep_cb is the plane of pairs
+  int32_t keep_ys, keep_cs;            // their rows, bytes
+  int32_t bx, by;                      // blocks across and down
+  int32_t keyframe;                    // every block is sent, entry i is block i (nothing is compared, no atomic)
+  int32_t device;                      // sent samples go to g.y, g.cb, g.cr; the slot's entries are records of 16 bytes
+};
 struct WrGrabPushArgs {
   const uint8_t* src; uint8_t* dst;    // device slot -> pinned host slot
   uint32_t capacity;                   // of either, bytes (a multiple of 16): the count read from the slot is held to it

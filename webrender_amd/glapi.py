@@ -151,6 +151,8 @@ EXTRA_SIGNATURES = {
     "WrhipDeviceWrite": (i32, [P, P, u64]),
     "WrhipPutTextureTensor": (i32, [u32, P, P]),
     "WrhipGrabTextureYuv": (i32, [u32, P, P]),
+    "WrhipGrabTextureYuvDelta": (i32, [u32, P, P, u32]),
+    "WrhipGrabDecodeYuv": (i32, [P, u64, u32, i32, i32, P, C.c_int64, P, P, C.c_int64, P, P]),
 }
 
 
@@ -394,6 +396,23 @@ class GL:
         d.y_stride, d.c_stride = int(strides[0]), int(strides[1])
         return self.WrhipGrabTextureYuv(tex, C.addressof(arr), C.addressof(d))
 
+    def grab_texture_yuv_delta(self, tex, rect, format, color_space, flags=0, dst=None, dst_bytes=0, strides=(0, 0), key=False):
+        """Enqueue a delta YUV grab (include/wrhip.h, WrhipGrabTextureYuvDelta): grab_texture_yuv's arguments, but only the 64 x 64
+        blocks whose samples differ from the texture's retained planes are sent -- to the host as entries that grab_result patches
+        into the caller's planes (`into`), or straight into the device planes at `dst`.  key: GRAB_KEY, every block is sent (an int is
+        passed on as the call's raw `flags`).  Returns the ticket, or -1 (GL_INVALID_VALUE / GL_OUT_OF_MEMORY is then set)."""
+        if rect is None:
+            w, h = i32(0), i32(0)
+            if not self.WrhipGetTextureSize(tex, C.byref(w), C.byref(h)):
+                w = h = i32(0)
+            rect = (0, 0, w.value, h.value)
+        arr = (i32 * 4)(*[int(v) for v in rect])
+        d = WrhipYuvDesc()
+        d.format, d.color_space, d.flags = int(format), int(color_space), int(flags)
+        d.dst, d.dst_bytes = (int(dst) or None) if dst is not None else None, int(dst_bytes)
+        d.y_stride, d.c_stride = int(strides[0]), int(strides[1])
+        return self.WrhipGrabTextureYuvDelta(tex, C.addressof(arr), C.addressof(d), GRAB_KEY if key is True else int(key))
+
     def device_alloc(self, nbytes):
         """Device memory for tensor grabs (WrhipDeviceAlloc): its address, 16-byte aligned; 0 with GL_OUT_OF_MEMORY set"""
         return self.WrhipDeviceAlloc(int(nbytes)) or 0
@@ -443,7 +462,7 @@ class GL:
 
     def grab_result(self, ticket, wait=True, into=None):
         """The result of a grab: (info dict, pixels).  Full mode: one array per rect ((h, w, 4) stored B, G, R, A bytes, or (h, w)
-        for R8) -- the array itself for a single rect, a list for several.  A scaled grab: the (scaled_h, scaled_w, 4) array.  A tensor grab: None.  A YUV grab: the planes as one flat uint8 array (yuv_split cuts it; empty for a device sink).  Delta mode: the caller's image `into` of the rect (a
+        for R8) -- the array itself for a single rect, a list for several.  A scaled grab: the (scaled_h, scaled_w, 4) array.  A tensor grab: None.  A YUV grab: the planes as one flat uint8 array (yuv_split cuts it; empty for a device sink).  A delta YUV grab: the caller's flat planes `into` (that layout) with the sent blocks patched in -- left alone by a device sink's ticket; None: the info alone.  Delta mode: the caller's image `into` of the rect (a
         C-contiguous uint8 array of the rect's shape; None: a fresh one of zeros) with the sent blocks patched in.  None if the
         result has not arrived (wait=False only); a ticket the ring no longer holds raises KeyError."""
         import numpy as np
@@ -458,6 +477,17 @@ class GL:
         shape = lambda w, h: (h, w) if bpp == 1 else (h, w, 4)
         if r.flags & GRAB_TENSOR:
             pixels = buf = None          # (the elements are in the caller's device memory)
+        elif r.flags & GRAB_YUV and r.flags & GRAB_DELTA:
+            # (a delta YUV grab: `into` is the caller's flat planes -- a full YUV grab's payload layout, yuv_split cuts it -- and the
+            # sent blocks are patched in.  A device sink's ticket carries records of 16 bytes: nothing to patch, `into` is left alone.
+            # `into` None: the info alone)
+            assert into is None or (into.dtype == np.uint8 and into.flags["C_CONTIGUOUS"] and into.ndim == 1), "grab_result: `into` is not flat uint8 planes"
+            if into is not None and r.blocks:
+                w, h = rects[0][2:]
+                entry = (int(r.bytes) - GRAB_HEADER) // r.blocks      # (16: records alone; I420 and NV12 planes are the same size)
+                fmt = YUV_I444 if entry == 16 + 3 * GRAB_BLOCK * GRAB_BLOCK else YUV_I420
+                assert entry == 16 or len(into) == sum(rows * row for rows, row in yuv_plane_shapes(w, h, fmt)), "grab_result: `into` is not the rect's planes"
+            pixels = buf = into
         elif r.flags & GRAB_YUV:
             # (the planes, tight, one after another -- yuv_split cuts them apart; a device sink's ticket carries none)
             pixels = buf = np.empty(int(r.bytes) - GRAB_HEADER, np.uint8)
@@ -508,6 +538,26 @@ class GL:
         rc = self.WrhipGrabDecode(src, len(payload), fmt, flags, into.shape[1], into.shape[0], into.ctypes.data, 0, damage, C.byref(blocks))
         if rc != 0:
             raise ValueError("grab_decode: malformed payload")
+        return tuple(damage), blocks.value
+
+    def grab_decode_yuv(self, payload, format, w, h, into):
+        """Patch a host-sink delta YUV payload (grab_payload's bytes) into `into`, the caller's flat planes of the w x h image in a
+        full YUV grab's payload layout (yuv_split cuts it); None: only checked.  (damage, blocks).  A pure host function
+        (WrhipGrabDecodeYuv); a malformed payload raises ValueError and leaves `into` as it was."""
+        import numpy as np
+        shapes = yuv_plane_shapes(w, h, format)
+        ptrs = [None, None, None]
+        if into is not None:
+            assert into.dtype == np.uint8 and into.flags["C_CONTIGUOUS"] and into.shape == (sum(rows * row for rows, row in shapes),), "grab_decode_yuv: `into` is not the image's planes"
+            at = 0
+            for k, (rows, row) in enumerate(shapes):
+                ptrs[k] = into.ctypes.data + at
+                at += rows * row
+        damage, blocks = (i32 * 4)(), u32(0)
+        src = (C.c_char * len(payload)).from_buffer_copy(payload)
+        rc = self.WrhipGrabDecodeYuv(src, len(payload), int(format), int(w), int(h), ptrs[0], 0, ptrs[1], ptrs[2], 0, damage, C.byref(blocks))
+        if rc != 0:
+            raise ValueError("grab_decode_yuv: malformed payload")
         return tuple(damage), blocks.value
 
 

@@ -294,7 +294,7 @@ def render_streamed_tensors(backend_path, frames, size, dtype, layout, channels,
     return out, stats, infos
 
 
-def render_streamed_yuv(backend_path, frames, format, color_space, device=False, flags=0):
+def render_streamed_yuv(backend_path, frames, format, color_space, device=False, flags=0, delta=False, key_every=None):
     """render_streamed_grabbed for a video encoder: after each frame's render the whole window is YUV-grabbed (GL.grab_texture_yuv:
     one launch in stream order behind that frame, 8-bit planes in `format` of the ranged colour space `color_space`) -- nothing
     between the frames drains the held-back raster launches, no Finish.  Frame k's ticket is fetched after frame k + 1 has been
@@ -302,7 +302,11 @@ def render_streamed_yuv(backend_path, frames, format, color_space, device=False,
     device=False: the planes cross to the host as the tickets' payloads.  device=True: each frame's planes go, tight, into a buffer
     of its own in device memory (GL.device_alloc) -- where an encoder on the card would take them -- 16 bytes per frame cross, and
     the buffers are read back at the end.  Returns the per-frame planes (glapi.yuv_split's lists), the backend's statistics
-    (`setup_carried` included) and the grabs' info dicts.  libwrhip only."""
+    (`setup_carried` included) and the grabs' info dicts.  libwrhip only.
+    delta=True: a delta YUV grab per frame (GL.grab_texture_yuv_delta) into ONE set of planes that lives across the frames -- a flat
+    host array the tickets' blocks are patched into, or one device buffer the blocks are written to -- so only the 64 x 64 blocks
+    whose samples changed cross or are written; the planes returned for frame k are a copy of the accumulated ones once frame k's
+    ticket has been fetched (device: read back then, while frame k + 1's grab is still parked).  key_every=N: every N-th grab passes GRAB_KEY."""
     from . import glapi
     gl = GL(backend_path)
     assert gl.is_wrhip, "render_streamed_yuv: grabs are a libwrhip addition"
@@ -310,6 +314,8 @@ def render_streamed_yuv(backend_path, frames, format, color_space, device=False,
     r = Renderer(gl, w, h)
     window = gl.WrhipGetFramebufferTexture(0)
     nbytes = sum(rows * row for rows, row in glapi.yuv_plane_shapes(w, h, format))
+    if delta:
+        return _render_streamed_yuv_delta(gl, r, window, frames, format, color_space, device, flags, key_every, nbytes)
     bufs = [gl.device_alloc(nbytes) for _ in frames] if device else []
     assert all(bufs), gl.GetError()
     tickets, flats, infos = [], [], []
@@ -335,6 +341,40 @@ def render_streamed_yuv(backend_path, frames, format, color_space, device=False,
         flats = [gl.device_read(b, nbytes) for b in bufs]
         for b in bufs:
             gl.device_free(b)
+    r.finish()
+    r.destroy()
+    return [glapi.yuv_split(fl, w, h, format) for fl in flats], stats, infos
+
+
+def _render_streamed_yuv_delta(gl, r, window, frames, format, color_space, device, flags, key_every, nbytes):
+    """render_streamed_yuv(delta=True): frame k - 1's ticket is fetched after frame k has been rendered and grabbed, as in the full
+    loop.  Frame k's grab is then parked behind frame k's held-back launches, so the accumulated planes -- the host's, or the device
+    buffer read back on the draw stream -- are frame k - 1's when they are copied"""
+    from . import glapi
+    w, h = frames[0].width, frames[0].height
+    host = np.zeros(nbytes, np.uint8)
+    acc = gl.device_alloc(nbytes) if device else 0
+    assert acc or not device, gl.GetError()
+    tickets, flats, infos = [], [], []
+
+    def fetch(k):
+        infos.append(gl.grab_result(tickets[k], into=None if device else host)[0])
+        flats.append(gl.device_read(acc, nbytes) if device else host.copy())
+    for k, f in enumerate(frames):
+        assert (f.width, f.height) == (w, h), "render_streamed_yuv: one window size"
+        r.render(f)
+        t = gl.grab_texture_yuv_delta(window, (0, 0, w, h), format, color_space, flags, dst=acc if device else None,
+                                      dst_bytes=nbytes if device else 0, key=bool(key_every) and k % key_every == 0)
+        assert t >= 0, (t, gl.GetError())
+        tickets.append(t)
+        if k >= 1:
+            fetch(k - 1)
+    fetch(len(frames) - 1)
+    err = gl.GetError()
+    stats = gl.stats()
+    stats["gl_error"] = int(err)
+    if device:
+        gl.device_free(acc)
     r.finish()
     r.destroy()
     return [glapi.yuv_split(fl, w, h, format) for fl in flats], stats, infos
