@@ -252,7 +252,7 @@ void WrhipSetProfiling(int enabled);
  * (picture targets of a few large gradient / image prims, likewise), 11 = wr_setup_tile_rows_kernel (10 fused with the next flush's setup stage), 12 = a thin launch of the raster kernel (13: the same with the next flush's setup stage in front, wr_setup_raster_thin_kernel) (wr_raster_kernel<fmt, false, 1, feat>:
  * small levels, several workgroups per bin), 14 = wr_tap_kernel (WrhipTapTexture: fmt of the tapped texture, feat 1 against an expected texture;
  * algo_bytes: the rect's bytes, twice with an expected texture), 15 = wr_grab_pack_kernel (WrhipGrabTexture: fmt of the grabbed texture,
- * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta, feat 3: wr_grab_scale_kernel, the launches of one WrhipGrabTextureScaled, feat 4: wr_grab_tensor_kernel or the launches of a scaled WrhipGrabTextureTensor, feat 5: wr_grab_yuv_kernel, a WrhipGrabTextureYuv (the rect read once plus the planes written), feat 6: wr_grab_yuv_delta_kernel, a WrhipGrabTextureYuvDelta (the rect plus the retained planes; what its sent blocks write is not known at the launch, as for feat 1); algo_bytes: bytes read plus bytes written, as far as they are known at the launch), 16 = wr_put_tensor_kernel (WrhipPutTextureTensor: fmt of the texture written;
+ * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta, feat 3: wr_grab_scale_kernel, the launches of one WrhipGrabTextureScaled, feat 4: wr_grab_tensor_kernel or the launches of a scaled WrhipGrabTextureTensor, feat 5: wr_grab_yuv_kernel, a WrhipGrabTextureYuv (the rect read once plus the planes written), feat 6: wr_grab_yuv_delta_kernel, a WrhipGrabTextureYuvDelta (the rect plus the retained planes; what its sent blocks write is not known at the launch, as for feat 1), feat 7: wr_grab_scale_yuv_kernel, the launches of one WrhipGrabTextureYuvScaled (the rect read once plus the planes of every rendition written); algo_bytes: bytes read plus bytes written, as far as they are known at the launch), 16 = wr_put_tensor_kernel (WrhipPutTextureTensor: fmt of the texture written;
  * algo_bytes: the elements read plus the rect's bytes written).  algo_bytes: the launch's algorithmic bytes:
  * raster launches count every destination pixel they own once (twice when the target's old content is loaded) plus
  * the source texels their draws can sample; the setup stage counts instance + descriptor + record bytes.  Returns the
@@ -575,6 +575,43 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  * Returns -1 and sets GL_INVALID_VALUE, launching and flushing nothing and leaving the retained copy as it was, for everything
  * WrhipGrabTextureYuv rejects and for any `flags` bit other than KEY; -1 with GL_OUT_OF_MEMORY as WrhipGrabTexture.
  *
+ * WrhipGrabTextureYuvScaled(tex, rect, out_w, out_h, descs, renditions): a grab of ONE rect of a GL_RGBA8 texture scaled down as
+ * WrhipGrabTextureScaled scales it and delivered as WrhipGrabTextureYuv's planes -- at up to four sizes, the lowest levels of the
+ * one chain, from a single pass over the source (wr_grab_scale_yuv_kernel: the levels of a tile's pyramid are converted while they
+ * are in LDS).  A page rendered at 3840 x 2160 leaves as the 1080p / 540p / 270p ladder of an adaptive stream for the cost of one
+ * scaled grab.  The contract -- any restatement must give the same bytes:
+ *   chain     WrhipGrabTextureScaled's level rule, unchanged: L is the smallest L >= 0 with rect_w <= 2 * out_w * 2^L, level k is
+ *             out_w << k x out_h << k, the top step is a GL_LINEAR BlitFramebuffer of the rect to level L (equal sizes: the nearest
+ *             copy), every lower step an exact 2:1 linear blit.
+ *   renditions  `renditions` is n, 1 <= n <= min(L + 1, 4).  Rendition k (0 <= k < n) is LEVEL k of that chain -- the definition is the
+ *             level, not "a second grab of that size".  Where WrhipGrabTextureScaled(tex, rect, out_w << k, out_h << k, 0) is itself
+ *             legal it delivers the same pixels: its L' is L - k and its top level the same.
+ *   samples   the level's pixels are treated exactly as WrhipGrabTextureYuv treats a rect of that size: stored B, G, R; A ignored;
+ *             FLIP_ROWS first, on the LEVEL's rows; 4:2:0 blocks formed on the flipped image and clamped to the level's last column
+ *             and row; the six rows, y0, rounding and the live clamp as there.
+ *   descs     descs[k] describes rendition k.  format, color_space and flags must be equal in all of them, and all sinks are the
+ *             host or all are the device.
+ *   host sink (dst == NULL; the strides and dst_bytes must be 0)  the payload is rendition 0's planes, then rendition 1's, and so on,
+ *             each laid out as a WrhipGrabTextureYuv payload of that size: tight, Y then chroma.  WrhipGrabResultGet copies the
+ *             payload to `dst` (dst_stride must be 0); slots are sized for the sum.
+ *   device sink (dst != NULL)  WrhipGrabTextureYuv's device layout and stride rules, per rendition; nothing but samples is written.
+ *             The renditions' extents must not overlap one another.  The ticket carries an empty payload (`bytes` = 16); the write
+ *             does NOT depend on the ticket surviving.  Every destination takes part in WrhipPutTextureTensor's overlap rule while
+ *             the grab is parked.
+ *   ticket    WrhipGrabResultGet reports flags | WRHIP_GRAB_YUV | WRHIP_GRAB_SCALED, format GL_RGBA8, the rect as given, scaled_w /
+ *             scaled_h = rendition 0's size, levels = L and renditions = n.  The other grab calls keep rejecting these flags.
+ *   ordering, parking, ring, slot growth, WRHIP_GRAB_PINNED_MAX  WrhipGrabTexture's, "later writes do not change the result" included.
+ *   cost      WrhipStats::kernel_launches grows by 1 + L / 4 (WrhipGrabTextureScaled's launches: each level is held in LDS by exactly
+ *             one of them, and rendition k leaves from the launch that holds level k), flushes by 0.  ONE launch more in a single
+ *             case: FLIP_ROWS with a 4:2:0 format and an ODD out_h.  The flipped rendition 0 then pairs level rows (e, e - 1), e
+ *             even, which straddle the tiles; the chain leaves level 0 in device scratch and wr_grab_yuv_kernel converts it from
+ *             there.  The other renditions of that grab still leave from the chain's launches.
+ * Returns -1 and sets GL_INVALID_VALUE, launching and flushing nothing, for everything WrhipGrabTextureScaled rejects for tex, rect,
+ * out_w and out_h; everything WrhipGrabTextureYuv rejects for a desc, per rendition, with that rendition's size; `renditions` outside
+ * 1 .. min(L + 1, 4); a NULL descs; descs that disagree in format, colour space, flags or sink kind; overlapping device extents; and
+ * while sharding is on.  -1 with GL_OUT_OF_MEMORY as WrhipGrabTexture.  out_w x out_h equal to the rect's size with renditions == 1
+ * is legal: L = 0 with the nearest copy, WrhipGrabTextureYuv's bytes.
+ *
  * WrhipGrabDecodeYuv(payload, bytes, format, rect_w, rect_h, y, y_stride, c0, c1, c_stride, damage, blocks): the pure host function
  * -- no context, no GPU -- behind the host sink's decode (webrender_amd/csrc/wr_grab_codec.h, which a program can include on its
  * own).  It patches a host-sink payload (`payload`: its header) into planes given by pointers and BYTE strides (0: tight); NV12: c0
@@ -585,7 +622,7 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  * Not routed through grabs: Finish, GetColorBuffer, ReadPixels.  Not supported: other formats, sharded targets; scaling other than
  * WrhipGrabTextureScaled's; delta or packed tensor grabs; gamma or colour-space conversion of tensors (values are the stored
  * premultiplied bytes); puts that scale or filter, into other formats, into sharded targets or host-backed textures; YUV grabs of 10-
- * or 16-bit samples (P010), 4:2:2 or YUY2, scaled YUV grabs, scaled or packed delta YUV grabs, several rects in one, R8 sources, un-premultiplying, GbrIdentity. */
+ * or 16-bit samples (P010), 4:2:2 or YUY2, scaled YUV grabs that scale up, whose renditions are not levels of one chain or differ in format, scaled or packed delta YUV grabs, several rects in one, R8 sources, un-premultiplying, GbrIdentity. */
 #define WRHIP_GRAB_FLIP_ROWS 1u   /* full mode: deliver the rect's last row first */
 #define WRHIP_GRAB_SWAP_RB   2u   /* full mode, RGBA8 only: bytes 0 and 2 of every pixel exchanged */
 #define WRHIP_GRAB_DELTA     4u   /* only the 64x64 blocks that differ from the previous DELTA grab of this texture and rect */
@@ -593,7 +630,7 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
 #define WRHIP_GRAB_PACKED    32u  /* with DELTA: sent blocks as SOLID / RUNS / RAW entries (the packed payload above); 16 is no flag */
 #define WRHIP_GRAB_SCALED    64u  /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureScaled ticket; no flag of WrhipGrabTexture, which rejects it */
 #define WRHIP_GRAB_TENSOR    128u /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureTensor ticket; no flag of the other grab calls, which reject it */
-#define WRHIP_GRAB_YUV       512u /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureYuv or (with DELTA) WrhipGrabTextureYuvDelta ticket; rejected by the other grab calls */
+#define WRHIP_GRAB_YUV       512u /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureYuv, (with DELTA) WrhipGrabTextureYuvDelta or (with SCALED) WrhipGrabTextureYuvScaled ticket; rejected by the other grab calls */
 #define WRHIP_YUV_I420 0u         /* WrhipYuvDesc::format: Y plane, Cb plane, Cr plane; chroma 4:2:0 */
 #define WRHIP_YUV_NV12 1u         /* Y plane, one plane of interleaved Cb,Cr pairs; chroma 4:2:0 */
 #define WRHIP_YUV_I444 2u         /* Y, Cb, Cr planes, all w x h */
@@ -616,6 +653,7 @@ typedef struct WrhipGrabInfo {
   uint64_t bytes;                  /* bytes that crossed to the host for this ticket (header + payload) */
   int32_t  scaled_w, scaled_h;     /* WrhipGrabTextureScaled: the delivered size; 0 for other grabs */
   uint32_t levels;                 /* WrhipGrabTextureScaled: L, the 2:1 steps below the top step */
+  uint32_t renditions;             /* WrhipGrabTextureYuvScaled: n, the levels delivered; 0 for other grabs */
 } WrhipGrabInfo;
 int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint32_t flags);
 int32_t WrhipGrabTextureScaled(GLuint tex, const int32_t rect[4], int32_t dst_w, int32_t dst_h, uint32_t flags);
@@ -653,6 +691,7 @@ typedef struct WrhipYuvDesc {
 } WrhipYuvDesc;
 int32_t WrhipGrabTextureYuv(GLuint tex, const int32_t rect[4], const WrhipYuvDesc* desc);
 int32_t WrhipGrabTextureYuvDelta(GLuint tex, const int32_t rect[4], const WrhipYuvDesc* desc, uint32_t flags);
+int32_t WrhipGrabTextureYuvScaled(GLuint tex, const int32_t rect[4], int32_t out_w, int32_t out_h, const WrhipYuvDesc* descs, int32_t renditions);
 int32_t WrhipGrabDecodeYuv(const void* payload, uint64_t bytes, uint32_t format, int32_t rect_w, int32_t rect_h, void* y, int64_t y_stride, void* c0, void* c1, int64_t c_stride, int32_t damage[4], uint32_t* blocks);
 int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64_t dst_stride, int32_t wait);
 int32_t WrhipGrabPayloadGet(int32_t ticket, void* dst, uint64_t capacity, uint64_t* bytes, int32_t wait);

@@ -28,10 +28,15 @@
              frame: a tensor grab and a put, against a tensor grab, WrhipDeviceRead, numpy and TexSubImage2D, frames/s
   yuv        WrhipGrabTextureYuv: wr_grab_yuv_kernel per launch for I420, NV12 and I444, host and device sink, beside the full-mode
              pack of the same job; the cfg2 stream with an I420 host grab per frame against a full grab plus numpy on the host
+  yuv_scaled WrhipGrabTextureYuvScaled on the 4K cfg2 window, NV12 and I420: one rendition at 1920 x 1080 (L = 0) and 960 x 540 (L = 1)
+             against L + 1 BlitFramebuffer calls plus a WrhipGrabTextureYuv of the last level, 50 enqueued and one Finish on the host
+             clock, the new call's launches by hipEvents (kind 15 feat 7); the 1080p / 540p / 270p ladder as one call of three
+             renditions against three calls of one; 3840 x 2158 -> 1920 x 1079 I420 with and without FLIP_ROWS (the two routes of
+             rendition 0); then cfg2 streamed: no grab, a full-size NV12 grab per frame, a scaled NV12 grab per frame
   ab         plain bench.py against another build of the library (WRHIP_LIB_PATH), alternated, no grab issued
 
 Every section runs three alternated rounds.  Needs the GPU: there is no fallback.
-  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor,put,yuv,yuv_delta] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
+  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor,put,yuv,yuv_delta,yuv_scaled] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -837,6 +842,154 @@ def section_yuv_stream(lib, frames):
     say(f"  (an I420 payload is {payload / 1e6:.2f} MB, a full grab's {W * H * 4 / 1e6:.2f} MB)")
 
 
+# ---- scaled YUV grabs (WrhipGrabTextureYuvScaled) -----------------------------------------------------------
+def section_yuv_scaled(lib):
+    say(f"## yuv_scaled: {W}x{H} RGBA8 window of cfg2, Rec709Narrow, host sink; 50 enqueued grabs behind one Finish, host clock, us per grab;")
+    say("##             launch times: hipEvents (WrhipSetProfiling(1)), all launches of a grab together")
+    w = Window(lib, "cfg2")
+    gl, d = w.gl, w.r.device
+    sp = glapi.YUV_REC709_NARROW
+    sizes = [(W // 2, H // 2), (W // 4, H // 4), (W // 8, H // 8)]
+    own = {}        # the baseline's textures of its own: one chain per size
+
+    def blit(src_fbo, sw, sh, dst):
+        gl.BindFramebuffer(G.GL_READ_FRAMEBUFFER, src_fbo)
+        gl.BindFramebuffer(G.GL_DRAW_FRAMEBUFFER, dst.fbo)
+        gl.BlitFramebuffer(0, 0, sw, sh, 0, 0, dst.width, dst.height, G.GL_COLOR_BUFFER_BIT, G.GL_LINEAR)
+
+    def chain(size, fmt):
+        """What a caller does without the call: L + 1 BlitFramebuffer calls into textures of its own, then a YUV grab of the last"""
+        L = _levels(size[0])
+        if size not in own:
+            own[size] = [d.create_texture(size[0] << k, size[1] << k, G.GL_RGBA8, render_target=True) for k in range(L + 1)]
+        lv = own[size]
+        blit(0, W, H, lv[L])
+        for k in range(L - 1, -1, -1):
+            blit(lv[k + 1].fbo, lv[k + 1].width, lv[k + 1].height, lv[k])
+        gl.BindFramebuffer(G.GL_DRAW_FRAMEBUFFER, 0)
+        gl.BindFramebuffer(G.GL_READ_FRAMEBUFFER, 0)
+        return gl.grab_texture_yuv(lv[0].id, None, fmt, sp)
+
+    def fused(size, fmt, n=1, rect=None, flags=0):
+        t = gl.grab_texture_yuv_scaled(w.tex, rect, size, fmt, sp, flags, renditions=n)
+        assert t >= 0, gl.GetError()
+        return t
+
+    def timed(fn, N=50):
+        gl.Finish()
+        t0 = time.perf_counter()
+        for _ in range(N):
+            t = fn()
+        gl.Finish()
+        dt = (time.perf_counter() - t0) / N * 1e6
+        gl.grab_result(t)
+        return dt
+
+    def events(fn, n=30):
+        gl.WrhipSetProfiling(1)
+        gl.WrhipResetStats()
+        for _ in range(n):
+            t = fn()
+        gl.grab_result(t)
+        ks = [k for k in kernel_stats(gl, 15) if k.feat == 7]
+        gl.WrhipSetProfiling(0)
+        assert len(ks) == 1 and ks[0].launches == n, [(k.feat, k.launches) for k in ks]
+        return ks[0].ns / n / 1e3
+    fmts = (glapi.YUV_NV12, glapi.YUV_I420)
+    # 1. a single rendition against the chain of blits plus a YUV grab; the two agree byte for byte (and both are warm)
+    for size in sizes[:2]:
+        for fmt in fmts:
+            a, b = gl.grab_result(chain(size, fmt))[1], gl.grab_result(fused(size, fmt))[1]
+            assert np.array_equal(a, b), "the fused pass and the blit chain differ"
+    rows = {}
+    for rnd in range(ROUNDS):
+        for size in sizes[:2]:
+            for fmt in fmts:
+                key = (size, fmt)
+                rows.setdefault(key, {"chain": [], "fused": [], "ev": []})
+                rows[key]["chain"].append(timed(lambda: chain(size, fmt)))
+                rows[key]["fused"].append(timed(lambda: fused(size, fmt)))
+                rows[key]["ev"].append(events(lambda: fused(size, fmt)))
+    for (size, fmt), v in rows.items():
+        L = _levels(size[0])
+        say(f"  1. {W}x{H} -> {size[0]}x{size[1]} {YUV_NAMES[fmt]}, L = {L}")
+        say(f"     {L + 1} x BlitFramebuffer + WrhipGrabTextureYuv   " + "  ".join(f"{us:8.1f}" for us in v["chain"]))
+        say("     WrhipGrabTextureYuvScaled                  " + "  ".join(f"{us:8.1f}" for us in v["fused"]) + "     launches, hipEvents: " + "  ".join(f"{us:7.1f}" for us in v["ev"]))
+    # 2. the ladder: one call with three renditions against three calls with one
+    lad = {}
+    for rnd in range(ROUNDS):
+        for fmt in fmts:
+            lad.setdefault(fmt, {"one": [], "three": [], "ev1": [], "ev3": []})
+            lad[fmt]["one"].append(timed(lambda: fused(sizes[2], fmt, 3)))
+
+            def three():
+                fused(sizes[0], fmt)
+                fused(sizes[1], fmt)
+                return fused(sizes[2], fmt)
+            lad[fmt]["three"].append(timed(three))
+            lad[fmt]["ev1"].append(events(lambda: fused(sizes[2], fmt, 3)))
+            lad[fmt]["ev3"].append(sum(events(lambda: fused(sz, fmt)) for sz in sizes))
+    for fmt, v in lad.items():
+        say(f"  2. ladder {W}x{H} -> {sizes[2][0]}x{sizes[2][1]}, renditions = 3 ({YUV_NAMES[fmt]}), against three calls of one rendition")
+        say("     one call, three renditions      " + "  ".join(f"{us:8.1f}" for us in v["one"]) + "     launches, hipEvents: " + "  ".join(f"{us:7.1f}" for us in v["ev1"]))
+        say("     three calls, one rendition each " + "  ".join(f"{us:8.1f}" for us in v["three"]) + "     launches, hipEvents: " + "  ".join(f"{us:7.1f}" for us in v["ev3"]))
+        say("     ratio three / one, host clock   " + "  ".join(f"{b / a:8.2f}" for a, b in zip(v["one"], v["three"])) + "     hipEvents: " + "  ".join(f"{b / a:7.2f}" for a, b in zip(v["ev1"], v["ev3"])))
+    # 3. the two routes for rendition 0: an odd out_h, without FLIP_ROWS (stored from LDS) and with it (scratch + wr_grab_yuv_kernel)
+    odd = {"plain": [], "flipped": [], "ev_plain": [], "ev_flipped": []}
+    rect, size = (0, 0, W, H - 2), (W // 2, (H - 2) // 2)
+    for rnd in range(ROUNDS):
+        for name, flags in (("plain", 0), ("flipped", glapi.GRAB_FLIP_ROWS)):
+            odd[name].append(timed(lambda: fused(size, glapi.YUV_I420, 1, rect, flags)))
+            odd["ev_" + name].append(events(lambda: fused(size, glapi.YUV_I420, 1, rect, flags)))
+    say(f"  3. {rect[2]}x{rect[3]} -> {size[0]}x{size[1]} I420 (odd out_h)")
+    say("     stored from LDS (no flip)              " + "  ".join(f"{us:8.1f}" for us in odd["plain"]) + "     launches, hipEvents: " + "  ".join(f"{us:7.1f}" for us in odd["ev_plain"]))
+    say("     scratch + wr_grab_yuv_kernel (flipped) " + "  ".join(f"{us:8.1f}" for us in odd["flipped"]) + "     launches, hipEvents: " + "  ".join(f"{us:7.1f}" for us in odd["ev_flipped"]))
+    w.close()
+
+
+def section_yuv_scaled_stream(lib, frames):
+    size = (W // 2, H // 2)
+    say(f"## yuv_scaled stream: cfg2 {W}x{H} streamed as in `stream`, {frames} frames per region, frames/s; NV12 to the host, tickets fetched one frame late")
+    rec, _ = record_scene(lib, scenes.make_workload("cfg2", width=W, height=H))
+    p = ScenePlayer(lib, rec)
+    gl = glapi.GL(lib)                          # (the same loaded library and current context as the player's)
+    window = gl.WrhipGetFramebufferTexture(0)
+    host = np.empty(W * H * 2, np.uint8)
+    info = glapi.WrhipGrabInfo()
+
+    def run(kind, n):
+        prev = -1
+        for k in range(n):
+            p.rp.exec(rec.stream)
+            t = -1
+            if kind == "full-size NV12 grab":
+                t = gl.grab_texture_yuv(window, (0, 0, W, H), glapi.YUV_NV12, glapi.YUV_REC709_NARROW)
+            elif kind != "no grab":
+                t = gl.grab_texture_yuv_scaled(window, (0, 0, W, H), size, glapi.YUV_NV12, glapi.YUV_REC709_NARROW)
+            if prev >= 0:
+                assert gl.WrhipGrabResultGet(prev, C.byref(info), host.ctypes.data, 0, 1) == 0
+            prev = t
+        if prev >= 0:
+            assert gl.WrhipGrabResultGet(prev, C.byref(info), host.ctypes.data, 0, 1) == 0
+        gl.Finish()
+    kinds = ["no grab", "full-size NV12 grab", f"scaled NV12 grab {size[0]}x{size[1]}"]
+    rows, carried, crossed = {}, {}, {}
+    for k in kinds:
+        run(k, 4)
+    for rnd in range(ROUNDS):
+        for k in kinds:
+            gl.WrhipResetStats()
+            t0 = time.perf_counter()
+            run(k, frames)
+            dt = time.perf_counter() - t0
+            st = gl.stats()
+            rows.setdefault(k, []).append(frames / dt)
+            carried[k] = (st["setup_carried"], frames)
+            crossed[k] = st["d2h_bytes"] / frames
+    for k in kinds:
+        say(f"  {k:28s} " + "  ".join(f"{v:9.1f}" for v in rows[k]) + f"   frames/s   (setup_carried {carried[k][0]} of {carried[k][1]} flushes; {crossed[k] / 1e6:.2f} MB per frame crossed)")
+
+
 # yuv_delta: what changes between two grabs -- nothing, everything (GRAB_KEY), or a square of noise that moves by a block a frame
 YUVD_CONTENTS = [("static", 0), ("keyframe", -1), ("moving 256x256", 256), ("moving 1024x1024", 1024)]
 
@@ -1030,7 +1183,10 @@ def main():
             elif s == "yuv_delta":
                 section_yuv_delta_kernel(lib)
                 section_yuv_delta_stream(lib, args.frames)
-            elif s == "tensor_parent":         # (run by `tensor` with WRHIP_LIB_PATH set: the parent path alone, on that library)
+            elif s == "yuv_scaled":
+                section_yuv_scaled(lib)
+                section_yuv_scaled_stream(lib, args.frames)
+            elif s == "tensor_parent":        # (run by `tensor` with WRHIP_LIB_PATH set: the parent path alone, on that library)
                 section_tensor_scaled(lib, with_tensor=False)
                 section_tensor_stream(lib, args.frames, with_tensor=False)
         if args.ab:

@@ -677,6 +677,7 @@ struct Context {
     bool keyframe = false; uint32_t blocks_total = 0;
     int scaled_w = 0, scaled_h = 0, levels = 0;      // WrhipGrabTextureScaled: the delivered size and L
     uint32_t yuv_format = 0; bool yuv_device = false;      // WrhipGrabTextureYuvDelta: what its entries hold
+    uint32_t renditions = 0;                         // WrhipGrabTextureYuvScaled: how many levels it delivers; 0 for other grabs
   };
   // WrhipGrabTextureScaled as it was asked for; its launches are laid out when it is issued (grab_issue_scaled), since the levels
   // that go through HBM live in a scratch that may have grown by then
@@ -689,8 +690,13 @@ struct Context {
   struct GrabYuv { bool device; WrGrabYuvArgs args; uint64_t out_bytes, dst_extent; };
   // WrhipGrabTextureYuvDelta: the launch as it goes out (the slot is filled in when it is issued).  dst_extent as GrabYuv's (device sink)
   struct GrabYuvDelta { WrGrabYuvDeltaArgs args; uint64_t keep_bytes, dst_extent; };
-  enum GrabKind { GRAB_PLAIN = 0, GRAB_SCALED = 1, GRAB_TENSOR = 2, GRAB_YUV = 3, GRAB_YUV_DELTA = 4 };
-  struct GrabParked { uint64_t n; GrabKind kind; WrGrabArgs args; GrabScaled scale; GrabTensor tensor; GrabYuv yuv; GrabYuvDelta yuvd; };
+  // WrhipGrabTextureYuvScaled as it was asked for: the chain (`scale`; flip and swap_rb unused) and the planes of its `n` renditions
+  // -- r[k]: level k as a YUV grab of a dw << k x dh << k image would lay it out; a host sink's offsets count from the start of the
+  // payload, the renditions one after another.  The launches are laid out when it is issued, as a scaled grab's.  cross: rendition 0
+  // is a flipped 4:2:0 image of odd height, which the chain leaves in the scratch for a launch of wr_grab_yuv_kernel
+  struct GrabYuvScaled { GrabScaled scale; int32_t n; bool device, cross; GrabYuv r[4]; uint64_t out_bytes; };
+  enum GrabKind { GRAB_PLAIN = 0, GRAB_SCALED = 1, GRAB_TENSOR = 2, GRAB_YUV = 3, GRAB_YUV_DELTA = 4, GRAB_YUV_SCALED = 5 };
+  struct GrabParked { uint64_t n; GrabKind kind; WrGrabArgs args; GrabScaled scale; GrabTensor tensor; GrabYuv yuv; GrabYuvDelta yuvd; GrabYuvScaled yuvs; };
   GrabSlot grab_slot[GRAB_RING];
   uint64_t grab_next = 0;
   std::vector<GrabParked> grab_parked;
@@ -1830,6 +1836,84 @@ void grab_issue_yuv_delta(uint64_t n, const Context::GrabYuvDelta& g, bool notif
   c->stats.kernel_launches++;
   if (notify) grab_push(gs, a.g.payload, true);
 }
+// One scaled YUV grab, now: the slot's previous ticket first, then the scaled grab's launches (grab_scale_launches' split and scratch
+// halves) as wr_grab_scale_yuv_kernel -- each stores the renditions among the levels it holds, every launch but the last hands its
+// lowest level on through the scratch, the last writes the header -- and the transport.  `cross`: the last launch of the chain leaves
+// level 0 behind the scratch's two halves instead, and wr_grab_yuv_kernel converts it from there as a flipped image of its own; it is
+// then the last launch and writes the header.  notify == false (device sink only): the ticket has been overwritten while the grab
+// was parked; the planes are written all the same, nobody is told.
+static size_t grab_yuv_scaled_scratch_need(const Context::GrabYuvScaled& g) {
+  return grab_scale_scratch_need(g.scale) + (g.cross ? grab_scale_level_bytes(g.scale, 0) : 0);
+}
+void grab_issue_yuv_scaled(uint64_t n, const Context::GrabYuvScaled& g, bool notify) {
+  Context* c = ctx;
+  Context::GrabSlot& gs = c->grab_slot[n % Context::GRAB_RING];
+  if (notify) wrrt::stream_wait_event(c->stream, &gs.ev);
+  const Context::GrabScaled& s = g.scale;
+  uint8_t* const slot = notify ? gs.dev : nullptr;
+  const uint32_t payload = g.device ? 0u : (uint32_t)g.out_bytes;
+  // the planes' addresses: the caller's, or offsets into the slot's payload
+  WrGrabYuvArgs r[4];
+  for (int k = 0; k < g.n; k++) {
+    r[k] = g.r[k].args;
+    if (!g.device) {
+      uint8_t* const base = gs.dev + WR_GRAB_HEADER;
+      r[k].y = base + (uintptr_t)r[k].y; r[k].cb = base + (uintptr_t)r[k].cb; r[k].cr = base + (uintptr_t)r[k].cr;
+    }
+  }
+  uint8_t* const scratch = (uint8_t*)c->grab_scale_scratch;
+  const size_t second_half = grab_scale_level_bytes(s, s.levels - std::min(WR_SCALE_STEPS, s.levels));
+  uint8_t* const level0 = scratch + grab_scale_scratch_need(s);
+  uint64_t launches = 0, workgroups = 0;
+  const uint8_t* prev = nullptr;
+  prof_begin();
+  for (int top = s.levels;;) {
+    WrGrabScaleYuvArgs b;
+    memset(&b, 0, sizeof(b));
+    WrGrabScaleArgs& a = b.s;
+    a.steps = std::min(WR_SCALE_STEPS, top);
+    a.tw = s.dw << top; a.th = s.dh << top;
+    if (!prev) {
+      a.src = s.tex; a.src_stride = s.tex_stride; a.sw = s.tex_w; a.sh = s.tex_h;
+      a.rx = s.rect[0]; a.ry = s.rect[1]; a.rw = s.rect[2]; a.rh = s.rect[3];
+      a.mode = !(a.rw == a.tw && a.rh == a.th) && s.tex_w >= 2 ? 0 : 1;      // (grab_scale_launches' rule)
+    } else {
+      a.src = prev; a.sw = 2 * a.tw; a.sh = 2 * a.th; a.src_stride = 4 * a.sw;
+      a.mode = 2;
+    }
+    const bool last = top == a.steps;
+    a.tiles_x = (a.tw + WR_SCALE_TILE - 1) / WR_SCALE_TILE;
+    const int grid = a.tiles_x * ((a.th + WR_SCALE_TILE - 1) / WR_SCALE_TILE);
+    b.g = r[0];
+    for (int j = 0; j <= a.steps; j++) {
+      const int k = top - j;
+      if (k >= g.n || (k == 0 && g.cross)) continue;
+      b.lv[j].y = r[k].y; b.lv[j].cb = r[k].cb; b.lv[j].cr = r[k].cr;
+      b.lv[j].y_stride = r[k].y_stride; b.lv[j].c_stride = r[k].c_stride;
+    }
+    b.rgba = !last || g.cross ? 1 : 0;
+    a.dst = last ? level0 : scratch + ((launches & 1) ? second_half : 0);
+    a.slot = last && !g.cross ? slot : nullptr; a.payload = payload;
+    WR_LAUNCH(wr_grab_scale_yuv_kernel, grid, 256, c->stream, b);
+    launches++; workgroups += (uint64_t)grid;
+    if (last) break;
+    prev = a.dst;
+    top -= a.steps + 1;
+  }
+  if (g.cross) {
+    WrGrabYuvArgs a = r[0];
+    a.tex = level0; a.tex_stride = 4 * s.dw; a.rx = a.ry = 0;
+    a.slot = slot; a.payload = payload;
+    const int units = (a.h + 1) / 2;
+    const int grid = (units + a.units_per_wg - 1) / a.units_per_wg;
+    WR_LAUNCH(wr_grab_yuv_kernel, grid, 256, c->stream, a);
+    launches++; workgroups += (uint64_t)grid;
+  }
+  // (15, feat 7: wr_grab_scale_yuv_kernel, all launches of the grab as one entry; the rect read once, the planes written)
+  prof_end(WR_KIND_GRAB, WR_FMT_RGBA8, 0, 7, (uint64_t)s.rect[2] * s.rect[3] * 4 + g.out_bytes, workgroups);
+  c->stats.kernel_launches += launches;
+  if (notify) grab_push(gs, payload, c->grab_full_kernel);
+}
 // tail_launched(): the grabs that waited for the held-back launches follow them, in the order they were made
 void grab_issue_parked() {
   Context* c = ctx;
@@ -1847,6 +1931,7 @@ void grab_issue_parked() {
     // (a tensor grab writes the caller's memory, not the slot: it goes out with or without its ticket)
     if (p.kind == Context::GRAB_TENSOR) { grab_issue_tensor(p.n, p.tensor, gs.n == p.n); continue; }
     if (p.kind == Context::GRAB_YUV && p.yuv.device) { grab_issue_yuv(p.n, p.yuv, gs.n == p.n); continue; }
+    if (p.kind == Context::GRAB_YUV_SCALED && p.yuvs.device) { grab_issue_yuv_scaled(p.n, p.yuvs, gs.n == p.n); continue; }
     if (p.kind == Context::GRAB_YUV_DELTA && p.yuvd.args.device) {
       // (it brings planes and retained copy up to date with or without its ticket.  Behind a HOST-sink one that was dropped it is
       // a keyframe already -- it named another sink --, and the planes are whole again)
@@ -1863,6 +1948,7 @@ void grab_issue_parked() {
     }
     if (p.kind == Context::GRAB_SCALED) grab_issue_scaled(p.n, p.scale);
     else if (p.kind == Context::GRAB_YUV) grab_issue_yuv(p.n, p.yuv, true);
+    else if (p.kind == Context::GRAB_YUV_SCALED) grab_issue_yuv_scaled(p.n, p.yuvs, true);
     else grab_issue(p.n, p.args);
   }
   for (const uint8_t* k : stale)
@@ -4285,7 +4371,7 @@ int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint3
   gs.format = t->internal_format; gs.flags = flags; gs.bpp = t->bpp; gs.nrects = nrects;
   memcpy(gs.rects, rects, sizeof(int32_t) * 4 * nrects);
   gs.keyframe = keyframe; gs.blocks_total = delta ? (uint32_t)(bx * by) : 0;
-  gs.scaled_w = gs.scaled_h = gs.levels = 0;
+  gs.scaled_w = gs.scaled_h = gs.levels = 0; gs.renditions = 0;
   if (c->tail.pending && t->tail_ref) {
     // the held-back launches write (or read) the texture: the grab waits for them to leave, and does not make them (see WrhipTapTexture)
     gs.parked = true;
@@ -4332,7 +4418,7 @@ int32_t WrhipGrabTextureScaled(GLuint tex, const int32_t rect[4], int32_t dst_w,
   gs.format = t->internal_format; gs.flags = flags | WRHIP_GRAB_SCALED; gs.bpp = t->bpp; gs.nrects = 1;
   memcpy(gs.rects, rect, sizeof(int32_t) * 4);
   gs.keyframe = false; gs.blocks_total = 0;
-  gs.scaled_w = dst_w; gs.scaled_h = dst_h; gs.levels = levels;
+  gs.scaled_w = dst_w; gs.scaled_h = dst_h; gs.levels = levels; gs.renditions = 0;
   if (c->tail.pending && t->tail_ref) {
     gs.parked = true;
     Context::GrabParked p;
@@ -4423,7 +4509,7 @@ int32_t WrhipGrabTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTen
   gs.format = t->internal_format; gs.flags = desc->flags | WRHIP_GRAB_TENSOR; gs.bpp = t->bpp; gs.nrects = 1;
   memcpy(gs.rects, rect, sizeof(int32_t) * 4);
   gs.keyframe = false; gs.blocks_total = 0;
-  gs.scaled_w = scaled ? o.ow : 0; gs.scaled_h = scaled ? o.oh : 0; gs.levels = levels;
+  gs.scaled_w = scaled ? o.ow : 0; gs.scaled_h = scaled ? o.oh : 0; gs.levels = levels; gs.renditions = 0;
   if (c->tail.pending && t->tail_ref) {
     gs.parked = true;
     Context::GrabParked p;
@@ -4448,16 +4534,16 @@ static const int32_t wr_yuv_rows[6][9] = {
 };
 // What WrhipGrabTextureYuv and WrhipGrabTextureYuvDelta share: the checks of texture, rect and desc -- false: GL_INVALID_VALUE is set
 // and nothing else has happened -- and the launch's arguments, the planes as the sink lays them out.
-static bool grab_yuv_prepare(Texture* t, const int32_t rect[4], const WrhipYuvDesc* desc, Context::GrabYuv& g) {
-  Context* c = ctx;
-  bool ok = t && t->dptr && t->internal_format == GL_RGBA8 && rect && desc;
+// (grab_yuv_planes: the desc alone, for an image of iw x ih pixels -- a rect, or a level of a scaled grab's chain.  false: nothing
+// has happened, no error is set; true: everything of `g` but the source -- tex, tex_stride, rx, ry)
+static bool grab_yuv_planes(int32_t iw, int32_t ih, const WrhipYuvDesc* desc, Context::GrabYuv& g) {
+  bool ok = desc && iw >= 1 && ih >= 1;
   ok = ok && desc->format <= WRHIP_YUV_I444 && desc->color_space <= 5u && (desc->flags & ~WRHIP_GRAB_FLIP_ROWS) == 0;
-  ok = ok && rect[2] >= 1 && rect[3] >= 1 && rect[0] >= 0 && rect[1] >= 0 && rect[0] <= t->width - rect[2] && rect[1] <= t->height - rect[3];
   // the planes: Y of w x h, chroma of cw x ch samples in rows of c_row bytes; strides (0: tight) no smaller than a row
   const int64_t stride_max = (int64_t)1 << 40;       // (keeps every product below in 64 bits)
   int64_t w = 0, h = 0, ch = 0, c_row = 0, ys = 0, cs = 0, extent = 0;
   if (ok) {
-    w = rect[2]; h = rect[3];
+    w = iw; h = ih;
     const bool i444 = desc->format == WRHIP_YUV_I444, nv12 = desc->format == WRHIP_YUV_NV12;
     ch = i444 ? h : (h + 1) / 2;
     c_row = i444 ? w : nv12 ? 2 * ((w + 1) / 2) : (w + 1) / 2;
@@ -4469,15 +4555,13 @@ static bool grab_yuv_prepare(Texture* t, const int32_t rect[4], const WrhipYuvDe
     extent = h * ys + ((nv12 ? 1 : 2) * ch - 1) * cs + c_row;
     ok = ok && (!desc->dst || (uint64_t)extent <= desc->dst_bytes);
   }
-  ok = ok && c->shard_world <= 1 && t->own_y0 == t->own_y1;      // (sharded targets hold a strip of the frame each: out of scope)
-  if (!ok) { c->last_error = GL_INVALID_VALUE; return false; }
+  if (!ok) return false;
   memset(&g, 0, sizeof(g));
   g.device = desc->dst != nullptr;
   g.out_bytes = (uint64_t)(w * h + (desc->format == WRHIP_YUV_NV12 ? 1 : 2) * ch * c_row);
   g.dst_extent = (uint64_t)extent;
   WrGrabYuvArgs& a = g.args;
-  a.tex = (const uint8_t*)t->dptr; a.tex_stride = t->stride;
-  a.rx = rect[0]; a.ry = rect[1]; a.w = rect[2]; a.h = rect[3];
+  a.w = iw; a.h = ih;
   a.format = (int32_t)desc->format; a.flip = (desc->flags & WRHIP_GRAB_FLIP_ROWS) ? 1 : 0;
   // (host sink: offsets from the payload's start, made addresses when the grab is issued -- the slot may grow until then)
   a.y = (uint8_t*)desc->dst; a.cb = a.y + h * ys; a.cr = a.cb + ch * cs;
@@ -4493,6 +4577,86 @@ static bool grab_yuv_prepare(Texture* t, const int32_t rect[4], const WrhipYuvDe
   a.units_per_wg = std::max(1, std::min(units, 512 / a.slots));
   return true;
 }
+static bool grab_yuv_prepare(Texture* t, const int32_t rect[4], const WrhipYuvDesc* desc, Context::GrabYuv& g) {
+  Context* c = ctx;
+  bool ok = t && t->dptr && t->internal_format == GL_RGBA8 && rect && desc;
+  ok = ok && rect[2] >= 1 && rect[3] >= 1 && rect[0] >= 0 && rect[1] >= 0 && rect[0] <= t->width - rect[2] && rect[1] <= t->height - rect[3];
+  ok = ok && c->shard_world <= 1 && t->own_y0 == t->own_y1;      // (sharded targets hold a strip of the frame each: out of scope)
+  ok = ok && grab_yuv_planes(rect[2], rect[3], desc, g);
+  if (!ok) { c->last_error = GL_INVALID_VALUE; return false; }
+  g.args.tex = (const uint8_t*)t->dptr; g.args.tex_stride = t->stride;
+  g.args.rx = rect[0]; g.args.ry = rect[1];
+  return true;
+}
+// A scaled YUV grab: see include/wrhip.h.  WrhipGrabTextureScaled's checks and chain, WrhipGrabTextureYuv's checks and planes for
+// every rendition; ticket ring, ordering and parking are WrhipGrabTexture's.  Everything is decided before anything changes.
+int32_t WrhipGrabTextureYuvScaled(GLuint tex, const int32_t rect[4], int32_t out_w, int32_t out_h, const WrhipYuvDesc* descs, int32_t renditions) {
+  if (!ctx) return -1;
+  Context* c = ctx;
+  Texture* t = tex ? c->textures.find(tex) : nullptr;
+  bool ok = t && t->dptr && t->internal_format == GL_RGBA8 && rect && descs;
+  ok = ok && rect[2] >= 1 && rect[3] >= 1 && rect[0] >= 0 && rect[1] >= 0 && rect[0] <= t->width - rect[2] && rect[1] <= t->height - rect[3];
+  ok = ok && out_w >= 1 && out_h >= 1 && out_w <= rect[2] && out_h <= rect[3];
+  // (WrhipGrabTextureScaled's level rule and its bound on the top level)
+  const int max_size = 1 << 15;                      // GL_MAX_TEXTURE_SIZE
+  int levels = 0;
+  while (ok && (int64_t)rect[2] > ((int64_t)2 * out_w << levels)) levels++;
+  ok = ok && ((int64_t)out_w << levels) <= max_size && ((int64_t)out_h << levels) <= max_size;
+  ok = ok && renditions >= 1 && renditions <= std::min(levels + 1, 4);
+  ok = ok && c->shard_world <= 1 && t->own_y0 == t->own_y1;      // (sharded targets hold a strip of the frame each: out of scope)
+  Context::GrabYuvScaled g;
+  memset(&g, 0, sizeof(g));
+  uint64_t at = 0;
+  for (int k = 0; ok && k < renditions; k++) {
+    const WrhipYuvDesc& d = descs[k];
+    ok = d.format == descs[0].format && d.color_space == descs[0].color_space && d.flags == descs[0].flags && !d.dst == !descs[0].dst;
+    ok = ok && grab_yuv_planes(out_w << k, out_h << k, &d, g.r[k]);
+    if (!ok) break;
+    // (device sink: no two renditions' extents may share a byte)
+    for (int i = 0; ok && d.dst && i < k; i++) {
+      const uint8_t* const a0 = g.r[i].args.y;
+      const uint8_t* const b0 = g.r[k].args.y;
+      ok = !(a0 < b0 + g.r[k].dst_extent && b0 < a0 + g.r[i].dst_extent);
+    }
+    // (host sink: the renditions' payloads follow one another; offsets until the grab is issued)
+    if (!d.dst) { WrGrabYuvArgs& a = g.r[k].args; a.y += at; a.cb += at; a.cr += at; }
+    at += g.r[k].out_bytes;
+  }
+  if (!ok) { c->last_error = GL_INVALID_VALUE; return -1; }
+  Context::GrabScaled& s = g.scale;
+  s.tex = (const uint8_t*)t->dptr; s.tex_stride = t->stride; s.tex_w = t->width; s.tex_h = t->height;
+  memcpy(s.rect, rect, sizeof(s.rect));
+  s.dw = out_w; s.dh = out_h; s.levels = levels;
+  g.n = renditions; g.device = descs[0].dst != nullptr; g.out_bytes = at;
+  const uint32_t flags = descs[0].flags;
+  g.cross = (flags & WRHIP_GRAB_FLIP_ROWS) && descs[0].format != WRHIP_YUV_I444 && (out_h & 1);
+  Context::GrabSlot* const slot = grab_reserve(g.device ? 0 : g.out_bytes);
+  if (!slot) return -1;
+  Context::GrabSlot& gs = *slot;
+  // (the scratch only grows: a parked grab finds at least what it asked for here when it is issued)
+  const size_t scratch = grab_yuv_scaled_scratch_need(g);
+  if (scratch > c->grab_scale_scratch_size) {
+    if (c->grab_scale_scratch) pool_free(c->grab_scale_scratch, c->grab_scale_scratch_size);
+    c->grab_scale_scratch = pool_alloc(scratch, &c->grab_scale_scratch_size);
+    if (!c->grab_scale_scratch) { c->grab_scale_scratch_size = 0; out_of_memory(); return -1; }
+  }
+  const uint64_t n = c->grab_next++;
+  gs.n = n; gs.counted = false;
+  gs.format = t->internal_format; gs.flags = flags | WRHIP_GRAB_YUV | WRHIP_GRAB_SCALED; gs.bpp = t->bpp; gs.nrects = 1;
+  memcpy(gs.rects, rect, sizeof(int32_t) * 4);
+  gs.keyframe = false; gs.blocks_total = 0;
+  gs.scaled_w = out_w; gs.scaled_h = out_h; gs.levels = levels; gs.renditions = (uint32_t)renditions;
+  if (c->tail.pending && t->tail_ref) {
+    gs.parked = true;
+    Context::GrabParked p;
+    memset(&p, 0, sizeof(p));
+    p.n = n; p.kind = Context::GRAB_YUV_SCALED; p.yuvs = g;
+    c->grab_parked.push_back(p);
+  } else {
+    grab_issue_yuv_scaled(n, g, true);
+  }
+  return (int32_t)(n & 0x7FFFFFFFull);
+}
 int32_t WrhipGrabTextureYuv(GLuint tex, const int32_t rect[4], const WrhipYuvDesc* desc) {
   if (!ctx) return -1;
   Context* c = ctx;
@@ -4507,7 +4671,7 @@ int32_t WrhipGrabTextureYuv(GLuint tex, const int32_t rect[4], const WrhipYuvDes
   gs.format = t->internal_format; gs.flags = desc->flags | WRHIP_GRAB_YUV; gs.bpp = t->bpp; gs.nrects = 1;
   memcpy(gs.rects, rect, sizeof(int32_t) * 4);
   gs.keyframe = false; gs.blocks_total = 0;
-  gs.scaled_w = gs.scaled_h = gs.levels = 0;
+  gs.scaled_w = gs.scaled_h = gs.levels = 0; gs.renditions = 0;
   if (c->tail.pending && t->tail_ref) {
     gs.parked = true;
     Context::GrabParked p;
@@ -4571,7 +4735,7 @@ int32_t WrhipGrabTextureYuvDelta(GLuint tex, const int32_t rect[4], const WrhipY
   gs.format = t->internal_format; gs.flags = desc->flags | flags | WRHIP_GRAB_YUV | WRHIP_GRAB_DELTA; gs.bpp = t->bpp; gs.nrects = 1;
   memcpy(gs.rects, rect, sizeof(int32_t) * 4);
   gs.keyframe = keyframe; gs.blocks_total = (uint32_t)(bx * by);
-  gs.scaled_w = gs.scaled_h = gs.levels = 0;
+  gs.scaled_w = gs.scaled_h = gs.levels = 0; gs.renditions = 0;
   gs.yuv_format = desc->format; gs.yuv_device = y.device;
   if (c->tail.pending && t->tail_ref) {
     gs.parked = true;
@@ -4628,6 +4792,12 @@ int32_t WrhipPutTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTens
     if (p.kind == Context::GRAB_YUV && p.yuv.device && y0 < s1 && s0 < y0 + p.yuv.dst_extent) { drain_tail(); break; }
     const uint8_t* const yd = p.yuvd.args.g.y;
     if (p.kind == Context::GRAB_YUV_DELTA && p.yuvd.args.device && yd < s1 && s0 < yd + p.yuvd.dst_extent) { drain_tail(); break; }
+    bool hit = false;      // (a scaled YUV grab: every rendition's planes)
+    for (int k = 0; p.kind == Context::GRAB_YUV_SCALED && p.yuvs.device && k < p.yuvs.n; k++) {
+      const uint8_t* const yk = p.yuvs.r[k].args.y;
+      hit = hit || (yk < s1 && s0 < yk + p.yuvs.r[k].dst_extent);
+    }
+    if (hit) { drain_tail(); break; }
   }
   // the write: draws recorded so far that sample or target the texture are flushed, held-back launches that reference it leave,
   // queued uploads go out ahead of it
@@ -4744,7 +4914,7 @@ int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64
   r.format = gs->format; r.flags = gs->flags; r.nrects = gs->nrects;
   memcpy(r.rects, gs->rects, sizeof(int32_t) * 4 * gs->nrects);
   r.bytes = (uint64_t)WR_GRAB_HEADER + payload;
-  r.scaled_w = gs->scaled_w; r.scaled_h = gs->scaled_h; r.levels = (uint32_t)gs->levels;
+  r.scaled_w = gs->scaled_w; r.scaled_h = gs->scaled_h; r.levels = (uint32_t)gs->levels; r.renditions = gs->renditions;
   if (yuv && delta) {
     // the entries one after the other, each record checked (wr_grab_codec.h) before its block is patched into the caller's tight
     // planes; one that is no block of the image is passed over: status 1.  A device sink's entries are the records alone

@@ -914,7 +914,7 @@ __global__ void __launch_bounds__(256) wr_grab_scale_tensor_kernel(WrGrabScaleTe
   WR_SCALE_PHASE(wr_grab_scale_store_tensor_any(a, b.o, g, from, WR_SCALE_TILE >> a.steps, t);
                  if (a.slot && blockIdx.x == 0 && t == 0) wr_grab_st16(a.slot, wr_u4{0u, 0u, 0u, 0u}))
 }
-#undef WR_SCALE_PHASE
+// (WR_SCALE_PHASE stays defined for wr_grab_scale_yuv_kernel, behind the YUV grab's helpers)
 // WrhipGrabTextureYuv (include/wrhip.h; WrGrabYuvArgs): the rect's stored B, G, R bytes as 8-bit Y, Cb and Cr planes for a video
 // encoder -- the inverse of the video wr_composite_yuv_kernel draws.  A streaming converter bound by its read, 4 bytes per pixel
 // against 1.5 or 3 written, so the work is cut along the SOURCE rows: a unit is two image rows (4:2:0: a chroma sample never needs
@@ -1059,6 +1059,117 @@ __global__ void __launch_bounds__(256) wr_grab_yuv_kernel(WrGrabYuvArgs a) {
   else if (a.format == WR_YUV_NV12) wr_grab_yuv_units<WR_YUV_NV12>(a, u0, u1, t, (int)blockDim.x);
   else wr_grab_yuv_units<WR_YUV_I444>(a, u0, u1, t, (int)blockDim.x);
 }
+// WrhipGrabTextureYuvScaled (include/wrhip.h; WrGrabScaleYuvArgs): the scaled grab's launch -- its coordinates, fill and halving
+// phases, called as they are -- with a store phase that turns levels of the tile's pyramid into samples while they are in LDS.  A
+// launch holds levels top .. top - steps, each exactly once in the grab, so rendition k leaves from the launch that holds level k:
+// the renditions of a ladder come out of the one pass over the source.  Level top - j of the tile is (64 >> j) pixels on a side
+// at an origin that is a multiple of that: the 2 x 2 chroma blocks of the unflipped level never leave the tile, nor do those of a
+// flipped level of even height (rows 2m + 1, 2m); only the clamp at an odd last column or row is left, and it is the tile's own
+// last column or row.  (The flipped 4:2:0 level of odd height pairs rows 2m, 2m - 1: the host routes it through
+// wr_grab_yuv_kernel.)  The work is cut as wr_grab_yuv_units cuts it: a unit is two level rows (4:2:0) or one (I444), an item the
+// 8-byte piece of the Y row it touches -- which eight pixels is decided per destination row from that row's ADDRESS at the tile's
+// first column, so a piece lying whole inside the tile's part of the row leaves as one aligned store and the rest as bytes.  A
+// level is converted in the phase that reads it for the next halving: behind the barrier that completes it, ahead of the one
+// after which its buffer is written again.
+// eight pixels of one row of the tile's level: columns c0 .. c0 + 7 of the tile, each held to [0, ow)
+WR_DEVICE void wr_yuv_fetch_tile(WrYuvRow& R, const uint32_t* row, int c0, int ow) {
+  if (R.x0 == c0) return;
+  R.x0 = c0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) R.px[k] = row[wr_iclamp(c0 + k, 0, ow - 1)];
+}
+// piece s of the tile's part -- samples [0, ow) at d -- of a Y row, or of an I444 chroma row (`c`: its coefficients; null: luma)
+WR_DEVICE void wr_yuv_tile_piece(const WrGrabYuvArgs& a, WrYuvRow& R, const uint32_t* row, uint8_t* d, int ow, int s, const int32_t* c) {
+  const int i0 = wr_yuv_first<8, 1>(d, s);
+  if (i0 >= ow || i0 + 8 <= 0) return;
+  wr_yuv_fetch_tile(R, row, i0, ow);
+  uint32_t v[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const uint32_t px = R.px[k];
+    v[k] = c ? wr_yuv_chroma<16>(c, (int)((px >> 16) & 0xFFu), (int)((px >> 8) & 0xFFu), (int)(px & 0xFFu)) : wr_yuv_luma(a, px);
+  }
+  wr_yuv_put<8, 1>(d, i0, ow, v);
+}
+// the tile's level after j halvings (pitch 64 >> j) into the planes L
+template <int FMT> WR_DEVICE void wr_grab_scale_store_yuv(const WrGrabScaleYuvArgs& b, const WrYuvLevel& L, const WrGrabScaleGeom& g, const uint32_t* src, int j, int t) {
+  const WrGrabYuvArgs& a = b.g;
+  const int pitch = WR_SCALE_TILE >> j, lh = b.s.th >> j;
+  const int ox = g.x0 >> j, oy = g.y0 >> j, ow = g.cw >> j, oh = g.ch >> j;
+  const int units = FMT == WR_YUV_I444 ? oh : (oh + 1) >> 1, slots = (ow + 7) / 8 + 1, cow = (ow + 1) >> 1;
+  for (int it = t; it < units * slots; it += 256) {
+    const int u = it / slots, s = it % slots;
+    // the unit's rows in the tile, in the level, and in the image
+    const int ta = FMT == WR_YUV_I444 ? u : 2 * u, tb = wr_imin(ta + 1, oh - 1);
+    const int ia = a.flip ? lh - 1 - (oy + ta) : oy + ta, ib = a.flip ? lh - 1 - (oy + tb) : oy + tb;
+    WrYuvRow A, B;
+    A.row = B.row = nullptr;
+    A.x0 = B.x0 = -0x40000000;      // (nothing fetched yet)
+    const uint32_t* const rowa = src + ta * pitch;
+    const uint32_t* const rowb = src + tb * pitch;
+    wr_yuv_tile_piece(a, A, rowa, L.y + ia * L.y_stride + ox, ow, s, nullptr);
+    if (FMT == WR_YUV_I444) {
+      wr_yuv_tile_piece(a, A, rowa, L.cb + ia * L.c_stride + ox, ow, s, a.ccb);
+      wr_yuv_tile_piece(a, A, rowa, L.cr + ia * L.c_stride + ox, ow, s, a.ccr);
+      continue;
+    }
+    if (tb != ta) wr_yuv_tile_piece(a, B, rowb, L.y + ib * L.y_stride + ox, ow, s, nullptr);
+    const int cr = wr_imin(ia, ib) >> 1;      // (the block's row of the image: rows 2 cr and 2 cr + 1, whichever of them the tile's row ta is)
+    if (FMT == WR_YUV_NV12) {
+      uint8_t* const d = L.cb + cr * L.c_stride + ox;      // (ox is even: ox / 2 pairs)
+      const int i0 = wr_yuv_first<4, 2>(d, s);
+      if (i0 >= cow || i0 + 4 <= 0) continue;
+      wr_yuv_fetch_tile(A, rowa, 2 * i0, ow); wr_yuv_fetch_tile(B, rowb, 2 * i0, ow);
+      uint32_t v[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) v[k] = wr_yuv_chroma420(a.ccb, A, B, k) | (wr_yuv_chroma420(a.ccr, A, B, k) << 8);
+      wr_yuv_put<4, 2>(d, i0, cow, v);
+    } else {
+#pragma unroll
+      for (int plane = 0; plane < 2; plane++) {
+        uint8_t* const d = (plane ? L.cr : L.cb) + cr * L.c_stride + (ox >> 1);
+        const int i0 = wr_yuv_first<4, 1>(d, s);
+        if (i0 >= cow || i0 + 4 <= 0) continue;
+        wr_yuv_fetch_tile(A, rowa, 2 * i0, ow); wr_yuv_fetch_tile(B, rowb, 2 * i0, ow);
+        uint32_t v[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] = wr_yuv_chroma420(plane ? a.ccr : a.ccb, A, B, k);
+        wr_yuv_put<4, 1>(d, i0, cow, v);
+      }
+    }
+  }
+}
+WR_DEVICE void wr_grab_scale_store_yuv_any(const WrGrabScaleYuvArgs& b, const WrGrabScaleGeom& g, const uint32_t* src, int j, int t) {
+  const WrYuvLevel& L = b.lv[j];
+  if (!L.y) return;
+  if (b.g.format == WR_YUV_I420) wr_grab_scale_store_yuv<WR_YUV_I420>(b, L, g, src, j, t);
+  else if (b.g.format == WR_YUV_NV12) wr_grab_scale_store_yuv<WR_YUV_NV12>(b, L, g, src, j, t);
+  else wr_grab_scale_store_yuv<WR_YUV_I444>(b, L, g, src, j, t);
+}
+__global__ void __launch_bounds__(256) wr_grab_scale_yuv_kernel(WrGrabScaleYuvArgs b) {
+  const WrGrabScaleArgs& a = b.s;
+  const WrGrabScaleGeom g = wr_grab_scale_geom(a, (int)blockIdx.x);
+#ifdef WRHIP_HOSTSIM
+  if (threadIdx.x != 0) return;
+  WrGrabScaleTile T;
+#else
+  __shared__ WrGrabScaleTile T;
+  const int t = (int)threadIdx.x;
+#endif
+  WR_SCALE_PHASE(wr_grab_scale_coords(a, g, T, t))
+  WR_SCALE_PHASE(wr_grab_scale_fill(a, g, T, t))
+  uint32_t* from = T.a;
+  uint32_t* to = T.b;
+  for (int k = 0; k < a.steps; k++) {
+    WR_SCALE_PHASE(wr_grab_scale_store_yuv_any(b, g, from, k, t);
+                   wr_grab_scale_halve(from, to, WR_SCALE_TILE >> k, g.cw >> k, g.ch >> k, t))
+    uint32_t* const was = from; from = to; to = was;
+  }
+  WR_SCALE_PHASE(wr_grab_scale_store_yuv_any(b, g, from, a.steps, t);
+                 if (b.rgba) wr_grab_scale_store(a, g, from, WR_SCALE_TILE >> a.steps, t);
+                 if (a.slot && blockIdx.x == 0 && t == 0) wr_grab_st16(a.slot, wr_u4{a.payload, 0u, 0u, 0u}))
+}
+#undef WR_SCALE_PHASE
 // WrhipGrabTextureYuvDelta (include/wrhip.h; WrGrabYuvDeltaArgs): the YUV grab's samples, block by block, and only the blocks whose
 // samples differ from the retained planes.  A workgroup per 64 x 64 block of the image (after the flip), as wr_grab_pack_kernel has
 // it; the YUV grab's item -- eight pixels of a row pair, or of one row of I444 -- tiles the block: 32 row pairs of 8 items are one

@@ -850,6 +850,23 @@ struct WrGrabYuvDeltaArgs {
   int32_t keyframe;                    // every block is sent, entry i is block i (nothing is compared, no atomic)
   int32_t device;                      // sent samples go to g.y, g.cb, g.cr; the slot's entries are records of 16 bytes
 };
+// WrhipGrabTextureYuvScaled: one launch of wr_grab_scale_yuv_kernel (the contract: include/wrhip.h).  `s` is the scaled grab's launch
+// (last, flip, swap_rb unused: a level leaves `s` unflipped; slot: non-null in the launch that writes the ticket's header), `g` the
+// YUV grab's colour rows, y0, format and flip (its rect, planes and texture unused).  The launch holds levels top .. top - s.steps of
+// the chain in LDS, the tile after j halvings being level top - j; lv[j].y non-null: that level is a rendition, and its samples go
+// to the planes lv[j] names -- WrGrabYuvArgs' layout, in the caller's memory or behind the slot's header.  `rgba`: the lowest level
+// is stored to s.dst as pixels, tight rows -- for the next launch, or for wr_grab_yuv_kernel in the one case a tile cannot serve
+// (a flipped 4:2:0 rendition 0 of odd height, whose row pairs straddle tiles).
+struct WrYuvLevel {
+  uint8_t* y; uint8_t* cb; uint8_t* cr;      // NV12: cb is the plane of pairs, cr unused
+  long long y_stride, c_stride;        // bytes per row
+};
+struct WrGrabScaleYuvArgs {
+  WrGrabScaleArgs s;
+  WrGrabYuvArgs g;
+  WrYuvLevel lv[WR_SCALE_STEPS + 1];
+  int32_t rgba;
+};
 struct WrGrabPushArgs {
   const uint8_t* src; uint8_t* dst;    // device slot -> pinned host slot
   uint32_t capacity;                   // of either, bytes (a multiple of 16): the count read from the slot is held to it

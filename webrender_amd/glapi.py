@@ -153,6 +153,7 @@ EXTRA_SIGNATURES = {
     "WrhipGrabTextureYuv": (i32, [u32, P, P]),
     "WrhipGrabTextureYuvDelta": (i32, [u32, P, P, u32]),
     "WrhipGrabDecodeYuv": (i32, [P, u64, u32, i32, i32, P, C.c_int64, P, P, C.c_int64, P, P]),
+    "WrhipGrabTextureYuvScaled": (i32, [u32, P, i32, i32, P, i32]),
 }
 
 
@@ -192,7 +193,7 @@ TENSOR_ELEM_BYTES = {TENSOR_U8: 1, TENSOR_F16: 2, TENSOR_BF16: 2, TENSOR_F32: 4}
 class WrhipGrabInfo(C.Structure):
     _fields_ = [("status", i32), ("format", u32), ("flags", u32), ("nrects", i32), ("rects", (i32 * 4) * GRAB_MAX_RECTS),
                 ("keyframe", u32), ("blocks", u32), ("blocks_total", u32), ("damage", i32 * 4), ("bytes", u64),
-                ("scaled_w", i32), ("scaled_h", i32), ("levels", u32)]
+                ("scaled_w", i32), ("scaled_h", i32), ("levels", u32), ("renditions", u32)]
 
 
 class WrhipTensorDesc(C.Structure):
@@ -231,6 +232,19 @@ def yuv_split(flat, w, h, format):
     assert at == len(flat), (at, len(flat))
     if format == YUV_NV12:
         out[1] = out[1].reshape(out[1].shape[0], -1, 2)
+    return out
+
+
+def yuv_split_renditions(flat, size, renditions, format):
+    """The flat uint8 array a scaled YUV ticket delivers (grab_texture_yuv_scaled to the host) as its renditions: a list of
+    yuv_split's lists, rendition k -- level k of the chain, (size[0] << k) x (size[1] << k) -- at index k; views, not copies"""
+    out, at = [], 0
+    for k in range(renditions):
+        w, h = size[0] << k, size[1] << k
+        n = sum(rows * row for rows, row in yuv_plane_shapes(w, h, format))
+        out.append(yuv_split(flat[at:at + n], w, h, format))
+        at += n
+    assert at == len(flat), (at, len(flat))
     return out
 
 
@@ -413,6 +427,30 @@ class GL:
         d.y_stride, d.c_stride = int(strides[0]), int(strides[1])
         return self.WrhipGrabTextureYuvDelta(tex, C.addressof(arr), C.addressof(d), GRAB_KEY if key is True else int(key))
 
+    def grab_texture_yuv_scaled(self, tex, rect, size, format, color_space, flags=0, renditions=1, dsts=None, strides=None):
+        """Enqueue a scaled YUV grab (include/wrhip.h, WrhipGrabTextureYuvScaled) of `rect` = (x, y, w, h) of the RGBA8 texture id
+        `tex` -- None: all of it -- scaled down to `size` = (width, height) as grab_texture_scaled scales it, as 8-bit planes in
+        `format` of the ranged colour space `color_space`: `renditions` of them, rendition k being level k of the chain, size << k.
+        dsts None: all planes cross to the host, grab_result delivers them flat (yuv_split_renditions cuts them); otherwise one
+        (device address, dst_bytes) per rendition, with strides = one (Y, chroma) pair in bytes per rendition (None: tight).
+        `flags`: 0 or GRAB_FLIP_ROWS.  Returns the ticket, or -1 (GL_INVALID_VALUE / GL_OUT_OF_MEMORY is then set)."""
+        if rect is None:
+            w, h = i32(0), i32(0)
+            if not self.WrhipGetTextureSize(tex, C.byref(w), C.byref(h)):
+                w = h = i32(0)
+            rect = (0, 0, w.value, h.value)
+        arr = (i32 * 4)(*[int(v) for v in rect])
+        n = int(renditions)
+        descs = (WrhipYuvDesc * max(1, n))()
+        for k in range(max(0, min(n, len(descs)))):
+            d = descs[k]
+            d.format, d.color_space, d.flags = int(format), int(color_space), int(flags)
+            if dsts is not None:
+                d.dst, d.dst_bytes = int(dsts[k][0]) or None, int(dsts[k][1])
+            if strides is not None:
+                d.y_stride, d.c_stride = int(strides[k][0]), int(strides[k][1])
+        return self.WrhipGrabTextureYuvScaled(tex, C.addressof(arr), int(size[0]), int(size[1]), C.addressof(descs), n)
+
     def device_alloc(self, nbytes):
         """Device memory for tensor grabs (WrhipDeviceAlloc): its address, 16-byte aligned; 0 with GL_OUT_OF_MEMORY set"""
         return self.WrhipDeviceAlloc(int(nbytes)) or 0
@@ -509,7 +547,7 @@ class GL:
             assert rc == 0, rc
         info = {"status": r.status, "format": r.format, "flags": r.flags, "rects": rects, "keyframe": r.keyframe, "blocks": r.blocks,
                 "blocks_total": r.blocks_total, "damage": tuple(r.damage), "bytes": int(r.bytes),
-                "scaled_w": r.scaled_w, "scaled_h": r.scaled_h, "levels": r.levels}
+                "scaled_w": r.scaled_w, "scaled_h": r.scaled_h, "levels": r.levels, "renditions": r.renditions}
         return info, pixels
 
     def grab_payload(self, ticket, wait=True):

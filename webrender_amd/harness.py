@@ -294,7 +294,7 @@ def render_streamed_tensors(backend_path, frames, size, dtype, layout, channels,
     return out, stats, infos
 
 
-def render_streamed_yuv(backend_path, frames, format, color_space, device=False, flags=0, delta=False, key_every=None):
+def render_streamed_yuv(backend_path, frames, format, color_space, device=False, flags=0, delta=False, key_every=None, scale_to=None, renditions=1):
     """render_streamed_grabbed for a video encoder: after each frame's render the whole window is YUV-grabbed (GL.grab_texture_yuv:
     one launch in stream order behind that frame, 8-bit planes in `format` of the ranged colour space `color_space`) -- nothing
     between the frames drains the held-back raster launches, no Finish.  Frame k's ticket is fetched after frame k + 1 has been
@@ -306,7 +306,9 @@ def render_streamed_yuv(backend_path, frames, format, color_space, device=False,
     delta=True: a delta YUV grab per frame (GL.grab_texture_yuv_delta) into ONE set of planes that lives across the frames -- a flat
     host array the tickets' blocks are patched into, or one device buffer the blocks are written to -- so only the 64 x 64 blocks
     whose samples changed cross or are written; the planes returned for frame k are a copy of the accumulated ones once frame k's
-    ticket has been fetched (device: read back then, while frame k + 1's grab is still parked).  key_every=N: every N-th grab passes GRAB_KEY."""
+    ticket has been fetched (device: read back then, while frame k + 1's grab is still parked).  key_every=N: every N-th grab passes GRAB_KEY.
+    scale_to=(w, h) (without delta): every grab is the scaled one (GL.grab_texture_yuv_scaled) with `renditions` renditions -- levels
+    0 .. renditions - 1 of the chain to scale_to -- and a frame's planes are glapi.yuv_split_renditions' list of them."""
     from . import glapi
     gl = GL(backend_path)
     assert gl.is_wrhip, "render_streamed_yuv: grabs are a libwrhip addition"
@@ -315,7 +317,13 @@ def render_streamed_yuv(backend_path, frames, format, color_space, device=False,
     window = gl.WrhipGetFramebufferTexture(0)
     nbytes = sum(rows * row for rows, row in glapi.yuv_plane_shapes(w, h, format))
     if delta:
+        assert scale_to is None, "render_streamed_yuv: a scaled YUV grab is a full one"
         return _render_streamed_yuv_delta(gl, r, window, frames, format, color_space, device, flags, key_every, nbytes)
+    # (scaled: rendition k is scale_to << k; a frame's renditions lie one after another, on the host and in the frame's device buffer)
+    sizes = [(scale_to[0] << k, scale_to[1] << k) for k in range(renditions)] if scale_to is not None else []
+    each = [sum(rows * row for rows, row in glapi.yuv_plane_shapes(sw, sh, format)) for sw, sh in sizes]
+    if scale_to is not None:
+        nbytes = sum(each)
     bufs = [gl.device_alloc(nbytes) for _ in frames] if device else []
     assert all(bufs), gl.GetError()
     tickets, flats, infos = [], [], []
@@ -327,8 +335,12 @@ def render_streamed_yuv(backend_path, frames, format, color_space, device=False,
     for k, f in enumerate(frames):
         assert (f.width, f.height) == (w, h), "render_streamed_yuv: one window size"
         r.render(f)
-        t = gl.grab_texture_yuv(window, (0, 0, w, h), format, color_space, flags, dst=bufs[k] if device else None,
-                                dst_bytes=nbytes if device else 0)
+        if scale_to is not None:
+            dsts = [(bufs[k] + sum(each[:i]), each[i]) for i in range(renditions)] if device else None
+            t = gl.grab_texture_yuv_scaled(window, (0, 0, w, h), scale_to, format, color_space, flags, renditions=renditions, dsts=dsts)
+        else:
+            t = gl.grab_texture_yuv(window, (0, 0, w, h), format, color_space, flags, dst=bufs[k] if device else None,
+                                    dst_bytes=nbytes if device else 0)
         assert t >= 0, (t, gl.GetError())
         tickets.append(t)
         if k >= 1:
@@ -343,6 +355,8 @@ def render_streamed_yuv(backend_path, frames, format, color_space, device=False,
             gl.device_free(b)
     r.finish()
     r.destroy()
+    if scale_to is not None:
+        return [glapi.yuv_split_renditions(fl, scale_to, renditions, format) for fl in flats], stats, infos
     return [glapi.yuv_split(fl, w, h, format) for fl in flats], stats, infos
 
 
