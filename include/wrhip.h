@@ -252,7 +252,7 @@ void WrhipSetProfiling(int enabled);
  * (picture targets of a few large gradient / image prims, likewise), 11 = wr_setup_tile_rows_kernel (10 fused with the next flush's setup stage), 12 = a thin launch of the raster kernel (13: the same with the next flush's setup stage in front, wr_setup_raster_thin_kernel) (wr_raster_kernel<fmt, false, 1, feat>:
  * small levels, several workgroups per bin), 14 = wr_tap_kernel (WrhipTapTexture: fmt of the tapped texture, feat 1 against an expected texture;
  * algo_bytes: the rect's bytes, twice with an expected texture), 15 = wr_grab_pack_kernel (WrhipGrabTexture: fmt of the grabbed texture,
- * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta, feat 3: wr_grab_scale_kernel, the launches of one WrhipGrabTextureScaled, feat 4: wr_grab_tensor_kernel or the launches of a scaled WrhipGrabTextureTensor, feat 5: wr_grab_yuv_kernel, a WrhipGrabTextureYuv (the rect read once plus the planes written), feat 6: wr_grab_yuv_delta_kernel, a WrhipGrabTextureYuvDelta (the rect plus the retained planes; what its sent blocks write is not known at the launch, as for feat 1), feat 7: wr_grab_scale_yuv_kernel, the launches of one WrhipGrabTextureYuvScaled (the rect read once plus the planes of every rendition written); algo_bytes: bytes read plus bytes written, as far as they are known at the launch), 16 = wr_put_tensor_kernel (WrhipPutTextureTensor: fmt of the texture written;
+ * feat 1 in delta mode, feat 2: wr_grab_pack_runs_kernel, a WRHIP_GRAB_PACKED delta, feat 3: wr_grab_scale_kernel, the launches of one WrhipGrabTextureScaled, feat 4: wr_grab_tensor_kernel or the launches of a scaled WrhipGrabTextureTensor, feat 5: wr_grab_yuv_kernel, a WrhipGrabTextureYuv (the rect read once plus the planes written), feat 6: wr_grab_yuv_delta_kernel, a WrhipGrabTextureYuvDelta (the rect plus the retained planes; what its sent blocks write is not known at the launch, as for feat 1), feat 7: wr_grab_scale_yuv_kernel, the launches of one WrhipGrabTextureYuvScaled (the rect read once plus the planes of every rendition written), feat 8: wr_grab_scroll_*_kernel, the WRHIP_GRAB_SCROLL_LAUNCHES launches of one scroll grab that is no keyframe as one entry (the rect plus the retained copy, as for feat 2); algo_bytes: bytes read plus bytes written, as far as they are known at the launch), 16 = wr_put_tensor_kernel (WrhipPutTextureTensor: fmt of the texture written;
  * algo_bytes: the elements read plus the rect's bytes written).  algo_bytes: the launch's algorithmic bytes:
  * raster launches count every destination pixel they own once (twice when the target's old content is loaded) plus
  * the source texels their draws can sample; the setup stage counts instance + descriptor + record bytes.  Returns the
@@ -389,6 +389,38 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  *                   bytes); then zero bytes to the next multiple of 16.
  *   A tie between RUNS and RAW goes to RAW: a full RGBA8 block is RUNS up to n = 3964 and RAW from 3965, a full R8 block RUNS up
  *   to n = 3568 and RAW from 3569.  No entry is larger than a plain delta entry, so slots are sized as for a plain delta grab.
+ *
+ * THE SCROLL GRAB (WRHIP_GRAB_DELTA | WRHIP_GRAB_PACKED | WRHIP_GRAB_SCROLL, with or without KEY; GL_RGBA8 and GL_R8): a packed delta
+ *   grab that first finds the one vertical scroll most of the changed content made, and sends a block that is found that many rows
+ *   away in the retained copy as a 16-byte COPY entry: "take it from your own image".  SCROLL in any other combination -- without
+ *   DELTA, without PACKED, with FLIP_ROWS / SWAP_RB, on the scaled, tensor and YUV calls -- is -1 with GL_INVALID_VALUE, nothing
+ *   launched.  It uses the plain and packed delta grabs' retained copy under the same validity rules and keeps no other state, so
+ *   plain, packed and scroll delta grabs of one texture and rect may alternate in any order without a keyframe.  A keyframe is the
+ *   packed grab's (one launch, scroll_dy 0, no COPY entry); any other scroll grab is WRHIP_GRAB_SCROLL_LAUNCHES launches on the draw
+ *   stream.  The contract -- any restatement must give the same bytes, up to the order of the entries:
+ *   prev is the retained copy, cur the rect's stored bytes, h the rect's height; a segment (r, c) is the bytes of rect row r inside
+ *   block column c; D = min(WRHIP_GRAB_SCROLL_MAX, h - 1).
+ *   vector    for 1 <= |dy| <= D, votes(dy) = the number of segments (r, c) with 0 <= r + dy < h, cur(r, c) != prev(r, c) and
+ *             cur(r, c) == prev(r + dy, c).  scroll_dy is the dy with the most votes; ties go to the smaller |dy|, then to the
+ *             positive dy; 0 if no dy has a vote.  Positive: the content moved up, a block's pixels are dy rows further DOWN in the
+ *             previous image.  One vector per grab, vertical only.  FOR THE VOTE ONLY the library decides segment equality by a
+ *             64-bit hash of the segment's bytes: the rule holds up to hash collisions, which can cost a COPY entry, never a pixel.
+ *   blocks    decided by exact byte comparison: a block equal to prev at its own place is not sent; otherwise it is a COPY entry if
+ *             scroll_dy != 0, its source rows lie inside the rect (0 <= y + dy, y + dy + block_h <= h) and it equals prev at
+ *             (x, y + dy); otherwise SOLID / RUNS / RAW by the packed rule.  The retained copy equals cur after the grab.
+ *   wire      header word 1 is scroll_dy as a two's-complement int32 (0 in every other grab's header).  COPY is mode 3: record x, y,
+ *             w | h << 8 | 3 << 16, aux 0, no body.  `blocks` counts all entries, `copied` the COPY ones, `damage` bounds all of
+ *             them, `bytes` = 16 + the entries' sizes: an unchanged frame crosses 16 bytes, a scrolled one 16 + 16 * copied + the
+ *             entries of the exposed strip.
+ *   decoding  (WrhipGrabResultGet into the caller's image, WrhipGrabDecode with the grab's flags) is in place, without a snapshot: a
+ *             COPY block holds the pixels the image had BEFORE the decode at (x, y + dy), other entries are patched as ever, nothing
+ *             else is touched.  All COPY entries are applied first -- by ascending y for dy > 0, descending y for dy < 0; block
+ *             columns are independent of each other --, every other entry after them; entries arrive in any order and the decoder
+ *             orders them itself.  Malformed, WrhipGrabDecode -1 with nothing written: a COPY entry with dy == 0, |dy| >
+ *             WRHIP_GRAB_SCROLL_MAX, a COPY source outside the rect, a COPY record with a non-zero aux, one that is not a whole
+ *             block of the rect or names a block twice, mode 3 or a non-zero header word 1 when `flags` lacks SCROLL.
+ *   Not supported: horizontal or per-region vectors, COPY of a block whose source is partly outside the rect, scroll detection for
+ *   WrhipGrabTextureYuvDelta, sharded targets.
  *
  * WrhipGrabTextureScaled(tex, rect, dst_w, dst_h, flags): a grab of ONE rect (x, y, w, h) of a GL_RGBA8 texture scaled down to
  * dst_w x dst_h (1 <= dst_w <= w, 1 <= dst_h <= h), byte for byte what the reference's screenshot chain (webrender's
@@ -631,6 +663,9 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
 #define WRHIP_GRAB_SCALED    64u  /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureScaled ticket; no flag of WrhipGrabTexture, which rejects it */
 #define WRHIP_GRAB_TENSOR    128u /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureTensor ticket; no flag of the other grab calls, which reject it */
 #define WRHIP_GRAB_YUV       512u /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureYuv, (with DELTA) WrhipGrabTextureYuvDelta or (with SCALED) WrhipGrabTextureYuvScaled ticket; rejected by the other grab calls */
+#define WRHIP_GRAB_SCROLL    1024u /* with DELTA | PACKED (with or without KEY): find the vertical scroll, send scrolled blocks as COPY entries (the scroll grab above); rejected in every other combination and by the other grab calls */
+#define WRHIP_GRAB_SCROLL_MAX 512      /* the largest |scroll_dy| that is looked for */
+#define WRHIP_GRAB_SCROLL_LAUNCHES 4   /* launches on the draw stream of a scroll grab that is no keyframe: probe, vote, pack, update */
 #define WRHIP_YUV_I420 0u         /* WrhipYuvDesc::format: Y plane, Cb plane, Cr plane; chroma 4:2:0 */
 #define WRHIP_YUV_NV12 1u         /* Y plane, one plane of interleaved Cb,Cr pairs; chroma 4:2:0 */
 #define WRHIP_YUV_I444 2u         /* Y, Cb, Cr planes, all w x h */
@@ -654,6 +689,8 @@ typedef struct WrhipGrabInfo {
   int32_t  scaled_w, scaled_h;     /* WrhipGrabTextureScaled: the delivered size; 0 for other grabs */
   uint32_t levels;                 /* WrhipGrabTextureScaled: L, the 2:1 steps below the top step */
   uint32_t renditions;             /* WrhipGrabTextureYuvScaled: n, the levels delivered; 0 for other grabs */
+  int32_t  scroll_dy;              /* WRHIP_GRAB_SCROLL: the scroll vector (header word 1); 0 for other grabs and for a keyframe */
+  uint32_t copied;                 /* WRHIP_GRAB_SCROLL: the COPY entries among `blocks`; 0 for other grabs */
 } WrhipGrabInfo;
 int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint32_t flags);
 int32_t WrhipGrabTextureScaled(GLuint tex, const int32_t rect[4], int32_t dst_w, int32_t dst_h, uint32_t flags);

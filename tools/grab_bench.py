@@ -33,10 +33,14 @@
              clock, the new call's launches by hipEvents (kind 15 feat 7); the 1080p / 540p / 270p ladder as one call of three
              renditions against three calls of one; 3840 x 2158 -> 1920 x 1079 I420 with and without FLIP_ROWS (the two routes of
              rendition 0); then cfg2 streamed: no grab, a full-size NV12 grab per frame, a scaled NV12 grab per frame
+  scroll     WRHIP_GRAB_SCROLL on a 4K window onto a tall page of noise: the grab's launches (kind 15 feat 8, one entry) beside the one
+             launch of DELTA | PACKED on the same frames -- nothing changed, 40 blocks changed, a scroll by 37, both -- with the bytes
+             crossed; then 200 frames each scrolled by 37, a grab per frame patched into the caller's image, against DELTA | PACKED and
+             no grab.  --scroll-case CASE runs one case's scroll grabs alone for a profiler's kernel trace (the launches one by one)
   ab         plain bench.py against another build of the library (WRHIP_LIB_PATH), alternated, no grab issued
 
 Every section runs three alternated rounds.  Needs the GPU: there is no fallback.
-  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor,put,yuv,yuv_delta,yuv_scaled] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
+  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor,put,yuv,yuv_delta,yuv_scaled,scroll] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -1108,6 +1112,119 @@ def section_yuv_delta_stream(lib, frames):
     say(f"  (a full I420 payload is {payload / 1e6:.2f} MB; a static delta grab crosses 16 bytes)")
 
 
+# ---- scroll grabs (WRHIP_GRAB_SCROLL) ----------------------------------------------------------------------
+SCROLL_CASES = ("nothing changed", "40 blocks changed", "scroll by 37", "scroll by 37, 40 blocks changed")
+
+
+def _scroll_frame(w, page, case, k, some, patches):
+    """Frame k of a case: the window shows rows [37 * k, 37 * k + H) of the page when the case scrolls; 40 blocks get a 16 x 16 patch"""
+    gl = w.gl
+    if case.startswith("scroll"):
+        w.upload(0, 0, page[37 * k:37 * k + H])
+    if case.endswith("40 blocks changed"):
+        for b in some:
+            w.upload(int(b % (W // 64)) * 64 + 5, int(b // (W // 64)) * 64 + 3, patches[k & 1])
+    gl.WrhipFlush()
+
+
+def section_scroll_kernel(lib, only=None, n=10):
+    """(a): every case with DELTA | PACKED | SCROLL and with DELTA | PACKED on the same frames; `only`: that case alone, with the scroll
+    grab alone and no event profiling -- for a kernel trace by a profiler, which gives the four launches one by one"""
+    say(f"## scroll: {W}x{H} RGBA8 window onto a page of noise, {n} grabs per case, hipEvents (WrhipSetProfiling(1)), us per grab (all its launches)")
+    w = Window(lib)
+    gl = w.gl
+    DP = glapi.GRAB_DELTA | glapi.GRAB_PACKED
+    DPS = DP | glapi.GRAB_SCROLL
+    rng = np.random.default_rng(3)
+    page = rng.integers(0, 256, (H + 37 * n, W, 4), dtype=np.uint8)
+    nblocks = ((W + 63) // 64) * ((H + 63) // 64)
+    some = rng.choice(nblocks, size=40, replace=False)
+    patches = [rng.integers(0, 256, (16, 16, 4), dtype=np.uint8) for _ in range(2)]
+    rows = {}
+    for rnd in range(1 if only else ROUNDS):
+        for case in SCROLL_CASES:
+            if only and case != only:
+                continue
+            for name, flags in (("scroll", DPS), ("packed", DP)):
+                if only and name != "scroll":
+                    continue
+                w.upload(0, 0, page[:H])
+                for b in some:          # (the patched places hold a patch from the start: every frame changes exactly these blocks)
+                    w.upload(int(b % (W // 64)) * 64 + 5, int(b // (W // 64)) * 64 + 3, patches[1])
+                w.grab(flags | glapi.GRAB_KEY)
+                w.grab(flags)           # (untimed: code objects, the work memory)
+                gl.WrhipSetProfiling(0 if only else 1)
+                gl.WrhipResetStats()
+                infos = []
+                for k in range(1, n + 1):
+                    _scroll_frame(w, page, case, k, some, patches)
+                    infos.append(w.grab(flags))
+                ks = kernel_stats(gl, 15)
+                gl.WrhipSetProfiling(0)
+                if only:
+                    continue
+                feat = 8 if flags & glapi.GRAB_SCROLL else 2
+                assert len(ks) == 1 and ks[0].launches == n and ks[0].feat == feat, [(k.kind, k.feat, k.launches) for k in ks]
+                last = infos[-1]
+                rows.setdefault((case, name), []).append((ks[0].ns / n / 1e3, int(last.blocks), int(last.copied), int(last.bytes), int(last.scroll_dy)))
+    for (case, name), v in rows.items():
+        say(f"  {case:32s} {name:7s} " + "  ".join(f"{us:8.1f}" for us, _, _, _, _ in v) +
+            f"   us   (scroll_dy {v[0][4]}; entries {v[0][1]} of {nblocks}, {v[0][2]} of them COPY; {v[0][3]} bytes crossed)")
+    w.close()
+
+
+def section_scroll_stream(lib, frames):
+    say(f"## scroll stream: {frames} frames, each the page scrolled by 37 (one TexSubImage2D of the window per frame), one grab per frame patched into the caller's image, frames/s")
+    w = Window(lib)
+    gl = w.gl
+    DP = glapi.GRAB_DELTA | glapi.GRAB_PACKED
+    page = np.random.default_rng(4).integers(0, 256, (H + 37 * frames, W, 4), dtype=np.uint8)
+    host = np.zeros((H, W, 4), np.uint8)
+    info = glapi.WrhipGrabInfo()
+
+    def run(flags, n):
+        waiting, crossed = [], []
+
+        def fetch(wait):
+            while waiting:
+                rc = gl.WrhipGrabResultGet(waiting[0], C.byref(info), host.ctypes.data, 0, 1 if wait else 0)
+                if rc == 1:
+                    return
+                assert rc == 0 and info.status == 0, (rc, info.status)
+                waiting.pop(0)
+                crossed.append(int(info.bytes))
+                wait = False
+        w.upload(0, 0, page[:H])
+        if flags is not None:
+            assert gl.WrhipGrabResultGet(gl.grab_texture(w.tex, None, flags | glapi.GRAB_KEY), C.byref(info), host.ctypes.data, 0, 1) == 0
+        gl.Finish()
+        t0 = time.perf_counter()
+        for k in range(1, n + 1):
+            w.upload(0, 0, page[37 * k:37 * k + H])
+            if flags is not None:
+                if len(waiting) == 8:
+                    fetch(True)
+                t = gl.grab_texture(w.tex, None, flags)
+                assert t >= 0
+                waiting.append(t)
+                fetch(False)
+        gl.Finish()
+        while waiting:
+            fetch(True)
+        dt = time.perf_counter() - t0
+        assert flags is None or np.array_equal(host, page[37 * n:37 * n + H]), "the patched image is not the window"
+        return n / dt, float(np.mean(crossed)) if crossed else 0.0
+    modes = {"no grab": None, "packed delta grab": DP, "scroll grab": DP | glapi.GRAB_SCROLL}
+    for flags in modes.values():
+        run(flags, 10)
+    rows = {}
+    for rnd in range(ROUNDS):
+        for name, flags in modes.items():
+            rows.setdefault(name, []).append(run(flags, frames))
+    for name, v in rows.items():
+        say(f"  {name:22s} " + "  ".join(f"{fps:9.1f}" for fps, _ in v) + "   frames/s   " + (f"({v[0][1] / 1e6:8.3f} MB per frame crossed)" if v[0][1] else ""))
+
+
 def section_ab(other, steps, warmup):
     say(f"## ab: bench.py --gpus 1 --steps {steps} --warmup {warmup} (cfg2), this library against {os.path.basename(other)}, alternated, frames/s")
     rows = {"parent": [], "this": []}
@@ -1140,6 +1257,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--size", default=None, metavar="WxH", help="another window size (the figures of DESIGN.md are for the default, 3840x2160)")
+    ap.add_argument("--scroll-case", default=None, choices=SCROLL_CASES, help="section scroll: this case's scroll grabs alone, unprofiled (for a profiler's kernel trace)")
     args = ap.parse_args()
     global ROUNDS, W, H
     ROUNDS = args.rounds
@@ -1186,6 +1304,10 @@ def main():
             elif s == "yuv_scaled":
                 section_yuv_scaled(lib)
                 section_yuv_scaled_stream(lib, args.frames)
+            elif s == "scroll":
+                section_scroll_kernel(lib, only=args.scroll_case)
+                if not args.scroll_case:
+                    section_scroll_stream(lib, args.frames)
             elif s == "tensor_parent":        # (run by `tensor` with WRHIP_LIB_PATH set: the parent path alone, on that library)
                 section_tensor_scaled(lib, with_tensor=False)
                 section_tensor_stream(lib, args.frames, with_tensor=False)

@@ -12,15 +12,22 @@
 //                    to the next multiple of 16
 //           Pixel i of the cut block in row-major order starts a run if i == 0 or its value differs from pixel i - 1's.  One run
 //           start: SOLID; otherwise RUNS if that entry is smaller than a RAW one, else RAW.
+//   scroll  (WRHIP_GRAB_SCROLL) a packed payload whose header word 1 is dy, the scroll vector (int32, |dy| <= 512), and that may hold
+//           COPY  3  aux 0; no body: the block -- one of the rect's 64 x 64 blocks, cut to it -- takes the pixels the image had
+//                    BEFORE the decode dy rows further down (y + dy; the source rows lie inside the rect).  dy is not 0 then.
+//           The decode is in place: the COPY entries first, by ascending y for dy > 0 and descending y for dy < 0 -- a block's
+//           source rows are then still the old ones --, every other entry after them.
 #ifndef WR_GRAB_CODEC_H
 #define WR_GRAB_CODEC_H
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #define WR_GC_HEADER 16
 #define WR_GC_BLOCK 64
-enum { WR_GC_RAW = 0, WR_GC_SOLID = 1, WR_GC_RUNS = 2 };
+#define WR_GC_SCROLL_MAX 512
+enum { WR_GC_RAW = 0, WR_GC_SOLID = 1, WR_GC_RUNS = 2, WR_GC_COPY = 3 };
 
 struct WrGrabEntry {
   int32_t x, y, w, h;      // the block, relative to the rect
@@ -42,15 +49,27 @@ static inline uint64_t wr_gc_load64(const uint8_t* p) { return (uint64_t)wr_gc_l
 
 // The entry at `p`, of which `avail` bytes belong to the payload, against a rect of rw x rh: false if its record or its body is
 // not one the format allows or does not fit.  Everything wr_gc_patch relies on is checked here.
-static inline bool wr_gc_entry(const uint8_t* p, size_t avail, int bpp, bool packed, int rw, int rh, WrGrabEntry* E, bool checked = false) {
+// scroll: the payload is a scroll grab's, dy its header word 1 -- a COPY entry is allowed, and checked against dy.
+static inline bool wr_gc_entry(const uint8_t* p, size_t avail, int bpp, bool packed, int rw, int rh, WrGrabEntry* E, bool checked = false,
+                               bool scroll = false, int32_t dy = 0) {
   if (avail < 16) return false;
   const uint32_t w0 = wr_gc_load32(p), w1 = wr_gc_load32(p + 4), w2 = wr_gc_load32(p + 8), w3 = wr_gc_load32(p + 12);
   uint32_t w, h, mode = WR_GC_RAW, aux = 0;
   if (packed) { w = w2 & 0xFFu; h = (w2 >> 8) & 0xFFu; mode = w2 >> 16; aux = w3; }
   else { w = w2; h = w3; }
-  if (w < 1 || h < 1 || w > WR_GC_BLOCK || h > WR_GC_BLOCK || mode > WR_GC_RUNS) return false;
+  if (w < 1 || h < 1 || w > WR_GC_BLOCK || h > WR_GC_BLOCK || mode > (scroll && packed ? WR_GC_COPY : WR_GC_RUNS)) return false;
   if (w > (uint32_t)rw || h > (uint32_t)rh || w0 > (uint32_t)rw - w || w1 > (uint32_t)rh - h) return false;
   E->x = (int32_t)w0; E->y = (int32_t)w1; E->w = (int32_t)w; E->h = (int32_t)h; E->mode = (int32_t)mode; E->aux = aux;
+  if (mode == WR_GC_COPY) {
+    // one of the rect's blocks, whole; its source rows inside the rect
+    if (aux != 0 || dy == 0 || dy < -WR_GC_SCROLL_MAX || dy > WR_GC_SCROLL_MAX) return false;
+    if (w0 % WR_GC_BLOCK || w1 % WR_GC_BLOCK) return false;
+    if (w != ((uint32_t)rw - w0 < WR_GC_BLOCK ? (uint32_t)rw - w0 : WR_GC_BLOCK) || h != ((uint32_t)rh - w1 < WR_GC_BLOCK ? (uint32_t)rh - w1 : WR_GC_BLOCK)) return false;
+    const int64_t sy = (int64_t)w1 + dy;
+    if (sy < 0 || sy + (int64_t)h > (int64_t)rh) return false;
+    E->size = 16;
+    return true;
+  }
   if (mode == WR_GC_SOLID) { E->size = 16; return true; }
   if (mode == WR_GC_RAW) { E->size = wr_gc_raw_size(bpp); return E->size <= avail; }
   const uint32_t n = aux;
@@ -104,12 +123,35 @@ static inline void wr_gc_patch(const uint8_t* p, const WrGrabEntry& E, int bpp, 
   }
 }
 
+// The COPY entries of a scroll payload in the order they are applied in: by y, ascending; a decoder walks them from the first on
+// for dy > 0 and from the last on for dy < 0.  false: two of them name one block.
+struct WrGrabCopy { int32_t x, y, w, h; };
+static inline int wr_gc_copy_cmp(const void* a, const void* b) {
+  const WrGrabCopy* p = (const WrGrabCopy*)a; const WrGrabCopy* q = (const WrGrabCopy*)b;
+  if (p->y != q->y) return p->y < q->y ? -1 : 1;
+  return p->x < q->x ? -1 : p->x > q->x ? 1 : 0;
+}
+static inline bool wr_gc_copy_order(WrGrabCopy* c, size_t n) {
+  if (n > 1) qsort(c, n, sizeof(WrGrabCopy), wr_gc_copy_cmp);
+  for (size_t i = 1; i < n; i++) if (c[i].x == c[i - 1].x && c[i].y == c[i - 1].y) return false;
+  return true;
+}
+// one COPY entry in place: the rows in the order in which a row's source has not been written yet
+static inline void wr_gc_copy(const WrGrabCopy& E, int32_t dy, int bpp, uint8_t* dst, size_t ds) {
+  const size_t row = (size_t)E.w * bpp;
+  for (int i = 0; i < E.h; i++) {
+    const int r = dy > 0 ? i : E.h - 1 - i;
+    memcpy(dst + (size_t)(E.y + r) * ds + (size_t)E.x * bpp, dst + (size_t)(E.y + r + dy) * ds + (size_t)E.x * bpp, row);
+  }
+}
 // A whole payload (`payload`: its header; `bytes`: what the caller holds of it) patched into `dst`: 0, with the bounding box of the
 // entries' blocks and their number, or -1 for a malformed one -- nothing is written then: every entry is checked before the first
-// is patched.
+// is patched.  scroll: a scroll grab's payload (header word 1: dy; COPY entries); any other payload's header word 1 is 0.
 static inline int wr_gc_decode(const void* payload, uint64_t bytes, int bpp, bool packed, int rw, int rh, void* dst, int64_t dst_stride,
-                               int32_t damage[4], uint32_t* blocks) {
-  if (!payload || bytes < WR_GC_HEADER || (bpp != 1 && bpp != 4) || rw < 1 || rh < 1) return -1;
+                               int32_t damage[4], uint32_t* blocks, bool scroll = false, uint32_t* copied = nullptr) {
+  if (!payload || bytes < WR_GC_HEADER || (bpp != 1 && bpp != 4) || rw < 1 || rh < 1 || (scroll && !packed)) return -1;
+  const int32_t dy = (int32_t)wr_gc_load32((const uint8_t*)payload + 4);
+  if (scroll ? dy < -WR_GC_SCROLL_MAX || dy > WR_GC_SCROLL_MAX : dy != 0) return -1;
   const int64_t tight = (int64_t)rw * bpp;
   if (dst && dst_stride != 0 && dst_stride < tight) return -1;
   const uint8_t* p = (const uint8_t*)payload;
@@ -118,19 +160,35 @@ static inline int wr_gc_decode(const void* payload, uint64_t bytes, int bpp, boo
   p += WR_GC_HEADER;
   int x0 = rw, y0 = rh, x1 = 0, y1 = 0;
   uint32_t n = 0;
+  size_t ncopy = 0;
   WrGrabEntry E;
   for (size_t at = 0; at < count; at += E.size, n++) {
-    if (!wr_gc_entry(p + at, (size_t)(count - at), bpp, packed, rw, rh, &E)) return -1;
+    if (!wr_gc_entry(p + at, (size_t)(count - at), bpp, packed, rw, rh, &E, false, scroll, dy)) return -1;
+    if (E.mode == WR_GC_COPY) ncopy++;
     x0 = E.x < x0 ? E.x : x0; y0 = E.y < y0 ? E.y : y0;
     x1 = E.x + E.w > x1 ? E.x + E.w : x1; y1 = E.y + E.h > y1 ? E.y + E.h : y1;
   }
-  if (dst) {
-    const size_t ds = dst_stride ? (size_t)dst_stride : (size_t)tight;
+  const size_t ds = dst_stride ? (size_t)dst_stride : (size_t)tight;
+  if (ncopy) {
+    // (two COPY entries of one block are refused whether or not anything is patched)
+    WrGrabCopy* copies = (WrGrabCopy*)malloc(ncopy * sizeof(WrGrabCopy));
+    if (!copies) return -1;
+    size_t k = 0;
     for (size_t at = 0; at < count; at += E.size) {
-      wr_gc_entry(p + at, (size_t)(count - at), bpp, packed, rw, rh, &E, true);
-      wr_gc_patch(p + at, E, bpp, (uint8_t*)dst, ds);
+      wr_gc_entry(p + at, (size_t)(count - at), bpp, packed, rw, rh, &E, true, scroll, dy);
+      if (E.mode == WR_GC_COPY) copies[k++] = WrGrabCopy{E.x, E.y, E.w, E.h};
+    }
+    if (!wr_gc_copy_order(copies, ncopy)) { free(copies); return -1; }
+    if (dst) for (size_t i = 0; i < ncopy; i++) wr_gc_copy(copies[dy > 0 ? i : ncopy - 1 - i], dy, bpp, (uint8_t*)dst, ds);
+    free(copies);
+  }
+  if (dst) {
+    for (size_t at = 0; at < count; at += E.size) {
+      wr_gc_entry(p + at, (size_t)(count - at), bpp, packed, rw, rh, &E, true, scroll, dy);
+      if (E.mode != WR_GC_COPY) wr_gc_patch(p + at, E, bpp, (uint8_t*)dst, ds);
     }
   }
+  if (copied) *copied = (uint32_t)ncopy;
   if (damage) {
     damage[0] = damage[1] = damage[2] = damage[3] = 0;
     if (x1 > x0 && y1 > y0) { damage[0] = x0; damage[1] = y0; damage[2] = x1 - x0; damage[3] = y1 - y0; }
@@ -253,5 +311,11 @@ static inline size_t wr_gc_encode_block(const uint8_t* px, size_t stride, int x,
       if ((bitmap[r] >> c) & 1ull) { memcpy(lit, px + (size_t)r * stride + (size_t)c * bpp, (size_t)bpp); lit += bpp; }
   }
   return size;
+}
+// The COPY entry of a cut block at (x, y) of the rect (a scroll grab's payload), written to `out`: -> its size
+static inline size_t wr_gc_encode_copy(int x, int y, int w, int h, uint8_t* out) {
+  wr_gc_store32(out, (uint32_t)x); wr_gc_store32(out + 4, (uint32_t)y);
+  wr_gc_store32(out + 8, (uint32_t)w | (uint32_t)h << 8 | (uint32_t)WR_GC_COPY << 16); wr_gc_store32(out + 12, 0u);
+  return 16;
 }
 #endif

@@ -703,6 +703,8 @@ struct Context {
   std::vector<std::pair<void*, size_t>> grab_keep_dead;      // retained copies replaced while a parked grab may still name them
   void* grab_scale_scratch = nullptr;              // the levels a scaled grab of more than WR_SCALE_STEPS halvings passes from launch to
   size_t grab_scale_scratch_size = 0;              // launch (pool storage, grown on demand; every user is on `stream`, one after the other)
+  void* grab_scroll_work = nullptr;                // WRHIP_GRAB_SCROLL: the work memory of one grab's launches (WrGrabScrollArgs; pool storage,
+  size_t grab_scroll_work_size = 0;                // grown on demand, every user on `stream`); nothing in it is read by a later grab
   wr_stream_t grab_stream;
   bool grab_ready = false;
   size_t grab_pinned_max = (size_t)512 << 20;      // WRHIP_GRAB_PINNED_MAX, bytes
@@ -1352,6 +1354,7 @@ Context::~Context() {
   }
   for (auto& kd : grab_keep_dead) wrrt::dev_free(kd.first);
   wrrt::dev_free(grab_scale_scratch);
+  wrrt::dev_free(grab_scroll_work);
   wrrt::event_destroy(ev_a); wrrt::event_destroy(ev_b);
   wrrt::event_destroy(ev_copy);
   for (RingFence& f : ring_fence) if (f.made) wrrt::event_destroy(f.ev);
@@ -1678,6 +1681,12 @@ static void grab_push(Context::GrabSlot& gs, uint32_t payload, bool by_kernel) {
 #endif
   gs.parked = false;
 }
+// the work memory of a scroll grab (WrGrabScrollArgs): two hashes per segment, a mask per block, the votes
+static_assert(WR_GRAB_SCROLL_MAX == WRHIP_GRAB_SCROLL_MAX && WR_GC_SCROLL_MAX == WRHIP_GRAB_SCROLL_MAX, "one bound of the scroll vector");
+static size_t grab_scroll_segments(int bx, int h) { return (size_t)bx * (size_t)h; }
+static size_t grab_scroll_work_need(int bx, int by, int h) {
+  return (2 * grab_scroll_segments(bx, h) + (size_t)bx * by) * 8 + (2 * WR_GRAB_SCROLL_MAX + 1) * 4;
+}
 // One grab, now: the pack on the draw stream -- behind the transport of the slot's previous ticket --, the transport on the grab
 // stream behind the pack, the ticket's event behind the transport.  Enqueued through the submit thread; nothing here waits.
 void grab_issue(uint64_t n, const WrGrabArgs& a) {
@@ -1690,6 +1699,29 @@ void grab_issue(uint64_t n, const WrGrabArgs& a) {
   uint64_t rect_bytes = 0;
   for (int i = 0; i < a.nrects; i++) { rows += a.rects[i][3]; rect_bytes += (uint64_t)a.rects[i][2] * a.rects[i][3] * a.bpp; }
   const int grid = a.delta ? a.bx * a.by : (rows + a.rows_per_wg - 1) / a.rows_per_wg;
+  if (a.scroll && !a.keyframe) {
+    // WRHIP_GRAB_SCROLL: probe, vote, pack, update (wrhip_k_pixels.h) -- a keyframe has no retained copy to scroll and is the packed one
+    WrGrabScrollArgs s;
+    s.g = a;
+    const int h = a.rects[0][3];
+    const size_t segs = grab_scroll_segments(a.bx, h);
+    s.hash_cur = (unsigned long long*)c->grab_scroll_work; s.hash_prev = s.hash_cur + segs;
+    s.rowdiff = s.hash_prev + segs; s.votes = (unsigned*)(s.rowdiff + grid);
+    s.dmax = std::min(WR_GRAB_SCROLL_MAX, h - 1);
+    s.row_tiles = (h + WR_SCROLL_VOTE_ROWS - 1) / WR_SCROLL_VOTE_ROWS; s.dy_chunks = (2 * s.dmax + 1 + 255) / 256;
+    const int vote_grid = a.bx * s.row_tiles * s.dy_chunks;
+    prof_begin();
+    WR_LAUNCH(wr_grab_scroll_probe_kernel, grid, 256, c->stream, s);
+    WR_LAUNCH(wr_grab_scroll_vote_kernel, vote_grid, 256, c->stream, s);
+    WR_LAUNCH(wr_grab_scroll_pack_kernel, grid, 256, c->stream, s);
+    WR_LAUNCH(wr_grab_scroll_update_kernel, grid, 256, c->stream, s);
+    // (15, feat 8: the four launches as one entry; rect and retained copy read by the probe -- what the changed blocks then read
+    // and write is not known here and is not counted)
+    prof_end(WR_KIND_GRAB, a.bpp == 4 ? WR_FMT_RGBA8 : WR_FMT_R8, 0, 8, 2 * rect_bytes, 3 * (uint64_t)grid + (uint64_t)vote_grid);
+    c->stats.kernel_launches += WRHIP_GRAB_SCROLL_LAUNCHES;
+    grab_push(gs, a.payload, true);
+    return;
+  }
   prof_begin();
   if (a.packed) WR_LAUNCH(wr_grab_pack_runs_kernel, grid, 256, c->stream, a);
   else WR_LAUNCH(wr_grab_pack_kernel, grid, 256, c->stream, a);
@@ -4313,8 +4345,9 @@ int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint3
   const bool delta = (flags & WRHIP_GRAB_DELTA) != 0;
   bool ok = t && t->dptr && (t->internal_format == GL_RGBA8 || t->internal_format == GL_R8);
   ok = ok && rects && nrects >= 1 && nrects <= WRHIP_GRAB_MAX_RECTS;
-  ok = ok && (flags & ~(WRHIP_GRAB_FLIP_ROWS | WRHIP_GRAB_SWAP_RB | WRHIP_GRAB_DELTA | WRHIP_GRAB_KEY | WRHIP_GRAB_PACKED)) == 0;
+  ok = ok && (flags & ~(WRHIP_GRAB_FLIP_ROWS | WRHIP_GRAB_SWAP_RB | WRHIP_GRAB_DELTA | WRHIP_GRAB_KEY | WRHIP_GRAB_PACKED | WRHIP_GRAB_SCROLL)) == 0;
   ok = ok && (delta || !(flags & WRHIP_GRAB_PACKED));
+  ok = ok && (!(flags & WRHIP_GRAB_SCROLL) || (delta && (flags & WRHIP_GRAB_PACKED)));
   ok = ok && (delta ? nrects == 1 && !(flags & (WRHIP_GRAB_FLIP_ROWS | WRHIP_GRAB_SWAP_RB)) : !(flags & WRHIP_GRAB_KEY));
   ok = ok && (!(flags & WRHIP_GRAB_SWAP_RB) || t->internal_format == GL_RGBA8);
   uint64_t payload = 0;
@@ -4356,6 +4389,14 @@ int32_t WrhipGrabTexture(GLuint tex, const int32_t* rects, int32_t nrects, uint3
     memcpy(t->grab_rect, rects, sizeof(t->grab_rect));
     t->grab_valid = true;
     a.delta = 1; a.keyframe = keyframe ? 1 : 0; a.packed = (flags & WRHIP_GRAB_PACKED) ? 1 : 0;
+    a.scroll = (flags & WRHIP_GRAB_SCROLL) ? 1 : 0;
+    // (the work memory only grows: a parked grab finds at least what it asked for when it is issued)
+    const size_t work = a.scroll ? grab_scroll_work_need(bx, by, h) : 0;
+    if (work > c->grab_scroll_work_size) {
+      if (c->grab_scroll_work) pool_free(c->grab_scroll_work, c->grab_scroll_work_size);
+      c->grab_scroll_work = pool_alloc(work, &c->grab_scroll_work_size);
+      if (!c->grab_scroll_work) { c->grab_scroll_work_size = 0; t->grab_valid = false; out_of_memory(); return -1; }
+    }
     a.keep = (uint8_t*)t->grab_keep; a.keep_stride = keep_stride;
     a.bx = bx; a.by = by;
   } else {
@@ -4890,7 +4931,9 @@ int32_t WrhipGrabPayloadGet(int32_t ticket, void* dst, uint64_t capacity, uint64
 int32_t WrhipGrabDecode(const void* payload, uint64_t bytes, uint32_t format, uint32_t flags, int32_t rect_w, int32_t rect_h, void* dst,
                         int64_t dst_stride, int32_t damage[4], uint32_t* blocks) {
   if ((format != GL_RGBA8 && format != GL_R8) || !(flags & WRHIP_GRAB_DELTA)) return -1;
-  return wr_gc_decode(payload, bytes, format == GL_RGBA8 ? 4 : 1, (flags & WRHIP_GRAB_PACKED) != 0, rect_w, rect_h, dst, dst_stride, damage, blocks);
+  if ((flags & WRHIP_GRAB_SCROLL) && !(flags & WRHIP_GRAB_PACKED)) return -1;
+  return wr_gc_decode(payload, bytes, format == GL_RGBA8 ? 4 : 1, (flags & WRHIP_GRAB_PACKED) != 0, rect_w, rect_h, dst, dst_stride, damage, blocks,
+                      (flags & WRHIP_GRAB_SCROLL) != 0);
 }
 int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64_t dst_stride, int32_t wait) {
   if (!ctx || !info) return -1;
@@ -4963,17 +5006,36 @@ int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64
     int x0 = rw, y0 = rh, x1 = 0, y1 = 0;
     WrGrabEntry E;
     std::vector<std::pair<size_t, WrGrabEntry>> found;      // packed: where the walk found the entries, for the copy pool
+    // (a scroll grab: header word 1 is the vector; its COPY entries are applied first, in the codec's order, then everything else)
+    const bool scroll = (gs->flags & WRHIP_GRAB_SCROLL) != 0;
+    int32_t dy = 0;
+    if (scroll) memcpy(&dy, gs->host + 4, 4);
+    if (dy < -WRHIP_GRAB_SCROLL_MAX || dy > WRHIP_GRAB_SCROLL_MAX) { r.status = 1; dy = 0; }
+    r.scroll_dy = dy;
+    std::vector<WrGrabCopy> copies;
     for (size_t at = 0; packed ? at < payload : at + entry <= payload; at += packed ? E.size : entry) {
-      if (!wr_gc_entry(src + at, payload - at, bpp, packed, rw, rh, &E)) {
+      if (!wr_gc_entry(src + at, payload - at, bpp, packed, rw, rh, &E, false, scroll, dy)) {
         r.status = 1;
         if (packed) break;
         continue;
       }
       if (packed) r.blocks++;
       x0 = std::min(x0, E.x); y0 = std::min(y0, E.y); x1 = std::max(x1, E.x + E.w); y1 = std::max(y1, E.y + E.h);
-      if (dst && packed) found.push_back(std::make_pair(at, E));
+      if (E.mode == WR_GC_COPY) { r.copied++; if (dst) copies.push_back(WrGrabCopy{E.x, E.y, E.w, E.h}); }
+      else if (dst && packed) found.push_back(std::make_pair(at, E));
       else if (dst) wr_gc_patch(src + at, E, bpp, (uint8_t*)dst, ds);
     }
+    // (block columns are independent of each other: the copy pool's threads take them in turn, each in the order of the rows)
+    const size_t nc = copies.size();
+    if (nc && !wr_gc_copy_order(copies.data(), nc)) { r.status = 1; copies.clear(); }
+    auto copy = [&](int part, int parts) {
+      for (size_t i = 0; i < copies.size(); i++) {
+        const WrGrabCopy& C = copies[dy > 0 ? i : copies.size() - 1 - i];
+        if ((C.x / WR_GC_BLOCK) % parts == part) wr_gc_copy(C, dy, bpp, (uint8_t*)dst, ds);
+      }
+    };
+    if (copies.size() >= 256) copy_pool().run(copy);
+    else if (!copies.empty()) copy(0, 1);
     // (the blocks of a packed payload are decoded side by side once there are enough of them: 256 blocks write 4 MB of RGBA8)
     const size_t nf = found.size();
     auto patch = [&](int part, int parts) {

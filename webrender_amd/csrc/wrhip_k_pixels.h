@@ -395,7 +395,8 @@ typedef uint16_t __attribute__((may_alias)) wr_u16a;
 template <int BPP> WR_DEVICE uint32_t wr_grab_staged(const wr_lu4* stage, int r, int c) {
   return BPP == 4 ? ((const uint32_t*)stage)[r * WR_GRAB_BLOCK + c] : (uint32_t)((const uint8_t*)stage)[r * WR_GRAB_BLOCK + c];
 }
-template <int BPP> WR_DEVICE void wr_grab_pack_runs(const WrGrabArgs& a, const WrGrabBlock& B, int t, wr_lu4* stage, wr_lu4* outb, unsigned* lw) {
+// (KEEP false: the retained copy is left as it is -- the scroll grab's pack launch, whose other workgroups are reading it)
+template <int BPP, bool KEEP = true> WR_DEVICE void wr_grab_pack_runs(const WrGrabArgs& a, const WrGrabBlock& B, int t, wr_lu4* stage, wr_lu4* outb, unsigned* lw) {
   constexpr int NP = BPP == 4 ? 4 : 1;          // 16-byte pieces of the block per thread
   wr_u4 v[NP];
   int n[NP], r[NP], o[NP];
@@ -414,9 +415,11 @@ template <int BPP> WR_DEVICE void wr_grab_pack_runs(const WrGrabArgs& a, const W
   if (__ballot(diff) != 0ull && (t & 63) == 0) lw[0] = 1u;
   __syncthreads();
   if (lw[0] == 0u) return;
+  if (KEEP) {
 #pragma unroll
-  for (int k = 0; k < NP; k++)
-    if (n[k]) wr_grab_st16(B.pk + (size_t)r[k] * a.keep_stride + o[k], v[k]);
+    for (int k = 0; k < NP; k++)
+      if (n[k]) wr_grab_st16(B.pk + (size_t)r[k] * a.keep_stride + o[k], v[k]);
+  }
   // this thread's 16 pixels in raster order, and which of them start a run
   const int row = t >> 2, c0 = (t & 3) * 16;
   uint32_t px[16];
@@ -1403,6 +1406,222 @@ __global__ void __launch_bounds__(256) wr_grab_push_kernel(WrGrabPushArgs a) {
     wr_grab_st16(a.dst + 16 * (i + 2 * step), v2); wr_grab_st16(a.dst + 16 * (i + 3 * step), v3);
   }
   for (; i < n16; i += step) wr_grab_st16(a.dst + 16 * i, wr_load16(a.src + 16 * i));
+}
+// WRHIP_GRAB_SCROLL (include/wrhip.h; WrGrabScrollArgs): a packed delta grab that first finds the one vertical scroll most of the
+// changed content made, and writes a block that equals the retained copy `scroll_dy` rows away as a 16-byte COPY record.  Four
+// launches on the draw stream, a workgroup per block in all but the vote; geometry and piece ownership are wr_grab_pack_kernel's.
+//   probe   compares the block with the retained copy at its own place (-> the block's mask of differing rows) and hashes every
+//           segment -- a block row -- of the texture and of the retained copy: the sum of its pieces' hashes (a multiply-xor fold of
+//           the 16 bytes with the piece's place in the row), added up over the 16 (RGBA8) or 4 (R8) lanes that share the row.  The
+//           retained copy is hashed here, every grab: nothing but the copy itself lives from one grab to the next.
+//   vote    all pairs of one block column: a workgroup takes WR_SCROLL_VOTE_ROWS rows of the column against 256 candidates, a
+//           candidate per lane -- the row's hash is a broadcast, the retained rows' hashes are consecutive LDS words -- and walks
+//           the differing rows alone; a workgroup whose rows do not differ leaves at once.  6 KB of LDS.
+//   pack    every workgroup of a changed block reduces the votes to scroll_dy (1025 words; block 0 stores it into header word 1),
+//           compares the block EXACTLY with the retained copy scroll_dy rows away and takes a COPY record, or packs the block as
+//           wr_grab_pack_runs_kernel does.  It does not write the retained copy: other workgroups are reading it.
+//   update  the changed blocks, texture -> retained copy.
+// Equality is decided by hashes in the vote only.
+WR_DEVICE unsigned long long wr_scroll_piece_hash(const wr_u4& v, int pos) {
+  const unsigned long long a = (unsigned long long)v.x | (unsigned long long)v.y << 32, b = (unsigned long long)v.z | (unsigned long long)v.w << 32;
+  const unsigned long long k = (unsigned long long)(pos + 1);
+  unsigned long long h = (a ^ (k * 0x9E3779B97F4A7C15ull)) * 0xFF51AFD7ED558CCDull;
+  h ^= h >> 32;
+  h += (b ^ (k * 0xC2B2AE3D27D4EB4Full)) * 0xC4CEB9FE1A85EC53ull;
+  h ^= h >> 29;
+  return h * 0x9FB21C651E98DF25ull;
+}
+// the rule of the vote as one number: most votes, then the smaller |dy|, then the positive dy; 0: no vote
+WR_DEVICE unsigned long long wr_scroll_key(unsigned votes, int dy) {
+  const int ad = dy < 0 ? -dy : dy;
+  return votes ? ((unsigned long long)votes << 11 | (unsigned long long)(WR_GRAB_SCROLL_MAX - ad) << 1 | (dy > 0 ? 1ull : 0ull)) : 0ull;
+}
+WR_DEVICE int wr_scroll_key_dy(unsigned long long key) {
+  if (key == 0ull) return 0;
+  const int ad = WR_GRAB_SCROLL_MAX - (int)((key >> 1) & 1023ull);
+  return (key & 1ull) ? ad : -ad;
+}
+WR_DEVICE const uint8_t* wr_scroll_kept(const WrGrabArgs& a, const WrGrabBlock& B, int r, int o) {
+  return B.pk + (ptrdiff_t)r * (ptrdiff_t)a.keep_stride + o;      // (r may be negative: a row above the block)
+}
+__global__ void __launch_bounds__(256) wr_grab_scroll_probe_kernel(WrGrabScrollArgs s) {
+  const WrGrabArgs& a = s.g;
+  const int t = (int)threadIdx.x, b = (int)blockIdx.x;
+  const WrGrabBlock B = wr_grab_block(a, b);
+  const size_t seg0 = (size_t)(b % a.bx) * (size_t)a.rects[0][3] + (size_t)B.y0;
+  unsigned long long* hc = s.hash_cur + seg0;
+  unsigned long long* hp = s.hash_prev + seg0;
+  const int ppr = WR_GRAB_BLOCK * a.bpp / 16;
+#ifdef WRHIP_HOSTSIM
+  if (t != 0) return;
+  if (b == 0) for (int i = 0; i < 2 * WR_GRAB_SCROLL_MAX + 1; i++) s.votes[i] = 0u;
+  unsigned long long mask = 0ull;
+  for (int row = 0; row < B.bh; row++) {
+    unsigned long long c = 0ull, p = 0ull;
+    bool diff = false;
+    for (int q = 0; q < ppr; q++) {
+      wr_u4 v; int r, o;
+      if (!wr_grab_piece(a, B, row * ppr + q, v, r, o)) continue;
+      const wr_u4 e = wr_load16(wr_scroll_kept(a, B, r, o));
+      c += wr_scroll_piece_hash(v, q); p += wr_scroll_piece_hash(e, q);
+      diff = diff || wr_grab_differs(v, e);
+    }
+    hc[row] = c; hp[row] = p;
+    if (diff) mask |= 1ull << row;
+  }
+  s.rowdiff[b] = mask;
+#else
+  __shared__ unsigned lm[2];           // the mask of differing rows
+  if (b == 0) for (int i = t; i < 2 * WR_GRAB_SCROLL_MAX + 1; i += 256) s.votes[i] = 0u;
+  if (t < 2) lm[t] = 0u;
+  __syncthreads();
+  const int pieces = WR_GRAB_BLOCK * ppr;
+  for (int k = 0; k < 4; k++) {
+    const int piece = k * 256 + t;
+    if (piece >= pieces) break;        // (uniform: 1024 pieces or 256)
+    wr_u4 v; int r, o;
+    unsigned long long c = 0ull, p = 0ull;
+    bool diff = false;
+    if (wr_grab_piece(a, B, piece, v, r, o)) {
+      const wr_u4 e = wr_load16(wr_scroll_kept(a, B, r, o));
+      c = wr_scroll_piece_hash(v, piece % ppr); p = wr_scroll_piece_hash(e, piece % ppr);
+      diff = wr_grab_differs(v, e);
+    }
+    for (int m = 1; m < ppr; m <<= 1) { c += __shfl_xor(c, m); p += __shfl_xor(p, m); }
+    const unsigned long long bal = __ballot(diff);
+    const int lane = t & 63;
+    if ((lane & (ppr - 1)) == 0 && r < B.bh) {
+      hc[r] = c; hp[r] = p;
+      if ((bal >> lane) & ((1ull << ppr) - 1ull)) atomicOr(&lm[r >> 5], 1u << (r & 31));
+    }
+  }
+  __syncthreads();
+  if (t == 0) s.rowdiff[b] = (unsigned long long)lm[0] | (unsigned long long)lm[1] << 32;
+#endif
+}
+__global__ void __launch_bounds__(256) wr_grab_scroll_vote_kernel(WrGrabScrollArgs s) {
+  const WrGrabArgs& a = s.g;
+  const int t = (int)threadIdx.x, h = a.rects[0][3], D = s.dmax;
+  int id = (int)blockIdx.x;
+  const int chunk = id % s.dy_chunks; id /= s.dy_chunks;
+  const int tile = id % s.row_tiles, c = id / s.row_tiles;
+  const int r0 = tile * WR_SCROLL_VOTE_ROWS, d0 = -D + chunk * 256;
+  const unsigned long long* hc = s.hash_cur + (size_t)c * (size_t)h;
+  const unsigned long long* hp = s.hash_prev + (size_t)c * (size_t)h;
+#ifdef WRHIP_HOSTSIM
+  if (t != 0) return;
+  for (int dy = d0; dy < d0 + 256 && dy <= D; dy++) {
+    if (dy == 0) continue;
+    unsigned n = 0u;
+    for (int r = r0; r < r0 + WR_SCROLL_VOTE_ROWS && r < h; r++) {
+      const bool differs = (s.rowdiff[(size_t)(r / WR_GRAB_BLOCK) * a.bx + c] >> (r % WR_GRAB_BLOCK)) & 1ull;
+      if (differs && r + dy >= 0 && r + dy < h && hc[r] == hp[r + dy]) n++;
+    }
+    if (n) atomicAdd(&s.votes[dy + WR_GRAB_SCROLL_MAX], n);
+  }
+#else
+  __shared__ unsigned long long lc[WR_SCROLL_VOTE_ROWS], lp[WR_SCROLL_VOTE_ROWS + 256], lmask[WR_SCROLL_VOTE_ROWS / WR_GRAB_BLOCK];
+  if (t < WR_SCROLL_VOTE_ROWS / WR_GRAB_BLOCK) {
+    const int q = r0 / WR_GRAB_BLOCK + t;
+    lmask[t] = q < a.by ? s.rowdiff[(size_t)q * a.bx + c] : 0ull;
+  }
+  __syncthreads();
+  unsigned long long any = 0ull;
+  for (int q = 0; q < WR_SCROLL_VOTE_ROWS / WR_GRAB_BLOCK; q++) any |= lmask[q];
+  if (any == 0ull) return;
+  for (int i = t; i < WR_SCROLL_VOTE_ROWS; i += 256) lc[i] = r0 + i < h ? hc[r0 + i] : 0ull;
+  for (int i = t; i < WR_SCROLL_VOTE_ROWS + 255; i += 256) {
+    const int rr = r0 + d0 + i;
+    lp[i] = rr >= 0 && rr < h ? hp[rr] : 0ull;
+  }
+  __syncthreads();
+  const int dy = d0 + t;
+  unsigned n = 0u;
+  for (int q = 0; q < WR_SCROLL_VOTE_ROWS / WR_GRAB_BLOCK; q++) {
+    unsigned long long m = lmask[q];
+    while (m) {
+      const int i = q * WR_GRAB_BLOCK + __builtin_ctzll(m);
+      m &= m - 1ull;
+      const int rr = r0 + i + dy;
+      if (rr >= 0 && rr < h && lc[i] == lp[i + t]) n++;
+    }
+  }
+  if (n && dy != 0 && dy <= D) atomicAdd(&s.votes[dy + WR_GRAB_SCROLL_MAX], n);
+#endif
+}
+__global__ void __launch_bounds__(256) wr_grab_scroll_pack_kernel(WrGrabScrollArgs s) {
+  const WrGrabArgs& a = s.g;
+  const int t = (int)threadIdx.x, b = (int)blockIdx.x;
+  const unsigned long long mask = s.rowdiff[b];
+  if (mask == 0ull && b != 0) return;
+  const int pieces = WR_GRAB_BLOCK * WR_GRAB_BLOCK * a.bpp / 16;
+#ifdef WRHIP_HOSTSIM
+  // (threads run one after the other: the first does it all)
+  if (t != 0) return;
+  unsigned long long key = 0ull;
+  for (int i = 0; i < 2 * WR_GRAB_SCROLL_MAX + 1; i++) { const unsigned long long k = wr_scroll_key(s.votes[i], i - WR_GRAB_SCROLL_MAX); key = k > key ? k : key; }
+  const int dy = wr_scroll_key_dy(key);
+  if (b == 0) wr_grab_st4(a.slot + 4, (uint32_t)dy);
+  if (mask == 0ull) return;
+  const WrGrabBlock B = wr_grab_block(a, b);
+  bool copy = dy != 0 && B.y0 + dy >= 0 && B.y0 + dy + B.bh <= a.rects[0][3];
+  for (int piece = 0; piece < pieces && copy; piece++) {
+    wr_u4 v; int r, o;
+    if (wr_grab_piece(a, B, piece, v, r, o)) copy = !wr_grab_differs(v, wr_load16(wr_scroll_kept(a, B, r + dy, o)));
+  }
+  uint8_t entry[WR_GRAB_ENTRY(4)];
+  const unsigned size = copy ? (unsigned)wr_gc_encode_copy(B.x0, B.y0, B.bw, B.bh, entry)
+                             : (unsigned)wr_gc_encode_block(B.ps, (size_t)a.tex_stride, B.x0, B.y0, B.bw, B.bh, a.bpp, entry);
+  __builtin_memcpy(a.slot + WR_GRAB_HEADER + atomicAdd((unsigned*)a.slot, size), entry, size);
+#else
+  __shared__ wr_lu4 stage[1024], outb[1024];
+  __shared__ unsigned lw[8];           // [0..5]: wr_grab_pack_runs'; [6]: the block is no copy
+  __shared__ unsigned long long lk[4];
+  unsigned long long key = 0ull;
+  for (int i = t; i < 2 * WR_GRAB_SCROLL_MAX + 1; i += 256) { const unsigned long long k = wr_scroll_key(s.votes[i], i - WR_GRAB_SCROLL_MAX); key = k > key ? k : key; }
+  for (int o = 32; o > 0; o >>= 1) { const unsigned long long k = __shfl_xor(key, o); key = k > key ? k : key; }
+  if ((t & 63) == 0) lk[t >> 6] = key;
+  if (t == 0) lw[6] = 0u;
+  __syncthreads();
+  for (int w = 0; w < 4; w++) key = lk[w] > key ? lk[w] : key;
+  const int dy = wr_scroll_key_dy(key);
+  if (b == 0 && t == 0) wr_grab_st4(a.slot + 4, (uint32_t)dy);
+  if (mask == 0ull) return;
+  const WrGrabBlock B = wr_grab_block(a, b);
+  if (dy != 0 && B.y0 + dy >= 0 && B.y0 + dy + B.bh <= a.rects[0][3]) {
+    bool diff = false;
+    for (int k = 0; k < 4; k++) {
+      const int piece = k * 256 + t;
+      if (piece >= pieces) break;
+      wr_u4 v; int r, o;
+      if (wr_grab_piece(a, B, piece, v, r, o)) diff = diff || wr_grab_differs(v, wr_load16(wr_scroll_kept(a, B, r + dy, o)));
+    }
+    if (__ballot(diff) != 0ull && (t & 63) == 0) lw[6] = 1u;
+    __syncthreads();
+    if (lw[6] == 0u) {
+      if (t == 0) wr_grab_st16(a.slot + WR_GRAB_HEADER + atomicAdd((unsigned*)a.slot, 16u), wr_u4{(uint32_t)B.x0, (uint32_t)B.y0, (uint32_t)B.bw | (uint32_t)B.bh << 8 | 3u << 16, 0u});
+      return;
+    }
+  }
+  if (a.bpp == 4) wr_grab_pack_runs<4, false>(a, B, t, stage, outb, lw);
+  else wr_grab_pack_runs<1, false>(a, B, t, stage, outb, lw);
+#endif
+}
+__global__ void __launch_bounds__(256) wr_grab_scroll_update_kernel(WrGrabScrollArgs s) {
+  const WrGrabArgs& a = s.g;
+  const int t = (int)threadIdx.x, b = (int)blockIdx.x;
+  if (s.rowdiff[b] == 0ull) return;
+  const WrGrabBlock B = wr_grab_block(a, b);
+  const int pieces = WR_GRAB_BLOCK * WR_GRAB_BLOCK * a.bpp / 16;
+#ifdef WRHIP_HOSTSIM
+  if (t != 0) return;
+  for (int piece = 0; piece < pieces; piece++) {
+#else
+  for (int piece = t; piece < pieces; piece += 256) {
+#endif
+    wr_u4 v; int r, o;
+    if (wr_grab_piece(a, B, piece, v, r, o)) wr_grab_st16(B.pk + (size_t)r * a.keep_stride + o, v);
+  }
 }
 #endif
 

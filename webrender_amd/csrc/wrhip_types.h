@@ -733,6 +733,24 @@ struct WrGrabArgs {
   int32_t bx, by;                      // delta: blocks across and down
   uint32_t payload;                    // full, and a keyframe: the payload's bytes (known on the host)
   int32_t rects[WR_GRAB_MAX_RECTS][4]; // x, y, w, h
+  int32_t scroll;                      // packed delta: WRHIP_GRAB_SCROLL was given (the host's: no kernel of this launch reads it)
+};
+// WRHIP_GRAB_SCROLL: the four launches of a scroll grab that is no keyframe (the contract: include/wrhip.h; the kernels:
+// wr_grab_scroll_*_kernel).  `g` is the packed delta grab's launch.  The rest is work memory of the context, written and read by
+// these launches alone and by no later grab: nothing of it outlives the grab.
+//   hash_cur, hash_prev  a 64-bit hash of every segment -- rect row r inside block column c, at [c * h + r] -- of the texture and of
+//                        the retained copy
+//   rowdiff              per block, bit r: the block's row r differs from the retained copy at its own place
+//   votes                2 * WR_GRAB_SCROLL_MAX + 1 words, votes[dy + WR_GRAB_SCROLL_MAX]; cleared by the probe
+#define WR_GRAB_SCROLL_MAX 512
+#define WR_SCROLL_VOTE_ROWS 256        // cur rows of a column one vote workgroup takes, against 256 candidates
+struct WrGrabScrollArgs {
+  WrGrabArgs g;
+  unsigned long long* hash_cur; unsigned long long* hash_prev;
+  unsigned long long* rowdiff;
+  unsigned* votes;
+  int32_t dmax;                        // D = min(WR_GRAB_SCROLL_MAX, h - 1)
+  int32_t row_tiles, dy_chunks;        // vote: the launch is bx * row_tiles * dy_chunks workgroups
 };
 // WrhipGrabTextureScaled: one launch of wr_grab_scale_kernel.  The chain of linear blits that scales a texture rect down -- a top
 // step of any ratio to level L (dw << L x dh << L), then L exact 2:1 steps to level 0 (dw x dh) -- walked tile by tile: a workgroup

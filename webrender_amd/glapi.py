@@ -179,6 +179,9 @@ GRAB_FLIP_ROWS, GRAB_SWAP_RB, GRAB_DELTA, GRAB_KEY, GRAB_PACKED = 1, 2, 4, 8, 32
 GRAB_SCALED = 64          # reported in a scaled grab's info["flags"] (WrhipGrabTextureScaled); no flag of WrhipGrabTexture
 GRAB_TENSOR = 128         # reported in a tensor grab's info["flags"] (WrhipGrabTextureTensor); no flag of the other grab calls
 GRAB_YUV = 512            # reported in a YUV grab's info["flags"] (WrhipGrabTextureYuv); no flag of the other grab calls
+GRAB_SCROLL = 1024        # with GRAB_DELTA | GRAB_PACKED: the scroll grab (scrolled blocks cross as 16-byte COPY entries)
+GRAB_SCROLL_MAX = 512     # the largest |scroll_dy| that is looked for
+GRAB_SCROLL_LAUNCHES = 4  # launches of a scroll grab that is no keyframe
 GRAB_MAX_RECTS, GRAB_HEADER, GRAB_BLOCK = 16, 16, 64
 # WrhipGrabTextureYuv: plane layouts, and the YuvRangedColorSpace values it converts to
 YUV_I420, YUV_NV12, YUV_I444 = 0, 1, 2
@@ -193,7 +196,8 @@ TENSOR_ELEM_BYTES = {TENSOR_U8: 1, TENSOR_F16: 2, TENSOR_BF16: 2, TENSOR_F32: 4}
 class WrhipGrabInfo(C.Structure):
     _fields_ = [("status", i32), ("format", u32), ("flags", u32), ("nrects", i32), ("rects", (i32 * 4) * GRAB_MAX_RECTS),
                 ("keyframe", u32), ("blocks", u32), ("blocks_total", u32), ("damage", i32 * 4), ("bytes", u64),
-                ("scaled_w", i32), ("scaled_h", i32), ("levels", u32), ("renditions", u32)]
+                ("scaled_w", i32), ("scaled_h", i32), ("levels", u32), ("renditions", u32),
+                ("scroll_dy", i32), ("copied", u32)]
 
 
 class WrhipTensorDesc(C.Structure):
@@ -547,7 +551,8 @@ class GL:
             assert rc == 0, rc
         info = {"status": r.status, "format": r.format, "flags": r.flags, "rects": rects, "keyframe": r.keyframe, "blocks": r.blocks,
                 "blocks_total": r.blocks_total, "damage": tuple(r.damage), "bytes": int(r.bytes),
-                "scaled_w": r.scaled_w, "scaled_h": r.scaled_h, "levels": r.levels, "renditions": r.renditions}
+                "scaled_w": r.scaled_w, "scaled_h": r.scaled_h, "levels": r.levels, "renditions": r.renditions,
+                "scroll_dy": r.scroll_dy, "copied": r.copied}
         return info, pixels
 
     def grab_payload(self, ticket, wait=True):

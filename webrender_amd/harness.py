@@ -185,13 +185,14 @@ def screenshot_size(window_size, buffer_size):
     return rnd(w * scale), rnd(h * scale)
 
 
-def render_streamed_grabbed(backend_path, frames, delta=False, rect=None, packed=False, scale_to=None):
+def render_streamed_grabbed(backend_path, frames, delta=False, rect=None, packed=False, scale_to=None, scroll=False):
     """render_streamed_tapped with the pixels: after each frame's render `rect` of the window (None: all of it) is grabbed
     (GL.grab_texture: packed on the device in stream order behind that frame, carried to the host on the library's second
     stream) -- still nothing between the frames that drains the held-back raster launches.  Results are fetched in order as they
     arrive, and the oldest is waited for (that ticket alone) only when the ring of 8 would otherwise lose it, so any number of
     frames goes through.  delta=True: delta grabs, patched one after the other into one host image; packed=True (with delta):
-    their blocks cross in the packed form (glapi.GRAB_PACKED).  scale_to=(w, h) (without delta): every grab is the scaled one
+    their blocks cross in the packed form (glapi.GRAB_PACKED); scroll=True (with delta and packed): scroll grabs (glapi.GRAB_SCROLL).
+    scale_to=(w, h) (without delta): every grab is the scaled one
     (GL.grab_texture_scaled) and every image the (h, w, 4) result.
     Returns the final window (RGBA8), the backend's statistics, the host's image of the rect after every frame's grab (stored
     bytes, B, G, R, A) and the grabs' info dicts.  libwrhip only."""
@@ -223,7 +224,8 @@ def render_streamed_grabbed(backend_path, frames, delta=False, rect=None, packed
             assert not delta, "render_streamed_grabbed: a scaled grab is a full one"
             t = gl.grab_texture_scaled(window, rect, scale_to)
         else:
-            t = gl.grab_texture(window, rect, (glapi.GRAB_DELTA if delta else 0) | (glapi.GRAB_PACKED if packed else 0))
+            assert not scroll or (delta and packed), "render_streamed_grabbed: a scroll grab is a packed delta one"
+            t = gl.grab_texture(window, rect, (glapi.GRAB_DELTA if delta else 0) | (glapi.GRAB_PACKED if packed else 0) | (glapi.GRAB_SCROLL if scroll else 0))
         assert t >= 0, (t, gl.GetError())
         waiting.append(t)
         fetch(False)
