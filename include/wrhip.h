@@ -393,8 +393,8 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  * THE SCROLL GRAB (WRHIP_GRAB_DELTA | WRHIP_GRAB_PACKED | WRHIP_GRAB_SCROLL, with or without KEY; GL_RGBA8 and GL_R8): a packed delta
  *   grab that first finds the one vertical scroll most of the changed content made, and sends a block that is found that many rows
  *   away in the retained copy as a 16-byte COPY entry: "take it from your own image".  SCROLL in any other combination -- without
- *   DELTA, without PACKED, with FLIP_ROWS / SWAP_RB, on the scaled, tensor and YUV calls -- is -1 with GL_INVALID_VALUE, nothing
- *   launched.  It uses the plain and packed delta grabs' retained copy under the same validity rules and keeps no other state, so
+ *   DELTA, without PACKED, with FLIP_ROWS / SWAP_RB, on the scaled and tensor calls, on WrhipGrabTextureYuv and
+ *   WrhipGrabTextureYuvScaled -- is -1 with GL_INVALID_VALUE, nothing launched.  It uses the plain and packed delta grabs' retained copy under the same validity rules and keeps no other state, so
  *   plain, packed and scroll delta grabs of one texture and rect may alternate in any order without a keyframe.  A keyframe is the
  *   packed grab's (one launch, scroll_dy 0, no COPY entry); any other scroll grab is WRHIP_GRAB_SCROLL_LAUNCHES launches on the draw
  *   stream.  The contract -- any restatement must give the same bytes, up to the order of the entries:
@@ -419,8 +419,8 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  *             orders them itself.  Malformed, WrhipGrabDecode -1 with nothing written: a COPY entry with dy == 0, |dy| >
  *             WRHIP_GRAB_SCROLL_MAX, a COPY source outside the rect, a COPY record with a non-zero aux, one that is not a whole
  *             block of the rect or names a block twice, mode 3 or a non-zero header word 1 when `flags` lacks SCROLL.
- *   Not supported: horizontal or per-region vectors, COPY of a block whose source is partly outside the rect, scroll detection for
- *   WrhipGrabTextureYuvDelta, sharded targets.
+ *   Not supported: horizontal or per-region vectors, COPY of a block whose source is partly outside the rect, sharded targets.
+ *   (Scroll detection for delta YUV grabs: WrhipGrabTextureYuvDelta with WRHIP_GRAB_DELTA | WRHIP_GRAB_SCROLL, below.)
  *
  * WrhipGrabTextureScaled(tex, rect, dst_w, dst_h, flags): a grab of ONE rect (x, y, w, h) of a GL_RGBA8 texture scaled down to
  * dst_w x dst_h (1 <= dst_w <= w, 1 <= dst_h <= h), byte for byte what the reference's screenshot chain (webrender's
@@ -570,8 +570,8 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  * WrhipGrabTextureYuvDelta(tex, rect, desc, flags): WrhipGrabTextureYuv for a page that is mostly still: only the 64 x 64 blocks
  * whose SAMPLES changed since the previous such grab cross the link (or are written to the caller's planes), with a damage rect
  * for the encoder's skip decisions.  `desc` is WrhipGrabTextureYuv's -- formats, the six colour spaces, FLIP_ROWS, host or device
- * sink --; `flags` is 0 or WRHIP_GRAB_KEY.  One launch (wr_grab_yuv_delta_kernel).  The contract -- any restatement must give the
- * same bytes:
+ * sink --; `flags` is 0, WRHIP_GRAB_KEY and / or WRHIP_GRAB_DELTA | WRHIP_GRAB_SCROLL (`scroll` below).  One launch (wr_grab_yuv_delta_kernel).  The
+ * contract -- any restatement must give the same bytes:
  *   samples   exactly those WrhipGrabTextureYuv produces for the same rect and desc: table, luma, chroma, the clamp, 4:2:0 blocks
  *             clamped to the RECT, the flip ahead of the chroma blocks.
  *   blocks    64 x 64 luma samples of the IMAGE (after the flip), aligned to the image's origin, edge blocks cut to the image.  A cut
@@ -604,8 +604,51 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  *   ordering, parking, ring, slot growth, WRHIP_GRAB_PINNED_MAX  WrhipGrabTexture's; slots are sized for all blocks of the rect.  A
  *             parked HOST-sink grab that lost its ticket is dropped, and the next delta YUV grab of that texture is a keyframe.
  *   cost      one launch: WrhipStats::kernel_launches grows by 1, flushes by 0.
+ *   scroll    (`flags` with WRHIP_GRAB_DELTA | WRHIP_GRAB_SCROLL, beside KEY or not: the flag is spelt with DELTA, as on
+ *             WrhipGrabTexture, and either of the two bits without the other stays refused)  a scrolled page changes every block, but nearly all of its samples
+ *             sit in the consumer's planes a few rows away: the grab finds the one vertical scroll and sends such blocks as 16-byte
+ *             COPY entries.  Without the flag every byte, launch and info field is as described above.  The contract -- any
+ *             restatement must give the same bytes, up to the order of the entries: prev is the retained planes, cur the samples
+ *             WrhipGrabTextureYuv would produce now for the same rect and desc, both in image space (after FLIP_ROWS); h is the
+ *             image's height, a segment (r, c) the LUMA samples of image row r inside block column c, D = min(WRHIP_GRAB_SCROLL_MAX,
+ *             h - 1).
+ *     candidates  1 <= |dy| <= D; in I420 and NV12 only EVEN dy -- an odd shift moves luma rows across chroma rows and no chroma
+ *             sample survives it --, in I444 every dy.
+ *     vector  votes(dy) = the number of segments with 0 <= r + dy < h, cur_Y(r, c) != prev_Y(r, c) and cur_Y(r, c) == prev_Y(r + dy,
+ *             c).  scroll_dy is the candidate with the most votes; ties go to the smaller |dy|, then to the positive dy; 0 if no
+ *             candidate has a vote.  Positive: the content moved up.  FOR THE VOTE ONLY segment equality is decided by a 64-bit hash.
+ *     blocks  by exact comparison of samples.  A block is not sent if ALL its samples, Y and chroma, equal prev at its own place.
+ *             Otherwise it is a COPY entry if scroll_dy != 0, 0 <= y + dy and y + dy + bh <= h, every Y sample equals prev_Y dy rows
+ *             away and every chroma sample equals prev's chroma dy / 2 rows away in 4:2:0, dy rows away in I444; otherwise a
+ *             SAMPLES entry.  After the grab the retained planes equal cur.
+ *     keyframe  (no valid retained copy, or KEY)  scroll_dy 0, no COPY entry, one launch.  The retained copy is the delta YUV grab's
+ *             own, under the same validity rules: delta YUV grabs with and without SCROLL may alternate on one texture, rect and
+ *             desc in any order without a keyframe.  (A texture that is grabbed with SCROLL holds a second set of planes of the
+ *             same size; the two exchange roles with every such grab.)
+ *     wire    (host sink)  header word 1 is scroll_dy as an int32.  EVERY record of a SCROLL grab is x, y, w | h << 8 | mode << 16,
+ *             0 -- the packed payload's record layout.  Mode 0, SAMPLES: the record, then the planes exactly as a delta YUV entry
+ *             lays them out (16 + 6144 or 16 + 12288 bytes).  Mode 3, COPY: the record alone.  On a keyframe entry i is still block
+ *             i.  `bytes` = 16 + the sum of the entries' sizes, `blocks` counts all entries, `copied` the COPY ones, `damage`
+ *             bounds all of them, info.flags carries WRHIP_GRAB_SCROLL; slots are sized as without the flag.
+ *     device sink  SAMPLES blocks are written into the caller's planes as without the flag.  A COPY block's samples are written
+ *             into the caller's planes FROM THE LIBRARY'S retained planes at the shifted place -- never from the caller's planes:
+ *             there is no in-place hazard, and it does not matter what the caller did to them.  The payload is the records alone,
+ *             16 bytes per entry with the mode word.  Nothing but samples of sent and copied blocks is written, and the write does
+ *             not depend on the ticket surviving.
+ *     decoding  WrhipGrabResultGet decodes into the caller's host planes; WrhipGrabDecodeYuv decodes with `format |
+ *             WRHIP_GRAB_SCROLL` as its format.  In place, without a snapshot: all COPY entries first -- by ascending y for dy > 0,
+ *             descending y for dy < 0, on all planes, chroma moved by dy / 2 rows in 4:2:0 --, then all SAMPLES entries.  Malformed,
+ *             WrhipGrabDecodeYuv -1 with nothing written: a mode other than 0 or 3; a non-zero word 3; a header word 1 beyond
+ *             WRHIP_GRAB_SCROLL_MAX; COPY with dy == 0 or an odd dy in a 4:2:0 format; a COPY source outside the image; an entry
+ *             that is not a whole block of the image; a block named twice; mode 3 or a non-zero header word 1 when the SCROLL bit
+ *             is absent.
+ *     cost    a scroll grab that is no keyframe is WRHIP_GRAB_YUV_SCROLL_LAUNCHES launches on the draw stream (probe, the scroll
+ *             grab's vote, pack; no update launch: the probe writes the second set of planes) and 0 flushes.
+ *     Not supported: horizontal or per-region vectors, luma-only copies for odd scrolls in 4:2:0, scroll for scaled YUV grabs,
+ *             sharded targets.
  * Returns -1 and sets GL_INVALID_VALUE, launching and flushing nothing and leaving the retained copy as it was, for everything
- * WrhipGrabTextureYuv rejects and for any `flags` bit other than KEY; -1 with GL_OUT_OF_MEMORY as WrhipGrabTexture.
+ * WrhipGrabTextureYuv rejects, for any `flags` bit other than KEY, DELTA and SCROLL, and for DELTA without SCROLL or SCROLL
+ * without DELTA; -1 with GL_OUT_OF_MEMORY as WrhipGrabTexture.
  *
  * WrhipGrabTextureYuvScaled(tex, rect, out_w, out_h, descs, renditions): a grab of ONE rect of a GL_RGBA8 texture scaled down as
  * WrhipGrabTextureScaled scales it and delivered as WrhipGrabTextureYuv's planes -- at up to four sizes, the lowest levels of the
@@ -650,7 +693,8 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  * is the plane of pairs and c1 NULL; y, c0 and c1 all NULL: only checked.  0 with the entries' bounding box and number (either may
  * be NULL); -1, having written nothing, for a malformed payload -- a length that is not header + k entries or more than `bytes`
  * holds, an x or y that is no multiple of 64 or outside the image, a w or h that is not the cut block's, more entries than the
- * image has blocks -- or for planes given in part or with a stride below a row.
+ * image has blocks, a non-zero header word 1 -- or for planes given in part or with a stride below a row.  `format |
+ * WRHIP_GRAB_SCROLL`: the payload of a SCROLL grab (above), with its own list of what is malformed.
  * Not routed through grabs: Finish, GetColorBuffer, ReadPixels.  Not supported: other formats, sharded targets; scaling other than
  * WrhipGrabTextureScaled's; delta or packed tensor grabs; gamma or colour-space conversion of tensors (values are the stored
  * premultiplied bytes); puts that scale or filter, into other formats, into sharded targets or host-backed textures; YUV grabs of 10-
@@ -663,9 +707,10 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
 #define WRHIP_GRAB_SCALED    64u  /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureScaled ticket; no flag of WrhipGrabTexture, which rejects it */
 #define WRHIP_GRAB_TENSOR    128u /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureTensor ticket; no flag of the other grab calls, which reject it */
 #define WRHIP_GRAB_YUV       512u /* reported in WrhipGrabInfo::flags by a WrhipGrabTextureYuv, (with DELTA) WrhipGrabTextureYuvDelta or (with SCALED) WrhipGrabTextureYuvScaled ticket; rejected by the other grab calls */
-#define WRHIP_GRAB_SCROLL    1024u /* with DELTA | PACKED (with or without KEY): find the vertical scroll, send scrolled blocks as COPY entries (the scroll grab above); rejected in every other combination and by the other grab calls */
+#define WRHIP_GRAB_SCROLL    1024u /* with DELTA | PACKED (with or without KEY): find the vertical scroll, send scrolled blocks as COPY entries (the scroll grab above); with DELTA a flag of WrhipGrabTextureYuvDelta too, and a bit of WrhipGrabDecodeYuv's format; rejected in every other combination and by the other grab calls */
 #define WRHIP_GRAB_SCROLL_MAX 512      /* the largest |scroll_dy| that is looked for */
 #define WRHIP_GRAB_SCROLL_LAUNCHES 4   /* launches on the draw stream of a scroll grab that is no keyframe: probe, vote, pack, update */
+#define WRHIP_GRAB_YUV_SCROLL_LAUNCHES 3 /* launches on the draw stream of a delta YUV grab with SCROLL that is no keyframe: probe, vote, pack */
 #define WRHIP_YUV_I420 0u         /* WrhipYuvDesc::format: Y plane, Cb plane, Cr plane; chroma 4:2:0 */
 #define WRHIP_YUV_NV12 1u         /* Y plane, one plane of interleaved Cb,Cr pairs; chroma 4:2:0 */
 #define WRHIP_YUV_I444 2u         /* Y, Cb, Cr planes, all w x h */

@@ -37,10 +37,14 @@
              launch of DELTA | PACKED on the same frames -- nothing changed, 40 blocks changed, a scroll by 37, both -- with the bytes
              crossed; then 200 frames each scrolled by 37, a grab per frame patched into the caller's image, against DELTA | PACKED and
              no grab.  --scroll-case CASE runs one case's scroll grabs alone for a profiler's kernel trace (the launches one by one)
+  yuvscroll  WrhipGrabTextureYuvDelta with GRAB_SCROLL on a 4K window onto a tall page of noise, I420, host sink: the grab's launches
+             (kind 15 feat 9, one entry) beside the plain delta YUV grab's one launch on the same frames -- a scroll by 64, nothing
+             changed, 40 blocks changed -- with the bytes crossed; then frames each scrolled by 64 and uploaded, a grab per frame,
+             host and device sink, with and without GRAB_SCROLL, against no grab
   ab         plain bench.py against another build of the library (WRHIP_LIB_PATH), alternated, no grab issued
 
 Every section runs three alternated rounds.  Needs the GPU: there is no fallback.
-  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor,put,yuv,yuv_delta,yuv_scaled,scroll] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
+  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor,put,yuv,yuv_delta,yuv_scaled,scroll,yuvscroll] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -1225,6 +1229,113 @@ def section_scroll_stream(lib, frames):
         say(f"  {name:22s} " + "  ".join(f"{fps:9.1f}" for fps, _ in v) + "   frames/s   " + (f"({v[0][1] / 1e6:8.3f} MB per frame crossed)" if v[0][1] else ""))
 
 
+# ---- scroll-aware delta YUV grabs (WrhipGrabTextureYuvDelta with GRAB_SCROLL) -----------------------------
+YUVSCROLL_CASES = ("scroll by 64", "nothing changed", "40 blocks changed")
+
+
+def _yuv_delta_grab(w, scroll, dst=0, nbytes=0, key=False, wait=True):
+    t = w.gl.grab_texture_yuv_delta(w.tex, None, glapi.YUV_I420, glapi.YUV_REC709_NARROW, dst=dst or None, dst_bytes=nbytes if dst else 0, key=key, scroll=scroll)
+    assert t >= 0, w.gl.GetError()
+    info = glapi.WrhipGrabInfo()
+    if wait:
+        assert w.gl.WrhipGrabResultGet(t, C.byref(info), None, 0, 1) == 0
+        return info
+    return t
+
+
+def section_yuvscroll_kernel(lib, n=10):
+    """Every case with and without GRAB_SCROLL on the same frames, host sink, I420: us per grab (all its launches), and what crossed"""
+    say(f"## yuvscroll: {W}x{H} window onto a page of noise, I420, host sink, {n} grabs per case, hipEvents (WrhipSetProfiling(1)), us per grab (all its launches)")
+    w = Window(lib)
+    gl = w.gl
+    rng = np.random.default_rng(5)
+    page = rng.integers(0, 256, (H + 64 * n, W, 4), dtype=np.uint8)
+    nblocks = ((W + 63) // 64) * ((H + 63) // 64)
+    some = rng.choice(nblocks, size=40, replace=False)
+    patches = [rng.integers(0, 256, (16, 16, 4), dtype=np.uint8) for _ in range(2)]
+    rows = {}
+    for rnd in range(ROUNDS):
+        for case in YUVSCROLL_CASES:
+            for name, scroll in (("scroll", True), ("plain", False)):
+                w.upload(0, 0, page[:H])
+                for b in some:
+                    w.upload(int(b % (W // 64)) * 64 + 5, int(b // (W // 64)) * 64 + 3, patches[1])
+                _yuv_delta_grab(w, scroll, key=True)
+                _yuv_delta_grab(w, scroll)          # (untimed: code objects, the second planes, the work memory)
+                gl.WrhipSetProfiling(1)
+                gl.WrhipResetStats()
+                infos = []
+                for k in range(1, n + 1):
+                    if case.startswith("scroll"):
+                        w.upload(0, 0, page[64 * k:64 * k + H])
+                    if case.startswith("40"):
+                        for b in some:
+                            w.upload(int(b % (W // 64)) * 64 + 5, int(b // (W // 64)) * 64 + 3, patches[k & 1])
+                    gl.WrhipFlush()
+                    infos.append(_yuv_delta_grab(w, scroll))
+                ks = kernel_stats(gl, 15)
+                gl.WrhipSetProfiling(0)
+                assert len(ks) == 1 and ks[0].launches == n and ks[0].feat == (9 if scroll else 6), [(k.kind, k.feat, k.launches) for k in ks]
+                last = infos[-1]
+                rows.setdefault((case, name), []).append((ks[0].ns / n / 1e3, int(last.blocks), int(last.copied), int(last.bytes), int(last.scroll_dy)))
+    for (case, name), v in rows.items():
+        say(f"  {case:20s} {name:7s} " + "  ".join(f"{us:8.1f}" for us, _, _, _, _ in v) +
+            f"   us   (scroll_dy {v[0][4]}; entries {v[0][1]} of {nblocks}, {v[0][2]} of them COPY; {v[0][3]} bytes crossed)")
+    w.close()
+
+
+def section_yuvscroll_stream(lib, frames):
+    say(f"## yuvscroll stream: {frames} frames, each the page scrolled by 64 (one TexSubImage2D of the window per frame), one I420 delta grab per frame, frames/s")
+    w = Window(lib)
+    gl = w.gl
+    page = np.random.default_rng(6).integers(0, 256, (H + 64 * frames, W, 4), dtype=np.uint8)
+    nbytes = W * H * 3 // 2
+    host = np.zeros(nbytes, np.uint8)
+    dev = gl.device_alloc(nbytes)
+    info = glapi.WrhipGrabInfo()
+
+    def run(mode, n):
+        waiting, crossed = [], []
+
+        def fetch(wait):
+            while waiting:
+                rc = gl.WrhipGrabResultGet(waiting[0], C.byref(info), host.ctypes.data, 0, 1 if wait else 0)
+                if rc == 1:
+                    return
+                assert rc == 0 and info.status == 0, (rc, info.status)
+                waiting.pop(0)
+                crossed.append(int(info.bytes))
+                wait = False
+        w.upload(0, 0, page[:H])
+        if mode is not None:
+            scroll, device = mode
+            _yuv_delta_grab(w, scroll, dev if device else 0, nbytes, key=True)
+        gl.Finish()
+        t0 = time.perf_counter()
+        for k in range(1, n + 1):
+            w.upload(0, 0, page[64 * k:64 * k + H])
+            if mode is not None:
+                if len(waiting) == 8:
+                    fetch(True)
+                waiting.append(_yuv_delta_grab(w, scroll, dev if device else 0, nbytes, wait=False))
+                fetch(False)
+        gl.Finish()
+        while waiting:
+            fetch(True)
+        return n / (time.perf_counter() - t0), float(np.mean(crossed)) if crossed else 0.0
+    modes = {"no grab": None, "plain delta, host": (False, False), "scroll delta, host": (True, False), "plain delta, device": (False, True), "scroll delta, device": (True, True)}
+    for mode in modes.values():
+        run(mode, 10)
+    rows = {}
+    for rnd in range(ROUNDS):
+        for name, mode in modes.items():
+            rows.setdefault(name, []).append(run(mode, frames))
+    for name, v in rows.items():
+        say(f"  {name:22s} " + "  ".join(f"{fps:9.1f}" for fps, _ in v) + "   frames/s   " + (f"({v[0][1] / 1e6:8.3f} MB per frame crossed)" if v[0][1] else ""))
+    gl.device_free(dev)
+    w.close()
+
+
 def section_ab(other, steps, warmup):
     say(f"## ab: bench.py --gpus 1 --steps {steps} --warmup {warmup} (cfg2), this library against {os.path.basename(other)}, alternated, frames/s")
     rows = {"parent": [], "this": []}
@@ -1304,6 +1415,9 @@ def main():
             elif s == "yuv_scaled":
                 section_yuv_scaled(lib)
                 section_yuv_scaled_stream(lib, args.frames)
+            elif s == "yuvscroll":
+                section_yuvscroll_kernel(lib)
+                section_yuvscroll_stream(lib, args.frames)
             elif s == "scroll":
                 section_scroll_kernel(lib, only=args.scroll_case)
                 if not args.scroll_case:

@@ -237,17 +237,118 @@ static inline void wr_gc_yuv_patch(const uint8_t* p, const WrGrabEntry& E, uint3
     }
   }
 }
+// The payload of a scroll-aware delta YUV grab (WrhipGrabTextureYuvDelta with WRHIP_GRAB_SCROLL): header word 1 is dy, the scroll
+// vector (int32, |dy| <= 512), and every record is x, y, w | h << 8 | mode << 16, 0 -- the packed payload's record layout.
+//   SAMPLES 0  the record, then the block's planes as a delta YUV entry lays them out: wr_gc_yuv_entry_size(format) bytes
+//   COPY    3  the record alone: the block takes, in every plane, the samples the planes had BEFORE the decode dy luma rows further
+//              down -- chroma rows dy / 2 further down in 4:2:0, where dy is even.  dy is not 0 then, and the source rows lie
+//              inside the image.
+// The decode is in place: the COPY entries first, by ascending y for dy > 0 and descending y for dy < 0, then the SAMPLES entries.
+// the record at `p` (avail bytes of the payload from it on) against an image of rw x rh and the vector dy: false unless it is one
+// the format allows; E->size: the whole entry's
+static inline bool wr_gc_yuv_scroll_record(const uint8_t* p, size_t avail, uint32_t format, int rw, int rh, int32_t dy, WrGrabEntry* E) {
+  if (avail < 16) return false;
+  const uint32_t x = wr_gc_load32(p), y = wr_gc_load32(p + 4), w2 = wr_gc_load32(p + 8), w3 = wr_gc_load32(p + 12);
+  const uint32_t w = w2 & 0xFFu, h = (w2 >> 8) & 0xFFu, mode = w2 >> 16;
+  if ((mode != WR_GC_RAW && mode != WR_GC_COPY) || w3 != 0) return false;
+  if (x % WR_GC_BLOCK || y % WR_GC_BLOCK || x >= (uint32_t)rw || y >= (uint32_t)rh) return false;
+  const uint32_t bw = (uint32_t)rw - x < WR_GC_BLOCK ? (uint32_t)rw - x : WR_GC_BLOCK, bh = (uint32_t)rh - y < WR_GC_BLOCK ? (uint32_t)rh - y : WR_GC_BLOCK;
+  if (w != bw || h != bh) return false;
+  E->x = (int32_t)x; E->y = (int32_t)y; E->w = (int32_t)w; E->h = (int32_t)h; E->mode = (int32_t)mode; E->aux = 0;
+  if (mode == WR_GC_COPY) {
+    if (dy == 0 || dy < -WR_GC_SCROLL_MAX || dy > WR_GC_SCROLL_MAX || (format != 2 && (dy & 1))) return false;
+    const int64_t sy = (int64_t)y + dy;
+    if (sy < 0 || sy + (int64_t)h > (int64_t)rh) return false;
+    E->size = 16;
+    return true;
+  }
+  E->size = wr_gc_yuv_entry_size(format);
+  return E->size <= avail;
+}
+// one COPY entry in place, all planes: each plane's rows in the order in which a row's source has not been written yet
+static inline void wr_gc_yuv_copy(const WrGrabCopy& E, int32_t dy, uint32_t format, uint8_t* y, size_t ys, uint8_t* c0, uint8_t* c1, size_t cs) {
+  wr_gc_copy(E, dy, 1, y, ys);
+  if (format == 2) { wr_gc_copy(E, dy, 1, c0, cs); wr_gc_copy(E, dy, 1, c1, cs); return; }
+  // (4:2:0: the block's chroma samples, (w + 1) / 2 x (h + 1) / 2 of them from (x / 2, y / 2) on, move by dy / 2 rows)
+  const WrGrabCopy C = {E.x / 2, E.y / 2, (E.w + 1) / 2, (E.h + 1) / 2};
+  if (format == 1) wr_gc_copy(C, dy / 2, 2, c0, cs);
+  else { wr_gc_copy(C, dy / 2, 1, c0, cs); wr_gc_copy(C, dy / 2, 1, c1, cs); }
+}
+// the record of a scroll payload's entry (mode: WR_GC_RAW for SAMPLES, WR_GC_COPY), written to `out`
+static inline void wr_gc_yuv_encode_record(int x, int y, int w, int h, int mode, uint8_t* out) {
+  wr_gc_store32(out, (uint32_t)x); wr_gc_store32(out + 4, (uint32_t)y);
+  wr_gc_store32(out + 8, (uint32_t)w | (uint32_t)h << 8 | (uint32_t)mode << 16); wr_gc_store32(out + 12, 0u);
+}
+// A whole scroll payload checked and patched: wr_gc_decode_yuv's second half (its arguments checked there).  A block named twice is
+// refused, and nothing is written before every entry has been checked.
+static inline int wr_gc_decode_yuv_scroll(const uint8_t* p, uint64_t count, uint32_t format, int rw, int rh, uint8_t* y, size_t ys,
+                                          uint8_t* c0, uint8_t* c1, size_t cs, int32_t dy, int32_t damage[4], uint32_t* blocks, uint32_t* copied) {
+  if (dy < -WR_GC_SCROLL_MAX || dy > WR_GC_SCROLL_MAX) return -1;
+  const size_t bx = (size_t)(rw + WR_GC_BLOCK - 1) / WR_GC_BLOCK, by = (size_t)(rh + WR_GC_BLOCK - 1) / WR_GC_BLOCK;
+  uint8_t* seen = (uint8_t*)calloc(bx * by, 1);
+  if (!seen) return -1;
+  int x0 = rw, y0 = rh, x1 = 0, y1 = 0;
+  uint32_t n = 0;
+  size_t ncopy = 0;
+  WrGrabEntry E;
+  for (uint64_t at = 0; at < count; at += E.size, n++) {
+    if (!wr_gc_yuv_scroll_record(p + at, (size_t)(count - at), format, rw, rh, dy, &E)) { free(seen); return -1; }
+    uint8_t& s = seen[(size_t)(E.y / WR_GC_BLOCK) * bx + (size_t)(E.x / WR_GC_BLOCK)];
+    if (s) { free(seen); return -1; }
+    s = 1;
+    if (E.mode == WR_GC_COPY) ncopy++;
+    x0 = E.x < x0 ? E.x : x0; y0 = E.y < y0 ? E.y : y0;
+    x1 = E.x + E.w > x1 ? E.x + E.w : x1; y1 = E.y + E.h > y1 ? E.y + E.h : y1;
+  }
+  free(seen);
+  if (y && ncopy) {
+    WrGrabCopy* copies = (WrGrabCopy*)malloc(ncopy * sizeof(WrGrabCopy));
+    if (!copies) return -1;
+    size_t k = 0;
+    for (uint64_t at = 0; at < count; at += E.size) {
+      wr_gc_yuv_scroll_record(p + at, (size_t)(count - at), format, rw, rh, dy, &E);
+      if (E.mode == WR_GC_COPY) copies[k++] = WrGrabCopy{E.x, E.y, E.w, E.h};
+    }
+    wr_gc_copy_order(copies, ncopy);
+    for (size_t i = 0; i < ncopy; i++) wr_gc_yuv_copy(copies[dy > 0 ? i : ncopy - 1 - i], dy, format, y, ys, c0, c1, cs);
+    free(copies);
+  }
+  if (y) {
+    for (uint64_t at = 0; at < count; at += E.size) {
+      wr_gc_yuv_scroll_record(p + at, (size_t)(count - at), format, rw, rh, dy, &E);
+      if (E.mode != WR_GC_COPY) wr_gc_yuv_patch(p + at, E, format, y, ys, c0, c1, cs);
+    }
+  }
+  if (copied) *copied = (uint32_t)ncopy;
+  if (damage) {
+    damage[0] = damage[1] = damage[2] = damage[3] = 0;
+    if (x1 > x0 && y1 > y0) { damage[0] = x0; damage[1] = y0; damage[2] = x1 - x0; damage[3] = y1 - y0; }
+  }
+  if (blocks) *blocks = n;
+  return 0;
+}
 // A whole payload patched into the caller's planes (byte strides, 0: tight; NV12: c0 the pairs, c1 NULL; y, c0 and c1 all NULL:
 // only checked): 0, with the bounding box of the entries' blocks and their number, or -1 for a malformed one -- a count that is
-// not k entries or more than the caller holds, a record that is not a block of the image, more entries than blocks -- or for
-// planes given in part or with a stride below a row; nothing is written then.
+// not k entries or more than the caller holds, a record that is not a block of the image, more entries than blocks, a non-zero
+// header word 1 -- or for planes given in part or with a stride below a row; nothing is written then.
+// scroll: a scroll grab's payload (above); `copied`: its COPY entries.
 static inline int wr_gc_decode_yuv(const void* payload, uint64_t bytes, uint32_t format, int rw, int rh, void* y, int64_t y_stride,
-                                   void* c0, void* c1, int64_t c_stride, int32_t damage[4], uint32_t* blocks) {
+                                   void* c0, void* c1, int64_t c_stride, int32_t damage[4], uint32_t* blocks, bool scroll = false,
+                                   uint32_t* copied = nullptr) {
   if (!payload || bytes < WR_GC_HEADER || format > 2 || rw < 1 || rh < 1) return -1;
   const int64_t c_row = format == 2 ? rw : format == 1 ? 2 * (((int64_t)rw + 1) / 2) : ((int64_t)rw + 1) / 2;
   const bool patch = y || c0 || c1;
   if (patch && (!y || !c0 || (format == 1 ? c1 != nullptr : c1 == nullptr))) return -1;
   if (patch && ((y_stride != 0 && y_stride < rw) || (c_stride != 0 && c_stride < c_row))) return -1;
+  const int32_t dy = (int32_t)wr_gc_load32((const uint8_t*)payload + 4);
+  if (!scroll && dy != 0) return -1;
+  if (copied) *copied = 0;
+  if (scroll) {
+    const uint64_t n = wr_gc_load32((const uint8_t*)payload);
+    if (n > bytes - WR_GC_HEADER) return -1;
+    return wr_gc_decode_yuv_scroll((const uint8_t*)payload + WR_GC_HEADER, n, format, rw, rh, (uint8_t*)y, y_stride ? (size_t)y_stride : (size_t)rw,
+                                   (uint8_t*)c0, (uint8_t*)c1, c_stride ? (size_t)c_stride : (size_t)c_row, dy, damage, blocks, copied);
+  }
   const uint8_t* p = (const uint8_t*)payload;
   const uint64_t count = wr_gc_load32(p), entry = wr_gc_yuv_entry_size(format);
   const uint64_t total = (uint64_t)((rw + WR_GC_BLOCK - 1) / WR_GC_BLOCK) * (uint64_t)((rh + WR_GC_BLOCK - 1) / WR_GC_BLOCK);

@@ -255,6 +255,10 @@ struct Texture {
   // keyframe.  Apart from the plain delta grabs' copy above: neither invalidates the other.
   void* yuv_keep = nullptr;
   size_t yuv_keep_size = 0;
+  // (WRHIP_GRAB_SCROLL: a second set of planes, which such a grab writes whole and then exchanges with yuv_keep; its content means
+  // nothing between grabs)
+  void* yuv_keep2 = nullptr;
+  size_t yuv_keep2_size = 0;
   int yuv_rect[4] = {0, 0, 0, 0};
   uint32_t yuv_format = 0, yuv_space = 0, yuv_flip = 0;
   const void* yuv_dst = nullptr;
@@ -689,7 +693,9 @@ struct Context {
   // and the ticket carries an empty payload; otherwise they are the ticket's payload, and args.y, cb, cr are offsets from its start
   struct GrabYuv { bool device; WrGrabYuvArgs args; uint64_t out_bytes, dst_extent; };
   // WrhipGrabTextureYuvDelta: the launch as it goes out (the slot is filled in when it is issued).  dst_extent as GrabYuv's (device sink)
-  struct GrabYuvDelta { WrGrabYuvDeltaArgs args; uint64_t keep_bytes, dst_extent; };
+  // scroll: WRHIP_GRAB_SCROLL -- next_y, next_cb, next_cr: the planes the grab leaves the image's samples in (WrGrabYuvScrollArgs): the
+  // second set, or, on a keyframe made when the call was, the retained planes themselves
+  struct GrabYuvDelta { WrGrabYuvDeltaArgs args; uint64_t keep_bytes, dst_extent; bool scroll; uint8_t* next_y; uint8_t* next_cb; uint8_t* next_cr; };
   // WrhipGrabTextureYuvScaled as it was asked for: the chain (`scale`; flip and swap_rb unused) and the planes of its `n` renditions
   // -- r[k]: level k as a YUV grab of a dw << k x dh << k image would lay it out; a host sink's offsets count from the start of the
   // payload, the renditions one after another.  The launches are laid out when it is issued, as a scaled grab's.  cross: rendition 0
@@ -1339,7 +1345,7 @@ Context::~Context() {
   flush_all();
   flush_uploads(1206);
   sync_stream();
-  for (Texture* t : textures.objects) if (t) { if (t->dptr) wrrt::dev_free(t->dptr); t->dptr = nullptr; free(t->hmirror); t->hmirror = nullptr; if (t->grab_keep) wrrt::dev_free(t->grab_keep); t->grab_keep = nullptr; if (t->yuv_keep) wrrt::dev_free(t->yuv_keep); t->yuv_keep = nullptr; }
+  for (Texture* t : textures.objects) if (t) { if (t->dptr) wrrt::dev_free(t->dptr); t->dptr = nullptr; free(t->hmirror); t->hmirror = nullptr; if (t->grab_keep) wrrt::dev_free(t->grab_keep); t->grab_keep = nullptr; if (t->yuv_keep) wrrt::dev_free(t->yuv_keep); t->yuv_keep = nullptr; if (t->yuv_keep2) wrrt::dev_free(t->yuv_keep2); t->yuv_keep2 = nullptr; }
   for (auto& kv : pool) wrrt::dev_free(kv.second);
   pool.clear();
   wrrt::dev_free(dupload); wrrt::dev_free(dcounters);
@@ -1860,6 +1866,41 @@ void grab_issue_yuv_delta(uint64_t n, const Context::GrabYuvDelta& g, bool notif
   a.g.slot = notify ? gs.dev : nullptr;
   if (a.g.slot && !a.keyframe) wrrt::memset8(a.g.slot, 0, WR_GRAB_HEADER, c->stream);
   const uint64_t workgroups = (uint64_t)a.bx * a.by;
+  if (g.scroll) {
+    // WRHIP_GRAB_SCROLL: probe, vote, pack (wrhip_k_pixels.h); a keyframe is the probe alone, and leaves its samples in next_* too
+    WrGrabYuvScrollArgs s;
+    memset(&s, 0, sizeof(s));
+    s.d = a;
+    s.next_y = g.next_y; s.next_cb = g.next_cb; s.next_cr = g.next_cr;
+    prof_begin();
+    if (a.keyframe) {
+      WR_LAUNCH(wr_grab_yuv_scroll_probe_kernel, (int)workgroups, 256, c->stream, s);
+      prof_end(WR_KIND_GRAB, WR_FMT_RGBA8, 0, 9, (uint64_t)a.g.w * a.g.h * 4 + g.keep_bytes, workgroups);
+      c->stats.kernel_launches++;
+    } else {
+      const int h = a.g.h;
+      const size_t segs = grab_scroll_segments(a.bx, h);
+      WrGrabScrollArgs v;              // (the vote's launch: the work memory, and of `g` the blocks and the image's height)
+      memset(&v, 0, sizeof(v));
+      v.g.bx = a.bx; v.g.by = a.by; v.g.rects[0][2] = a.g.w; v.g.rects[0][3] = h;
+      v.hash_cur = (unsigned long long*)c->grab_scroll_work; v.hash_prev = v.hash_cur + segs;
+      v.rowdiff = v.hash_prev + segs; v.votes = (unsigned*)(v.rowdiff + workgroups);
+      v.dmax = std::min(WR_GRAB_SCROLL_MAX, h - 1);
+      v.row_tiles = (h + WR_SCROLL_VOTE_ROWS - 1) / WR_SCROLL_VOTE_ROWS; v.dy_chunks = (2 * v.dmax + 1 + 255) / 256;
+      s.hash_cur = v.hash_cur; s.hash_prev = v.hash_prev; s.rowdiff = v.rowdiff; s.votes = v.votes;
+      s.changed = v.votes + (2 * WR_GRAB_SCROLL_MAX + 1);
+      const int vote_grid = a.bx * v.row_tiles * v.dy_chunks;
+      WR_LAUNCH(wr_grab_yuv_scroll_probe_kernel, (int)workgroups, 256, c->stream, s);
+      WR_LAUNCH(wr_grab_scroll_vote_kernel, vote_grid, 256, c->stream, v);
+      WR_LAUNCH(wr_grab_yuv_scroll_pack_kernel, (int)workgroups, 256, c->stream, s);
+      // (15, feat 9: the three launches as one entry; the rect and the retained planes read and the second planes written by the
+      // probe -- what the changed blocks then read and write is not known here and is not counted)
+      prof_end(WR_KIND_GRAB, WR_FMT_RGBA8, 0, 9, (uint64_t)a.g.w * a.g.h * 4 + 2 * g.keep_bytes, 2 * workgroups + (uint64_t)vote_grid);
+      c->stats.kernel_launches += WRHIP_GRAB_YUV_SCROLL_LAUNCHES;
+    }
+    if (notify) grab_push(gs, a.g.payload, true);
+    return;
+  }
   prof_begin();
   WR_LAUNCH(wr_grab_yuv_delta_kernel, (int)workgroups, 256, c->stream, a);
   // (15, feat 6: wr_grab_yuv_delta_kernel; the rect and -- unless a keyframe, which writes them -- the retained planes read; what
@@ -1971,7 +2012,13 @@ void grab_issue_parked() {
       grab_issue_yuv_delta(p.n, p.yuvd, gs.n == p.n);
       continue;
     }
-    if (gs.n != p.n) { if (p.args.delta && st == stale.end()) stale.push_back(p.args.keep); continue; }
+    if (gs.n != p.n) {
+      // (a scroll YUV grab would have left the image in its next_* planes, which are the retained ones for whatever follows it)
+      const uint8_t* const left = p.kind == Context::GRAB_YUV_DELTA && p.yuvd.scroll ? p.yuvd.next_y : p.args.keep;
+      if (p.args.delta && st == stale.end()) stale.push_back(left);
+      else if (p.args.delta) *st = left;
+      continue;
+    }
     if (p.args.delta && st != stale.end()) { p.args.keyframe = 1; gs.keyframe = true; stale.erase(st); }
     if (p.kind == Context::GRAB_YUV_DELTA) {
       if (p.args.keyframe) { p.yuvd.args.keyframe = 1; p.yuvd.args.g.payload = (uint32_t)WR_YUVD_ENTRY(p.yuvd.args.g.format) * (uint32_t)(p.yuvd.args.bx * p.yuvd.args.by); }
@@ -2002,6 +2049,7 @@ void grab_forget(Texture& t, bool release) {
   if (!release) return;
   grab_release(t.grab_keep, t.grab_keep_size);
   grab_release(t.yuv_keep, t.yuv_keep_size);
+  grab_release(t.yuv_keep2, t.yuv_keep2_size);
 }
 Context::GrabSlot* grab_find(int32_t ticket) {
   Context* c = ctx;
@@ -4730,7 +4778,10 @@ int32_t WrhipGrabTextureYuvDelta(GLuint tex, const int32_t rect[4], const WrhipY
   if (!ctx) return -1;
   Context* c = ctx;
   Texture* t = tex ? c->textures.find(tex) : nullptr;
-  if (flags & ~WRHIP_GRAB_KEY) { c->last_error = GL_INVALID_VALUE; return -1; }
+  // (SCROLL is spelt DELTA | SCROLL, as on WrhipGrabTexture: either bit without the other is refused, as both have always been here)
+  const uint32_t ds = WRHIP_GRAB_DELTA | WRHIP_GRAB_SCROLL;
+  const bool scroll = (flags & ds) == ds;
+  if ((flags & ~(WRHIP_GRAB_KEY | ds)) || ((flags & ds) && !scroll)) { c->last_error = GL_INVALID_VALUE; return -1; }
   Context::GrabYuv y;
   if (!grab_yuv_prepare(t, rect, desc, y)) return -1;
   Context::GrabYuvDelta g;
@@ -4763,6 +4814,23 @@ int32_t WrhipGrabTextureYuvDelta(GLuint tex, const int32_t rect[4], const WrhipY
     if (!t->yuv_keep) { out_of_memory(); return -1; }
     keyframe = true;
   }
+  // WRHIP_GRAB_SCROLL: the second planes, which the probe writes whole, and the work memory of the three launches (the scroll
+  // grab's, with a word per block behind it; it only grows: a parked grab finds at least what it asked for when it is issued)
+  if (scroll && !keyframe) {
+    if (!t->yuv_keep2 || t->yuv_keep2_size < keep_need) {
+      grab_release(t->yuv_keep2, t->yuv_keep2_size);
+      size_t actual = 0;
+      t->yuv_keep2 = pool_alloc(keep_need, &actual);
+      t->yuv_keep2_size = actual;
+      if (!t->yuv_keep2) { t->yuv_valid = false; out_of_memory(); return -1; }
+    }
+    const size_t work = grab_scroll_work_need(bx, by, rect[3]) + (size_t)bx * by * 4;
+    if (work > c->grab_scroll_work_size) {
+      if (c->grab_scroll_work) pool_free(c->grab_scroll_work, c->grab_scroll_work_size);
+      c->grab_scroll_work = pool_alloc(work, &c->grab_scroll_work_size);
+      if (!c->grab_scroll_work) { c->grab_scroll_work_size = 0; t->yuv_valid = false; out_of_memory(); return -1; }
+    }
+  }
   memcpy(t->yuv_rect, rect, sizeof(t->yuv_rect));
   t->yuv_format = desc->format; t->yuv_space = desc->color_space; t->yuv_flip = desc->flags & WRHIP_GRAB_FLIP_ROWS;
   t->yuv_dst = desc->dst; memcpy(t->yuv_strides, strides, sizeof(strides));
@@ -4771,6 +4839,15 @@ int32_t WrhipGrabTextureYuvDelta(GLuint tex, const int32_t rect[4], const WrhipY
   a.keyframe = keyframe ? 1 : 0;
   a.g.payload = keyframe ? (uint32_t)((uint64_t)bx * by * entry) : 0u;
   g.keep_bytes = keep_need;
+  g.scroll = scroll;
+  g.next_y = a.keep_y; g.next_cb = a.keep_cb; g.next_cr = a.keep_cr;
+  if (scroll && !keyframe) {
+    // (the exchange: the grab reads the retained planes and leaves the image in the second set, which every later grab -- in
+    // stream order behind this one -- finds as the retained planes)
+    g.next_y = (uint8_t*)t->yuv_keep2; g.next_cb = g.next_y + y_bytes; g.next_cr = g.next_cb + c_bytes;
+    std::swap(t->yuv_keep, t->yuv_keep2);
+    std::swap(t->yuv_keep_size, t->yuv_keep2_size);
+  }
   const uint64_t n = c->grab_next++;
   gs.n = n; gs.counted = false;
   gs.format = t->internal_format; gs.flags = desc->flags | flags | WRHIP_GRAB_YUV | WRHIP_GRAB_DELTA; gs.bpp = t->bpp; gs.nrects = 1;
@@ -4792,7 +4869,9 @@ int32_t WrhipGrabTextureYuvDelta(GLuint tex, const int32_t rect[4], const WrhipY
 }
 int32_t WrhipGrabDecodeYuv(const void* payload, uint64_t bytes, uint32_t format, int32_t rect_w, int32_t rect_h, void* y, int64_t y_stride,
                            void* c0, void* c1, int64_t c_stride, int32_t damage[4], uint32_t* blocks) {
-  return wr_gc_decode_yuv(payload, bytes, format, rect_w, rect_h, y, y_stride, c0, c1, c_stride, damage, blocks);
+  // (format | WRHIP_GRAB_SCROLL: a scroll grab's payload)
+  const bool scroll = (format & WRHIP_GRAB_SCROLL) != 0;
+  return wr_gc_decode_yuv(payload, bytes, format & ~WRHIP_GRAB_SCROLL, rect_w, rect_h, y, y_stride, c0, c1, c_stride, damage, blocks, scroll);
 }
 // A tensor put: see include/wrhip.h.  A texture write at its place in the call order -- TexSubImage2D's ordering, one launch on the
 // draw stream instead of staged rows.  Arguments are checked before anything is flushed or launched.
@@ -4973,7 +5052,31 @@ int32_t WrhipGrabResultGet(int32_t ticket, WrhipGrabInfo* info, void* dst, int64
     r.blocks = (uint32_t)(payload / entry); r.blocks_total = gs->blocks_total;
     int x0 = rw, y0 = rh, x1 = 0, y1 = 0;
     WrGrabEntry E;
-    for (size_t at = 0; at + entry <= payload; at += entry) {
+    // (a scroll grab: header word 1 is the vector, records carry a mode and entries differ in size -- behind one that is not an entry
+    // nothing can be found any more.  Its COPY entries are applied first, in the codec's order, then the SAMPLES entries)
+    const bool scroll = (gs->flags & WRHIP_GRAB_SCROLL) != 0;
+    if (scroll) {
+      int32_t dy = 0;
+      memcpy(&dy, gs->host + 4, 4);
+      if (dy < -WRHIP_GRAB_SCROLL_MAX || dy > WRHIP_GRAB_SCROLL_MAX) { r.status = 1; dy = 0; }
+      r.scroll_dy = dy;
+      r.blocks = 0;
+      std::vector<WrGrabCopy> copies;
+      std::vector<std::pair<size_t, WrGrabEntry>> found;
+      for (size_t at = 0; at + 16 <= payload; at += gs->yuv_device ? 16 : E.size) {
+        // (device sink: the records alone, so a SAMPLES entry's size is not looked for in the payload)
+        if (!wr_gc_yuv_scroll_record(src + at, gs->yuv_device ? ~(size_t)0 : payload - at, fmt, rw, rh, dy, &E)) { r.status = 1; break; }
+        r.blocks++;
+        x0 = std::min(x0, E.x); y0 = std::min(y0, E.y); x1 = std::max(x1, E.x + E.w); y1 = std::max(y1, E.y + E.h);
+        if (E.mode == WR_GC_COPY) { r.copied++; if (py) copies.push_back(WrGrabCopy{E.x, E.y, E.w, E.h}); }
+        else if (py) found.push_back(std::make_pair(at, E));
+      }
+      const size_t nc = copies.size();
+      if (nc && !wr_gc_copy_order(copies.data(), nc)) { r.status = 1; copies.clear(); }
+      for (size_t i = 0; i < copies.size(); i++) wr_gc_yuv_copy(copies[dy > 0 ? i : copies.size() - 1 - i], dy, fmt, py, (size_t)rw, pc0, pc1, c_row);
+      for (const auto& f : found) wr_gc_yuv_patch(src + f.first, f.second, fmt, py, (size_t)rw, pc0, pc1, c_row);
+    }
+    for (size_t at = 0; !scroll && at + entry <= payload; at += entry) {
       if (!wr_gc_yuv_record(src + at, rw, rh, &E)) { r.status = 1; continue; }
       x0 = std::min(x0, E.x); y0 = std::min(y0, E.y); x1 = std::max(x1, E.x + E.w); y1 = std::max(y1, E.y + E.h);
       if (py) wr_gc_yuv_patch(src + at, E, fmt, py, (size_t)rw, pc0, pc1, c_row);

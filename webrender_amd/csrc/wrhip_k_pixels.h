@@ -1623,6 +1623,304 @@ __global__ void __launch_bounds__(256) wr_grab_scroll_update_kernel(WrGrabScroll
     if (wr_grab_piece(a, B, piece, v, r, o)) wr_grab_st16(B.pk + (size_t)r * a.keep_stride + o, v);
   }
 }
+// WrhipGrabTextureYuvDelta with WRHIP_GRAB_DELTA | WRHIP_GRAB_SCROLL (include/wrhip.h; WrGrabYuvScrollArgs): the delta YUV grab that first finds the one
+// vertical scroll most of the changed LUMA made, and sends a block whose samples -- every plane -- equal the retained planes
+// scroll_dy rows away as a 16-byte COPY record.  Three launches on the draw stream; blocks, items and their six words are
+// wr_grab_yuv_delta_kernel's.
+//   probe   converts the block once and writes its samples into the SECOND set of planes (next_*), whole.  It compares them with the
+//           retained planes at their own place -- luma rows into the block's row mask, any plane into `changed` -- and hashes every
+//           luma segment of both: a thread's eight bytes of a row through wr_scroll_piece_hash, added up over the eight lanes that
+//           share the row.  A keyframe is this launch alone: it compares nothing and writes entry i = block i.
+//   vote    wr_grab_scroll_vote_kernel, as it is: it sees hashes, row masks and the image's height.  It votes for odd vectors too.
+//   pack    every workgroup of a changed block reduces the votes to scroll_dy -- odd candidates passed over in 4:2:0, where no chroma
+//           sample survives them; block 0 stores it into header word 1 --, compares the block's samples in next_* EXACTLY with the
+//           retained planes scroll_dy luma rows away (chroma: scroll_dy / 2 rows in 4:2:0) and takes a COPY record or a SAMPLES
+//           entry with ONE returning atomic on the slot's byte count.  Device sink: a COPY block's samples go from the RETAINED
+//           planes into the caller's, a SAMPLES block's from next_*.  Neither set of planes is written by this launch.
+// The host then exchanges the two sets: no update launch.
+template <int FMT> WR_DEVICE WrYuvdHome wr_yuvs_home(uint8_t* y, uint8_t* cb, uint8_t* cr, int ys, int cs, int x0, int y0) {
+  WrYuvdHome K;
+  K.ys = ys; K.cs = cs;
+  K.y = y + (size_t)y0 * ys + x0;
+  const size_t c = FMT == WR_YUV_I444 ? (size_t)y0 * cs + x0 : (size_t)(y0 >> 1) * cs + (FMT == WR_YUV_NV12 ? x0 : x0 >> 1);
+  K.c0 = cb + c; K.c1 = cr + c;
+  return K;
+}
+// item j's six words as a home holds them (wr_yuvd_store's places)
+template <int FMT> WR_DEVICE void wr_yuvs_load(const WrYuvdHome& K, int j, uint32_t (&e)[6]) {
+  const int i = j & 7, r = j >> 3;
+  if (FMT == WR_YUV_I444) {
+    wr_yuv_ld8(K.y + (size_t)r * K.ys + 8 * i, e[0], e[1]);
+    wr_yuv_ld8(K.c0 + (size_t)r * K.cs + 8 * i, e[2], e[3]);
+    wr_yuv_ld8(K.c1 + (size_t)r * K.cs + 8 * i, e[4], e[5]);
+  } else {
+    wr_yuv_ld8(K.y + (size_t)(2 * r) * K.ys + 8 * i, e[0], e[1]);
+    wr_yuv_ld8(K.y + (size_t)(2 * r + 1) * K.ys + 8 * i, e[2], e[3]);
+    if (FMT == WR_YUV_NV12) wr_yuv_ld8(K.c0 + (size_t)r * K.cs + 8 * i, e[4], e[5]);
+    else { e[4] = wr_load4(K.c0 + (size_t)r * K.cs + 4 * i); e[5] = wr_load4(K.c1 + (size_t)r * K.cs + 4 * i); }
+  }
+}
+// -> item j of the block at (x0, y0) has samples inside the image (wr_yuvd_convert's rule); second: so has its lower luma row (4:2:0)
+template <int FMT> WR_DEVICE bool wr_yuvs_on(const WrGrabYuvArgs& a, int x0, int y0, int j, bool& second) {
+  const int cx = x0 + 8 * (j & 7), ra = y0 + (FMT == WR_YUV_I444 ? j >> 3 : 2 * (j >> 3));
+  second = FMT != WR_YUV_I444 && ra + 1 < a.h;
+  return cx < a.w && ra < a.h;
+}
+// the words that are luma: of the item's row, and of its lower row (4:2:0)
+WR_DEVICE bool wr_yuvs_luma_differs(const uint32_t (&w)[6], const uint32_t (&e)[6], int k) { return ((w[2 * k] ^ e[2 * k]) | (w[2 * k + 1] ^ e[2 * k + 1])) != 0u; }
+// any sample of the item; a lower luma row outside the image is not one
+template <int FMT> WR_DEVICE bool wr_yuvs_differs(const uint32_t (&w)[6], const uint32_t (&e)[6], bool second) {
+  uint32_t x = (w[0] ^ e[0]) | (w[1] ^ e[1]) | (w[4] ^ e[4]) | (w[5] ^ e[5]);
+  if (FMT == WR_YUV_I444 || second) x |= (w[2] ^ e[2]) | (w[3] ^ e[3]);
+  return x != 0u;
+}
+WR_DEVICE unsigned long long wr_yuvs_hash(uint32_t lo, uint32_t hi, int pos) { return wr_scroll_piece_hash(wr_u4{lo, hi, 0u, 0u}, pos); }
+WR_DEVICE wr_u4 wr_yuvs_record(int x0, int y0, int bw, int bh, unsigned mode) { return wr_u4{(uint32_t)x0, (uint32_t)y0, (uint32_t)bw | (uint32_t)bh << 8 | mode << 16, 0u}; }
+// lm: three LDS words -- the mask of differing luma rows, and "a sample differs"; unused by the host simulation
+template <int FMT> WR_DEVICE void wr_grab_yuv_scroll_probe_block(const WrGrabYuvScrollArgs& s, unsigned* lm) {
+  constexpr int ITEMS = FMT == WR_YUV_I444 ? 2 : 1;      // per thread
+  const WrGrabYuvDeltaArgs& d = s.d;
+  const WrGrabYuvArgs& a = d.g;
+  const int t = (int)threadIdx.x, b = (int)blockIdx.x;
+  const int x0 = (b % d.bx) * WR_GRAB_BLOCK, y0 = (b / d.bx) * WR_GRAB_BLOCK;
+  const int bw = wr_imin(WR_GRAB_BLOCK, a.w - x0), bh = wr_imin(WR_GRAB_BLOCK, a.h - y0);
+  const WrYuvdHome N = wr_yuvs_home<FMT>(s.next_y, s.next_cb, s.next_cr, d.keep_ys, d.keep_cs, x0, y0);
+  if (d.keyframe) {
+    // (entry i is block i; nothing is compared)
+    const unsigned entry_bytes = d.device ? 16u : (unsigned)WR_YUVD_ENTRY(FMT);
+    uint8_t* const e = a.slot ? a.slot + WR_GRAB_HEADER + (size_t)b * entry_bytes : nullptr;
+    if (e && t == 0) wr_grab_st16(e, wr_yuvs_record(x0, y0, bw, bh, 0u));
+    const WrYuvdHome E = wr_yuvd_body<FMT>(e ? e + 16 : nullptr);
+#ifdef WRHIP_HOSTSIM
+    (void)lm;
+    if (t != 0) return;
+    for (int j = 0; j < 256 * ITEMS; j++) {
+#else
+#pragma unroll
+    for (int k = 0; k < ITEMS; k++) {
+      const int j = k * 256 + t;
+#endif
+      uint32_t w[6];
+      if (!wr_yuvd_convert<FMT>(a, x0, y0, j, w)) continue;
+      if (d.device) wr_yuvd_put<FMT>(a, x0, y0, j, w);
+      else if (e) wr_yuvd_store<FMT>(E, j, w);
+      wr_yuvd_store<FMT>(N, j, w);
+    }
+    return;
+  }
+  const WrYuvdHome K = wr_yuvs_home<FMT>(d.keep_y, d.keep_cb, d.keep_cr, d.keep_ys, d.keep_cs, x0, y0);
+  const size_t seg0 = (size_t)(b % d.bx) * (size_t)a.h + (size_t)y0;
+  unsigned long long* hc = s.hash_cur + seg0;
+  unsigned long long* hp = s.hash_prev + seg0;
+#ifdef WRHIP_HOSTSIM
+  if (t != 0) return;
+  if (b == 0) for (int i = 0; i < 2 * WR_GRAB_SCROLL_MAX + 1; i++) s.votes[i] = 0u;
+  for (int r = 0; r < bh; r++) hc[r] = hp[r] = 0ull;
+  unsigned long long mask = 0ull;
+  bool changed = false;
+  for (int j = 0; j < 256 * ITEMS; j++) {
+    uint32_t w[6], e[6];
+    bool second;
+    if (!wr_yuvd_convert<FMT>(a, x0, y0, j, w)) continue;
+    wr_yuvs_on<FMT>(a, x0, y0, j, second);
+    wr_yuvs_load<FMT>(K, j, e);
+    wr_yuvd_store<FMT>(N, j, w);
+    const int i = j & 7, row = FMT == WR_YUV_I444 ? j >> 3 : 2 * (j >> 3);
+    hc[row] += wr_yuvs_hash(w[0], w[1], i); hp[row] += wr_yuvs_hash(e[0], e[1], i);
+    if (wr_yuvs_luma_differs(w, e, 0)) mask |= 1ull << row;
+    if (second) {
+      hc[row + 1] += wr_yuvs_hash(w[2], w[3], i); hp[row + 1] += wr_yuvs_hash(e[2], e[3], i);
+      if (wr_yuvs_luma_differs(w, e, 1)) mask |= 1ull << (row + 1);
+    }
+    changed = changed || wr_yuvs_differs<FMT>(w, e, second);
+  }
+  s.rowdiff[b] = mask;
+  s.changed[b] = changed ? 1u : 0u;
+#else
+  if (b == 0) for (int i = t; i < 2 * WR_GRAB_SCROLL_MAX + 1; i += 256) s.votes[i] = 0u;
+  if (t < 3) lm[t] = 0u;
+  __syncthreads();
+  const int lane = t & 63;
+#pragma unroll
+  for (int k = 0; k < ITEMS; k++) {
+    const int j = k * 256 + t, i = j & 7, row = FMT == WR_YUV_I444 ? j >> 3 : 2 * (j >> 3);
+    uint32_t w[6], e[6];
+    bool second = false;
+    unsigned long long c0 = 0ull, p0 = 0ull, c1 = 0ull, p1 = 0ull;
+    bool dl0 = false, dl1 = false, any = false;
+    if (wr_yuvd_convert<FMT>(a, x0, y0, j, w)) {
+      wr_yuvs_on<FMT>(a, x0, y0, j, second);
+      wr_yuvs_load<FMT>(K, j, e);
+      wr_yuvd_store<FMT>(N, j, w);
+      c0 = wr_yuvs_hash(w[0], w[1], i); p0 = wr_yuvs_hash(e[0], e[1], i);
+      dl0 = wr_yuvs_luma_differs(w, e, 0);
+      if (second) {
+        c1 = wr_yuvs_hash(w[2], w[3], i); p1 = wr_yuvs_hash(e[2], e[3], i);
+        dl1 = wr_yuvs_luma_differs(w, e, 1);
+      }
+      any = wr_yuvs_differs<FMT>(w, e, second);
+    }
+    // (the eight lanes of a row, or of a row pair, are neighbours)
+    for (int m = 1; m < 8; m <<= 1) {
+      c0 += __shfl_xor(c0, m); p0 += __shfl_xor(p0, m);
+      if (FMT != WR_YUV_I444) { c1 += __shfl_xor(c1, m); p1 += __shfl_xor(p1, m); }
+    }
+    const unsigned long long bal0 = __ballot(dl0), bal1 = __ballot(dl1), bala = __ballot(any);
+    if ((lane & 7) == 0) {
+      if (row < bh) {
+        hc[row] = c0; hp[row] = p0;
+        if ((bal0 >> lane) & 0xFFull) atomicOr(&lm[row >> 5], 1u << (row & 31));
+      }
+      if (FMT != WR_YUV_I444 && row + 1 < bh) {
+        hc[row + 1] = c1; hp[row + 1] = p1;
+        if ((bal1 >> lane) & 0xFFull) atomicOr(&lm[(row + 1) >> 5], 1u << ((row + 1) & 31));
+      }
+    }
+    if (bala != 0ull && lane == 0) lm[2] = 1u;
+  }
+  __syncthreads();
+  if (t == 0) { s.rowdiff[b] = (unsigned long long)lm[0] | (unsigned long long)lm[1] << 32; s.changed[b] = lm[2]; }
+#endif
+}
+__global__ void __launch_bounds__(256) wr_grab_yuv_scroll_probe_kernel(WrGrabYuvScrollArgs s) {
+  // (a keyframe's byte count is known on the host and written here, with a vector of 0)
+  if (s.d.keyframe && s.d.g.slot && blockIdx.x == 0 && threadIdx.x == 0) wr_grab_st16(s.d.g.slot, wr_u4{s.d.g.payload, 0u, 0u, 0u});
+#ifdef WRHIP_HOSTSIM
+  unsigned* const lm = nullptr;
+#else
+  __shared__ unsigned lm[3];
+#endif
+  if (s.d.g.format == WR_YUV_I420) wr_grab_yuv_scroll_probe_block<WR_YUV_I420>(s, lm);
+  else if (s.d.g.format == WR_YUV_NV12) wr_grab_yuv_scroll_probe_block<WR_YUV_NV12>(s, lm);
+  else wr_grab_yuv_scroll_probe_block<WR_YUV_I444>(s, lm);
+}
+// lw: two LDS words -- [0]: a lane found the block to be no copy (cleared by the caller, behind a barrier); [1]: the entry's offset
+template <int FMT> WR_DEVICE void wr_grab_yuv_scroll_pack_block(const WrGrabYuvScrollArgs& s, int dy, unsigned* lw) {
+  constexpr int ITEMS = FMT == WR_YUV_I444 ? 2 : 1;      // per thread
+  const WrGrabYuvDeltaArgs& d = s.d;
+  const WrGrabYuvArgs& a = d.g;
+  const int t = (int)threadIdx.x, b = (int)blockIdx.x;
+  const int x0 = (b % d.bx) * WR_GRAB_BLOCK, y0 = (b / d.bx) * WR_GRAB_BLOCK;
+  const int bw = wr_imin(WR_GRAB_BLOCK, a.w - x0), bh = wr_imin(WR_GRAB_BLOCK, a.h - y0);
+  const WrYuvdHome N = wr_yuvs_home<FMT>(s.next_y, s.next_cb, s.next_cr, d.keep_ys, d.keep_cs, x0, y0);
+  // (the block's source in the retained planes: its rows inside the image, or the block is no copy.  dy is even in 4:2:0)
+  bool copy = dy != 0 && y0 + dy >= 0 && y0 + dy + bh <= a.h;
+  const WrYuvdHome S = wr_yuvs_home<FMT>(d.keep_y, d.keep_cb, d.keep_cr, d.keep_ys, d.keep_cs, x0, copy ? y0 + dy : y0);
+#ifdef WRHIP_HOSTSIM
+  (void)lw;
+  for (int j = 0; j < 256 * ITEMS && copy; j++) {
+    uint32_t w[6], e[6];
+    bool second;
+    if (!wr_yuvs_on<FMT>(a, x0, y0, j, second)) continue;
+    wr_yuvs_load<FMT>(N, j, w); wr_yuvs_load<FMT>(S, j, e);
+    copy = !wr_yuvs_differs<FMT>(w, e, second);
+  }
+  const unsigned size = copy || d.device ? 16u : (unsigned)WR_YUVD_ENTRY(FMT);
+  uint8_t* e = nullptr;
+  if (a.slot) {
+    e = a.slot + WR_GRAB_HEADER + atomicAdd((unsigned*)a.slot, size);
+    uint8_t rec[16];
+    wr_gc_yuv_encode_record(x0, y0, bw, bh, copy ? WR_GC_COPY : WR_GC_RAW, rec);
+    __builtin_memcpy(e, rec, 16);
+  }
+  if (copy && !d.device) return;
+  const WrYuvdHome E = wr_yuvd_body<FMT>(e ? e + 16 : nullptr);
+  for (int j = 0; j < 256 * ITEMS; j++) {
+    uint32_t w[6];
+    bool second;
+    if (!wr_yuvs_on<FMT>(a, x0, y0, j, second)) continue;
+    wr_yuvs_load<FMT>(copy ? S : N, j, w);
+    if (d.device) wr_yuvd_put<FMT>(a, x0, y0, j, w);
+    else if (e) wr_yuvd_store<FMT>(E, j, w);
+  }
+#else
+  uint32_t w[ITEMS][6];
+  bool on[ITEMS], second[ITEMS];
+#pragma unroll
+  for (int k = 0; k < ITEMS; k++) {
+    on[k] = wr_yuvs_on<FMT>(a, x0, y0, k * 256 + t, second[k]);
+    if (on[k]) wr_yuvs_load<FMT>(N, k * 256 + t, w[k]);
+  }
+  if (copy) {
+    bool diff = false;
+#pragma unroll
+    for (int k = 0; k < ITEMS; k++) {
+      if (!on[k]) continue;
+      uint32_t e[6];
+      wr_yuvs_load<FMT>(S, k * 256 + t, e);
+      diff = diff || wr_yuvs_differs<FMT>(w[k], e, second[k]);
+    }
+    if (__ballot(diff) != 0ull && (t & 63) == 0) lw[0] = 1u;
+    __syncthreads();
+    copy = lw[0] == 0u;
+  }
+  const unsigned size = copy || d.device ? 16u : (unsigned)WR_YUVD_ENTRY(FMT);
+  uint8_t* e = nullptr;
+  if (a.slot) {
+    if (t == 0) lw[1] = atomicAdd((unsigned*)a.slot, size);
+    __syncthreads();
+    e = a.slot + WR_GRAB_HEADER + lw[1];
+    if (t == 0) wr_grab_st16(e, wr_yuvs_record(x0, y0, bw, bh, copy ? 3u : 0u));
+  }
+  if (copy) {
+    // (device sink: the samples come from the library's retained planes, whatever the caller's hold)
+    if (!d.device) return;
+#pragma unroll
+    for (int k = 0; k < ITEMS; k++) {
+      if (!on[k]) continue;
+      uint32_t r[6];
+      wr_yuvs_load<FMT>(S, k * 256 + t, r);
+      wr_yuvd_put<FMT>(a, x0, y0, k * 256 + t, r);
+    }
+    return;
+  }
+  const WrYuvdHome E = wr_yuvd_body<FMT>(e ? e + 16 : nullptr);
+#pragma unroll
+  for (int k = 0; k < ITEMS; k++) {
+    if (!on[k]) continue;
+    if (d.device) wr_yuvd_put<FMT>(a, x0, y0, k * 256 + t, w[k]);
+    else if (e) wr_yuvd_store<FMT>(E, k * 256 + t, w[k]);
+  }
+#endif
+}
+__global__ void __launch_bounds__(256) wr_grab_yuv_scroll_pack_kernel(WrGrabYuvScrollArgs s) {
+  const WrGrabYuvArgs& a = s.d.g;
+  const int t = (int)threadIdx.x, b = (int)blockIdx.x;
+  const unsigned changed = s.changed[b];
+  if (changed == 0u && b != 0) return;
+  // the votes reduced to the vector (wr_scroll_key's rule); 4:2:0: even candidates alone
+  const bool even = a.format != WR_YUV_I444;
+  unsigned long long key = 0ull;
+#ifdef WRHIP_HOSTSIM
+  // (threads run one after the other: the first does it all)
+  if (t != 0) return;
+  unsigned* const lw = nullptr;
+  for (int i = 0; i < 2 * WR_GRAB_SCROLL_MAX + 1; i++) {
+    if (even && (i & 1)) continue;      // (WR_GRAB_SCROLL_MAX is even: i and dy have the same parity)
+    const unsigned long long k = wr_scroll_key(s.votes[i], i - WR_GRAB_SCROLL_MAX);
+    key = k > key ? k : key;
+  }
+#else
+  __shared__ unsigned lw[2];
+  __shared__ unsigned long long lk[4];
+  for (int i = t; i < 2 * WR_GRAB_SCROLL_MAX + 1; i += 256) {
+    if (even && (i & 1)) continue;      // (WR_GRAB_SCROLL_MAX is even: i and dy have the same parity)
+    const unsigned long long k = wr_scroll_key(s.votes[i], i - WR_GRAB_SCROLL_MAX);
+    key = k > key ? k : key;
+  }
+  for (int o = 32; o > 0; o >>= 1) { const unsigned long long k = __shfl_xor(key, o); key = k > key ? k : key; }
+  if ((t & 63) == 0) lk[t >> 6] = key;
+  if (t == 0) lw[0] = 0u;
+  __syncthreads();
+  for (int w = 0; w < 4; w++) key = lk[w] > key ? lk[w] : key;
+#endif
+  const int dy = wr_scroll_key_dy(key);
+  if (b == 0 && t == 0 && a.slot) wr_grab_st4(a.slot + 4, (uint32_t)dy);
+  if (changed == 0u) return;
+  if (a.format == WR_YUV_I420) wr_grab_yuv_scroll_pack_block<WR_YUV_I420>(s, dy, lw);
+  else if (a.format == WR_YUV_NV12) wr_grab_yuv_scroll_pack_block<WR_YUV_NV12>(s, dy, lw);
+  else wr_grab_yuv_scroll_pack_block<WR_YUV_I444>(s, dy, lw);
+}
 #endif
 
 // A solid colour on a general quad, one row at a time: the row's span from the edge instances of its run (aa_span / aa_edge /

@@ -868,6 +868,21 @@ struct WrGrabYuvDeltaArgs {
   int32_t keyframe;                    // every block is sent, entry i is block i (nothing is compared, no atomic)
   int32_t device;                      // sent samples go to g.y, g.cb, g.cr; the slot's entries are records of 16 bytes
 };
+// WrhipGrabTextureYuvDelta with WRHIP_GRAB_SCROLL: the launches of wr_grab_yuv_scroll_probe_kernel, wr_grab_scroll_vote_kernel (which
+// reads `s` alone) and wr_grab_yuv_scroll_pack_kernel (the contract: include/wrhip.h).  `d` is the delta YUV grab's launch, its
+// retained planes READ ONLY here; next_*: a second set of planes of the same layout, which the probe writes whole -- the samples of
+// the image as it is now -- and which the texture regards as its retained planes once the grab has been made.  hash_cur, hash_prev,
+// rowdiff, votes: the scroll grab's work memory (WrGrabScrollArgs, which the vote is launched with: bx, by and rects[0][3], the
+// image's height, are all it reads of `g`), the hashes of LUMA segments and rowdiff from luma rows alone; `changed`: per block, non-zero if any of its samples, chroma included, differs from the retained
+// planes at its own place.  A keyframe (d.keyframe) is the probe alone: no compare, entry i is block i, next_* written.
+struct WrGrabYuvScrollArgs {
+  WrGrabYuvDeltaArgs d;
+  uint8_t* next_y; uint8_t* next_cb; uint8_t* next_cr;
+  unsigned long long* hash_cur; unsigned long long* hash_prev;
+  unsigned long long* rowdiff;
+  unsigned* votes;
+  unsigned* changed;
+};
 // WrhipGrabTextureYuvScaled: one launch of wr_grab_scale_yuv_kernel (the contract: include/wrhip.h).  `s` is the scaled grab's launch
 // (last, flip, swap_rb unused: a level leaves `s` unflipped; slot: non-null in the launch that writes the ticket's header), `g` the
 // YUV grab's colour rows, y0, format and flip (its rect, planes and texture unused).  The launch holds levels top .. top - s.steps of

@@ -182,6 +182,7 @@ GRAB_YUV = 512            # reported in a YUV grab's info["flags"] (WrhipGrabTex
 GRAB_SCROLL = 1024        # with GRAB_DELTA | GRAB_PACKED: the scroll grab (scrolled blocks cross as 16-byte COPY entries)
 GRAB_SCROLL_MAX = 512     # the largest |scroll_dy| that is looked for
 GRAB_SCROLL_LAUNCHES = 4  # launches of a scroll grab that is no keyframe
+GRAB_YUV_SCROLL_LAUNCHES = 3  # launches of a delta YUV grab with GRAB_SCROLL that is no keyframe
 GRAB_MAX_RECTS, GRAB_HEADER, GRAB_BLOCK = 16, 16, 64
 # WrhipGrabTextureYuv: plane layouts, and the YuvRangedColorSpace values it converts to
 YUV_I420, YUV_NV12, YUV_I444 = 0, 1, 2
@@ -414,11 +415,12 @@ class GL:
         d.y_stride, d.c_stride = int(strides[0]), int(strides[1])
         return self.WrhipGrabTextureYuv(tex, C.addressof(arr), C.addressof(d))
 
-    def grab_texture_yuv_delta(self, tex, rect, format, color_space, flags=0, dst=None, dst_bytes=0, strides=(0, 0), key=False):
+    def grab_texture_yuv_delta(self, tex, rect, format, color_space, flags=0, dst=None, dst_bytes=0, strides=(0, 0), key=False, scroll=False):
         """Enqueue a delta YUV grab (include/wrhip.h, WrhipGrabTextureYuvDelta): grab_texture_yuv's arguments, but only the 64 x 64
         blocks whose samples differ from the texture's retained planes are sent -- to the host as entries that grab_result patches
         into the caller's planes (`into`), or straight into the device planes at `dst`.  key: GRAB_KEY, every block is sent (an int is
-        passed on as the call's raw `flags`).  Returns the ticket, or -1 (GL_INVALID_VALUE / GL_OUT_OF_MEMORY is then set)."""
+        passed on as the call's raw `flags`).  scroll: GRAB_DELTA | GRAB_SCROLL beside it -- blocks found scroll_dy rows away in the retained planes are
+        sent as 16-byte COPY entries, or written into the device planes from the retained ones.  Returns the ticket, or -1 (GL_INVALID_VALUE / GL_OUT_OF_MEMORY is then set)."""
         if rect is None:
             w, h = i32(0), i32(0)
             if not self.WrhipGetTextureSize(tex, C.byref(w), C.byref(h)):
@@ -429,7 +431,7 @@ class GL:
         d.format, d.color_space, d.flags = int(format), int(color_space), int(flags)
         d.dst, d.dst_bytes = (int(dst) or None) if dst is not None else None, int(dst_bytes)
         d.y_stride, d.c_stride = int(strides[0]), int(strides[1])
-        return self.WrhipGrabTextureYuvDelta(tex, C.addressof(arr), C.addressof(d), GRAB_KEY if key is True else int(key))
+        return self.WrhipGrabTextureYuvDelta(tex, C.addressof(arr), C.addressof(d), (GRAB_KEY if key is True else int(key)) | (GRAB_DELTA | GRAB_SCROLL if scroll else 0))
 
     def grab_texture_yuv_scaled(self, tex, rect, size, format, color_space, flags=0, renditions=1, dsts=None, strides=None):
         """Enqueue a scaled YUV grab (include/wrhip.h, WrhipGrabTextureYuvScaled) of `rect` = (x, y, w, h) of the RGBA8 texture id
@@ -524,7 +526,7 @@ class GL:
             # sent blocks are patched in.  A device sink's ticket carries records of 16 bytes: nothing to patch, `into` is left alone.
             # `into` None: the info alone)
             assert into is None or (into.dtype == np.uint8 and into.flags["C_CONTIGUOUS"] and into.ndim == 1), "grab_result: `into` is not flat uint8 planes"
-            if into is not None and r.blocks:
+            if into is not None and r.blocks and not r.flags & GRAB_SCROLL:      # (a scroll grab's entries differ in size)
                 w, h = rects[0][2:]
                 entry = (int(r.bytes) - GRAB_HEADER) // r.blocks      # (16: records alone; I420 and NV12 planes are the same size)
                 fmt = YUV_I444 if entry == 16 + 3 * GRAB_BLOCK * GRAB_BLOCK else YUV_I420
@@ -583,9 +585,10 @@ class GL:
             raise ValueError("grab_decode: malformed payload")
         return tuple(damage), blocks.value
 
-    def grab_decode_yuv(self, payload, format, w, h, into):
+    def grab_decode_yuv(self, payload, format, w, h, into, scroll=False):
         """Patch a host-sink delta YUV payload (grab_payload's bytes) into `into`, the caller's flat planes of the w x h image in a
-        full YUV grab's payload layout (yuv_split cuts it); None: only checked.  (damage, blocks).  A pure host function
+        full YUV grab's payload layout (yuv_split cuts it); None: only checked.  (damage, blocks).  scroll: the payload is a
+        GRAB_SCROLL grab's -- COPY entries are applied in place first.  A pure host function
         (WrhipGrabDecodeYuv); a malformed payload raises ValueError and leaves `into` as it was."""
         import numpy as np
         shapes = yuv_plane_shapes(w, h, format)
@@ -598,7 +601,7 @@ class GL:
                 at += rows * row
         damage, blocks = (i32 * 4)(), u32(0)
         src = (C.c_char * len(payload)).from_buffer_copy(payload)
-        rc = self.WrhipGrabDecodeYuv(src, len(payload), int(format), int(w), int(h), ptrs[0], 0, ptrs[1], ptrs[2], 0, damage, C.byref(blocks))
+        rc = self.WrhipGrabDecodeYuv(src, len(payload), int(format) | (GRAB_SCROLL if scroll else 0), int(w), int(h), ptrs[0], 0, ptrs[1], ptrs[2], 0, damage, C.byref(blocks))
         if rc != 0:
             raise ValueError("grab_decode_yuv: malformed payload")
         return tuple(damage), blocks.value

@@ -296,7 +296,7 @@ def render_streamed_tensors(backend_path, frames, size, dtype, layout, channels,
     return out, stats, infos
 
 
-def render_streamed_yuv(backend_path, frames, format, color_space, device=False, flags=0, delta=False, key_every=None, scale_to=None, renditions=1):
+def render_streamed_yuv(backend_path, frames, format, color_space, device=False, flags=0, delta=False, key_every=None, scale_to=None, renditions=1, scroll=False):
     """render_streamed_grabbed for a video encoder: after each frame's render the whole window is YUV-grabbed (GL.grab_texture_yuv:
     one launch in stream order behind that frame, 8-bit planes in `format` of the ranged colour space `color_space`) -- nothing
     between the frames drains the held-back raster launches, no Finish.  Frame k's ticket is fetched after frame k + 1 has been
@@ -309,6 +309,7 @@ def render_streamed_yuv(backend_path, frames, format, color_space, device=False,
     host array the tickets' blocks are patched into, or one device buffer the blocks are written to -- so only the 64 x 64 blocks
     whose samples changed cross or are written; the planes returned for frame k are a copy of the accumulated ones once frame k's
     ticket has been fetched (device: read back then, while frame k + 1's grab is still parked).  key_every=N: every N-th grab passes GRAB_KEY.
+    scroll=True (with delta): every grab passes GRAB_SCROLL -- scrolled blocks cross as COPY entries, or are written from the retained planes.
     scale_to=(w, h) (without delta): every grab is the scaled one (GL.grab_texture_yuv_scaled) with `renditions` renditions -- levels
     0 .. renditions - 1 of the chain to scale_to -- and a frame's planes are glapi.yuv_split_renditions' list of them."""
     from . import glapi
@@ -320,7 +321,8 @@ def render_streamed_yuv(backend_path, frames, format, color_space, device=False,
     nbytes = sum(rows * row for rows, row in glapi.yuv_plane_shapes(w, h, format))
     if delta:
         assert scale_to is None, "render_streamed_yuv: a scaled YUV grab is a full one"
-        return _render_streamed_yuv_delta(gl, r, window, frames, format, color_space, device, flags, key_every, nbytes)
+        return _render_streamed_yuv_delta(gl, r, window, frames, format, color_space, device, flags, key_every, nbytes, scroll)
+    assert not scroll, "render_streamed_yuv: a scroll YUV grab is a delta one"
     # (scaled: rendition k is scale_to << k; a frame's renditions lie one after another, on the host and in the frame's device buffer)
     sizes = [(scale_to[0] << k, scale_to[1] << k) for k in range(renditions)] if scale_to is not None else []
     each = [sum(rows * row for rows, row in glapi.yuv_plane_shapes(sw, sh, format)) for sw, sh in sizes]
@@ -362,7 +364,7 @@ def render_streamed_yuv(backend_path, frames, format, color_space, device=False,
     return [glapi.yuv_split(fl, w, h, format) for fl in flats], stats, infos
 
 
-def _render_streamed_yuv_delta(gl, r, window, frames, format, color_space, device, flags, key_every, nbytes):
+def _render_streamed_yuv_delta(gl, r, window, frames, format, color_space, device, flags, key_every, nbytes, scroll=False):
     """render_streamed_yuv(delta=True): frame k - 1's ticket is fetched after frame k has been rendered and grabbed, as in the full
     loop.  Frame k's grab is then parked behind frame k's held-back launches, so the accumulated planes -- the host's, or the device
     buffer read back on the draw stream -- are frame k - 1's when they are copied"""
@@ -380,7 +382,7 @@ def _render_streamed_yuv_delta(gl, r, window, frames, format, color_space, devic
         assert (f.width, f.height) == (w, h), "render_streamed_yuv: one window size"
         r.render(f)
         t = gl.grab_texture_yuv_delta(window, (0, 0, w, h), format, color_space, flags, dst=acc if device else None,
-                                      dst_bytes=nbytes if device else 0, key=bool(key_every) and k % key_every == 0)
+                                      dst_bytes=nbytes if device else 0, key=bool(key_every) and k % key_every == 0, scroll=scroll)
         assert t >= 0, (t, gl.GetError())
         tickets.append(t)
         if k >= 1:
