@@ -520,6 +520,42 @@ int32_t WrhipTapResultGet(int32_t ticket, WrhipTapResult* out, int32_t wait);
  * a NULL desc or src; a src not aligned to its element; a stride below the tensor grab's minimum or above 2^40; an extent in bytes
  * above src_bytes; an alpha above 255; and while sharding is on.
  *
+ * WrhipPutTexturePayload(tex, rect, payload, bytes, flags): the way IN for delta payloads, the inverse of a delta, packed or scroll
+ * grab: the payload is decoded ON THE DEVICE into `rect` of a GL_RGBA8 or GL_R8 texture, at its place in the call order.  Only the
+ * payload's bytes (and a small index of its entries) cross to the device; the blocks are expanded there -- WrhipGrabDecode into a
+ * host image and TexSubImage2D of the damage rect would carry the uncompressed pixels.  The contract -- any restatement must give
+ * the same bytes:
+ *   payload   host memory: the 16-byte header, then the entries, as WrhipGrabPayloadGet hands them out; `bytes` is header plus
+ *             payload (16 + header word 0).  `flags` are the producing grab's: WRHIP_GRAB_DELTA is required; PACKED, SCROLL (with
+ *             PACKED only) and KEY are allowed (KEY changes nothing here); any other flag is an error.  The format is the texture's.
+ *             The payload is copied before the call returns: the caller may free it at once.
+ *   meaning   after the put, the bytes of `rect` in `tex` are what WrhipGrabDecode(payload, bytes, format, flags, rect.w, rect.h, img,
+ *             stride, ..) leaves in `img` when `img` held the rect's bytes before the put.  COPY entries follow the in-place rule:
+ *             all are applied first, by ascending y for dy > 0 and descending y for dy < 0, and a COPY block holds what the rect
+ *             had BEFORE the put at (x, y + dy); every other entry is applied after them.  Entries may arrive in any order.  Plain
+ *             delta entries (record plus block at the fixed pitch), RAW, SOLID, RUNS and COPY are all accepted.
+ *   written   exactly the cut blocks the entries name; no other byte of the texture is touched -- not the rest of the rect, not a
+ *             byte beyond a cut block.
+ *   checked   the whole payload, on the host, with the decoder's own checks (wr_grab_codec.h: wr_gc_entry and the COPY rules)
+ *             before anything is launched, staged or flushed: whatever makes WrhipGrabDecode return -1 makes the put return -1.
+ *             One payload more is refused: one in which two entries that are no COPY share a pixel.  The host decoder applies
+ *             those in payload order; the device gives every entry a workgroup of its own, which has no order.  No grab emits one.
+ *   ordering  WrhipPutTextureTensor's: a texture write at its place in the call order.  Draws recorded before it that sample or
+ *             target `tex` see the old bytes (recorded work is flushed), held-back launches that reference `tex` leave first, queued
+ *             uploads go out ahead of it (the payload travels with their DMA); everything recorded, uploaded, tapped or grabbed
+ *             afterwards sees the new bytes; a tap or grab issued before it is unchanged.  On a texture that nothing pending
+ *             touches the put flushes no recorded work and leaves held-back launches held.  Retained copies of delta grabs stay
+ *             valid (they compare content): a delta grab of `tex` after a put sends the blocks whose bytes the put changed.
+ *   cost      WrhipStats::kernel_launches grows by 1 (wr_put_patch_kernel), or by WRHIP_PUT_PAYLOAD_LAUNCHES when the payload has a
+ *             COPY entry (wr_put_copy_kernel first; by 1 again if it has nothing else); by 0 for a payload with no entry, which
+ *             orders and stages nothing.  h2d_bytes grows by what is staged: `bytes` plus the index, 4 bytes per entry and 4 per
+ *             block column with a COPY entry plus 4 -- never more than 16 per entry.  d2h_bytes grows by 0.  Nothing is waited for.
+ * Returns 0; -1 and sets GL_INVALID_VALUE, launching, staging, flushing and changing nothing, for: a malformed payload (above); an
+ * unknown texture or one without storage; a format other than GL_RGBA8, GL_R8; a texture whose storage is a caller's host buffer
+ * (SetTextureBuffer) or that is locked; a rect that is empty or not inside `tex`; a NULL payload; `bytes` below 16 or not 16 plus
+ * header word 0; a missing DELTA, SCROLL without PACKED or any other flag; and while sharding is on.  Not supported: YUV delta
+ * payloads, payloads in device memory, GL_RG8.
+ *
  * WrhipGrabTextureYuv(tex, rect, desc): a grab of ONE rect of a GL_RGBA8 texture as 8-bit Y'CbCr planes for a video encoder -- the
  * inverse of the video that CompositeYUV and brush_yuv_image draw.  One launch (wr_grab_yuv_kernel) converts the rect; the planes
  * cross to the host as the ticket's payload (desc->dst == NULL: 1.5 bytes per pixel in 4:2:0 against a full grab's 4), or are
@@ -763,6 +799,8 @@ typedef struct WrhipTensorSrc {
   uint32_t flags;                  /* WRHIP_GRAB_FLIP_ROWS and / or WRHIP_TENSOR_BGR */
 } WrhipTensorSrc;
 int32_t WrhipPutTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTensorSrc* desc);
+#define WRHIP_PUT_PAYLOAD_LAUNCHES 2   /* most launches of one payload put: the COPY pass, then the patch pass */
+int32_t WrhipPutTexturePayload(GLuint tex, const int32_t rect[4], const void* payload, uint64_t bytes, uint32_t flags);
 typedef struct WrhipYuvDesc {
   uint32_t format;                 /* WRHIP_YUV_* */
   uint32_t color_space;            /* YuvRangedColorSpace 0..5: Rec601Narrow, Rec601Full, Rec709Narrow, Rec709Full, Rec2020Narrow, Rec2020Full */

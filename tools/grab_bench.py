@@ -41,10 +41,15 @@
              (kind 15 feat 9, one entry) beside the plain delta YUV grab's one launch on the same frames -- a scroll by 64, nothing
              changed, 40 blocks changed -- with the bytes crossed; then frames each scrolled by 64 and uploaded, a grab per frame,
              host and device sink, with and without GRAB_SCROLL, against no grab
+  mirror     WrhipPutTexturePayload into a second 4K texture: the COPY pass and the patch pass by hipEvents (kind 16 feat 2 / feat 1) and
+             the put on the host clock, with the bytes staged, for a packed keyframe of cfg2, 40 changed blocks, a keyframe of noise
+             (all RAW) and a scroll by 37 -- beside the path there is without it on the same payloads, WrhipGrabDecode into a host
+             image and TexSubImage2D of the damage rect; then frames mirrored in a loop without Finish, the scroll case and cfg2 frames
+             of four seeds in turn, put against that path, frames/s and bytes per frame each way
   ab         plain bench.py against another build of the library (WRHIP_LIB_PATH), alternated, no grab issued
 
 Every section runs three alternated rounds.  Needs the GPU: there is no fallback.
-  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor,put,yuv,yuv_delta,yuv_scaled,scroll,yuvscroll] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
+  python tools/grab_bench.py [--sections pack,transport,stream,scaled,tensor,put,yuv,yuv_delta,yuv_scaled,scroll,yuvscroll,mirror] [--ab PATH_TO_OTHER_LIBWRHIP] [--out FILE]"""
 import argparse
 import ctypes as C
 import json
@@ -1336,6 +1341,189 @@ def section_yuvscroll_stream(lib, frames):
     w.close()
 
 
+# ---- payload puts (WrhipPutTexturePayload) ----------------------------------------------------------------
+class Mirror:
+    """A 4K window and a second RGBA8 texture of its size in one context; payloads are fetched into and put from one buffer, and the
+    parent path -- WrhipGrabDecode into a host image, TexSubImage2D of the damage rect -- runs on the same payloads"""
+
+    def __init__(self, lib, content="noise"):
+        self.w = Window(lib, content)
+        gl = self.gl = self.w.gl
+        self.tex = self.w.r.device.create_texture(W, H, G.GL_RGBA8, render_target=True)
+        self.buf = C.create_string_buffer(16 + ((W + 63) // 64) * ((H + 63) // 64) * (16 + 64 * 64 * 4))
+        self.img = np.zeros((H, W, 4), np.uint8)
+        self.rect = (C.c_int32 * 4)(0, 0, W, H)
+        self.damage, self.blocks, self.n = (C.c_int32 * 4)(), C.c_uint32(0), C.c_uint64(0)
+        self.set_both(np.zeros((H, W, 4), np.uint8))
+
+    def set_both(self, px):
+        """the mirror texture and the host image hold `px` (a frame a payload is a delta against)"""
+        self.img[...] = px
+        self.upload_mirror(0, 0, W, H)
+        self.gl.Finish()
+
+    def upload_mirror(self, x, y, w, h):
+        gl = self.gl
+        gl.ActiveTexture(G.GL_TEXTURE0)
+        gl.BindTexture(G.GL_TEXTURE_2D, self.tex.id)
+        gl.PixelStorei(G.GL_UNPACK_ROW_LENGTH, W)
+        gl.TexSubImage2D(G.GL_TEXTURE_2D, 0, x, y, w, h, G.GL_BGRA, G.GL_UNSIGNED_BYTE, self.img.ctypes.data + (y * W + x) * 4)
+        gl.PixelStorei(G.GL_UNPACK_ROW_LENGTH, 0)
+
+    def grab_payload(self, flags):
+        """A grab of the window, its payload in self.buf: -> bytes"""
+        t = self.gl.grab_texture(self.w.tex, None, flags)
+        assert t >= 0, self.gl.GetError()
+        assert self.gl.WrhipGrabPayloadGet(t, self.buf, len(self.buf), C.byref(self.n), 1) == 0
+        return int(self.n.value)
+
+    def put(self, nbytes, flags):
+        assert self.gl.WrhipPutTexturePayload(self.tex.id, C.addressof(self.rect), self.buf, nbytes, flags) == 0, self.gl.GetError()
+
+    def parent(self, nbytes, flags):
+        """-> the bytes TexSubImage2D carries"""
+        assert self.gl.WrhipGrabDecode(self.buf, nbytes, G.GL_RGBA8, flags, W, H, self.img.ctypes.data, 0, self.damage, C.byref(self.blocks)) == 0
+        x, y, w, h = self.damage
+        if w and h:
+            self.upload_mirror(x, y, w, h)
+        return w * h * 4
+
+    def mirror_pixels(self):
+        return self.w.r.device.read_texture(self.tex)
+
+    def close(self):
+        self.w.close()
+
+
+def section_mirror_put(lib, n=10):
+    say(f"## mirror: WrhipPutTexturePayload into a {W}x{H} RGBA8 texture, {n} puts of one payload per line; hipEvents (WrhipSetProfiling(1)) us per put: COPY pass "
+        "(wr_put_copy_kernel) + patch pass (wr_put_patch_kernel); host clock us per put, n puts and one Finish, beside the parent path on the same payload "
+        "(WrhipGrabDecode into a host image, TexSubImage2D of the damage rect)")
+    DP = glapi.GRAB_DELTA | glapi.GRAB_PACKED
+    DPS = DP | glapi.GRAB_SCROLL
+    rng = np.random.default_rng(3)
+    nblocks = ((W + 63) // 64) * ((H + 63) // 64)
+    some = rng.choice(nblocks, size=40, replace=False)
+    patch = rng.integers(0, 256, (16, 16, 4), dtype=np.uint8)
+    page = rng.integers(0, 256, (H + 37, W, 4), dtype=np.uint8)
+    cases = ("packed keyframe of cfg2", "40 of %d blocks changed" % nblocks, "noise keyframe (all RAW)", "scroll by 37")
+    rows = {}
+    for rnd in range(ROUNDS):
+        for case in cases:
+            m = Mirror(lib, "cfg2" if case.startswith("packed") else "noise")
+            gl = m.gl
+            flags = DPS if case.startswith("scroll") else DP
+            if case.startswith("scroll"):
+                m.w.upload(0, 0, page[:H])
+            before = np.zeros((H, W, 4), np.uint8)
+            if not case.endswith("keyframe of cfg2") and not case.startswith("noise"):
+                # (a delta: the mirror and the host image hold the frame the payload is a delta against)
+                key = m.grab_payload(flags | glapi.GRAB_KEY)
+                m.parent(key, flags)
+                before = m.img.copy()
+                if case.startswith("scroll"):
+                    m.w.upload(0, 0, page[37:37 + H])
+                else:
+                    for b in some:
+                        m.w.upload(int(b % (W // 64)) * 64 + 5, int(b // (W // 64)) * 64 + 3, patch)
+            nbytes = m.grab_payload(flags | (glapi.GRAB_KEY if "keyframe" in case else 0))
+            entries = gl.grab_decode(m.buf.raw[:nbytes], G.GL_RGBA8, flags, np.zeros((H, W, 4), np.uint8) if "keyframe" in case else before.copy())[1]
+            # once each, checked against the other: the put's texture is the parent path's image
+            m.set_both(before)
+            m.put(nbytes, flags)
+            want = before.copy()
+            gl.grab_decode(m.buf.raw[:nbytes], G.GL_RGBA8, flags, want)
+            assert np.array_equal(m.mirror_pixels(), want), f"{case}: the put's texture is not WrhipGrabDecode's image"
+            gl.Finish()
+            # the put: events, then the host clock
+            gl.WrhipSetProfiling(1)
+            gl.WrhipResetStats()
+            for _ in range(n):
+                m.put(nbytes, flags)
+            gl.Finish()
+            ks = {k.feat: k.ns / n / 1e3 for k in kernel_stats(gl, 16)}
+            staged = gl.stats()["h2d_bytes"] / n
+            gl.WrhipSetProfiling(0)
+            t0 = time.perf_counter()
+            for _ in range(n):
+                m.put(nbytes, flags)
+            gl.Finish()
+            t_put = (time.perf_counter() - t0) / n * 1e6
+            t0 = time.perf_counter()
+            for _ in range(n):
+                up = m.parent(nbytes, flags)
+            gl.Finish()
+            t_parent = (time.perf_counter() - t0) / n * 1e6
+            rows.setdefault(case, []).append((ks.get(2, 0.0), ks.get(1, 0.0), t_put, t_parent, int(staged), up, entries, nbytes))
+            m.close()
+    for case, v in rows.items():
+        say(f"  {case:28s} events: copy " + " ".join(f"{r[0]:7.1f}" for r in v) + "  patch " + " ".join(f"{r[1]:7.1f}" for r in v) +
+            "   host clock: put " + " ".join(f"{r[2]:8.1f}" for r in v) + "  parent " + " ".join(f"{r[3]:9.1f}" for r in v) +
+            f"   us   ({v[0][6]} entries; payload {v[0][7]} bytes; staged {v[0][4]} bytes per put; the parent path uploads {v[0][5]} bytes)")
+
+
+def section_mirror_stream(lib, frames):
+    say(f"## mirror stream: {frames} frames mirrored into a second {W}x{H} texture, no Finish in the loop: a grab per frame, its payload fetched, then the payload put, "
+        "or the parent path (WrhipGrabDecode into a host image, TexSubImage2D of the damage rect); frames/s and bytes per frame to the host / back to the device")
+    DP = glapi.GRAB_DELTA | glapi.GRAB_PACKED
+    page = np.random.default_rng(4).integers(0, 256, (H + 37 * frames, W, 4), dtype=np.uint8)
+    cfg2 = []
+
+    def run(m, case, kind, n):
+        gl = m.gl
+        flags = DP | glapi.GRAB_SCROLL if case == "scroll by 37" else DP
+        if case == "scroll by 37":
+            m.w.upload(0, 0, page[:H])
+        else:
+            m.w.upload(0, 0, cfg2[0])
+        key = m.grab_payload(flags | glapi.GRAB_KEY)
+        m.parent(key, flags)                   # (both start from the mirror and the host image of frame 0)
+        gl.Finish()
+        gl.WrhipResetStats()
+        down = up = 0
+        t0 = time.perf_counter()
+        for k in range(1, n + 1):
+            m.w.upload(0, 0, page[37 * k:37 * k + H] if case == "scroll by 37" else cfg2[k % len(cfg2)])
+            nbytes = m.grab_payload(flags)
+            down += nbytes
+            if kind == "put":
+                m.put(nbytes, flags)
+            else:
+                up += m.parent(nbytes, flags)
+        gl.Finish()
+        dt = time.perf_counter() - t0
+        if kind == "put":
+            up = gl.stats()["h2d_bytes"] - n * W * H * 4      # (without the frames' own uploads of the window)
+        want = page[37 * n:37 * n + H] if case == "scroll by 37" else cfg2[n % len(cfg2)]
+        assert np.array_equal(m.mirror_pixels(), want), f"{case}, {kind}: the mirror is not the window"
+        return n / dt, down / n, up / n
+    # the "every block changes" frames: cfg2 of four seeds, rendered once each and read back; the stream uploads them in turn
+    w = Window(lib, "cfg2")
+    for sd in (1, 2, 3, 4):
+        w.r.render(scenes.make_workload("cfg2", width=W, height=H, seed=sd))
+        w.r.finish()
+        cfg2.append(w.r.device.read_texture(glapi_window_texture(w)).copy())
+    w.close()
+    rows = {}
+    m = Mirror(lib)
+    for case in ("scroll by 37", "cfg2 of seeds 1..4 in turn"):
+        for kind in ("put", "parent"):
+            run(m, case, kind, 5)
+    for rnd in range(ROUNDS):
+        for case in ("scroll by 37", "cfg2 of seeds 1..4 in turn"):
+            for kind in ("put", "parent"):
+                rows.setdefault((case, kind), []).append(run(m, case, kind, frames))
+    m.close()
+    for (case, kind), v in rows.items():
+        say(f"  {case:28s} {kind:7s} " + "  ".join(f"{fps:8.1f}" for fps, _, _ in v) + f"   frames/s   ({v[0][1] / 1e6:8.3f} MB per frame to the host, {v[0][2] / 1e6:8.3f} MB back to the device)")
+    say(f"  (every frame also uploads the window itself, {W * H * 4 / 1e6:.1f} MB, in both loops: the source of the stream, not part of either path)")
+
+
+def glapi_window_texture(w):
+    from webrender_amd.device import Texture
+    return Texture(0, W, H, G.GL_RGBA8, fbo=0)
+
+
 def section_ab(other, steps, warmup):
     say(f"## ab: bench.py --gpus 1 --steps {steps} --warmup {warmup} (cfg2), this library against {os.path.basename(other)}, alternated, frames/s")
     rows = {"parent": [], "this": []}
@@ -1422,6 +1610,9 @@ def main():
                 section_scroll_kernel(lib, only=args.scroll_case)
                 if not args.scroll_case:
                     section_scroll_stream(lib, args.frames)
+            elif s == "mirror":
+                section_mirror_put(lib)
+                section_mirror_stream(lib, args.frames)
             elif s == "tensor_parent":        # (run by `tensor` with WRHIP_LIB_PATH set: the parent path alone, on that library)
                 section_tensor_scaled(lib, with_tensor=False)
                 section_tensor_stream(lib, args.frames, with_tensor=False)

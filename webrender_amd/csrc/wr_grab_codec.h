@@ -197,6 +197,100 @@ static inline int wr_gc_decode(const void* payload, uint64_t bytes, int bpp, boo
   return 0;
 }
 
+// The index of a payload put (include/wrhip.h, WrhipPutTexturePayload): what wr_gc_decode's checking walk learns about a payload,
+// kept for a decoder that gives every entry a worker of its own and so cannot find entry k by walking.  `words`, malloc'ed:
+//   [0, n_patch)            the byte offset, from the payload's header on, of every entry that is no COPY, in payload order
+//   [.., + n_cols + 1)      for every block column of the rect that has a COPY entry, where its blocks start among the n_copy below;
+//                           the last word is n_copy
+//   [.., + n_copy)          the COPY blocks, x / 64 | (y / 64) << 16, column by column and inside a column in the order the in-place
+//                           rule applies them in: ascending y for dy > 0, descending for dy < 0.  (Block columns do not touch each
+//                           other, so this order gives the bytes of wr_gc_decode's, which goes by y first.)
+// -1 for everything wr_gc_decode refuses -- the same calls of wr_gc_entry and wr_gc_copy_order decide --, and for one thing more: two
+// entries that are no COPY and share a pixel.  wr_gc_decode patches those in payload order; workers of their own have no order.  No
+// grab emits such a payload.  Nothing is allocated then.
+struct WrGcPutIndex {
+  uint32_t n_patch, n_copy, n_cols;
+  int32_t dy;
+  uint32_t* words;
+  size_t nwords;
+};
+static inline void wr_gc_put_index_free(WrGcPutIndex* I) { free(I->words); I->words = nullptr; I->nwords = 0; }
+static inline int wr_gc_put_index(const void* payload, uint64_t bytes, int bpp, bool packed, bool scroll, int rw, int rh, WrGcPutIndex* I) {
+  I->n_patch = I->n_copy = I->n_cols = 0; I->dy = 0; I->words = nullptr; I->nwords = 0;
+  if (!payload || bytes < WR_GC_HEADER || (bpp != 1 && bpp != 4) || rw < 1 || rh < 1 || (scroll && !packed)) return -1;
+  const int32_t dy = (int32_t)wr_gc_load32((const uint8_t*)payload + 4);
+  if (scroll ? dy < -WR_GC_SCROLL_MAX || dy > WR_GC_SCROLL_MAX : dy != 0) return -1;
+  const uint8_t* p = (const uint8_t*)payload;
+  const uint64_t count = wr_gc_load32(p);
+  if (count > bytes - WR_GC_HEADER) return -1;
+  p += WR_GC_HEADER;
+  size_t n = 0, ncopy = 0;
+  WrGrabEntry E;
+  for (size_t at = 0; at < count; at += E.size, n++) {
+    if (!wr_gc_entry(p + at, (size_t)(count - at), bpp, packed, rw, rh, &E, false, scroll, dy)) return -1;
+    if (E.mode == WR_GC_COPY) ncopy++;
+  }
+  const size_t npatch = n - ncopy;
+  const size_t bxn = ((size_t)rw + WR_GC_BLOCK - 1) / WR_GC_BLOCK, byn = ((size_t)rh + WR_GC_BLOCK - 1) / WR_GC_BLOCK;
+  // work memory: the COPY blocks; the other entries' blocks; per cell of the rect's 64 x 64 grid the list of entries that touch it
+  // (a node per entry and cell: a block of at most 64 x 64 touches four); per block column its COPY blocks
+  WrGrabCopy* copies = (WrGrabCopy*)malloc((ncopy + npatch + 1) * sizeof(WrGrabCopy));
+  int32_t* cell = (int32_t*)malloc((bxn * byn + 4 * npatch + 1) * sizeof(int32_t));
+  uint32_t* col = (uint32_t*)calloc(bxn + 1, sizeof(uint32_t));
+  uint32_t* words = (uint32_t*)malloc((npatch + ncopy + bxn + 2) * sizeof(uint32_t));
+  bool ok = copies && cell && col && words;
+  if (ok) {
+    WrGrabCopy* patches = copies + ncopy;
+    int32_t* next = cell + bxn * byn;
+    for (size_t i = 0; i < bxn * byn; i++) cell[i] = -1;
+    size_t k = 0, q = 0;
+    for (size_t at = 0; at < count && ok; at += E.size) {
+      wr_gc_entry(p + at, (size_t)(count - at), bpp, packed, rw, rh, &E, true, scroll, dy);
+      if (E.mode == WR_GC_COPY) { copies[k++] = WrGrabCopy{E.x, E.y, E.w, E.h}; continue; }
+      const size_t cx0 = (size_t)E.x / WR_GC_BLOCK, cx1 = (size_t)(E.x + E.w - 1) / WR_GC_BLOCK;
+      const size_t cy0 = (size_t)E.y / WR_GC_BLOCK, cy1 = (size_t)(E.y + E.h - 1) / WR_GC_BLOCK;
+      int node = 4 * (int)q;
+      for (size_t cy = cy0; cy <= cy1 && ok; cy++) {
+        for (size_t cx = cx0; cx <= cx1 && ok; cx++, node++) {
+          int32_t& head = cell[cy * bxn + cx];
+          for (int32_t j = head; j >= 0 && ok; j = next[j]) {
+            const WrGrabCopy& o = patches[j / 4];
+            ok = !(o.x < E.x + E.w && E.x < o.x + o.w && o.y < E.y + E.h && E.y < o.y + o.h);
+          }
+          next[node] = head; head = node;
+        }
+      }
+      patches[q] = WrGrabCopy{E.x, E.y, E.w, E.h};
+      words[q++] = (uint32_t)(WR_GC_HEADER + at);
+    }
+    ok = ok && wr_gc_copy_order(copies, ncopy);
+  }
+  if (ok) {
+    // the columns that have COPY blocks, in order; then the blocks, each to its column's next place
+    for (size_t i = 0; i < ncopy; i++) col[(size_t)copies[i].x / WR_GC_BLOCK + 1]++;
+    uint32_t* starts = words + npatch;
+    size_t ncols = 0;
+    uint32_t sum = 0;
+    for (size_t cx = 0; cx < bxn; cx++) {
+      const uint32_t c = col[cx + 1];
+      col[cx + 1] = sum;             // (col[cx + 1]: where column cx's next block goes)
+      if (c) { starts[ncols++] = sum; sum += c; }
+    }
+    starts[ncols] = sum;
+    uint32_t* blocks = starts + ncols + 1;
+    for (size_t i = 0; i < ncopy; i++) {
+      const WrGrabCopy& C = copies[dy > 0 ? i : ncopy - 1 - i];
+      blocks[col[(size_t)C.x / WR_GC_BLOCK + 1]++] = (uint32_t)(C.x / WR_GC_BLOCK) | (uint32_t)(C.y / WR_GC_BLOCK) << 16;
+    }
+    I->n_patch = (uint32_t)npatch; I->n_copy = (uint32_t)ncopy; I->n_cols = (uint32_t)ncols; I->dy = dy;
+    I->words = words; I->nwords = npatch + (ncopy ? ncols + 1 + ncopy : 0);
+    if (!ncopy) I->n_cols = 0;
+  }
+  free(copies); free(cell); free(col);
+  if (!ok) free(words);
+  return ok ? 0 : -1;
+}
+
 // The payload of a delta YUV grab (include/wrhip.h, WrhipGrabTextureYuvDelta; format 0: I420, 1: NV12, 2: I444): entries of one
 // size, a record x, y, w, h -- a block of 64 x 64 luma samples of the image, aligned to its origin, cut to it -- and the block's
 // planes at fixed pitches: Y, 64 rows of 64; then I420: Cb, Cr, 32 rows of 32 each; NV12: 32 rows of 32 pairs; I444: Cb, Cr, 64

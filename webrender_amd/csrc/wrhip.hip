@@ -4948,6 +4948,59 @@ int32_t WrhipPutTextureTensor(GLuint tex, const int32_t rect[4], const WrhipTens
   c->stats.kernel_launches++;
   return 0;
 }
+// A payload put: see include/wrhip.h.  A texture write at its place in the call order, like the tensor put; what crosses is the
+// payload and the index the checking walk leaves (wr_gc_put_index), through the staging ring and with the open upload batch's DMA.
+// Everything is checked on the caller's copy before anything is staged, flushed or launched.
+int32_t WrhipPutTexturePayload(GLuint tex, const int32_t rect[4], const void* payload, uint64_t bytes, uint32_t flags) {
+  if (!ctx) return -1;
+  Context* c = ctx;
+  Texture* t = tex ? c->textures.find(tex) : nullptr;
+  bool ok = t && t->dptr && (t->internal_format == GL_RGBA8 || t->internal_format == GL_R8) && rect && payload;
+  ok = ok && !t->ext_buf && !t->locked;
+  ok = ok && (flags & WRHIP_GRAB_DELTA) && (flags & ~(WRHIP_GRAB_DELTA | WRHIP_GRAB_PACKED | WRHIP_GRAB_SCROLL | WRHIP_GRAB_KEY)) == 0;
+  ok = ok && (!(flags & WRHIP_GRAB_SCROLL) || (flags & WRHIP_GRAB_PACKED));
+  ok = ok && rect[2] >= 1 && rect[3] >= 1 && rect[0] >= 0 && rect[1] >= 0 && rect[0] <= t->width - rect[2] && rect[1] <= t->height - rect[3];
+  ok = ok && bytes >= WR_GC_HEADER && bytes - WR_GC_HEADER == (uint64_t)wr_gc_load32((const uint8_t*)payload);
+  ok = ok && c->shard_world <= 1 && t->own_y0 == t->own_y1;
+  WrGcPutIndex I;
+  memset(&I, 0, sizeof(I));
+  ok = ok && wr_gc_put_index(payload, bytes, t->bpp, (flags & WRHIP_GRAB_PACKED) != 0, (flags & WRHIP_GRAB_SCROLL) != 0, rect[2], rect[3], &I) == 0;
+  if (!ok) { c->last_error = GL_INVALID_VALUE; return -1; }
+  if (I.n_patch + I.n_copy == 0) { wr_gc_put_index_free(&I); return 0; }      // (no entry: nothing is written, so nothing is ordered)
+  sync_texture_for_write(*t);
+  const size_t index_bytes = I.nwords * sizeof(uint32_t);
+  const size_t off = staging_alloc((size_t)bytes + index_bytes);
+  stage_copy(c->staging + off, payload, (size_t)bytes);
+  memcpy(c->staging + off + (size_t)bytes, I.words, index_bytes);
+  c->stats.h2d_bytes += bytes + index_bytes;
+  flush_uploads(4400);
+  t->view_batch = 0;
+  WrPutPayloadArgs a;
+  memset(&a, 0, sizeof(a));
+  a.tex = (uint8_t*)t->dptr; a.tex_stride = t->stride; a.bpp = t->bpp;
+  a.rx = rect[0]; a.ry = rect[1]; a.rw = rect[2]; a.rh = rect[3];
+  a.payload = c->dupload + off; a.index = (const uint32_t*)(c->dupload + off + (size_t)bytes);
+  a.count = (uint32_t)(bytes - WR_GC_HEADER);
+  a.packed = (flags & WRHIP_GRAB_PACKED) ? 1 : 0; a.dy = I.dy;
+  a.n_patch = I.n_patch; a.n_copy = I.n_copy; a.n_cols = I.n_cols;
+  wr_gc_put_index_free(&I);
+  const uint64_t block_bytes = (uint64_t)WR_GRAB_BLOCK * WR_GRAB_BLOCK * a.bpp;
+  if (a.n_copy) {
+    prof_begin();
+    WR_LAUNCH(wr_put_copy_kernel, (int)a.n_cols, 256, c->stream, a);
+    // (16, feat 2: wr_put_copy_kernel; its blocks read and written, whole ones assumed)
+    prof_end(WR_KIND_PUT, wr_format(t->internal_format), 0, 2, 2 * block_bytes * a.n_copy, (uint64_t)a.n_cols);
+    c->stats.kernel_launches++;
+  }
+  if (a.n_patch) {
+    prof_begin();
+    WR_LAUNCH(wr_put_patch_kernel, (int)a.n_patch, 256, c->stream, a);
+    // (16, feat 1: wr_put_patch_kernel; the payload read, its blocks written, whole ones assumed)
+    prof_end(WR_KIND_PUT, wr_format(t->internal_format), 0, 1, bytes + block_bytes * a.n_patch, (uint64_t)a.n_patch);
+    c->stats.kernel_launches++;
+  }
+  return 0;
+}
 // Device memory for tensor grabs: see include/wrhip.h
 void* WrhipDeviceAlloc(uint64_t bytes) {
   if (!ctx) return nullptr;

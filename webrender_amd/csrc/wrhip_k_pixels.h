@@ -507,6 +507,175 @@ __global__ void __launch_bounds__(256) wr_grab_pack_runs_kernel(WrGrabArgs a) {
   else wr_grab_pack_runs<1>(a, B, t, stage, outb, lw);
 #endif
 }
+// WrhipPutTexturePayload (include/wrhip.h; WrPutPayloadArgs): the pack kernels the other way -- a delta, packed or scroll payload in
+// the staging mirror becomes the bytes of its blocks in a texture rect.  The host has checked every entry and left an index
+// (wr_grab_codec.h, wr_gc_put_index), so no workgroup walks the payload and nothing read here decides an address unchecked.  Both
+// kernels keep wr_grab_pack_runs' ownership: thread t of 256 has the 16 pixels of block row t / 4 from column 16 * (t & 3) on, as
+// pieces of 16 bytes (four for RGBA8, one for R8).  A piece that lies whole inside the cut block and whose TEXTURE address is a
+// multiple of 16 is one 16-byte load or store; any other piece goes pixel by pixel, and only its pixels inside the cut block are
+// touched.  (The rect's origin is arbitrary: with rect.x = 3 no RGBA8 piece is aligned.)
+//   copy    wr_put_copy_kernel, a workgroup per block COLUMN that has COPY entries.  COPY sources overlap their own block, other
+//           COPY blocks and blocks that the patch pass writes, so a workgroup per block cannot be in place; columns share no byte.
+//           The workgroup walks its column in the in-place order (ascending y for dy > 0, descending for dy < 0).  Per block: all
+//           source pieces into registers, a barrier, the stores.  One barrier is enough: in that order a block's stores lie wholly
+//           on the side of every LATER block's source that the scroll came from, and a later block's stores follow the barrier that
+//           follows every earlier load.  No snapshot, no scratch memory, no LDS.
+//   patch   wr_put_patch_kernel, a workgroup per entry that is no COPY.  SOLID: the record's value.  RAW and plain entries: the
+//           body's pieces, which are 16-byte aligned in the mirror.  RUNS: the bitmap words and the values go to LDS as 16-byte
+//           pieces; a thread's 16 bits of its row's word give its count of run starts, the counts are scanned as the encoder scans
+//           them (lane shifts in a wave, four LDS words across the waves), and pixel j's value is values[starts before the thread +
+//           popcount(bits up to j) - 1].  16.5 KB of LDS.
+// Nothing is atomic, nothing spills (tests/test_put_payload.py reads the code object).
+WR_DEVICE wr_u4 wr_put_ld_piece(const uint8_t* p, int n, int bpp) {
+  if (n == 16 / bpp && ((uintptr_t)p & 15) == 0) return wr_load16(p);
+  uint32_t w[4] = {0u, 0u, 0u, 0u};
+  if (bpp == 4) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) if (k < n) w[k] = wr_load4(p + 4 * k);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; k++) if (k < n) w[k >> 2] |= (uint32_t)p[k] << (8 * (k & 3));
+  }
+  return wr_u4{w[0], w[1], w[2], w[3]};
+}
+WR_DEVICE void wr_put_st_piece(uint8_t* p, const wr_u4& v, int n, int bpp) {
+  if (n == 16 / bpp && ((uintptr_t)p & 15) == 0) { wr_grab_st16(p, v); return; }
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  if (bpp == 4) {
+#pragma unroll
+    for (int k = 0; k < 4; k++) if (k < n) wr_grab_st4(p + 4 * k, w[k]);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 16; k++) if (k < n) p[k] = (uint8_t)(w[k >> 2] >> (8 * (k & 3)));
+  }
+}
+// the pixels of piece k of thread t's 16 that lie inside a cut block of w x h
+template <int BPP> WR_DEVICE int wr_put_piece_n(int t, int k, int w, int h) {
+  constexpr int PPV = 16 / BPP;
+  return (t >> 2) < h ? wr_imax(0, wr_imin(PPV, w - ((t & 3) * 16 + k * PPV))) : 0;
+}
+#ifndef WRHIP_HOSTSIM
+template <int BPP> WR_DEVICE void wr_put_copy_column(const WrPutPayloadArgs& a, int t) {
+  constexpr int NP = BPP == 4 ? 4 : 1;
+  const uint32_t* starts = a.index + a.n_patch;
+  const uint32_t* blocks = starts + a.n_cols + 1;
+  const uint32_t b0 = starts[blockIdx.x], b1 = starts[blockIdx.x + 1];
+  const int row = t >> 2, c0 = (t & 3) * 16;
+  for (uint32_t b = b0; b < b1; b++) {
+    const uint32_t word = blocks[b];
+    const int x = (int)(word & 0xFFFFu) * WR_GRAB_BLOCK, y = (int)(word >> 16) * WR_GRAB_BLOCK;
+    const int w = wr_imin(WR_GRAB_BLOCK, a.rw - x), h = wr_imin(WR_GRAB_BLOCK, a.rh - y);
+    uint8_t* d = a.tex + (size_t)(a.ry + y + row) * a.tex_stride + (size_t)(a.rx + x + c0) * BPP;
+    const uint8_t* s = d + (long long)a.dy * a.tex_stride;
+    wr_u4 v[NP];
+    int n[NP];
+#pragma unroll
+    for (int k = 0; k < NP; k++) {
+      n[k] = wr_put_piece_n<BPP>(t, k, w, h);
+      v[k] = wr_u4{0u, 0u, 0u, 0u};
+      if (n[k]) v[k] = wr_put_ld_piece(s + 16 * k, n[k], BPP);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NP; k++) if (n[k]) wr_put_st_piece(d + 16 * k, v[k], n[k], BPP);
+  }
+}
+template <int BPP> WR_DEVICE void wr_put_patch_entry(const WrPutPayloadArgs& a, int t, wr_lu4* body, unsigned* lw) {
+  constexpr int NP = BPP == 4 ? 4 : 1;
+  const uint8_t* e = a.payload + a.index[blockIdx.x];
+  const wr_u4 rec = wr_load16(e);
+  const int x = (int)rec.x, y = (int)rec.y;
+  int w = (int)rec.z, h = (int)rec.w;
+  unsigned mode = 0u, aux = 0u;
+  if (a.packed) { w = (int)(rec.z & 0xFFu); h = (int)((rec.z >> 8) & 0xFFu); mode = rec.z >> 16; aux = rec.w; }
+  const int row = t >> 2, c0 = (t & 3) * 16;
+  uint8_t* d = a.tex + (size_t)(a.ry + y + row) * a.tex_stride + (size_t)(a.rx + x + c0) * BPP;
+  wr_u4 v[NP];
+  int n[NP];
+#pragma unroll
+  for (int k = 0; k < NP; k++) { n[k] = wr_put_piece_n<BPP>(t, k, w, h); v[k] = wr_u4{0u, 0u, 0u, 0u}; }
+  if (mode == 0u) {
+    // (a body row is 64 pixels: thread t's 16 are pieces NP * t ... of the body)
+#pragma unroll
+    for (int k = 0; k < NP; k++) if (n[k]) v[k] = wr_load16(e + 16 + 16 * (size_t)(NP * t + k));
+  } else if (mode == 1u) {
+    const uint32_t f = BPP == 4 ? aux : (aux & 0xFFu) * 0x01010101u;
+#pragma unroll
+    for (int k = 0; k < NP; k++) v[k] = wr_u4{f, f, f, f};
+  } else {
+    const unsigned pieces = (8u * (unsigned)h + aux * BPP + 15u) / 16u;
+    for (unsigned p = (unsigned)t; p < pieces; p += 256u) { const wr_u4 q = wr_load16(e + 16 + 16 * (size_t)p); body[p] = wr_lu4{q.x, q.y, q.z, q.w}; }
+    __syncthreads();
+    unsigned m16 = 0u;
+    if (row < h) m16 = (((const uint32_t*)body)[2 * row + (c0 >> 5)] >> (c0 & 31)) & 0xFFFFu;
+    const unsigned cnt = (unsigned)__popc(m16);
+    const int lane = t & 63, wave = t >> 6;
+    unsigned inc = cnt;
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) { const unsigned u = __shfl_up(inc, s); if (lane >= s) inc += u; }
+    if (lane == 63) lw[wave] = inc;
+    __syncthreads();
+    unsigned before = 0u;
+#pragma unroll
+    for (int q = 0; q < 4; q++) if (q < wave) before += lw[q];
+    const unsigned base = before + inc - cnt;
+    const uint8_t* values = (const uint8_t*)body + 8 * h;
+    uint32_t px[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      px[j] = 0u;
+      if (row < h && c0 + j < w) {
+        const unsigned i = base + (unsigned)__popc(m16 & ((2u << j) - 1u)) - 1u;
+        px[j] = BPP == 4 ? ((const uint32_t*)values)[i] : (uint32_t)values[i];
+      }
+    }
+    if (BPP == 4) {
+#pragma unroll
+      for (int k = 0; k < NP; k++) v[k] = wr_u4{px[4 * k], px[4 * k + 1], px[4 * k + 2], px[4 * k + 3]};
+    } else {
+      uint32_t ww[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int j = 0; j < 16; j++) ww[j >> 2] |= px[j] << (8 * (j & 3));
+      v[0] = wr_u4{ww[0], ww[1], ww[2], ww[3]};
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < NP; k++) if (n[k]) wr_put_st_piece(d + 16 * k, v[k], n[k], BPP);
+}
+#endif
+__global__ void __launch_bounds__(256) wr_put_copy_kernel(WrPutPayloadArgs a) {
+  const int t = (int)threadIdx.x;
+#ifdef WRHIP_HOSTSIM
+  // (threads run one after the other: the first applies the column's blocks through the serial decoder of wr_grab_codec.h)
+  if (t != 0) return;
+  const uint32_t* starts = a.index + a.n_patch;
+  const uint32_t* blocks = starts + a.n_cols + 1;
+  uint8_t* rect = a.tex + (size_t)a.ry * a.tex_stride + (size_t)a.rx * a.bpp;
+  for (uint32_t b = starts[blockIdx.x]; b < starts[blockIdx.x + 1]; b++) {
+    const int x = (int)(blocks[b] & 0xFFFFu) * WR_GRAB_BLOCK, y = (int)(blocks[b] >> 16) * WR_GRAB_BLOCK;
+    wr_gc_copy(WrGrabCopy{x, y, wr_imin(WR_GRAB_BLOCK, a.rw - x), wr_imin(WR_GRAB_BLOCK, a.rh - y)}, a.dy, a.bpp, rect, (size_t)a.tex_stride);
+  }
+#else
+  if (a.bpp == 4) wr_put_copy_column<4>(a, t);
+  else wr_put_copy_column<1>(a, t);
+#endif
+}
+__global__ void __launch_bounds__(256) wr_put_patch_kernel(WrPutPayloadArgs a) {
+  const int t = (int)threadIdx.x;
+#ifdef WRHIP_HOSTSIM
+  // (threads run one after the other: the first patches the entry through the serial decoder of wr_grab_codec.h)
+  if (t != 0) return;
+  const uint32_t off = a.index[blockIdx.x];
+  WrGrabEntry E;
+  wr_gc_entry(a.payload + off, (size_t)WR_GC_HEADER + a.count - off, a.bpp, a.packed != 0, a.rw, a.rh, &E, true);
+  wr_gc_patch(a.payload + off, E, a.bpp, a.tex + (size_t)a.ry * a.tex_stride + (size_t)a.rx * a.bpp, (size_t)a.tex_stride);
+#else
+  __shared__ wr_lu4 body[1056];        // a RUNS body at its largest: 64 bitmap words and 4096 RGBA8 values
+  __shared__ unsigned lw[4];
+  if (a.bpp == 4) wr_put_patch_entry<4>(a, t, body, lw);
+  else wr_put_patch_entry<1>(a, t, body, lw);
+#endif
+}
 // WrhipGrabTextureScaled (include/wrhip.h; the launch: WrGrabScaleArgs): a workgroup per 64 x 64 tile of the launch's top level.
 //   coords  (modes 0, 1) the source coordinate of each of the tile's columns and rows, once, into LDS: the blit kernel's own walk
 //           (wr_blit_walk_u / _v -- wr_accum is not cheap) in mode 0, scale_blit's integer stepping in mode 1

@@ -832,6 +832,19 @@ struct WrPutTensorArgs {
   int32_t rows_per_wg, slots;
   WrTensorIn in;
 };
+// WrhipPutTexturePayload: the launches of wr_put_copy_kernel and wr_put_patch_kernel (the contract: include/wrhip.h).  `payload` is
+// the caller's payload, header included, and `index` the host's index of it (wr_grab_codec.h, WrGcPutIndex::words), both in the
+// staging mirror, 16-byte aligned.  The host has checked every entry: the kernels read records, bitmaps and counts as they are.
+struct WrPutPayloadArgs {
+  uint8_t* tex;                        // the texture's storage (its origin)
+  int32_t tex_stride, bpp;             // bytes; 4: RGBA8, 1: R8
+  int32_t rx, ry, rw, rh;              // the rect
+  const uint8_t* payload;
+  const uint32_t* index;
+  uint32_t count;                      // the payload's header word 0: the bytes of the entries
+  int32_t packed, dy;
+  uint32_t n_patch, n_copy, n_cols;
+};
 // WrhipGrabTextureYuv: one launch of wr_grab_yuv_kernel (the contract: include/wrhip.h).  The rect's stored B, G, R bytes become
 // 8-bit Y, Cb and Cr samples in 16.16 fixed point; 4:2:0 chroma is taken from the sum of a 2 x 2 block whose positions are clamped
 // to the rect.  The planes lie in the caller's device memory or behind the header of the ticket's device slot: either way the launch

@@ -150,6 +150,7 @@ EXTRA_SIGNATURES = {
     "WrhipDeviceRead": (i32, [P, P, u64]),
     "WrhipDeviceWrite": (i32, [P, P, u64]),
     "WrhipPutTextureTensor": (i32, [u32, P, P]),
+    "WrhipPutTexturePayload": (i32, [u32, P, P, u64, u32]),
     "WrhipGrabTextureYuv": (i32, [u32, P, P]),
     "WrhipGrabTextureYuvDelta": (i32, [u32, P, P, u32]),
     "WrhipGrabDecodeYuv": (i32, [P, u64, u32, i32, i32, P, C.c_int64, P, P, C.c_int64, P, P]),
@@ -503,6 +504,21 @@ class GL:
             d.bias[k] = float(bias[k]) if k < len(bias) else 0.0
         d.alpha, d.flags = int(alpha), int(flags)
         return self.WrhipPutTextureTensor(tex, C.addressof(arr), C.addressof(d))
+
+    def put_texture_payload(self, tex, rect, payload, flags):
+        """A payload put (include/wrhip.h, WrhipPutTexturePayload): the delta, packed or scroll payload `payload` (grab_payload's
+        bytes, header included; `flags`: the producing grab's) is decoded on the device into `rect` = (x, y, w, h) of texture id
+        `tex` -- None: all of it.  Returns 0, or -1 (GL_INVALID_VALUE is then set)."""
+        if rect is None:
+            w, h = i32(0), i32(0)
+            if not self.WrhipGetTextureSize(tex, C.byref(w), C.byref(h)):
+                w = h = i32(0)
+            rect = (0, 0, w.value, h.value)
+        arr = (i32 * 4)(*[int(v) for v in rect])
+        if payload is None:
+            return self.WrhipPutTexturePayload(tex, C.addressof(arr), None, 0, int(flags))
+        src = (C.c_char * max(1, len(payload))).from_buffer_copy(bytes(payload).ljust(1, b"\0"))
+        return self.WrhipPutTexturePayload(tex, C.addressof(arr), src, len(payload), int(flags))
 
     def grab_result(self, ticket, wait=True, into=None):
         """The result of a grab: (info dict, pixels).  Full mode: one array per rect ((h, w, 4) stored B, G, R, A bytes, or (h, w)

@@ -398,6 +398,58 @@ def _render_streamed_yuv_delta(gl, r, window, frames, format, color_space, devic
     return [glapi.yuv_split(fl, w, h, format) for fl in flats], stats, infos
 
 
+def render_streamed_mirrored(backend_path, frames, packed=True, scroll=False, check=True):
+    """A mirror on the device: after each frame's render the window is delta-grabbed (GL.grab_texture with GRAB_DELTA, GRAB_PACKED if
+    `packed`, GRAB_SCROLL if `scroll` -- a scroll grab is a packed one), the payload is fetched as it crossed (GL.grab_payload: that
+    ticket alone is waited for) and forwarded into a second, window-sized RGBA8 texture of the same context with a payload put
+    (GL.put_texture_payload) -- what a viewer at the other end of a link does.  No Finish, no ReadPixels and no TexSubImage2D of the
+    mirror anywhere in the loop: the mirror's pixels reach it only as payloads.  check: after every put the window and the mirror
+    are both grabbed whole (plain grabs, in stream order behind the put), fetched one frame later.
+    Returns the mirror's stored bytes after the last frame (B, G, R, A; read after one Finish), the backend's statistics at the end
+    of the loop, the windows and the mirrors after every frame (empty without check) and the bytes of every payload.  libwrhip only."""
+    from . import glapi
+    gl = GL(backend_path)
+    assert gl.is_wrhip, "render_streamed_mirrored: grabs and puts are libwrhip additions"
+    assert packed or not scroll, "render_streamed_mirrored: a scroll grab is a packed delta one"
+    w, h = frames[0].width, frames[0].height
+    r = Renderer(gl, w, h)
+    d = r.device
+    window = gl.WrhipGetFramebufferTexture(0)
+    mirror = d.create_texture(w, h, G.GL_RGBA8, render_target=True)      # (a render target: read_texture reads it at the end)
+    d.upload_texture(mirror, 0, 0, w, h, G.GL_BGRA, G.GL_UNSIGNED_BYTE, np.zeros((h, w, 4), np.uint8))
+    flags = glapi.GRAB_DELTA | (glapi.GRAB_PACKED if packed else 0) | (glapi.GRAB_SCROLL if scroll else 0)
+    rect = (0, 0, w, h)
+    windows, mirrors, crossed, waiting = [], [], [], []
+
+    def fetch():
+        while waiting:
+            windows.append(gl.grab_result(waiting.pop(0))[1])
+            mirrors.append(gl.grab_result(waiting.pop(0))[1])
+    for f in frames:
+        assert (f.width, f.height) == (w, h), "render_streamed_mirrored: one window size"
+        r.render(f)
+        t = gl.grab_texture(window, rect, flags)
+        assert t >= 0, (t, gl.GetError())
+        payload = gl.grab_payload(t)
+        fetch()                          # (the frame before: in stream order ahead of the payload that has just arrived)
+        crossed.append(len(payload))
+        rc = gl.put_texture_payload(mirror.id, rect, payload, flags)
+        assert rc == 0, (rc, gl.GetError())
+        if check:
+            for tex in (window, mirror.id):
+                t = gl.grab_texture(tex, [rect], 0)
+                assert t >= 0, (t, gl.GetError())
+                waiting.append(t)
+    stats = gl.stats()
+    fetch()
+    r.finish()
+    stats["gl_error"] = int(gl.GetError())
+    px = d.read_texture(mirror).copy()
+    d.delete_texture(mirror)
+    r.destroy()
+    return px, stats, windows, mirrors, crossed
+
+
 def _fed_bytes(window_bgra):
     """What render_streamed_fed feeds back, restated in numpy for a backend without tensor calls: the window's stored bytes (B, G, R,
     A) as a tensor grab's F16 elements of R, G, B with scale 1 / 255 (a float32 multiply, then the rounding to float16), and those as
